@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- images/sec of the LAUDNet dynamic-inference hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
 
 A "step" is one eval forward of the headline model over one synthetic batch that is already resident in HBM:
@@ -12,14 +12,19 @@ average pool and classifier are library ops.  Weights are seeded random (no chec
 randomised; the channel maskers' keep-bias is calibrated once, before timing, so that the realised FLOPs ratio is
 the "target-0.5" operating point of the released model.
 
-One JSON line is printed by rank 0 (contract in the task statement) with two extra objects:
+A plain run sets up, warms up, times the K steps, writes the last step's outputs with --dump-outputs DIR (DIR/<name>.npy: the
+7-tuple of the forward -- logits, the per-block s3 / s2 / s1 / cs sparsities concatenated over the stages, flops_perc, flops --
+float32 or float64) and prints one JSON line: `value` (images/sec), `ms_per_step`, the workload's `config` and `block_densities`.
+Everything else below is measured only with --full, which adds to the line (rank 0):
   roofline     : the kernel with the most time per step -- algorithmic FLOPs / bytes per launch / mean launch duration measured with
                  HIP events on the launch stream in a separate leg of event-bracketed forwards right AFTER the timed region (the
                  timed region itself carries no instrumentation); `bound` is the larger of the HBM floor and the matrix floor
   cpu_baseline : the oracle (dense-emulation restatement of the reference, torch CPU) timed on the host cores on
                  a bounded sample of the same workload
 and, unless --no-dense, `dense_emulation_gpu`: the same oracle run on the same GPU through PyTorch-ROCm
-(the "reference dense-emulation PyTorch path" the north star's >=5x is quoted against).
+(the "reference dense-emulation PyTorch path" the north star's >=5x is quoted against); the other arithmetic mode, the hipGraph
+replay, the same kernels with every unit kept, alternating batches, the decision audits, the predicted speedups and the
+`secondary` workloads (--no-legs / --brief / --no-* trim these).
 """
 from __future__ import annotations
 
@@ -63,6 +68,34 @@ WORKLOADS = {
     "adavit": dict(name="DeiT-S shaped token-skip trunk (12 blocks, 197 tokens, dim 384, 6 heads, MLP x4), token keep 0.5"),
 }
 
+DUMP_BYTES = 64 << 20          # --dump-outputs: at most this much in all
+DUMP_SAMPLE = 1 << 22          # elements kept of an array too large for that (fixed seeded positions, the same every run)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: {name: tensor} -> out_dir/<name>.npy, float64 kept, everything else as float32.  An array of more than
+    DUMP_SAMPLE elements is written as <name>_sample.npy: its flattened elements at DUMP_SAMPLE sorted positions drawn with seed 0."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach().cpu()
+        a = (t.double() if t.dtype == torch.float64 else t.float()).numpy()
+        if a.size > DUMP_SAMPLE:
+            pos = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))
+            a, name = a.reshape(-1)[pos], name + "_sample"
+        total += a.nbytes
+        assert total <= DUMP_BYTES, f"--dump-outputs: more than {DUMP_BYTES} bytes"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def forward_outputs(out):
+    """The 7-tuple of a forward (logits, s3, s2, s1, cs, flops_perc, flops) by name; the per-stage lists of per-block sparsities are
+    concatenated in block order."""
+    cat = lambda grp: torch.cat([t.reshape(-1) for t in grp])
+    return {"logits": out[0], "s3": cat(out[1]), "s2": cat(out[2]), "s1": cat(out[3]), "cs": cat(out[4]), "flops_perc": out[5],
+            "flops": out[6]}
+
 
 def bench_adavit(args):
     """--workload adavit: the packed-token trunk of laudnet_amd/adavit.py (ldn_packed_mha + k_dense linears) on one GPU, beside its
@@ -102,6 +135,28 @@ def bench_adavit(args):
             out = hip(x, keeps)
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"tokens": out})
+    kept = float(sum(k.sum().item() for k in keeps)) / (depth * args.batch * L)
+    # algorithmic FLOPs per image.  EXECUTED: q / k / v, attention, projection and MLP all on the kept tokens (TokenSkipBlock.qkv_kept_only:
+    # a dropped token is neither query nor key).  The reference's latency model prices q / k / v on EVERY token (simulate_adavit.py:90-93):
+    # reported beside it as `reference_model_tflops`, not used for the roofline
+    lk = kept * L
+    lq = lk if TokenSkipViT.blocks_qkv_kept_only() else L
+    flops = depth * 2.0 * (lq * dim * 3 * dim + 2 * lk * lk * dim + lk * dim * dim + 2 * lk * dim * 4 * dim)
+    flops_ref_model = depth * 2.0 * (L * dim * 3 * dim + 2 * lk * lk * dim + lk * dim * dim + 2 * lk * dim * 4 * dim)
+    result = {"metric": f"images/sec, DeiT-S shaped token-skip trunk @197 tokens bs{args.batch} (dynamic-token packed MHA)",
+              "value": args.batch / dt, "unit": "images/sec", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+              "ms_per_step": 1e3 * dt, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+              "dtype": "bf16x3 (fp32 tensors; fp32 softmax / LayerNorm / GELU)", "data": "synthetic (seeded randn tokens, seeded random weights and keep masks)",
+              "config": {"workload": WORKLOADS["adavit"]["name"].replace("keep 0.5", f"keep {keep_p}") + f" bs{args.batch}/GPU",
+                         "kept_token_fraction": round(kept, 4), "algorithmic_tflops": flops * args.batch / dt / 1e12,
+                         "reference_model_tflops": flops_ref_model * args.batch / dt / 1e12,
+                         "parity": "UNPINNED: the reference holds no model code for this configuration (oracle/adavit_ref.py header)"}}
+    if not args.full:
+        print(json.dumps(result))
+        return
+    with torch.no_grad():
         for _ in range(3):
             want = refg(x, keeps)
         torch.cuda.synchronize()
@@ -151,28 +206,12 @@ def bench_adavit(args):
                                               "max_abs_diff_vs_dense_restatement": (o2 - w2).abs().max().item()}
     except Exception as e:   # informative only
         extra["token_head_layer_skipping"] = {"error": repr(e)[:200]}
-    kept = float(sum(k.sum().item() for k in keeps)) / (depth * args.batch * L)
-    # algorithmic FLOPs per image.  EXECUTED: q / k / v, attention, projection and MLP all on the kept tokens (TokenSkipBlock.qkv_kept_only:
-    # a dropped token is neither query nor key).  The reference's latency model prices q / k / v on EVERY token (simulate_adavit.py:90-93):
-    # reported beside it as `reference_model_tflops`, not used for the roofline
-    lk = kept * L
-    lq = lk if TokenSkipViT.blocks_qkv_kept_only() else L
-    flops = depth * 2.0 * (lq * dim * 3 * dim + 2 * lk * lk * dim + lk * dim * dim + 2 * lk * dim * 4 * dim)
-    flops_ref_model = depth * 2.0 * (L * dim * 3 * dim + 2 * lk * lk * dim + lk * dim * dim + 2 * lk * dim * 4 * dim)
-    result = {"metric": f"images/sec, DeiT-S shaped token-skip trunk @197 tokens bs{args.batch} (dynamic-token packed MHA)",
-              "value": args.batch / dt, "unit": "images/sec", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-              "ms_per_step": 1e3 * dt, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-              "dtype": "bf16x3 (fp32 tensors; fp32 softmax / LayerNorm / GELU)", "data": "synthetic (seeded randn tokens, seeded random weights and keep masks)",
-              "config": {"workload": WORKLOADS["adavit"]["name"].replace("keep 0.5", f"keep {keep_p}") + f" bs{args.batch}/GPU",
-                         "kept_token_fraction": round(kept, 4), "algorithmic_tflops": flops * args.batch / dt / 1e12,
-                         "reference_model_tflops": flops_ref_model * args.batch / dt / 1e12,
-                         "parity": "UNPINNED: the reference holds no model code for this configuration (oracle/adavit_ref.py header)"},
-              "roofline": roof,
-              "dense_emulation_gpu": {"value": args.batch / dtd, "unit": "images/sec", "ms_per_step": 1e3 * dtd,
-                                      "kind": "oracle/adavit_ref.py (dense masked attention, every token through every linear), PyTorch-ROCm fp32, same GPU",
-                                      "max_abs_diff_vs_hip_same_masks": (out - want).abs().max().item(),
-                                      "output_scale": want.abs().max().item()},
-              "realised_speedup_vs_dense_emulation": dtd / dt, **extra}
+    result.update({"roofline": roof,
+                   "dense_emulation_gpu": {"value": args.batch / dtd, "unit": "images/sec", "ms_per_step": 1e3 * dtd,
+                                           "kind": "oracle/adavit_ref.py (dense masked attention, every token through every linear), PyTorch-ROCm fp32, same GPU",
+                                           "max_abs_diff_vs_hip_same_masks": (out - want).abs().max().item(),
+                                           "output_scale": want.abs().max().item()},
+                   "realised_speedup_vs_dense_emulation": dtd / dt, **extra})
     print(json.dumps(result))
 
 
@@ -281,7 +320,8 @@ def run_secondary(args):
         # (30 timed forwards behind 10 warm-up ones: windows of ten forwards right after a process start read up to 2-3x slow now and then -- RegNet 10.8 vs 3.5 ms,
         # layer 14.1 vs 10.5 ms with every kernel at its usual duration in the event leg of the same process, i.e. a host-side stall of tens of milliseconds)
         n_steps, n_warm = "30", "10"
-        cmd = [sys.executable, os.path.abspath(__file__), "--workload", w, "--steps", n_steps, "--warmup", n_warm, "--batch", str(args.batch), "--brief"]
+        cmd = [sys.executable, os.path.abspath(__file__), "--workload", w, "--steps", n_steps, "--warmup", n_warm, "--batch", str(args.batch), "--brief",
+               "--full"]
         t0 = time.perf_counter()
         try:
             pr = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
@@ -681,6 +721,11 @@ def main():
                     "(SURVEY 8d's p = 0.62 / 0.5 realise 0.513 / 0.59)")
     ap.add_argument("--math", choices=["fp32", "bf16x3"], default="bf16x3",
                     help="arithmetic of the MFMA convolutions (include/ldn_hip.h: ldn_set_math_mode); fp32 storage either way")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed "
+                    "as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: roofline leg, PMC traffic, other "
+                    "arithmetic mode, hipGraph replay, keep-1.0 and alternating-batch legs, dense-emulation and CPU baselines, decision "
+                    "audits, predicted speedups and the `secondary` workloads (the --no-* / --brief options trim these)")
     args = ap.parse_args()
     if args.no_legs:
         args.no_dense = args.no_cpu = True
@@ -804,6 +849,8 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, forward_outputs(out))
 
     # ---- the roofline leg: the same forwards again, now with two HIP-event records (on the launch stream) around the launches
     # of the kernel kinds below; run AFTER the timed region so that the records cost nothing inside it
@@ -815,7 +862,7 @@ def main():
     orig_grouped = ops.grouped16_conv3x3_images
     orig_rows_ps, orig_rows3 = ops.conv_rows_ps, ops.conv3x3_rows_ps
     ev_steps = 0
-    if rank == 0 and graphed is None and not os.environ.get("LDN_BENCH_NO_EVENTS"):
+    if args.full and rank == 0 and graphed is None and not os.environ.get("LDN_BENCH_NO_EVENTS"):
         ops.conv_image = timer.wrap(orig_conv_image)
         ops.conv_rows = timer.wrap_rows(orig_conv_rows)
         ops.bottleneck_tail = timer.wrap_tail(orig_tail)
@@ -992,7 +1039,7 @@ def main():
 
     result["block_densities"] = block_densities
     result.setdefault("roofline", None)   # workloads whose hot kernels are not timed per launch (RegNet grouped conv, --graph)
-    if rank == 0 and world == 1 and not args.graph and not args.no_legs and not args.brief:
+    if args.full and rank == 0 and world == 1 and not args.graph and not args.no_legs and not args.brief:
         # same forward, same kernels, replayed as one hipGraph (launch gaps removed)
         try:
             from laudnet_amd.laud_resnet import GraphedForward
@@ -1014,7 +1061,7 @@ def main():
                 hb.last_channel_mask, hb.last_spatial_mask = cm, sm
         except Exception as e:   # informative only
             result["hipgraph_replay"] = {"error": repr(e)[:200]}
-    if rank == 0 and world == 1 and args.math != "fp32" and not args.no_legs and not args.graph and not args.brief:
+    if args.full and rank == 0 and world == 1 and args.math != "fp32" and not args.no_legs and not args.graph and not args.brief:
         # the same workload with fp32 operands on v_mfma_f32_32x32x2_f32 (reported beside the headline, not as `value`)
         def grab_masks():
             return [m for hb, _ in blocks_of(model) for m in (getattr(hb, "last_channel_mask", None), getattr(hb, "last_spatial_mask", None))
@@ -1041,7 +1088,7 @@ def main():
         ops.set_math_mode(args.math)
         out = step()   # leave the modules' last_*_mask in the headline mode for the same-mask parity leg below
         torch.cuda.synchronize()
-    if (rank == 0 and world == 1 and not args.no_legs and not args.graph and wl["p_spatial"] is not None):
+    if (args.full and rank == 0 and world == 1 and not args.no_legs and not args.graph and wl["p_spatial"] is not None):
         # Two DIFFERENT batches alternating: the timed region replays one resident batch, so the row-count hints the
         # packed-row kernels size their tiles with (ops.RowsHint = the PREVIOUS forward's device-side counts) are exact there.  Here every forward
         # sees the counts of the other batch: the hint is stale by one forward, as on a stream of real batches.  Results are hint-independent
@@ -1069,7 +1116,7 @@ def main():
             torch.cuda.synchronize()
         except Exception as e:   # informative only
             result["alternating_batches"] = {"error": repr(e)[:200]}
-    if (rank == 0 and world == 1 and not args.no_legs and not args.graph
+    if (args.full and rank == 0 and world == 1 and not args.no_legs and not args.graph
             and (wl["p_channel"] is not None or wl["p_spatial"] is not None)):
         # the SAME kernels with every unit kept (maskers recalibrated to keep 1.0): what the dynamic masks buy on this implementation
         # (in --brief runs too since round 6: the secondary legs report it as `mi355x_model.realised_speedup_of_the_masks`)
@@ -1091,7 +1138,7 @@ def main():
         model.load_state_dict({k: v.to(dev) for k, v in calibrated_sd.items()})
         out = step()
         torch.cuda.synchronize()
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         from oracle import torch_ref as TR
         if "ref" in wl:
             ref = getattr(TR, wl["ref"])(**kw).eval()
@@ -1188,7 +1235,7 @@ def main():
     # second half of the BASELINE metric: the reference's analytic predictor with MI355X parameters (tools/predict_speedup.py,
     # generated in the build container by importing the reference's DyNetSimulator; committed under profiles/)
     pj = os.path.join(ROOT, "profiles", "predicted_speedup_mi355x.json")
-    if os.path.exists(pj):
+    if args.full and os.path.exists(pj):
         key = {"channel": "channel-2222", "spatial": "spatial S=4-4-2-1", "layer": "ResNet101 layer skip", "regnet": "RegNetY-800MF"}.get(args.workload)
         pd = json.load(open(pj))
         rows = [r for r in pd["rows"] if key is not None and key in r["workload"]]
@@ -1212,7 +1259,7 @@ def main():
                 k1 = result.get("same_kernels_keep_1.0", {})
                 if "realised_speedup_of_the_masks" in k1:   # static baseline = the same kernels with nothing skipped (not eager PyTorch)
                     result["realised_over_predicted"]["vs_same_kernels_keep_1.0"] = k1["realised_speedup_of_the_masks"] / best
-    if rank == 0:
+    if args.full and rank == 0:
         # the MI355X-native latency model of THIS implementation (laudnet_amd/predictor.py; constants fitted on four keep probabilities
         # of profiles/r03_density_sweep_*.jsonl, validated on three held-out ones): predicted step time from the per-block densities of
         # this run, and its predicted speedup over the same kernels with every unit kept
@@ -1243,7 +1290,7 @@ def main():
                 result["mi355x_model"]["note"] += "; NOT fitted on per-pixel masks (its masker term is the pooled-mean masker's): indicative only"
         except Exception as e:   # informative only
             result["mi355x_model"] = {"error": repr(e)[:200]}
-    if (rank == 0 and world == 1 and args.workload == "channel" and not args.no_legs and not args.brief and not args.graph
+    if (args.full and rank == 0 and world == 1 and args.workload == "channel" and not args.no_legs and not args.brief and not args.graph
             and not args.no_secondary and args.keep is None and args.target_flops is None and args.math == "bf16x3"):
         result["secondary"] = run_secondary(args)
     if rank == 0:

@@ -1,7 +1,9 @@
 """Predictor side of the metric: tools/predict_speedup.py drives the reference's analytic latency model with
 the reference's own block formulas.  The harness is pinned by reproducing, on the V100 preset, the four latencies the
 reference's DyNetSimulator/eval_example.py computes -- stored in tests/golden/predictor_v100.json by
-tests/golden/make_predictor_golden.py, which RUNS that script unmodified.  Needs /root/reference (build container only)."""
+tests/golden/make_predictor_golden.py, which RUNS that script unmodified.  The reference's block formulas are replayed from
+tests/golden/predictor_v100_calls.json (what they returned to this harness, recorded by tests/golden/make_predictor_calls_golden.py),
+so the reference itself is not needed here."""
 import json
 import os
 import sys
@@ -10,7 +12,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "predictor_v100.json")
-needs_ref = pytest.mark.skipif(not os.path.isdir("/root/reference/DyNetSimulator"), reason="the reference simulator is not on this box")
+CALLS = os.path.join(ROOT, "tests", "golden", "predictor_v100_calls.json")
 
 
 def test_golden_file_is_sane():
@@ -21,12 +23,34 @@ def test_golden_file_is_sane():
         assert all(v > 0 for v in m.values())
 
 
-@needs_ref
+class _RecordedReference:
+    """Stands in for the reference's eval_example module and predictor class: each block-latency call must be the next recorded one
+    (same function, same arguments) and returns the latency the reference returned for it."""
+
+    def __init__(self, rec):
+        self.ctor, self.calls = rec["predictor"], list(rec["calls"])
+
+    def predictor(self, *a, **kw):
+        assert self.ctor == [{"args": list(a), "kwargs": kw}], (a, kw)
+        return "predictor"
+
+    def __getattr__(self, fn):
+        def call(predictor, **kw):
+            assert predictor == "predictor" and self.calls, (fn, kw)
+            want = self.calls.pop(0)
+            assert (fn, kw) == (want["fn"], want["kw"]), (fn, kw, want)
+            return want["latency"]
+        return call
+
+
 @pytest.mark.parametrize("model", ["resnet50", "resnet101", "regnety008"])
-def test_harness_reproduces_reference_v100_numbers(model):
+def test_harness_reproduces_reference_v100_numbers(model, monkeypatch):
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import predict_speedup as PS
+    ref = _RecordedReference(json.load(open(CALLS))["models"][model])
+    monkeypatch.setattr(PS, "load_reference", lambda: (ref, ref.predictor))
     got = PS.reproduce_v100(model)
+    assert not ref.calls, f"{len(ref.calls)} recorded block calls were not made"
     want = json.load(open(GOLD))["models"][model]
     for k, v in want.items():
         assert abs(got[k] - v) <= 1e-12 + 1e-9 * v, (model, k, got[k], v)

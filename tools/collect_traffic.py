@@ -14,7 +14,7 @@ import bench  # noqa: E402
 out = {}
 date = time.strftime("%Y-%m-%d")
 for w in ("spatial", "layer", "regnet"):
-    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", w, "--brief", "--pmc-legs", "--no-cpu"], capture_output=True, text=True, timeout=1200)
+    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", w, "--brief", "--pmc-legs", "--no-cpu", "--full"], capture_output=True, text=True, timeout=1200)
     try:
         d = json.loads([l for l in pr.stdout.splitlines() if l.startswith("{")][-1])
         r = d["roofline"]
@@ -31,7 +31,7 @@ for w in ("spatial", "layer", "regnet"):
     except Exception as e:
         print(w, "failed:", repr(e)[:200], pr.stderr[-500:], flush=True)
 # headline: the chained launch and the fused tails (keep from a brief run's calibration)
-pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--brief", "--no-cpu", "--no-pmc"], capture_output=True, text=True, timeout=1200)
+pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--brief", "--no-cpu", "--no-pmc", "--full"], capture_output=True, text=True, timeout=1200)
 d = json.loads([l for l in pr.stdout.splitlines() if l.startswith("{")][-1])
 keep = d["config"]["keep_probability_calibrated_to"]
 ch = bench.measure_chain_traffic(keep, 256)

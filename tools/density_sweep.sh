@@ -7,7 +7,7 @@ mkdir -p $OUT
 for w in ${@:-channel spatial layer regnet}; do
   rm -f $OUT/${ROUND_TAG:-r06}_density_sweep_$w.jsonl
   for k in 0.25 0.4 0.5 0.62 0.75 0.9 1.0; do
-    python $R/bench.py --workload $w --no-legs --steps 8 --warmup 2 --keep $k 2>/dev/null | tail -1 >> $OUT/${ROUND_TAG:-r06}_density_sweep_$w.jsonl
+    python $R/bench.py --workload $w --no-legs --full --steps 8 --warmup 2 --keep $k 2>/dev/null | tail -1 >> $OUT/${ROUND_TAG:-r06}_density_sweep_$w.jsonl
   done
   python - <<PY
 import json

@@ -4,7 +4,7 @@
 # Every step writes under gpurun_out/<out-tag>/ (merged back by gpurun).  Steps:
 #   tests[:<pytest -k expr>]          pytest -m gpu (optionally filtered)           -> tests.log
 #   testfile:<path>[::k]              one test file                                  -> tests_<name>.log
-#   bench[:<workload>[:extra args]]   bench.py --brief of a workload (default: all legs of the headline when workload = full)
+#   bench[:<workload>[:extra args]]   bench.py --brief --full of a workload (default: all legs of the headline when workload = full)
 #   trace:<workload>[:<keep>]         rocprofv3 --kernel-trace --stats over bench.py --no-legs  -> <w>_kernel_stats.txt, period_<w>.txt
 #   pmc:<workload>:<kernel-substr>[:<keep>]  MFMA-busy / traffic counters of the matching kernels (separate passes)  -> pmc_<w>.txt
 #   py:<script and args>              python <script> (tools/*.py micro-benchmarks)  -> py_<n>.log
@@ -48,8 +48,8 @@ for step in "$@"; do
       cd $R
       w=${rest%%:*}; extra=${rest#*:}; [ "$extra" = "$rest" ] && extra=""
       [ -z "$w" ] && w=full
-      if [ "$w" = full ]; then timeout 1200 python bench.py $extra > $OUT/bench_headline.json 2> $OUT/bench_headline.err
-      else timeout 900 python bench.py --workload $w --brief $extra > $OUT/bench_$w.json 2> $OUT/bench_$w.err; fi
+      if [ "$w" = full ]; then timeout 1200 python bench.py --full $extra > $OUT/bench_headline.json 2> $OUT/bench_headline.err
+      else timeout 900 python bench.py --workload $w --brief --full $extra > $OUT/bench_$w.json 2> $OUT/bench_$w.err; fi
       python - $OUT/bench_$([ "$w" = full ] && echo headline || echo $w).json <<'PY'
 import json, sys
 try:

@@ -9,11 +9,11 @@ EXCL="naive_conv|igemm_|grouped_conv_fwd|SubTensorOp|Im2d2Col|Cijk"
 # 0. the bench lines themselves (all legs) -- same box, same call as the profiles below (ONLY_TRACE=1 skips to step 1 and reuses them)
 cd $R
 if [ -z "$ONLY_TRACE" ]; then
-timeout 900 python bench.py > $OUT/bench_headline.json 2> $OUT/bench_headline.err
+timeout 900 python bench.py --full > $OUT/bench_headline.json 2> $OUT/bench_headline.err
 for w in ${WORKLOADS:-spatial layer regnet adavit}; do
-  timeout 900 python bench.py --workload $w --no-cpu > $OUT/bench_$w.json 2> $OUT/bench_$w.err
+  timeout 900 python bench.py --workload $w --full --no-cpu > $OUT/bench_$w.json 2> $OUT/bench_$w.err
 done
-timeout 900 python bench.py --keep 0.5 --no-cpu > $OUT/bench_keep05.json 2> $OUT/bench_keep05.err
+timeout 900 python bench.py --keep 0.5 --full --no-cpu > $OUT/bench_keep05.json 2> $OUT/bench_keep05.err
 fi
 cd /tmp
 # the keep probability the bench line's bisection arrived at (seeded: the same every run): the profiled command passes it with --keep, so
