@@ -195,3 +195,20 @@ def test_integration_md_stub_matches_header():
         assert got == protos[name], f"INTEGRATION.md: {name} has {len(got)} arguments {''.join(got)}, header {len(protos[name])} {''.join(protos[name])}"
         found += 1
     assert found >= 5
+
+
+# ---- every public wrapper of laudnet_amd.ops is named by a direct GPU test ------------------------------------------------------
+HOST_ONLY_OPS = {"as_nhwc", "from_nhwc", "split_rows_weight", "chain_table", "dense_kernel_ok", "fused_kernel_ok"}
+
+
+def test_every_public_op_is_named_in_a_direct_gpu_test():
+    """A wrapper that only a whole block or a whole model reaches has no test at the shapes where its kernel goes wrong: every public
+    function of laudnet_amd.ops must appear by name in at least one tests/test_hip_*.py.  The exemptions are host-only helpers."""
+    import glob
+    import inspect
+    from laudnet_amd import ops
+    public = sorted(n for n, f in inspect.getmembers(ops, inspect.isfunction) if f.__module__ == ops.__name__ and not n.startswith("_"))
+    assert len(public) >= 40 and HOST_ONLY_OPS <= set(public)
+    text = "\n".join(open(p).read() for p in sorted(glob.glob(os.path.join(ROOT, "tests", "test_hip_*.py"))))
+    missing = [n for n in public if n not in HOST_ONLY_OPS and not re.search(rf"\b{n}\b", text)]
+    assert not missing, f"no tests/test_hip_*.py names these ops: {missing}"

@@ -142,6 +142,7 @@ def test_chain_rejects_bad_arguments():
     x = torch.zeros(2, 20, 20, 64, device=DEV)             # 400 pixels: does not fit one workgroup
     table = torch.zeros(2, ops.CHAIN_BLOCK_FIELDS, dtype=torch.int64, device=DEV)
     gap = torch.zeros(2, 8, 64, device=DEV)
+    assert ops.bottleneck_chain_fits(14, 14, 1024, 256, 16, 128) and not ops.bottleneck_chain_fits(20, 20, 64, 64, 16, 32)     # stage 3 of R101 fits, the map below does not
     with pytest.raises(LdnError):
         ops.bottleneck_chain(x, x, table, 64, 16, 32, 2, gap)
     with pytest.raises(LdnError):

@@ -37,6 +37,7 @@ def _affine(c, seed):
 
 
 def test_presplit_helpers_round_trip(ops):
+    assert ops.rows_ps_ok(256, 64, 256) and not ops.rows_ps_ok(256, 96, 256)      # widths k_rows3 tiles (width % 64) and one it does not
     x = seeded_randn((37, 64), 1).to(DEV)
     ps = ops.presplit_rows(x)
     assert ps.shape == x.shape and ps.dtype == torch.float32

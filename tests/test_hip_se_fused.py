@@ -142,6 +142,7 @@ def test_conv_c_gated_rejects_what_it_does_not_run(ops):
         ops.conv_rows_gated(h_b, w, None, sh, out, torch.ones(1, 32, device=DEV), 32)        # gate covers one image, the rows span two
     with pytest.raises(LdnError):
         ops.conv_rows_gated(h_b, w, None, sh, out, torch.ones(2, 16, device=DEV), 32)        # gate width != cin
+    assert ops.conv_rows_gated_fits(784, 49) and not ops.conv_rows_gated_fits(1024, 1)      # the predicate the callers ask: a 7 x 7 stage fits, the launch below does not
     with pytest.raises(LdnError):     # one gate row per input row of a 1024-wide layer: 257 gate vectors per tile do not fit the LDS
         ops.conv_rows_gated(torch.zeros(64, 1024, device=DEV), torch.zeros(32, 1, 1024, device=DEV), None, sh, out, torch.ones(64, 1024, device=DEV), 1)
 

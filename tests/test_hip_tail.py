@@ -85,6 +85,13 @@ def _tail_vs_reference_algebra(ops, B, H, cin, W, gran, st):
     # conv1 on k_head: same pre-split output (identical arithmetic up to the order of the K sum)
     if cin % 32 == 0:
         h1h = torch.full((B, H, H, W), float("nan"), device=DEV)
+        # pack_w1_split's layout, against a plain hi / lo split: [n][octet][8 hi | 8 lo] bf16 (include/ldn_hip.h: ldn_bottleneck_head)
+        w1 = hb.conv1.weight.detach().reshape(W, cin)
+        w1_hi = w1.to(torch.bfloat16)
+        w1_lo = (w1 - w1_hi.float()).to(torch.bfloat16)
+        w1s = ops.pack_w1_split(w1)
+        assert tuple(w1s.shape) == (W, cin // 8, 2, 8) and w1s.dtype == torch.bfloat16 and torch.equal(w1s, p["w1s"])
+        assert torch.equal(w1s[:, :, 0].reshape(W, cin), w1_hi) and torch.equal(w1s[:, :, 1].reshape(W, cin), w1_lo)
         ops.bottleneck_head(xn, p["w1s"], idx, cnt, p["s1"], p["t1"], p["c1"], h1h)
         dech = _decode_split(h1h).cpu()
         for b in range(B):
