@@ -45,7 +45,8 @@ int ldn_version(void);
  * laudnet_amd.build --debug -> libldn_hip_debug.so) every kernel checks the index lists it consumes or produces on the device
  * (entries inside their tensor, counts inside the list capacity, channel pairs aligned and ascending, every in-bounds 3x3 tap
  * of an active pixel present in the dilated list); violations are counted, never trapped.  *count = violations since the last
- * reset (synchronises the device), *first_code = code of the first one (1xx conv, 2xx index build, 3xx fused tail, 4xx RegNet, 5xx packed-row 1x1);
+ * reset (synchronises the device), *first_code = code of the first one (1xx conv, 2xx index build, 3xx fused tail, 4xx RegNet, 5xx packed-row 1x1,
+ * 6xx weight gradient);
  * the release build reports *count = -1 (checks compiled away).  Debug-only tooling: not on the hot path. */
 int ldn_debug_violations(int* count, int* first_code, int reset);
 /* Robustness counter of the one-launch list build (ldn_mask_plan, and ldn_mask_to_index on maps it runs as one launch): its
@@ -215,6 +216,26 @@ int ldn_conv_rows_f32(const float* a, int lda, const int32_t* a_rows, int taps, 
  * count, copied to pinned memory asynchronously).  It only selects the tile width (a launch takes rounds-of-workgroups x tile time,
  * DESIGN.md 4n / 4t); results are bit-identical with any hint or none.  Calls without a device-side count know their rows exactly. */
 int ldn_hint_rows(int rows);   /* returns 0 */
+
+/* ---- the WEIGHT GRADIENT of ldn_conv_rows (training under frozen BatchNorm statistics; the reference takes it from autograd's
+ * cuDNN backward-filter behind laud_resnet.py:115-144): the reduction runs over the packed rows
+ *   dW[n, t, k] = sum_{r < count} dY[r, n] * A[src(r, t), k]          for n < cout, t < taps, k < cin
+ *   src(r, t)   = a_rows ? a_rows[r * taps + t] : r;   an index < 0 or >= a_valid is a ZERO row (a missing 3x3 neighbour)
+ *   count       = m_count ? clamp(*m_count, 0, m_cap) : m_cap, read on the device (no host read, no synchronisation)
+ * dY [m_cap][lddy >= cout] fp32, A [a_valid][lda >= cin] fp32, a_rows [m_cap][taps] (the neighbour table of ldn_mask_to_index for
+ * taps == 9, a pixel list for taps == 1; without a_rows A is read at row r itself, and m_cap > a_valid is LDN_EINVAL).  Rows r >= count are NOT READ -- neither dY nor a_rows: they may hold anything, NaN included.
+ * dW [cout][taps][cin] fp32 = the weight layout of ldn_conv_rows, fully overwritten (count == 0: zeros).
+ * math_mode as ldn_conv_rows: LDN_MATH_BF16X3 splits BOTH operands in the kernel (both are activations: nothing to pre-split) and adds
+ * lo*hi + hi*lo + hi*hi on v_mfma_f32_32x32x16_bf16; LDN_MATH_FP32 runs on v_mfma_f32_32x32x2_f32.
+ * Deterministic: the rows are split over workgroups -- how many ways is a function of m_cap and the shapes only, never of *m_count, so the
+ * launch can be captured into a graph -- the partial tiles go to `work` (ldn_wgrad_rows_workspace_bytes; may be NULL when that is 0)
+ * and are added in a fixed order by a second small launch.  No floating-point atomics: two runs are bit-identical.
+ * Shapes (ldn_wgrad_rows_ok): taps 1 | 9, cin % 8 == 0, cout % 4 == 0, cin and cout <= 2048 (taps 1) / <= 512 (taps 9); lddy, lda % 4 == 0,
+ * 16-byte aligned pointers.  Anything else is LDN_EINVAL.  LDN_DEBUG build: a_rows entries below -1 are counted (code 601). */
+int ldn_wgrad_rows_ok(int cin, int cout, int taps);
+size_t ldn_wgrad_rows_workspace_bytes(int m_cap, int cin, int cout, int taps);
+int ldn_wgrad_rows(const float* dy, int lddy, const float* a, int lda, int a_valid, const int32_t* a_rows, int taps,
+                   const int32_t* m_count, int m_cap, int cin, int cout, float* dw, float* work, int math_mode, void* stream);
 
 /* ldn_conv_rows_split / ldn_conv_rows_f32 with taps == 1, plus a by-product: pool [B][S*Sx][cout] receives, for every patch
  * this launch writes, the MEAN of the final output (after residual and ReLU) over the patch's Ho/S x Wo/Sx pixels (4 or 16) --

@@ -506,6 +506,40 @@ def conv_rows(a2d, w, scale, shift, out2d, *, a_rows=None, taps=1, m_count=None,
     return out2d
 
 
+def wgrad_rows_ok(cin, cout, taps):
+    """Does ldn_wgrad_rows take this shape (taps 1 | 9, cin % 8 == 0, cout % 4 == 0, both <= 2048 for taps 1 / <= 512 for taps 9)?"""
+    return bool(L.load().ldn_wgrad_rows_ok(int(cin), int(cout), int(taps)))
+
+
+def wgrad_rows(dy2d, a2d, *, a_rows=None, taps=1, m_count=None, m_cap=None, a_valid=None, out=None, math=None):
+    """Weight gradient of a packed-row convolution (see ldn_wgrad_rows): dW[n, t, k] = sum_{r < count} dy2d[r, n] * a2d[src(r, t), k] with
+    src(r, t) = a_rows[r * taps + t] (an index < 0 or >= a_valid is a zero row) or r.  dy2d [m_cap, lddy >= cout], a2d [rows, lda >= cin];
+    rows past the device-side count are not read.  Returns out [cout, taps, cin] (= the weight layout of conv_rows), fully overwritten.
+    Deterministic (no atomics); a shape outside wgrad_rows_ok raises LdnError."""
+    L.require_device(dy2d, a2d, a_rows, m_count, out)
+    lib = L.load()
+    cout, cin = dy2d.shape[1], a2d.shape[1]
+    if taps not in (1, 9):
+        raise L.LdnError(f"wgrad_rows: taps must be 1 or 9, got {taps}")
+    if m_cap is None:
+        m_cap = dy2d.shape[0] if a_rows is None else a_rows.numel() // taps
+    if m_cap > dy2d.shape[0] or (a_rows is not None and a_rows.numel() < m_cap * taps):
+        raise L.LdnError(f"wgrad_rows: m_cap {m_cap} exceeds dy2d ({dy2d.shape[0]} rows) or a_rows")
+    if a_valid is None:
+        a_valid = a2d.shape[0]
+    if a_valid > a2d.shape[0] or (a_rows is None and m_cap > a_valid):
+        raise L.LdnError(f"wgrad_rows: a_valid {a_valid} / m_cap {m_cap} exceed a2d ({a2d.shape[0]} rows)")
+    if out is None:
+        out = torch.empty(cout, taps, cin, device=dy2d.device, dtype=torch.float32)
+    elif tuple(out.shape) != (cout, taps, cin):
+        raise L.LdnError(f"wgrad_rows: out must be [{cout}, {taps}, {cin}], got {tuple(out.shape)}")
+    work = _work(lib.ldn_wgrad_rows_workspace_bytes(m_cap, cin, cout, taps), dy2d.device)
+    L.check(lib.ldn_wgrad_rows(L.ptr(_f32rows(dy2d, "dy")), dy2d.stride(0), L.ptr(_f32rows(a2d, "a")), a2d.stride(0), a_valid,
+                               L.ptr(_i32c(a_rows, "a_rows")), taps, L.ptr(_i32c(m_count, "m_count")), m_cap, cin, cout,
+                               L.ptr(_f32c(out, "out")), L.ptr(work), _mm(math), L.stream_ptr(out)), "ldn_wgrad_rows")
+    return out
+
+
 USE_ROWS_PS = os.environ.get("LDN_ROWS_PS", "1") != "0"      # the pre-split packed path (k_dense<PS / OF> + k_rows3); 0 = round 4's three launches
 
 

@@ -20,7 +20,9 @@ on the library's kernels:
   channel masks (any stride): the row kernels over ALL pixels with the channel mask and the constants of the channel algebra as epilogue
       terms (a masked channel is the constant relu(shift); the library's "dense channel execution").  Correct for every
       gradient, but dense in the channels: the masks save no FLOPs here (stated, not hidden).
-  Weight gradients are library GEMMs over the packed rows; the gradients of BatchNorm's affine parameters come out of the folded
+  Weight gradients are the library's own kernel (`ops.wgrad_rows`: dW = sum over the packed rows of dY x A, the nine taps' rows gathered through
+  the neighbour table inside the kernel, rows past the device-side count never read, deterministic) wherever `ops.wgrad_rows_ok` holds and
+  `USE_WGRAD_KERNEL` is on (the default; env LDN_WGRAD=0 turns it off); otherwise, and for other shapes, the gather + GEMM path; the gradients of BatchNorm's affine parameters come out of the folded
   (scale, shift) pairs, which stay differentiable functions of (weight, bias); the straight-through terms of the hard masks need the branch at
   DROPPED units too -- computed by the library's own dense execution (that term is dense in the reference as well).
   The residual add, the final ReLU, the projection shortcut, the maskers' tiny heads, the static stem and the classifier are plain autograd
@@ -34,11 +36,17 @@ frozen).  Checked against the oracle's autograd -- blocks on the reference-gener
 dilated conv2, BatchNorm in batch-statistics mode."""
 from __future__ import annotations
 
+import os
+
 import torch
 import torch.nn.functional as F
 
 from . import ops
 from ._lib import LdnError
+
+# weight gradients on ldn_wgrad_rows; LDN_WGRAD=0 = the gather + PyTorch GEMM path.  On by default: the median step is shorter with the kernel for
+# all three full-width workloads at batch 32 and 128 (profiles/train_step_wgrad.jsonl, DESIGN.md 8)
+USE_WGRAD_KERNEL = os.environ.get("LDN_WGRAD", "1") != "0"
 
 
 # ------------------------------------------------------------------------------------------------------------------ index helpers
@@ -96,6 +104,11 @@ def _weight_grad_3x3(du2, h1, nbr, cap1, count3=None):
     nb = torch.where(nb >= 0, nb, torch.full_like(nb, cap1))
     cols = h1z[nb.reshape(-1)].view(nb.shape[0], 9 * h1.shape[1])          # [rows, 9 K]: the nine taps' rows side by side -- ONE GEMM
     return (du2.t() @ cols).view(W, 9, h1.shape[1]).permute(0, 2, 1).reshape(W, h1.shape[1], 3, 3)
+
+
+def _wgrad_kernel(cin, cout, taps):
+    """Does this weight gradient run on ldn_wgrad_rows (the module switch and the kernel's shape predicate)?"""
+    return USE_WGRAD_KERNEL and ops.wgrad_rows_ok(cin, cout, taps)
 
 
 # ------------------------------------------------------------------------------------------------------------------ pixel masks
@@ -156,13 +169,22 @@ class _PixelBranchFn(torch.autograd.Function):
             ops.conv_rows(du1, w1r.reshape(W, Cin).t().reshape(Cin, 1, W).contiguous(), None, zC, gx, taps=1, m_count=ix.cnt[1:2], m_cap=ix.cap1,
                           relu=0, out_rows=ix.idx1, residual2d=gx)
             grad_x = ops.from_nhwc(gx.view(B, Hi, Wi, Cin))
-        # weight gradients: library GEMMs over the packed rows (rows past the counts are zero in g3 / du2 / du1)
+        # weight gradients: ldn_wgrad_rows over the packed rows (it reads no row past the counts); shapes outside its predicate keep the
+        # gather + GEMM path (which relies on g3 / du2 / du1 being zero past the counts)
         gw1 = gw2 = gw3 = None
         if need[3]:
-            gw3 = ((g3.t() @ h2) * s3.view(-1, 1)).reshape(cout, W, 1, 1)
+            if _wgrad_kernel(W, cout, 1):
+                gw3 = (ops.wgrad_rows(g3, h2, m_count=ix.cnt[0:1], m_cap=ix.cap3).view(cout, W) * s3.view(-1, 1)).reshape(cout, W, 1, 1)
+            else:
+                gw3 = ((g3.t() @ h2) * s3.view(-1, 1)).reshape(cout, W, 1, 1)
         if need[2]:
-            gw2 = _weight_grad_3x3(du2, h1, ix.nbr, ix.cap1, ix.cnt[0])
-        if need[1]:
+            if _wgrad_kernel(W, W, 9):
+                gw2 = ops.wgrad_rows(du2, h1, a_rows=ix.nbr, taps=9, m_count=ix.cnt[0:1], m_cap=ix.cap3, a_valid=ix.cap1).permute(0, 2, 1).reshape(W, W, 3, 3)
+            else:
+                gw2 = _weight_grad_3x3(du2, h1, ix.nbr, ix.cap1, ix.cnt[0])
+        if need[1] and _wgrad_kernel(Cin, W, 1):
+            gw1 = ops.wgrad_rows(du1, x2d, a_rows=ix.idx1, taps=1, m_count=ix.cnt[1:2], m_cap=ix.cap1).reshape(W, Cin, 1, 1)
+        elif need[1]:
             rows1 = torch.where(v1.squeeze(1) > 0, ix.idx1.long(), torch.zeros_like(ix.idx1, dtype=torch.long)).clamp(0, x2d.shape[0] - 1)
             gw1 = (du1.t() @ x2d[rows1]).reshape(W, Cin, 1, 1)      # (list entries past the count are uninitialised: du1 is zero there)
         # folded BatchNorm vectors: z = s y + t  =>  d t = sum d z,  d s = sum d z * y,  y = (z - t) / s wherever d z != 0 (there z = the stored ReLU output)
@@ -284,10 +306,18 @@ class _ChannelBranchFn(torch.autograd.Function):
             grad_x = ops.from_nhwc(gx.view(B, Hi, Wi, Cin))
         gw1 = gw2 = gw3 = None
         if need[3]:     # conv3 sees h2 = u2 + c2 at every channel (the constants of the masked ones included)
-            gw3 = ((go.t() @ h2f) * s3.view(-1, 1)).reshape(cout, W, 1, 1)
+            if _wgrad_kernel(W, cout, 1):
+                gw3 = (ops.wgrad_rows(go, h2f, m_cap=ix.cap3).view(cout, W) * s3.view(-1, 1)).reshape(cout, W, 1, 1)
+            else:
+                gw3 = ((go.t() @ h2f) * s3.view(-1, 1)).reshape(cout, W, 1, 1)
         if need[2]:     # conv2 sees h1 = u1 + c1 inside the map, zeros in the padding ring
-            gw2 = _weight_grad_3x3(du2, h1f, ix.nbr, ix.cap1)
-        if need[1]:
+            if _wgrad_kernel(W, W, 9):
+                gw2 = ops.wgrad_rows(du2, h1f, a_rows=ix.nbr, taps=9, m_cap=ix.cap3, a_valid=ix.cap1).permute(0, 2, 1).reshape(W, W, 3, 3)
+            else:
+                gw2 = _weight_grad_3x3(du2, h1f, ix.nbr, ix.cap1)
+        if need[1] and _wgrad_kernel(Cin, W, 1):
+            gw1 = ops.wgrad_rows(du1, x2d, a_rows=ix.idx1, taps=1, m_cap=ix.cap1).reshape(W, Cin, 1, 1)
+        elif need[1]:
             gw1 = (du1.t() @ x2d[ix.idx1.long().clamp(0, x2d.shape[0] - 1)]).reshape(W, Cin, 1, 1)
         safe = lambda s: torch.where(s == 0, torch.ones_like(s), s)
         # z = s (c . y) + t: d t sums d z over EVERY channel's pixels (a masked channel's z = t still feeds the ReLU); d s only sees active channels

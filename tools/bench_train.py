@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """One training step (forward + backward, frozen BatchNorm statistics, Gumbel-hard masks, sparsity criterion) of a full-width LAUD-ResNet on the row
-kernels (laudnet_amd.training.train_forward) beside the oracle's dense emulation run through PyTorch on the same GPU.  One JSON line per workload.
-usage: tools/bench_train.py [--batch 32] [--steps 5] [--workloads layer,spatial,channel]"""
+kernels (laudnet_amd.training.train_forward) beside the oracle's dense emulation run through PyTorch on the same GPU.  One JSON line per workload;
+it names the weight-gradient path (`wgrad_kernel`: laudnet_amd.training.USE_WGRAD_KERNEL, env LDN_WGRAD=0 | 1) and the peak memory of ONE step on
+the row kernels (`peak_MiB_one_step`: torch.cuda.max_memory_allocated of a step of its own after the timed ones).
+usage: [LDN_WGRAD=0] tools/bench_train.py [--batch 32] [--steps 5] [--warmup 2] [--workloads layer,spatial,channel] [--no-reference]"""
 import argparse
 import json
 import os
@@ -16,7 +18,7 @@ import torch  # noqa: E402
 import bench  # noqa: E402
 import laudnet_amd  # noqa: E402
 from fill import fill_state_dict, seeded_randn  # noqa: E402
-from laudnet_amd import ops  # noqa: E402
+from laudnet_amd import ops, training  # noqa: E402
 from laudnet_amd.training import prepare_for_training, train_forward  # noqa: E402
 from oracle import torch_ref as TR  # noqa: E402
 
@@ -25,6 +27,8 @@ ap.add_argument("--batch", type=int, default=32)
 ap.add_argument("--steps", type=int, default=5)
 ap.add_argument("--workloads", default="layer,spatial,channel")
 ap.add_argument("--math", default="bf16x3")
+ap.add_argument("--warmup", type=int, default=2)
+ap.add_argument("--no-reference", action="store_true", help="time the row kernels only (no dense emulation through PyTorch, no speedup)")
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
 ops.set_math_mode(args.math)
@@ -59,9 +63,12 @@ for w in args.workloads.split(","):
         return out
 
     res = {}
-    for name, fwd, model in (("hip_row_kernels", lambda: train_forward(hip, x, 1.0), hip), ("dense_emulation_pytorch", lambda: ref(x, 1.0), ref)):
+    legs = [("hip_row_kernels", lambda: train_forward(hip, x, 1.0), hip)]
+    if not args.no_reference:
+        legs.append(("dense_emulation_pytorch", lambda: ref(x, 1.0), ref))
+    for name, fwd, model in legs:
         torch.manual_seed(3)
-        for _ in range(2):
+        for _ in range(args.warmup):
             out = step(fwd, model)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -69,8 +76,17 @@ for w in args.workloads.split(","):
             out = step(fwd, model)
         torch.cuda.synchronize()
         res[name] = {"ms_per_step": 1e3 * (time.perf_counter() - t0) / args.steps, "mean_block_flops_ratio": round(float(out[5].detach().mean()), 4)}
-    res["speedup"] = res["dense_emulation_pytorch"]["ms_per_step"] / res["hip_row_kernels"]["ms_per_step"]
-    print(json.dumps({"workload": wl["name"], "batch": args.batch, "steps": args.steps, "math": args.math,
+        if name == "hip_row_kernels":      # one more step, alone between a reset and a read of the allocator's high-water mark
+            out = None
+            for p in model.parameters():
+                p.grad = None
+            torch.cuda.reset_peak_memory_stats()
+            step(fwd, model)
+            torch.cuda.synchronize()
+            res[name]["peak_MiB_one_step"] = round(torch.cuda.max_memory_allocated() / 2 ** 20, 1)
+    if not args.no_reference:
+        res["speedup"] = res["dense_emulation_pytorch"]["ms_per_step"] / res["hip_row_kernels"]["ms_per_step"]
+    print(json.dumps({"workload": wl["name"], "batch": args.batch, "steps": args.steps, "math": args.math, "wgrad_kernel": training.USE_WGRAD_KERNEL,
                       "what": "one training step = forward + backward of every parameter, frozen BatchNorm statistics, Gumbel-hard masks", **res}), flush=True)
     del hip, ref
     torch.cuda.empty_cache()
