@@ -24,6 +24,7 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import LdnError
+from ._shared import dense_index, identity_residual, rows_hint, sparse_flops, strided_rows
 from .laud_resnet import (Masker_channel_conv_linear, Masker_channel_MLP, Masker_spatial, ExpandMask, _PrepCache,
                           _eval_only, _fold_bn)
 
@@ -194,16 +195,6 @@ class ResBottleneckBlock(_PrepCache):
                 self._cache_store((w.to(device), sp.to(device), tp.to(device)))
         return self._prep
 
-    def _ds_rows(self, B, Hi, Wi, Ho, Wo, s, dev):
-        key = (B, Hi, Wi, s, str(dev))
-        cache = self.__dict__.setdefault("_ds_cache", {})
-        if key not in cache:
-            b = torch.arange(B, device=dev).view(B, 1, 1)
-            y = torch.arange(Ho, device=dev).view(1, Ho, 1) * s
-            xx = torch.arange(Wo, device=dev).view(1, 1, Wo) * s
-            cache[key] = ((b * Hi + y) * Wi + xx).reshape(-1).to(torch.int32).contiguous()
-        return cache[key]
-
     def flops_terms(self, x_shape):
         """(masker, conv a, conv b, conv c, proj, se) of laud_regnet.py:179-203,286-288 (a counted at the input resolution)."""
         f = self.f
@@ -249,9 +240,7 @@ class ResBottleneckBlock(_PrepCache):
             f.last_carry = (f.masker_spatial.last_work, ix.pre3, getattr(f.masker_spatial.last_work, "ldn_shape_key", None))   # which images this block leaves unchanged, and their channel sums
         x2d = xn.reshape(B * Hi * Wi, Cin)
         w_b = f.w_b
-        hint = getattr(f, "_rows_hint", None)     # row counts of this block's previous forward: tile-width hint of the row kernels
-        if hint is None:
-            hint = f._rows_hint = ops.RowsHint(2)
+        hint = rows_hint(f)     # row counts of this block's previous forward: tile-width hint of the row kernels
         n3, n1 = hint.get(0), hint.get(1)
         hint.update(ix.cnt)
         h_a = torch.empty(ix.cap1, w_b, device=dev, dtype=torch.float32)
@@ -274,13 +263,11 @@ class ResBottleneckBlock(_PrepCache):
             # hides here -- 3.22 -> 3.31 ms per forward: RegNet's launches are 30-70 us, the fork / join and the contention outweigh the overlap)
             wp, sp, tp = self._proj(dev)
             out2d = torch.empty(ix.cap3, cout, device=dev, dtype=torch.float32)
-            ops.conv_rows(x2d, wp, sp, tp, out2d, a_rows=self._ds_rows(B, Hi, Wi, Ho, Wo, self.stride, dev), taps=1,
+            ops.conv_rows(x2d, wp, sp, tp, out2d, a_rows=strided_rows(B, Hi, Wi, Ho, Wo, self.stride, dev), taps=1,
                           m_cap=ix.cap3, relu=2, relu_if_neg=ix.pos3)
             resid = out2d
-        elif inplace:
-            resid = out2d = x2d
         else:
-            resid, out2d = x2d, torch.relu(x2d)
+            resid, out2d = identity_residual(x2d, inplace)
         if gate is not None:
             ops.conv_rows_gated(h_b, p["wc"], p["sc"], p["tc"], out2d, gate, Ho * Wo, m_count=ix.cnt[0:1], m_cap=ix.cap3, relu=1,
                                 out_rows=ix.idx3, residual2d=resid)
@@ -341,7 +328,7 @@ class ResBottleneckBlock(_PrepCache):
             ops.se_packed(h_b2d, self._img_prefix(B, Ho * Wo, dev), p["se_w1"], p["se_b1"], p["se_w2"], p["se_b2"], Ho * Wo,
                           ch_idx=idx, ch_cnt=cnt)
         else:
-            dense = self._dense_index(B, Ho, Wo, dev)                          # every pixel: the neighbour table of conv b
+            dense = dense_index(B, Ho, Wo, s, dev)                            # every pixel: the neighbour table of conv b
             h_a = torch.empty(B * Hi * Wi, w_b, device=dev, dtype=torch.float32)
             ops.conv_rows(x2d, p["wa"], p["sa"], p["ta"], h_a, taps=1, m_cap=B * Hi * Wi)
             h_b2d = torch.empty(B * Ho * Wo, w_b, device=dev, dtype=torch.float32)
@@ -350,15 +337,13 @@ class ResBottleneckBlock(_PrepCache):
         if self.proj is not None:
             wp, sp, tp = self._proj(dev)
             out2d = torch.empty(ix.cap3, cout, device=dev, dtype=torch.float32)
-            ds_rows = self._ds_rows(B, Hi, Wi, Ho, Wo, s, dev)
+            ds_rows = strided_rows(B, Hi, Wi, Ho, Wo, s, dev)
             for ig, cs_ in groups:   # ReLU directly where the (pixel, group) is inactive: no branch output is added there
                 ops.conv_rows(x2d, wp[cs_], sp[cs_], tp[cs_], out2d[:, cs_], a_rows=ds_rows, taps=1, m_cap=ix.cap3, relu=2,
                               relu_if_neg=ig.pos3)
             resid = out2d
-        elif inplace:
-            resid = out2d = x2d
         else:
-            resid, out2d = x2d, torch.relu(x2d)
+            resid, out2d = identity_residual(x2d, inplace)
         if both:   # c: gathered input channels (per image) x packed active pixels (per output-channel group)
             for g, (ig, cs_) in enumerate(groups):
                 if G == 1:
@@ -379,13 +364,6 @@ class ResBottleneckBlock(_PrepCache):
             cs = None if defer_stats else torch.ones(1, device=dev)
         f.last_spatial_mask = patch
         return ops.from_nhwc(out2d.view(B, Ho, Wo, cout)), (ix.stats if cs is None else torch.cat((ix.stats, cs)))
-
-    def _dense_index(self, B, Ho, Wo, dev):
-        key = (B, Ho, Wo, self.stride, str(dev))
-        cache = self.__dict__.setdefault("_dense_ix_cache", {})
-        if key not in cache:
-            cache[key] = ops.mask_to_index(torch.ones(B, 1, 1, device=dev), Ho, Wo, self.stride)
-        return cache[key]
 
     def _run_channel(self, x, inplace):
         """dyn_mode 'channel' (laud_regnet.py:160-170,182-189): the mask multiplies the outputs of a and b AFTER conv+BN+ReLU, so
@@ -505,7 +483,7 @@ class BlockParams:
 
 class LAD_RegNet(nn.Module):
     """laud_regnet.py:468-672."""
-    use_layer_carry = __import__("os").environ.get("LDN_LAYER_CARRY", "1") != "0"
+    use_layer_carry = os.environ.get("LDN_LAYER_CARRY", "1") != "0"
 
     def __init__(self, block_params, num_classes=1000, stem_width=32, stem_type=None, block_type=None, norm_layer=None,
                  activation=None, input_size=224, spatial_mask_channel_group=[1, 1, 1, 1],
@@ -633,21 +611,9 @@ class LAD_RegNet(nn.Module):
 
     def flops_from_sparsities(self, x_shape, s3, s2, s1, cs):
         """(flops_perc [n_blocks], flops) from per-block sparsities; see laud_resnet.ResNet.flops_from_sparsities."""
-        flat = lambda v: torch.cat([t.reshape(-1) for t in v]) if isinstance(v, (list, tuple)) else v
-        s3, s2, s1, cs = (flat(v).double() for v in (s3, s2, s1, cs))   # fp64 inside: the result does not depend on summation order
-        key = (str(s3.device), tuple(x_shape[1:]))
-        if getattr(self, "_terms_key", None) != key:
-            terms, static = self.flops_table(x_shape)
-            self._terms_key = key
-            self._terms = torch.tensor(terms, dtype=torch.float64, device=s3.device)      # [n_blocks, 6]
-            self._static_flops = float(static)
-        tm = self._terms
-        sparse = tm[:, 0] + tm[:, 1] * cs * s1
-        sparse = sparse + tm[:, 2] * cs ** 2 * s2
-        sparse = sparse + tm[:, 3] * cs * s3
-        sparse = sparse + tm[:, 4]
+        tm, static, sparse = sparse_flops(self, x_shape, s3, s2, s1, cs)   # tm [n_blocks, 6]: the SE column is spent whatever the masks
         perc = sparse / tm[:, :5].sum(dim=1)
-        flops = sparse.sum() + tm[:, 5].sum() + self._static_flops
+        flops = sparse.sum() + tm[:, 5].sum() + static
         return perc.float(), flops.float()
 
     def get_optim_policies(self):

@@ -27,6 +27,8 @@ import torch.nn.functional as F
 
 from . import ops
 from ._lib import LdnError
+from ._shared import (channel_constants, dense_channel_convs, dense_index, denoms, flops_constants, identity_residual, rows_hint,
+                      sparse_flops, strided_rows)
 
 
 def _pair(v):
@@ -64,7 +66,7 @@ _SIDE_STREAMS = {}
 # one-workgroup-per-CU kernels of round 2 the overlap only stole their CUs (inline 1.3 % faster: 16.05 vs 16.27 ms).  Round 4: the
 # first blocks of stages 2-4 are k_head + one strided tail launch whose conv2 phase leaves the memory pipe idle, and the projection
 # (k_dense) fills it: 12.16-12.19 -> 12.09 ms, four interleaved runs on one box.  LDN_SIDE_STREAM=0 runs it inline.
-_USE_SIDE_STREAM = __import__("os").environ.get("LDN_SIDE_STREAM", "1") == "1"
+_USE_SIDE_STREAM = os.environ.get("LDN_SIDE_STREAM", "1") == "1"
 
 
 def _side_stream(dev):
@@ -73,6 +75,27 @@ def _side_stream(dev):
     if key not in _SIDE_STREAMS:
         _SIDE_STREAMS[key] = torch.cuda.Stream(device=dev)
     return _SIDE_STREAMS[key]
+
+
+def _fork(dev):
+    """-> the side stream, made to wait for what is queued on the current one.  Work that only depends on what is queued so far runs
+    under `with torch.cuda.stream(side)` next to the main chain (a fork / join that hipGraph capture records as such)."""
+    side = _side_stream(dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    return side
+
+
+def _join(side, dev):
+    """The current stream waits for the side stream's work (side None: nothing was forked)."""
+    if side is not None:
+        torch.cuda.current_stream(dev).wait_stream(side)
+
+
+def _takes_gap(blk):
+    """Can this block's channel masker decide from the GAP partials its producer leaves (a channel-mode block, no forced mask, a
+    masker that accepts the fused GAP)?"""
+    return (blk is not None and blk.dyn_mode == "channel" and blk.forced_channel_mask is None
+            and getattr(blk.masker_channel, "accepts_fused_gap", False))
 
 
 def _after_load(module, _incompatible_keys):
@@ -152,11 +175,7 @@ class Masker_spatial(_PrepCache):
         """carry = (work, prefix) of the previous layer-skip block on the same residual stream (ldn_spatial_masker): the images that
         block skipped are unchanged, their channel sums are reused.  self.last_work = this call's sums (None unless mask_size 1)."""
         _eval_only(self, x)
-        if not self._cache_valid():
-            with torch.no_grad():
-                self._cache_store((self.conv.weight.detach().reshape(self.conv.weight.shape[0], -1).float().contiguous(),
-                                   self.conv.bias.detach().float().contiguous()))
-        w, b = self._prep
+        w, b = self._wb()
         mask, logits, self.last_work = ops.spatial_masker(ops.as_nhwc(x), w, b, self.mask_channel_group, self.mask_size, want_logits,
                                                           carry=carry, return_work=True)
         out = (mask, mask.mean(), self.flops_for(x))
@@ -196,11 +215,7 @@ class Masker_spatial(_PrepCache):
         """The mask alone (what the blocks of the HIP path consume; their sparsities come from ldn_mask_to_index): forward()
         without the mean over the mask, a reduction launch per block."""
         _eval_only(self, x)
-        if not self._cache_valid():
-            with torch.no_grad():
-                self._cache_store((self.conv.weight.detach().reshape(self.conv.weight.shape[0], -1).float().contiguous(),
-                                   self.conv.bias.detach().float().contiguous()))
-        w, b = self._prep
+        w, b = self._wb()
         mask, _, self.last_work = ops.spatial_masker(ops.as_nhwc(x), w, b, self.mask_channel_group, self.mask_size, False,
                                                      carry=carry, return_work=True)
         return mask
@@ -399,22 +414,19 @@ class Bottleneck(_PrepCache):
             p["w1"] = self.conv1.weight.detach().reshape(W, 1, -1).float().contiguous()
             w2 = self.conv2.weight.detach().float()
             w3 = self.conv3.weight.detach().float().reshape(-1, W)
-            if self.dyn_mode in ("channel", "both"):
-                # k-major [taps][cin][cout]: the per-image input-channel gather becomes a ROW gather
-                p["w2"] = w2.permute(2, 3, 1, 0).reshape(9, W, W).contiguous()
-                p["w3"] = w3.t().reshape(1, W, -1).contiguous()
-            else:
-                p["w2"] = w2.permute(0, 2, 3, 1).reshape(W, 9, W).contiguous()
-                p["w3"] = w3.reshape(-1, 1, W).contiguous()
             p["s1"], p["t1"] = _fold_bn(self.bn1)
             p["s2"], p["t2"] = _fold_bn(self.bn2)
             p["s3"], p["t3"] = _fold_bn(self.bn3)
             # conv3 carries bn3's scale in its weights and is called with scale=None: the kernel then starts its
-            # accumulators from the residual tile (include/ldn_hip.h, "scale == NULL")
-            w3s = w3 * p["s3"].view(-1, 1)
+            # accumulators from the residual tile (include/ldn_hip.h, "scale == NULL").  w3s [cout, W] (n-major) is what every
+            # layout of conv3's weights is derived from (w3, w3_nk, tail_weights)
+            w3s = p["w3s"] = w3 * p["s3"].view(-1, 1)
             if self.dyn_mode in ("channel", "both"):
+                # k-major [taps][cin][cout]: the per-image input-channel gather becomes a ROW gather
+                p["w2"] = w2.permute(2, 3, 1, 0).reshape(9, W, W).contiguous()
                 p["w3"] = w3s.t().reshape(1, W, -1).contiguous()
             else:
+                p["w2"] = w2.permute(0, 2, 3, 1).reshape(W, 9, W).contiguous()
                 p["w3"] = w3s.reshape(-1, 1, W).contiguous()
             if self.downsample is not None:
                 dconv, dbn = self.downsample[0], self.downsample[1]
@@ -422,75 +434,44 @@ class Bottleneck(_PrepCache):
                 p["sd"], p["td"] = _fold_bn(dbn)
                 p["ds_stride"] = dconv.stride[0]
             if self.dyn_mode in ("channel", "both"):
-                # Channel algebra: a masked channel k of conv1's output is the CONSTANT
-                # c1[k] = relu(t1[k]) (mask applied before BN, laud_resnet.py:116-118).  Writing
-                # h1 = u1 + c1 with u1 = 0 on masked channels makes conv2 = W2[A,A] (*) u1 + (W2 (*) c1),
-                # whose second term does not depend on the image: 16 border classes x W shifts.
-                c1 = torch.relu(p["t1"])
-                c2 = torch.relu(p["t2"])
-                wc = torch.einsum("okyx,k->oyx", self.conv2.weight.detach().float(), c1)  # [W,3,3]
-                tab = torch.empty(16, W, device=wc.device)
-                for cls in range(16):
-                    rb, cb = cls // 4, cls % 4
-                    ys = [ky for ky in range(3) if not ((ky == 0 and rb & 1) or (ky == 2 and rb & 2))]
-                    xs = [kx for kx in range(3) if not ((kx == 0 and cb & 1) or (kx == 2 and cb & 2))]
-                    v = wc[:, ys][:, :, xs].sum(dim=(1, 2))
-                    tab[cls] = p["t2"] + p["s2"] * v
-                p["c1"], p["c2"], p["t2_tab"] = c1.contiguous(), c2.contiguous(), tab.contiguous()
-                bias3 = self.conv3.weight.detach().reshape(-1, W).float() @ c2
-                p["t3c"] = (p["t3"] + p["s3"] * bias3).contiguous()
+                p["c1"], p["c2"], p["t2_tab"], p["t3c"] = channel_constants(w2, w3, p["s2"], p["t2"], p["t1"], p["s3"], p["t3"])
             self._cache_store({k: (v.to(device) if torch.is_tensor(v) else v) for k, v in p.items()})
         return self._prep
 
     # ---- execution ----------------------------------------------------------------------------
-    def _dense_ix(self, B, Ho, Wo, dev):
-        """Index lists of an all-active batch (every pixel of every image), cached per shape: the packed-row machinery of the
-        spatial mode then is a dense convolution whose M tiles span images."""
-        key = (B, Ho, Wo, self.stride, str(dev))
-        cache = self.__dict__.setdefault("_dense_ix_cache", {})
-        if key not in cache:
-            cache[key] = ops.mask_to_index(torch.ones(B, 1, 1, device=dev), Ho, Wo, self.stride)
-        return cache[key]
+    def _channel_lists(self, x, gap_in=None):
+        """The block's ONE call of its channel masker -> (mask [B,G], ch_idx, ch_cnt [B]).  gap_in: the GAP partials the producing
+        conv's epilogue left, for a masker that accepts them (it then needs no pass over x)."""
+        mk, gran = self.masker_channel, self.channel_dyn_granularity
+        if gap_in is not None and getattr(mk, "accepts_fused_gap", False):
+            return mk.lists(x, gran, mask_in=self.forced_channel_mask, gap=gap_in)[:3]
+        return mk.lists(x, gran, mask_in=self.forced_channel_mask)[:3]
+
+    def _finish_channel(self, out, mask, cnt, gap_out):
+        self.last_channel_mask = mask       # kept for parity tooling (bench/tests feed it to the oracle)
+        self.last_gap = gap_out             # the GAP partials of `out` for the next block's masker (None: not asked for / not left)
+        self.last_channel_cnt = cnt         # [B] active channels per image: mean(mask) = cnt.sum() / (B * width)
+        return ops.from_nhwc(out), mask
 
     def _run_channel_dense(self, x, p, gap_in=None):
         """Channel mode without gathers: conv1/conv2 run over all channels with shared (n-major) weights on row tiles that
         span images, their outputs u = relu(bn(.)) - c are zeroed on the masked channels of each image (exactly what the
-        gathered form stores / skips), conv3 reads the zero-filled u2.  Same channel algebra, same results."""
+        gathered form stores / skips; _shared.dense_channel_convs), conv3 reads the zero-filled u2.  Same channel algebra, same results."""
         B, Cin, Hi, Wi = x.shape
         W, gran = self.width, self.channel_dyn_granularity
         Ho, Wo = (Hi - 1) // self.stride + 1, (Wi - 1) // self.stride + 1
         xn = ops.as_nhwc(x)
-        if gap_in is not None and getattr(self.masker_channel, "accepts_fused_gap", False):   # GAP partials left by the producer
-            mask, _, cnt, _ = self.masker_channel.lists(x, gran, mask_in=self.forced_channel_mask, gap=gap_in)
-        else:
-            mask, _, cnt, _ = self.masker_channel.lists(x, gran, mask_in=self.forced_channel_mask)
-        # [B,1,W]: every group's decision repeated over its gran channels (one small copy; repeat_interleave is a 12 us index kernel)
-        chm = (mask.unsqueeze(2).expand(-1, -1, gran).reshape(mask.shape[0], 1, -1) if gran > 1 else mask.unsqueeze(1))
+        mask, _, cnt = self._channel_lists(x, gap_in)
+        # [B,W]: every group's decision repeated over its gran channels (one small copy; repeat_interleave is a 12 us index kernel)
+        chm2d = (mask.unsqueeze(2).expand(-1, -1, gran).reshape(B, W) if gran > 1 else mask).contiguous()
         dev = x.device
         if "w2_nk" not in p:
             with torch.no_grad():
                 p["w2_nk"] = self.conv2.weight.detach().float().permute(0, 2, 3, 1).reshape(W, 9, W).contiguous().to(dev)
-                p["w3_nk"] = (self.conv3.weight.detach().float().reshape(-1, W) * p["s3"].view(-1, 1).to(self.conv3.weight.device)
-                              ).reshape(-1, 1, W).contiguous().to(dev)
-        ix = self._dense_ix(B, Ho, Wo, dev)
-        x2d = xn.reshape(B * Hi * Wi, Cin)
-        fused_mask = ops.dense_kernel_ok() and Cin % 32 == 0 and W % 32 == 0
-        chm2d = chm.reshape(B, W).contiguous()
-        h1 = torch.empty(ix.cap1, W, device=dev, dtype=torch.float32)
-        if fused_mask:   # k_dense: the per-image channel mask and the post-ReLU constant are epilogue terms (no pass over h1)
-            ops.conv_rows(x2d, p["w1"], p["s1"], p["t1"], h1, taps=1, m_cap=ix.cap1, relu=1, post_sub=p["c1"], chan_mask=chm2d,
-                          rows_per_image=Hi * Wi)
-        else:
-            ops.conv_packed(x2d, p["w1"], p["s1"], p["t1"], h1, taps=1, m_cap=ix.cap1, post_sub=p["c1"], relu=1)
-            h1.view(B, -1, W).mul_(chm)
-        h2 = torch.empty(ix.cap3, W, device=dev, dtype=torch.float32)
-        if fused_mask and 9 in ops.DENSE_TAPS and ops.DENSE_CHANNEL_3X3:
-            ops.conv_rows(h1, p["w2_nk"], p["s2"], p["t2_tab"], h2, a_rows=ix.nbr, taps=9, m_cap=ix.cap3, pix_map=ix.idx3,
-                          geom=(Hi, Wi, Ho, Wo, self.stride), post_sub=p["c2"], relu=1, chan_mask=chm2d, rows_per_image=Ho * Wo)
-        else:
-            ops.conv_packed(h1, p["w2_nk"], p["s2"], p["t2_tab"], h2, a_map=ix.nbr, taps=9, m_cap=ix.cap3, pix_map=ix.idx3,
-                            geom=(Hi, Wi, Ho, Wo, self.stride), post_sub=p["c2"], relu=1)
-            h2.view(B, -1, W).mul_(chm)
+                p["w3_nk"] = p["w3s"].reshape(-1, 1, W)
+        ix = dense_index(B, Ho, Wo, self.stride, dev)
+        _, h2 = dense_channel_convs(xn.reshape(B * Hi * Wi, Cin), B, (Hi, Wi, Ho, Wo, self.stride), p["w1"], p["w2_nk"], p["s1"], p["t1"],
+                                    p["c1"], p["s2"], p["t2_tab"], p["c2"], chm2d, ix)
         cout = p["w3_nk"].shape[0]
         if self.downsample is not None:
             # (round 6: the projection on the side stream next to conv1 / conv2, as the gathered execution below does, was measured here and does
@@ -503,10 +484,7 @@ class Bottleneck(_PrepCache):
             out = xn if self._inplace else torch.empty_like(xn)
         ops.conv_rows(h2, p["w3_nk"], None, p["t3c"], out.view(B * Ho * Wo, cout), taps=1, m_cap=ix.cap3, relu=1,
                       residual2d=identity.view(B * Ho * Wo, cout))
-        self.last_channel_mask = mask
-        self.last_gap = None
-        self.last_channel_cnt = cnt
-        return ops.from_nhwc(out), mask
+        return self._finish_channel(out, mask, cnt, None)
 
     use_fused_head = True    # conv1 on k_head (False: the general ldn_conv_image with out_format 1)
     fused_head_widths = tuple(int(t) for t in os.environ.get("LDN_HEAD_WIDTHS", "64,128,256").split(","))   # ... for these widths when a block runs on its own (with the pipelined fragment reads k_head is ahead at every width: 13.73 -> 13.62 ms)
@@ -539,42 +517,27 @@ class Bottleneck(_PrepCache):
 
     def _run_channel_smallmap(self, x, p, gap_in=None, want_gap=False):
         B, Cin, Hi, Wi = x.shape
-        gran = self.channel_dyn_granularity
         xn = ops.as_nhwc(x)
-        if gap_in is not None and getattr(self.masker_channel, "accepts_fused_gap", False):
-            mask, idx, cnt, _ = self.masker_channel.lists(x, gran, mask_in=self.forced_channel_mask, gap=gap_in)
-        else:
-            mask, idx, cnt, _ = self.masker_channel.lists(x, gran, mask_in=self.forced_channel_mask)
+        mask, idx, cnt = self._channel_lists(x, gap_in)
         w2p, w3p = self.tail_weights(p)
         out = xn if self._inplace else torch.empty_like(xn)
         gap_out = torch.empty(B, 2, Cin, device=x.device, dtype=torch.float32) if want_gap else None
         ops.bottleneck_smallmap(xn, p["w1s"], w2p, w3p, idx, cnt, p["s1"], p["t1"], p["c1"], p["s2"], p["t2_tab"], p["c2"], p["t3c"], out,
                                 residual=xn, colsum=gap_out)
-        self.last_channel_mask = mask
-        self.last_gap = gap_out
-        self.last_channel_cnt = cnt
-        return ops.from_nhwc(out), mask
+        return self._finish_channel(out, mask, cnt, gap_out)
 
     def tail_weights(self, p):
         """conv2 / conv3 weights in the pre-split pair-interleaved layouts of ldn_bottleneck_tail (built once, cached with the
         other folded parameters).  In the fp32 math mode: their fp32 twins (ldn_bottleneck_*_f32), kept under their own keys."""
-        if ops.get_math_mode() == "fp32":
-            if "w2p32" not in p:
-                with torch.no_grad():
-                    dev = p["s3"].device
-                    p["w2p32"] = ops.pack_w2_pairs(self.conv2.weight.detach().float().to(dev), f32=True)
-                    w3 = self.conv3.weight.detach().float().reshape(-1, self.width).to(dev) * p["s3"].view(-1, 1)
-                    p["w3p32"] = ops.pack_w3_pairs(w3, f32=True)
-                    p["w1s32"] = ops.pack_w1_split(self.conv1.weight.detach().float().reshape(self.width, -1).to(dev), f32=True)
-            return p["w2p32"], p["w3p32"]
-        if "w2p" not in p:
+        f32 = ops.get_math_mode() == "fp32"
+        k2, k3, k1 = ("w2p32", "w3p32", "w1s32") if f32 else ("w2p", "w3p", "w1s")
+        if k2 not in p:
             with torch.no_grad():
                 dev = p["s3"].device
-                p["w2p"] = ops.pack_w2_pairs(self.conv2.weight.detach().float().to(dev))
-                w3 = self.conv3.weight.detach().float().reshape(-1, self.width).to(dev) * p["s3"].view(-1, 1)
-                p["w3p"] = ops.pack_w3_pairs(w3)
-                p["w1s"] = ops.pack_w1_split(self.conv1.weight.detach().float().reshape(self.width, -1).to(dev))
-        return p["w2p"], p["w3p"]
+                p[k2] = ops.pack_w2_pairs(self.conv2.weight.detach().float().to(dev), f32=f32)
+                p[k3] = ops.pack_w3_pairs(p["w3s"], f32=f32)
+                p[k1] = ops.pack_w1_split(self.conv1.weight.detach().float().reshape(self.width, -1).to(dev), f32=f32)
+        return p[k2], p[k3]
 
     @staticmethod
     def _w1s_key():
@@ -588,7 +551,7 @@ class Bottleneck(_PrepCache):
         if Ho * Wo < 96 or (ops.dense_kernel_ok() and Cin % 32 == 0 and cout % 32 == 0):
             # one list of strided pixel rows over the batch (k_dense in bf16x3 mode: pre-split shared weights, 256-row tiles)
             ops.conv_rows(xn.reshape(B * Hi * Wi, Cin), p["wd"], p["sd"], p["td"], identity.view(B * Ho * Wo, cout), taps=1,
-                          m_cap=B * Ho * Wo, a_rows=self._ds_rows(B, Hi, Wi, Ho, Wo, p["ds_stride"], xn.device), relu=0)
+                          m_cap=B * Ho * Wo, a_rows=strided_rows(B, Hi, Wi, Ho, Wo, p["ds_stride"], xn.device), relu=0)
         else:
             ops.conv_image(xn, p["wd"], p["sd"], p["td"], identity, stride=p["ds_stride"], relu=0)
 
@@ -607,10 +570,7 @@ class Bottleneck(_PrepCache):
         if dense_ok and (self.channel_exec == "dense" or (self.channel_exec == "auto" and Ho * Wo <= 64)):
             return self._run_channel_dense(x, p, gap_in)
         xn = ops.as_nhwc(x)
-        if gap_in is not None and getattr(self.masker_channel, "accepts_fused_gap", False):
-            mask, idx, cnt, _ = self.masker_channel.lists(x, gran, mask_in=self.forced_channel_mask, gap=gap_in)
-        else:
-            mask, idx, cnt, _ = self.masker_channel.lists(x, gran, mask_in=self.forced_channel_mask)
+        mask, idx, cnt = self._channel_lists(x, gap_in)
         dev = x.device
         cout = p["w3"].shape[2]
         side = None
@@ -631,21 +591,13 @@ class Bottleneck(_PrepCache):
             ops.bottleneck_head(xn, p["w1s"], idx, cnt, p["s1"], p["t1"], p["c1"], h1, x_split=xs)
             gap_out = (torch.empty(B, ops.bottleneck_tail_splits(Hi, Wi, W, 1), cout, device=dev, dtype=torch.float32) if want_gap else None)
             ops.bottleneck_tail_proj(h1, w2p, w3p, idx, cnt, p["s2"], p["t2_tab"], p["c2"], p["t3cd"], xs, p["wdp"], out, colsum=gap_out)
-            self.last_channel_mask = mask
-            self.last_gap = gap_out
-            self.last_channel_cnt = cnt
-            return ops.from_nhwc(out), mask
+            return self._finish_channel(out, mask, cnt, gap_out)
         if self.downsample is not None:
             # the projection shortcut only depends on x: it runs on a side stream next to conv1 / conv2 and is joined
-            # before conv3 (a fork/join that hipGraph capture records as such)
+            # before conv3 (LDN_SIDE_STREAM=0: inline -- torch.cuda.stream(None) is a no-op)
             identity = torch.empty(B, Ho, Wo, cout, device=dev, dtype=torch.float32)
-            if _USE_SIDE_STREAM:
-                cur = torch.cuda.current_stream(dev)
-                side = _side_stream(dev)
-                side.wait_stream(cur)
-                with torch.cuda.stream(side):
-                    self._shortcut(xn, p, identity)
-            else:
+            side = _fork(dev) if _USE_SIDE_STREAM else None
+            with torch.cuda.stream(side):
                 self._shortcut(xn, p, identity)
             out = identity
         else:
@@ -664,29 +616,21 @@ class Bottleneck(_PrepCache):
                 ops.bottleneck_head(xn, p[self._w1s_key()], idx, cnt, p["s1"], p["t1"], p["c1"], h1)
             else:
                 ops.conv_image(xn, p["w1"], p["s1"], p["t1"], h1, n_idx=idx, n_cnt=cnt, post_sub=p["c1"], relu=1, out_split=True)
-            if side is not None:
-                torch.cuda.current_stream(dev).wait_stream(side)
+            _join(side, dev)
             gap_out = (torch.empty(B, ops.bottleneck_tail_splits(Hi, Wi, W, self.stride), cout, device=dev, dtype=torch.float32)
                        if want_gap else None)
             ops.bottleneck_tail(h1, w2p, w3p, idx, cnt, p["s2"], p["t2_tab"], p["c2"], p["t3c"], out, residual=identity,
                                 colsum=gap_out, stride=self.stride)
-            self.last_channel_mask = mask
-            self.last_gap = gap_out
-            self.last_channel_cnt = cnt
-            return ops.from_nhwc(out), mask
+            return self._finish_channel(out, mask, cnt, gap_out)
         ops.conv_image(xn, p["w1"], p["s1"], p["t1"], h1, n_idx=idx, n_cnt=cnt, post_sub=p["c1"], relu=1)
         h2 = torch.empty(B, Ho, Wo, W, device=dev, dtype=torch.float32)
         ops.conv_image(h1, p["w2"], p["s2"], p["t2_tab"], h2, ksize=3, stride=self.stride, k_idx=idx, k_cnt=cnt,
                        kgran=gran, n_idx=idx, n_cnt=cnt, post_sub=p["c2"], relu=1)
-        if side is not None:
-            torch.cuda.current_stream(dev).wait_stream(side)
+        _join(side, dev)
         gap_out = torch.empty(B, (Ho * Wo + 31) // 32, cout, device=dev, dtype=torch.float32) if want_gap else None
         ops.conv_image(h2, p["w3"], None, p["t3c"], out, k_idx=idx, k_cnt=cnt, kgran=gran, relu=1,
                        residual=identity, colsum=gap_out)
-        self.last_channel_mask = mask       # kept for parity tooling (bench/tests feed it to the oracle)
-        self.last_gap = gap_out
-        self.last_channel_cnt = cnt         # [B] active channels per image: mean(mask) = cnt.sum() / (B * width)
-        return ops.from_nhwc(out), mask
+        return self._finish_channel(out, mask, cnt, gap_out)
 
     use_fused_spatial_masker = os.environ.get("LDN_FUSED_SPATIAL_MASKER", "1") != "0"   # class-level switch (A/B, tests)
 
@@ -700,12 +644,18 @@ class Bottleneck(_PrepCache):
                 and self.downsample is None and self.stride == 1 and self._inplace and cout % 128 == 0 and self.width % 8 == 0
                 and ops.dense_kernel_ok()):
             return None
-        S = ms.mask_size
+        return self._cell_grid(Hi, Wi, (4, 16), (Ho, Wo), 1)
+
+    def _cell_grid(self, H, W, cells, plan_hw, stride):
+        """S of the S x S grid of cells on an H x W map (None: there is none): layer skip (mask_size 1): a tiling of the square map by
+        4x4 or 2x2 pixel tiles; else the masker's own even patch grid when a patch has one of the pixel counts in `cells` and
+        ldn_mask_plan can build the lists of the plan_hw output map at this stride."""
+        S = self.masker_spatial.mask_size
         if S == 1:
-            if Hi != Wi:
+            if H != W:
                 return None
-            return Hi // 4 if Hi % 4 == 0 else (Hi // 2 if Hi % 2 == 0 else None)
-        if 1 < S < Hi and Hi % S == 0 and Wi % S == 0 and (Hi // S) * (Wi // S) in (4, 16) and ops.mask_plan_fits(S, S, Ho, Wo, 1):
+            return H // 4 if H % 4 == 0 else (H // 2 if H % 2 == 0 else None)
+        if 1 < S < H and H % S == 0 and W % S == 0 and (H // S) * (W // S) in cells and ops.mask_plan_fits(S, S, plan_hw[0], plan_hw[1], stride):
             return S
         return None
 
@@ -718,14 +668,7 @@ class Bottleneck(_PrepCache):
                 and self.downsample is not None and cout % 128 == 0 and self.width % 8 == 0 and ops.dense_kernel_ok()
                 and ops.get_math_mode() == "bf16x3"):
             return None
-        S = ms.mask_size
-        if S == 1:
-            if Ho != Wo:
-                return None
-            return Ho // 4 if Ho % 4 == 0 else (Ho // 2 if Ho % 2 == 0 else None)
-        if 1 < S < Ho and Ho % S == 0 and Wo % S == 0 and (Ho // S) * (Wo // S) in (4, 16) and ops.mask_plan_fits(S, S, Ho, Wo, self.stride):
-            return S
-        return None
+        return self._cell_grid(Ho, Wo, (4, 16), (Ho, Wo), self.stride)
 
     use_fused_projection_means = os.environ.get("LDN_FUSED_PROJECTION_MEANS", "1") != "0"   # class-level switch (A/B, tests)
 
@@ -754,14 +697,8 @@ class Bottleneck(_PrepCache):
         ms = self.masker_spatial
         if not (self.use_fused_spatial_masker and ms.mask_channel_group == 1 and self.forced_spatial_mask is None and ops.dense_kernel_ok()):
             return None
-        S = ms.mask_size
-        if S == 1:
-            if Hi != Wi:
-                return None
-            return Hi // 4 if Hi % 4 == 0 else (Hi // 2 if Hi % 2 == 0 else None)
-        if 1 < S < Hi and Hi % S == 0 and Wi % S == 0 and (Hi // S) * (Wi // S) in (4, 16, 64) and ops.mask_plan_fits(S, S, Ho, Wo, self.stride):
-            return S            # (64-pixel cells: only as the 2 x 2 groups of a predecessor's 16-pixel cells, see _run_spatial)
-        return None
+        # (64-pixel cells: only as the 2 x 2 groups of a predecessor's 16-pixel cells, see _run_spatial)
+        return self._cell_grid(Hi, Wi, (4, 16, 64), (Ho, Wo), self.stride)
 
     def _run_spatial(self, x, p):
         B, Cin, Hi, Wi = x.shape
@@ -833,9 +770,7 @@ class Bottleneck(_PrepCache):
                 self.last_carry = (ms.last_work, None, key, union.contiguous(), False)   # patch masks: the patches this block touches, every patch's pooled means
         x2d = xn.reshape(B * Hi * Wi, Cin)
         # row counts of the previous forward of THIS block (pinned memory, no synchronisation): the tile-width hint of the row kernels
-        hint = getattr(self, "_rows_hint", None)
-        if hint is None:
-            hint = self._rows_hint = ops.RowsHint(2)
+        hint = rows_hint(self)
         n3, n1 = hint.get(0), hint.get(1)
         hint.update(ix.cnt)
         cout = p["w3"].shape[0]
@@ -852,7 +787,7 @@ class Bottleneck(_PrepCache):
                 ops.conv_rows(x2d, p["wd"], p["sd"], p["td"], out2d, a_rows=src_pm, taps=1, m_cap=ix.cap3, relu=2,
                               relu_if_neg=ix.pos3.view(-1)[out_pm_long].contiguous(), out_rows=out_pm, pool=pool, pool_grid=(gS_ds, gS_ds, Ho, Wo))
             else:
-                ds_rows = self._ds_rows(B, Hi, Wi, Ho, Wo, p["ds_stride"], dev)
+                ds_rows = strided_rows(B, Hi, Wi, Ho, Wo, p["ds_stride"], dev)
                 for ig, _, cs in groups:   # ReLU directly where the (pixel, group) is inactive: no branch output is added there
                     ops.conv_rows(x2d, p["wd"][cs], p["sd"][cs], p["td"][cs], out2d[:, cs], a_rows=ds_rows, taps=1, m_cap=ix.cap3,
                                   relu=2, relu_if_neg=ig.pos3)
@@ -862,9 +797,7 @@ class Bottleneck(_PrepCache):
             # round 6: it only depends on x and the lists -- on the side stream next to conv1 / the 3x3, joined in front of conv3 (as the channel path
             # does; the first block of every stage ran it between the 3x3 and conv3)
             out2d_ds = torch.empty(ix.cap3, cout, device=dev, dtype=torch.float32)
-            cur = torch.cuda.current_stream(dev)
-            side = _side_stream(dev)
-            side.wait_stream(cur)
+            side = _fork(dev)
             with torch.cuda.stream(side):
                 projection(out2d_ds, [(ix, None, slice(0, cout))])
         h1 = torch.empty(ix.cap1, W, device=dev, dtype=torch.float32)
@@ -875,30 +808,17 @@ class Bottleneck(_PrepCache):
         else:
             ops.conv_rows(x2d, p["w1"], p["s1"], p["t1"], h1, a_rows=ix.idx1, taps=1, m_count=ix.cnt[1:2], m_cap=ix.cap1, rows_hint=n1)
             ops.conv_rows(h1, p["w2"], p["s2"], p["t2"], h2, a_rows=ix.nbr, taps=9, m_count=ix.cnt[0:1], m_cap=ix.cap3, rows_hint=n3)
-        if G == 1:
-            groups = [(ix, None, slice(0, cout))]
-        else:
-            if cout % (4 * G) != 0:
-                raise LdnError("HIP path: spatial_mask_channel_group must divide the output channels into multiples of 4")
-            groups = []
-            ar = torch.arange(ix.cap3, device=dev, dtype=torch.int32)
-            for g in range(G):
-                ig = ops.mask_to_index(patch[:, g].contiguous(), Ho, Wo, self.stride)
-                # packed h2 row (union list) of every pixel of this group's list; entries past the device-side count are unused
-                rows = torch.where(ar < ig.cnt[0], ix.pos3[ig.idx3.clamp(0, ix.cap3 - 1).long()], torch.full_like(ar, -1))
-                groups.append((ig, rows.contiguous(), slice(g * (cout // G), (g + 1) * (cout // G))))
+        groups = self._group_lists(patch, ix, Ho, Wo, cout)
         if self.downsample is not None:
             if side is not None:
-                torch.cuda.current_stream(dev).wait_stream(side)
+                _join(side, dev)
                 out2d = out2d_ds
             else:
                 out2d = torch.empty(ix.cap3, cout, device=dev, dtype=torch.float32)
                 projection(out2d, groups)
             resid = out2d
-        elif self._inplace:
-            resid = out2d = x2d          # x >= 0 (post-ReLU) inside the network: inactive pixels pass through
         else:
-            resid, out2d = x2d, torch.relu(x2d)
+            resid, out2d = identity_residual(x2d, self._inplace)
         for ig, rows, cs in groups:
             if ps and (cs.stop - cs.start) % 64 == 0:
                 ops.conv_rows_ps(h2, p["w3"][cs], None, p["t3"][cs], out2d[:, cs], a_presplit=True, a_rows=rows, m_count=ig.cnt[0:1],
@@ -924,7 +844,7 @@ class Bottleneck(_PrepCache):
         G = ms.mask_channel_group
         xn = ops.as_nhwc(x)
         dev = x.device
-        cmask, idx, cnt, _ = self.masker_channel.lists(x, gran, mask_in=self.forced_channel_mask)
+        cmask, idx, cnt = self._channel_lists(x)
         if self.forced_spatial_mask is not None:
             patch = self.forced_spatial_mask.to(device=dev, dtype=torch.float32).contiguous()
         else:
@@ -941,32 +861,21 @@ class Bottleneck(_PrepCache):
                         pix_map=ix.idx3, geom=geom, k_idx=idx, k_cnt=cnt, kgran=gran, n_idx=idx, n_cnt=cnt,
                         post_sub=p["c2"], relu=1)
         cout = p["w3"].shape[2]
-        if G == 1:
-            # (a_map: the packed h2 row of every list entry -- the identity for one group)
-            groups = [(ix, None, slice(0, cout), p["w3"], p["t3c"])]
-        else:
-            if cout % (4 * G) != 0:
-                raise LdnError("HIP path: spatial_mask_channel_group must divide the output channels into multiples of 4")
-            if "w3_groups" not in p or len(p["w3_groups"]) != G:
-                p["w3_groups"] = [p["w3"][:, :, g * (cout // G):(g + 1) * (cout // G)].contiguous() for g in range(G)]
-            groups = []
-            ar = torch.arange(ix.cap3, device=dev, dtype=torch.int32)
-            for g in range(G):
-                ig = ops.mask_to_index(patch[:, g].contiguous(), Ho, Wo, self.stride)
-                rows = torch.where(ar < ig.cnt[0], ix.pos3[ig.idx3.clamp(0, ix.cap3 - 1).long()], torch.full_like(ar, -1))
-                cs = slice(g * (cout // G), (g + 1) * (cout // G))
-                groups.append((ig, rows.contiguous(), cs, p["w3_groups"][g], p["t3c"][cs]))
+        # (rows None = the packed h2 row of every list entry is the identity: one group); on top, every group's slice of conv3's
+        # k-major weights (copied once per module) and of its shift
+        groups = self._group_lists(patch, ix, Ho, Wo, cout)
+        if len(p.get("w3_groups", ())) != G:
+            p["w3_groups"] = [p["w3"]] if G == 1 else [p["w3"][:, :, cs].contiguous() for _, _, cs in groups]
+        groups = [(ig, rows, cs, w3g, p["t3c"][cs]) for (ig, rows, cs), w3g in zip(groups, p["w3_groups"])]
         if self.downsample is not None:
             out2d = torch.empty(ix.cap3, cout, device=dev, dtype=torch.float32)
-            ds_rows = self._ds_rows(B, Hi, Wi, Ho, Wo, p["ds_stride"], dev)
+            ds_rows = strided_rows(B, Hi, Wi, Ho, Wo, p["ds_stride"], dev)
             for ig, _, cs, _, _ in groups:   # ReLU directly where the (pixel, group) is inactive: no branch output is added there
                 ops.conv_rows(x2d, p["wd"][cs], p["sd"][cs], p["td"][cs], out2d[:, cs], a_rows=ds_rows, taps=1, m_cap=ix.cap3,
                               relu=2, relu_if_neg=ig.pos3)
             resid = out2d
-        elif self._inplace:
-            resid = out2d = x2d
         else:
-            resid, out2d = x2d, torch.relu(x2d)
+            resid, out2d = identity_residual(x2d, self._inplace)
         for ig, rows, cs, w3g, t3g in groups:
             ops.conv_packed(h2, w3g, None, t3g, out2d[:, cs], B=B, row_prefix=ig.pre3, m_cap=Ho * Wo, a_map=rows, taps=1,
                             out_map=ig.idx3, k_idx=idx, k_cnt=cnt, kgran=gran, relu=1, residual2d=resid[:, cs])
@@ -984,15 +893,23 @@ class Bottleneck(_PrepCache):
             raise LdnError(f"Bottleneck: a {Hi}x{Wi} input is not a multiple of the block's stride {s} (spatial / layer / both modes)")
         return Hi // s, Wi // s
 
-    def _ds_rows(self, B, Hi, Wi, Ho, Wo, s, dev):
-        key = (B, Hi, Wi, s, str(dev))
-        cache = self.__dict__.setdefault("_ds_cache", {})
-        if key not in cache:
-            b = torch.arange(B, device=dev).view(B, 1, 1)
-            y = torch.arange(Ho, device=dev).view(1, Ho, 1) * s
-            xx = torch.arange(Wo, device=dev).view(1, 1, Wo) * s
-            cache[key] = ((b * Hi + y) * Wi + xx).reshape(-1).to(torch.int32).contiguous()
-        return cache[key]
+    def _group_lists(self, patch, ix, Ho, Wo, cout):
+        """[(IndexSet, packed h2 rows, output-channel slice)] per spatial mask group (models/utils.py:27-33,74-89): group g of the
+        OUTPUT channels has its own pixel mask, conv1 / conv2 live on the union list `ix`, only conv3's scatter is per group.  One
+        group: the union list itself (rows None)."""
+        G = self.masker_spatial.mask_channel_group
+        if G == 1:
+            return [(ix, None, slice(0, cout))]
+        if cout % (4 * G) != 0:
+            raise LdnError("HIP path: spatial_mask_channel_group must divide the output channels into multiples of 4")
+        groups = []
+        ar = torch.arange(ix.cap3, device=patch.device, dtype=torch.int32)
+        for g in range(G):
+            ig = ops.mask_to_index(patch[:, g].contiguous(), Ho, Wo, self.stride)
+            # packed h2 row (union list) of every pixel of this group's list; entries past the device-side count are unused
+            rows = torch.where(ar < ig.cnt[0], ix.pos3[ig.idx3.clamp(0, ix.cap3 - 1).long()], torch.full_like(ar, -1))
+            groups.append((ig, rows.contiguous(), slice(g * (cout // G), (g + 1) * (cout // G))))
+        return groups
 
     def run_dynamic(self, x, gap_in=None, want_gap=False, defer_stats=False, inplace=None):
         """Execute the block on the HIP path.  gap_in / want_gap: fused global-average-pool hand-off between
@@ -1164,8 +1081,7 @@ class ResNet(nn.Module):
         if self._stem_fused_ok(x):
             # one launch: conv 7x7 -> max-pool -> + shift -> ReLU; the full-resolution conv output never exists (ldn_stem_conv_pool)
             first = self.layer1[0]
-            if (self.use_stem_gap and first.dyn_mode == "channel" and first.forced_channel_mask is None and self._tap is None
-                    and getattr(first.masker_channel, "accepts_fused_gap", False)):
+            if self.use_stem_gap and self._tap is None and _takes_gap(first):
                 # ... and leaves the channel sums of its output for the first block's channel masker (no pass over x for its GAP)
                 y, self._stem_gap = ops.stem_conv_pool(ops.as_nhwc(x), self._stem_frag, b, self.conv1.out_channels, want_gap=True)
                 return ops.from_nhwc(y)
@@ -1201,15 +1117,13 @@ class ResNet(nn.Module):
                 stats.extend(run_stats)
                 j += n_run - 1
                 nxt = blocks[j + 1] if j + 1 < len(blocks) else None
-                if not (nxt is not None and nxt.dyn_mode == "channel" and nxt.forced_channel_mask is None
-                        and getattr(nxt.masker_channel, "accepts_fused_gap", False)):
+                if not _takes_gap(nxt):
                     gap = None
                 if stage_outs is not None and j + 1 in ends:
                     stage_outs.append(x)
                 continue
             # a channel-mode block leaves the GAP partials of its output for the next block's MLP masker
-            want_gap = (nxt is not None and blk.dyn_mode == "channel" and nxt.dyn_mode == "channel"
-                        and getattr(nxt.masker_channel, "accepts_fused_gap", False) and nxt.forced_channel_mask is None)
+            want_gap = blk.dyn_mode == "channel" and _takes_gap(nxt)
             if self._tap is not None:     # debug tap (bench / tests): sees every block's input; off by default
                 self._tap(j, blk, x)
             # layer skip: the images the previous block skipped reach this block unchanged -> their channel sums (the masker's global
@@ -1339,21 +1253,9 @@ class ResNet(nn.Module):
     def flops_from_sparsities(self, x_shape, s3, s2, s1, cs):
         """(flops_perc [n_blocks], flops) from per-block sparsities (flat [n_blocks] tensors or per-stage lists).  This is the
         ONLY place the model forms them: forward() calls it, and so does the multi-GPU gather with global-batch sparsities."""
-        flat = lambda v: torch.cat([t.reshape(-1) for t in v]) if isinstance(v, (list, tuple)) else v
-        s3, s2, s1, cs = (flat(v).double() for v in (s3, s2, s1, cs))   # fp64 inside: the result does not depend on summation order
-        key = (str(s3.device), tuple(x_shape[1:]))
-        if getattr(self, "_terms_key", None) != key:
-            terms, static = self.flops_table(x_shape)
-            self._terms_key = key
-            self._terms = torch.tensor(terms, dtype=torch.float64, device=s3.device)   # [n_blocks, 5]
-            self._static_flops = float(static)
-        tm = self._terms
-        sparse = tm[:, 0] + tm[:, 1] * cs * s1
-        sparse = sparse + tm[:, 2] * cs ** 2 * s2
-        sparse = sparse + tm[:, 3] * cs * s3
-        sparse = sparse + tm[:, 4]
+        tm, static, sparse = sparse_flops(self, x_shape, s3, s2, s1, cs)   # tm [n_blocks, 5]
         perc = sparse / tm.sum(dim=1)
-        flops = sparse.sum() + self._static_flops
+        flops = sparse.sum() + static
         return perc.float(), flops.float()
 
     def _stem_fused_ok(self, x):
@@ -1390,23 +1292,15 @@ class ResNet(nn.Module):
         spent ~28 tiny kernels = 0.13 ms of a 13 ms step here).  Mixed models take the tensor-op path below."""
         chan = [isinstance(s_, tuple) for s_ in stats]
         if self.use_fused_stats and dev.type == "cuda" and (all(chan) or not any(chan)):
-            key = (str(dev), tuple(in_shape[1:]))
-            if getattr(self, "_terms_key", None) != key:
-                terms, static = self.flops_table(in_shape)
-                self._terms_key = key
-                self._terms = torch.tensor(terms, dtype=torch.float64, device=dev)
-                self._static_flops = float(static)
+            terms, static = flops_constants(self, in_shape, dev)
             if all(chan):
                 same = len({tuple(s_[0].shape) for s_ in stats}) == 1
                 if same:
-                    dkey = (str(dev), tuple(s_[1] for s_ in stats))
-                    if getattr(self, "_denoms_key", None) != dkey:
-                        self._denoms_key = dkey
-                        self._denoms = torch.tensor(dkey[1], dtype=torch.float32, device=dev)
+                    denom = denoms(self, (s_[1] for s_ in stats), dev)
                     cnt = torch.stack([s_[0] for s_ in stats])
-                    return ops.forward_stats(self._terms, self._static_flops, cnt=cnt, denom=self._denoms)
+                    return ops.forward_stats(terms, static, cnt=cnt, denom=denom)
             elif all((not isinstance(s_, tuple)) and s_.numel() == stats[0].numel() for s_ in stats):
-                return ops.forward_stats(self._terms, self._static_flops, st_in=torch.stack(stats))
+                return ops.forward_stats(terms, static, st_in=torch.stack(stats))
         st = self._stack_stats(stats, dev)
         perc, flops = self.flops_from_sparsities(in_shape, st[:, 0], st[:, 1], st[:, 2], st[:, 3])
         return st, perc, flops
@@ -1426,11 +1320,7 @@ class ResNet(nn.Module):
         if not deferred:
             return torch.stack(stats)
         cs = torch.stack([stats[j][0] for j in deferred]).sum(dim=1).to(torch.float32)
-        dkey = (str(dev), tuple(stats[j][1] for j in deferred))
-        if getattr(self, "_denoms_key", None) != dkey:
-            self._denoms_key = dkey
-            self._denoms = torch.tensor(dkey[1], dtype=torch.float32, device=dev)
-        cs = cs / self._denoms
+        cs = cs / denoms(self, (stats[j][1] for j in deferred), dev)
         rows = torch.ones(len(deferred), 4, device=dev)
         rows[:, 3] = cs
         if len(deferred) == len(stats):

@@ -43,6 +43,7 @@ import torch.nn.functional as F
 
 from . import ops
 from ._lib import LdnError
+from ._shared import channel_constants, dense_channel_convs, dense_index
 
 # weight gradients on ldn_wgrad_rows; LDN_WGRAD=0 = the gather + PyTorch GEMM path.  On by default: the median step is shorter with the kernel for
 # all three full-width workloads at batch 32 and 128 (profiles/train_step_wgrad.jsonl)
@@ -72,19 +73,6 @@ def transposed_neighbour_table(ix, B, H, W, stride=1, Ho=None, Wo=None):
     out = torch.where(ok, pos3[q], torch.full_like(q, -1)).to(torch.int32)
     valid = torch.arange(cap1, device=dev) < ix.cnt[1]
     return torch.where(valid[:, None], out, torch.full_like(out, -1)).contiguous()
-
-
-_DENSE_IX = {}
-
-
-def _dense_lists(B, Ho, Wo, stride, dev):
-    """Index lists of an all-active batch, cached per shape (Bottleneck._dense_ix)."""
-    key = (B, Ho, Wo, stride, str(dev))
-    if key not in _DENSE_IX:
-        if len(_DENSE_IX) > 64:
-            _DENSE_IX.clear()
-        _DENSE_IX[key] = ops.mask_to_index(torch.ones(B, 1, 1, device=dev), Ho, Wo, stride)
-    return _DENSE_IX[key]
 
 
 def _rows_valid(n_cap, count, dev):
@@ -213,26 +201,10 @@ class _PixelBranchFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------------------------ channel masks
-def _channel_constants(w2, w3, s2, t2, t1, s3, t3):
-    """The constants of the channel algebra for the CURRENT weights: c1 = relu(t1), c2 = relu(t2), the 16 border classes of
-    t2 + s2 * (W2 (*) c1), and t3 + s3 * (W3 c2)."""
-    W = w2.shape[0]
-    c1, c2 = torch.relu(t1), torch.relu(t2)
-    wc = torch.einsum("okyx,k->oyx", w2, c1)
-    tab = torch.empty(16, W, device=w2.device)
-    for cls in range(16):
-        rb, cb = cls // 4, cls % 4
-        ys = [ky for ky in range(3) if not ((ky == 0 and rb & 1) or (ky == 2 and rb & 2))]
-        xs = [kx for kx in range(3) if not ((kx == 0 and cb & 1) or (kx == 2 and cb & 2))]
-        tab[cls] = t2 + s2 * wc[:, ys][:, :, xs].sum(dim=(1, 2))
-    t3c = t3 + s3 * (w3.reshape(w3.shape[0], W) @ c2)
-    return c1.contiguous(), c2.contiguous(), tab.contiguous(), t3c.contiguous()
-
-
 class _ChannelBranchFn(torch.autograd.Function):
     """branch = s3 * conv3(relu(s2 * (c . conv2(relu(s1 * (c . conv1(x)) + t1))) + t2)) + t3  with a {0,1} channel mask c [B, W] applied before bn1 / bn2
     (laud_resnet.py:116-118,124-126), on the row kernels over all pixels: u = relu(bn(.)) - relu(shift) is stored, zeroed on the masked channels
-    of each image (the library's dense channel execution, Bottleneck._run_channel_dense)."""
+    of each image (the library's dense channel execution, _shared.dense_channel_convs -- what Bottleneck._run_channel_dense runs)."""
 
     @staticmethod
     def forward(ctx, x, w1, w2, w3, chm, s1, t1, s2, t2, s3, t3, stride):
@@ -244,27 +216,14 @@ class _ChannelBranchFn(torch.autograd.Function):
         x2d = xn.reshape(B * Hi * Wi, Cin)
         s1, t1, s2, t2, s3, t3 = (v.detach().float().contiguous() for v in (s1, t1, s2, t2, s3, t3))
         w2f, w3f = w2.detach().float(), w3.detach().float()
-        c1, c2, tab, t3c = _channel_constants(w2f, w3f, s2, t2, t1, s3, t3)
+        c1, c2, tab, t3c = channel_constants(w2f, w3f, s2, t2, t1, s3, t3)
         w1r = w1.detach().reshape(W, 1, Cin).float().contiguous()
         w2r = w2f.permute(0, 2, 3, 1).reshape(W, 9, W).contiguous()
         w3r = w3f.reshape(cout, W)
         w3s = (w3r * s3.view(-1, 1)).reshape(cout, 1, W).contiguous()
         chm2d = chm.detach().float().reshape(B, W).contiguous()
-        ix = _dense_lists(B, Ho, Wo, stride, dev)
-        fused = ops.dense_kernel_ok() and Cin % 32 == 0 and W % 32 == 0
-        h1 = torch.empty(ix.cap1, W, device=dev)
-        if fused:
-            ops.conv_rows(x2d, w1r, s1, t1, h1, taps=1, m_cap=ix.cap1, relu=1, post_sub=c1, chan_mask=chm2d, rows_per_image=Hi * Wi)
-        else:
-            ops.conv_packed(x2d, w1r, s1, t1, h1, taps=1, m_cap=ix.cap1, post_sub=c1, relu=1)
-            h1.view(B, -1, W).mul_(chm2d.view(B, 1, W))
-        h2 = torch.empty(ix.cap3, W, device=dev)
-        if fused and 9 in ops.DENSE_TAPS and ops.DENSE_CHANNEL_3X3:
-            ops.conv_rows(h1, w2r, s2, tab, h2, a_rows=ix.nbr, taps=9, m_cap=ix.cap3, pix_map=ix.idx3, geom=(Hi, Wi, Ho, Wo, stride), post_sub=c2,
-                          relu=1, chan_mask=chm2d, rows_per_image=Ho * Wo)
-        else:
-            ops.conv_packed(h1, w2r, s2, tab, h2, a_map=ix.nbr, taps=9, m_cap=ix.cap3, pix_map=ix.idx3, geom=(Hi, Wi, Ho, Wo, stride), post_sub=c2, relu=1)
-            h2.view(B, -1, W).mul_(chm2d.view(B, 1, W))
+        ix = dense_index(B, Ho, Wo, stride, dev)
+        h1, h2 = dense_channel_convs(x2d, B, (Hi, Wi, Ho, Wo, stride), w1r, w2r, s1, t1, c1, s2, tab, c2, chm2d, ix)
         br = torch.empty(B * Ho * Wo, cout, device=dev)
         ops.conv_rows(h2, w3s, None, t3c, br, taps=1, m_cap=ix.cap3, relu=0)
         ctx.save_for_backward(x2d, h1, h2, br, w1r, w2r, w3r, s1, t1, s2, t2, s3, t3, chm2d, c1, c2, tab)
