@@ -237,6 +237,38 @@ size_t ldn_wgrad_rows_workspace_bytes(int m_cap, int cin, int cout, int taps);
 int ldn_wgrad_rows(const float* dy, int lddy, const float* a, int lda, int a_valid, const int32_t* a_rows, int taps,
                    const int32_t* m_count, int m_cap, int cin, int cout, float* dw, float* work, int math_mode, void* stream);
 
+/* ---- the ELEMENTWISE backward chain of training on packed rows (csrc/ldn_train_rows.hip).  Both are bandwidth-bound row kernels over
+ * [m_cap][ld >= C] fp32 matrices, C % 4 == 0, ld % 4 == 0, 16-byte aligned pointers, every access 16 bytes wide.
+ *   count  = m_count ? clamp(*m_count, 0, m_cap) : m_cap, read on the device (no host read, no synchronisation)
+ *   img(r) = the image b < B with row_prefix[b] <= r < row_prefix[b + 1] (row_prefix [B + 1] = the pre1 / pre3 output of
+ *            ldn_mask_to_index), found inside the kernel: there is no [m_cap] image-id tensor.
+ *
+ * ldn_rows_chanmask, in place: u[r][k] *= chan_mask[img(r)][k] for r < count (chan_mask [B][C]); rows [count, m_cap) are written as
+ * exact zeros without being read. */
+int ldn_rows_chanmask(float* u, int ldu, const int32_t* row_prefix, int B, const float* chan_mask, const int32_t* m_count, int m_cap,
+                      int C, void* stream);
+
+/* ldn_rows_act_bwd: the backward of  u = m * (relu(s * y + t) - c)  on packed rows, given d L / d h (h = u + c) and the STORED u.
+ * Per element of a row r < count:
+ *   h = u + c;   a = h > 0 ? dh : 0;   dz = a * m[img(r)][k];   du = dz * s[k]
+ * Inputs: dh [m_cap][lddh], u [m_cap][ldu], post_sub c [C] (NULL = 0), scale s [C], shift t [C], chan_mask m [B][C] (NULL = all
+ * ones), row_prefix [B + 1] (required with chan_mask or zy), zy [m_cap][ldzy] (nullable) = the UNMASKED convolution output in its
+ * affine form  zy = s * y + t  -- what a relu = 0 launch of ldn_conv_rows with (scale, shift) stores -- so that a * s * y = a * (zy - t)
+ * needs no division by s.  Rows r >= count of dh / u / zy are NOT READ (they may hold anything, NaN included).
+ * Outputs: du [m_cap][lddu] (may be dh itself), exactly 0 on rows >= count;
+ *   g_shift[k]     = sum_r a                      (every channel: a masked channel's z = t still feeds the ReLU)
+ *   g_scale_num[k] = sum_r dz * (h - t[k])        (d L / d s = g_scale_num / s wherever s != 0; h - t carries one rounding)
+ *   g_mask[b][k]   = sum_{r of image b} a * (zy[r][k] - t[k])      [B][C], with zy only (both NULL otherwise)
+ * Deterministic: the rows are split over workgroups by a plan that is a function of m_cap and C only (never of *m_count: the launch can
+ * be captured into a graph); partial sums go to `work` (ldn_rows_act_bwd_workspace_bytes(m_cap, C, B); B = 0 without zy; never NULL)
+ * and a second small launch adds them in ascending order -- the partial g_mask of an image whose rows straddle workgroups included.
+ * No floating-point atomics: two runs are bit-identical. */
+size_t ldn_rows_act_bwd_workspace_bytes(int m_cap, int C, int B);
+int ldn_rows_act_bwd(const float* dh, int lddh, const float* u, int ldu, const float* post_sub, const float* scale, const float* shift,
+                     const float* chan_mask, const int32_t* row_prefix, int B, const float* zy, int ldzy, const int32_t* m_count,
+                     int m_cap, int C, float* du, int lddu, float* g_shift, float* g_scale_num, float* g_mask, float* work,
+                     void* stream);
+
 /* ldn_conv_rows_split / ldn_conv_rows_f32 with taps == 1, plus a by-product: pool [B][S*Sx][cout] receives, for every patch
  * this launch writes, the MEAN of the final output (after residual and ReLU) over the patch's Ho/S x Wo/Sx pixels (4 or 16) --
  * the pooled means the next block's spatial masker needs (adaptive_avg_pool2d of models/utils.py:48-52 on an even grid), so

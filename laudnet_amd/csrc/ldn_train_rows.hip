@@ -1,0 +1,257 @@
+// ldn_train_rows.hip -- the elementwise backward chain of training on packed rows (ldn_rows_chanmask, ldn_rows_act_bwd; include/ldn_hip.h).
+//
+// Both are bandwidth-bound row kernels over [m_cap, C] fp32 matrices with a leading dimension: C % 4 == 0, every access 16 bytes wide, a wave
+// reads consecutive quads of a row.  The count is read on the device; rows r >= count are never read and are written as exact zeros.
+//
+// The image of a packed row comes from the per-image row prefix ([B + 1]: image b owns rows [prefix[b], prefix[b + 1])) inside the kernel --
+// a binary search per thread (ldn_rows_chanmask) or per workgroup, followed by a walk over the images of the workgroup's rows
+// (ldn_rows_act_bwd).  There is no [m_cap] image-id tensor and no host read.
+//
+// ldn_rows_act_bwd, per element of a row r < count of image b:
+//     h  = u + c                      (the forward value: u = m * (relu(z) - c) is what the forward stored)
+//     a  = h > 0 ? dh : 0             (through the ReLU)
+//     dz = a * m[b, k]                (d L / d z on the active channels)
+//     du = dz * s[k]
+//     g_shift[k]     += a             (every channel: a masked channel's z = t still feeds the ReLU)
+//     g_scale_num[k] += dz * (h - t[k])
+//     g_mask[b, k]   += a * (zy - t[k])        zy = s * y + t, the unmasked convolution in the affine form a relu = 0 launch stores
+// h and h - t are formed in double from the three fp32 inputs, so h - t carries ONE rounding: with h = fl(u + c) first, a channel whose
+// h is close to t would lose the leading digits of s * y to the rounding of u + c.
+//
+// Determinism: the rows are split over `splits` workgroups per column tile -- a function of m_cap and C only, never of the device-side count
+// (the launch is graph-capturable).  Inside a workgroup a thread owns one channel quad and every RL-th row; the row lanes' sums are added in
+// ascending lane order through the LDS.  A workgroup writes its partial g_shift / g_scale_num to work[split], and the partial g_mask of
+// every image b that owns rows of the split to the slot split + b: an image's rows may straddle splits, and because images and splits both
+// ascend along the rows, (split, b) -> split + b is one-to-one over the pairs that meet (splits + B slots instead of splits * B).
+// k_act_reduce adds the partials in ascending split order.  No floating-point atomics.
+#include "ldn_common.h"
+
+namespace ldn {
+
+constexpr int ACT_THREADS = 256;
+constexpr int ACT_QT = 64;             // quads per column tile (256 channels)
+constexpr int ACT_MIN_SPLIT_ROWS = 64;
+constexpr int ACT_TARGET_WGS = 2048;
+constexpr int ACT_MAX_SPLITS = 256;
+
+struct ActArgs {
+    const float* dh; const float* u; const float* post_sub; const float* scale; const float* shift; const float* chan_mask;
+    const int32_t* prefix; const float* zy; const int32_t* m_count;
+    float* du; float* g_shift; float* g_scale; float* g_mask; float* work;
+    int lddh, ldu, ldzy, lddu, B, m_cap, C, splits, rps;
+};
+
+__device__ __forceinline__ int rows_count(const int32_t* m_count, int m_cap) {
+    int c = m_count ? *m_count : m_cap;
+    return c < 0 ? 0 : (c > m_cap ? m_cap : c);
+}
+
+// the image b in [0, B) with prefix[b] <= r < prefix[b + 1] (images without rows are stepped over; rows past prefix[B] fall to B - 1)
+__device__ __forceinline__ int image_of_row(const int32_t* prefix, int B, int r) {
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (prefix[mid + 1] > r) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+// work layout: [splits][C] g_shift partials | [splits][C] g_scale_num partials | [splits + B][C] g_mask partials
+__device__ __forceinline__ float* act_work_shift(const ActArgs& p) { return p.work; }
+__device__ __forceinline__ float* act_work_scale(const ActArgs& p) { return p.work + (size_t)p.splits * p.C; }
+__device__ __forceinline__ float* act_work_mask(const ActArgs& p) { return p.work + (size_t)2 * p.splits * p.C; }
+
+// u[r, k] *= chan_mask[img(r), k] for r < count; rows [count, m_cap) = 0.  One thread per (row, quad).
+__global__ __launch_bounds__(256) void k_rows_chanmask(float* u, int ldu, const int32_t* prefix, int B, const float* chan_mask,
+                                                       const int32_t* m_count, int m_cap, int C) {
+    const int Q = C >> 2;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t r64 = i / Q;
+    if (r64 >= (size_t)m_cap) return;
+    const int r = (int)r64, q = (int)(i - r64 * Q);
+    float* dst = u + (size_t)r * ldu + 4 * q;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (r < rows_count(m_count, m_cap)) {
+        const int b = image_of_row(prefix, B, r);
+        v = *reinterpret_cast<const f32x4*>(dst) * *reinterpret_cast<const f32x4*>(chan_mask + (size_t)b * C + 4 * q);
+    }
+    store16(dst, v);
+}
+
+// grid = (column tiles, splits); thread = (row lane rl, quad ql) of a QT-quad tile, QT = min(C / 4, 64), RL = 256 / QT row lanes
+__global__ __launch_bounds__(ACT_THREADS) void k_rows_act_bwd(const ActArgs p) {
+    __shared__ f32x4 s_red[ACT_THREADS];
+    const int Q = p.C >> 2;
+    const int QT = Q < ACT_QT ? Q : ACT_QT;
+    const int RL = ACT_THREADS / QT;
+    const int tid = threadIdx.x, rl = tid / QT, ql = tid - rl * QT;
+    const int q = blockIdx.x * ACT_QT + ql;
+    const bool active = rl < RL && q < Q;
+    const int split = blockIdx.y;
+    const int count = rows_count(p.m_count, p.m_cap);
+    const int r_begin = split * p.rps;
+    const int r_cap_end = min(p.m_cap, r_begin + p.rps);
+    const int r_end = min(count, r_cap_end);
+    const int k = 4 * q;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+
+    // rows past the count: exact zeros, nothing read
+    if (active)
+        for (int r = max(r_end, r_begin) + rl; r < r_cap_end; r += RL) store16(p.du + (size_t)r * p.lddu + k, zero);
+    if (r_begin >= r_end) return;          // (uniform) no rows: k_act_reduce does not read this split's partials
+
+    // lane-order sum over the row lanes; the result is valid in row lane 0
+    auto lane_sum = [&](f32x4 v) {
+        s_red[tid] = v;
+        __syncthreads();
+        f32x4 s = zero;
+        if (rl == 0)
+            for (int j = 0; j < RL; ++j) s += s_red[j * QT + ql];
+        __syncthreads();
+        return s;
+    };
+
+    f32x4 sc = zero, sh = zero, c = zero;
+    if (active) {
+        sc = *reinterpret_cast<const f32x4*>(p.scale + k);
+        sh = *reinterpret_cast<const f32x4*>(p.shift + k);
+        if (p.post_sub) c = *reinterpret_cast<const f32x4*>(p.post_sub + k);
+    }
+    const bool per_image = p.chan_mask || p.zy;
+    int b = per_image ? image_of_row(p.prefix, p.B, r_begin) : 0;
+    f32x4 g_sh = zero, g_sc = zero;
+    int r0 = r_begin;
+    while (r0 < r_end) {                   // (uniform) one segment per image that owns rows of this split
+        int seg_end = r_end;
+        if (per_image && b < p.B - 1) seg_end = min(r_end, max(p.prefix[b + 1], r0));
+        if (seg_end > r0) {
+            f32x4 m = {1.f, 1.f, 1.f, 1.f}, g_m = zero;
+            if (active && p.chan_mask) m = *reinterpret_cast<const f32x4*>(p.chan_mask + (size_t)b * p.C + k);
+            if (active)
+                for (int r = r0 + rl; r < seg_end; r += RL) {
+                    const f32x4 dh = *reinterpret_cast<const f32x4*>(p.dh + (size_t)r * p.lddh + k);
+                    const f32x4 u = *reinterpret_cast<const f32x4*>(p.u + (size_t)r * p.ldu + k);
+                    f32x4 zy = zero;
+                    if (p.zy) zy = *reinterpret_cast<const f32x4*>(p.zy + (size_t)r * p.ldzy + k);
+                    f32x4 du;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const double h = (double)u[i] + (double)c[i];
+                        const float a = h > 0.0 ? dh[i] : 0.f;
+                        const float dz = a * m[i];
+                        du[i] = dz * sc[i];
+                        g_sh[i] += a;
+                        g_sc[i] += dz * (float)(h - (double)sh[i]);
+                        g_m[i] += a * (zy[i] - sh[i]);
+                    }
+                    store16(p.du + (size_t)r * p.lddu + k, du);
+                }
+            if (p.zy) {
+                const f32x4 s = lane_sum(g_m);
+                if (active && rl == 0) *reinterpret_cast<f32x4*>(act_work_mask(p) + (size_t)(split + b) * p.C + k) = s;
+            }
+        }
+        r0 = seg_end;
+        ++b;
+    }
+    const f32x4 s1 = lane_sum(g_sh), s2 = lane_sum(g_sc);
+    if (active && rl == 0) {
+        *reinterpret_cast<f32x4*>(act_work_shift(p) + (size_t)split * p.C + k) = s1;
+        *reinterpret_cast<f32x4*>(act_work_scale(p) + (size_t)split * p.C + k) = s2;
+    }
+}
+
+// one thread per quad of g_shift (j == 0), g_scale_num (j == 1) and g_mask[b] (j == 2 + b): the partials in ascending split order
+__global__ __launch_bounds__(256) void k_act_reduce(const ActArgs p, int nvec) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int Q = p.C >> 2;
+    if (i >= nvec * Q) return;
+    const int j = i / Q, k = 4 * (i - j * Q);
+    const int count = rows_count(p.m_count, p.m_cap);
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    if (j < 2) {
+        const int live = min(p.splits, ceil_div(count, p.rps));
+        const float* w = j == 0 ? act_work_shift(p) : act_work_scale(p);
+        for (int t = 0; t < live; ++t) s += *reinterpret_cast<const f32x4*>(w + (size_t)t * p.C + k);
+        *reinterpret_cast<f32x4*>((j == 0 ? p.g_shift : p.g_scale) + k) = s;
+        return;
+    }
+    const int b = j - 2;
+    const int lo = min(p.prefix[b], count), hi = b == p.B - 1 ? count : min(p.prefix[b + 1], count);     // (the walk of k_rows_act_bwd)
+    if (lo < hi) {
+        // image b meets the splits lo / rps .. (hi - 1) / rps -- unless an earlier image reaches past prefix[b] (never with a monotone prefix)
+        const int t_hi = min(p.splits - 1, (hi - 1) / p.rps);
+        for (int t = lo / p.rps; t <= t_hi; ++t) s += *reinterpret_cast<const f32x4*>(act_work_mask(p) + (size_t)(t + b) * p.C + k);
+    }
+    *reinterpret_cast<f32x4*>(p.g_mask + (size_t)b * p.C + k) = s;
+}
+
+// the launch plan: a function of m_cap and C ONLY
+static void act_plan(int m_cap, int C, int* tiles, int* splits, int* rps) {
+    *tiles = ceil_div(C / 4, ACT_QT);
+    int s = ceil_div(ACT_TARGET_WGS, *tiles);
+    const int most = m_cap / ACT_MIN_SPLIT_ROWS;
+    if (s > most) s = most;
+    if (s > ACT_MAX_SPLITS) s = ACT_MAX_SPLITS;
+    if (s < 1) s = 1;
+    *rps = ceil_div(m_cap > 0 ? m_cap : 1, s);
+    *splits = ceil_div(m_cap > 0 ? m_cap : 1, *rps);
+}
+
+static bool aligned16(const void* ptr) { return (uintptr_t)ptr % 16 == 0; }
+
+}  // namespace ldn
+
+using namespace ldn;
+
+extern "C" int ldn_rows_chanmask(float* u, int ldu, const int32_t* row_prefix, int B, const float* chan_mask, const int32_t* m_count,
+                                 int m_cap, int C, void* stream) {
+    LDN_REQUIRE(u && row_prefix && chan_mask, "ldn_rows_chanmask: null pointer");
+    LDN_REQUIRE(B >= 1 && m_cap >= 0, "ldn_rows_chanmask: B >= 1, m_cap >= 0 (got %d, %d)", B, m_cap);
+    LDN_REQUIRE(C > 0 && C % 4 == 0 && ldu >= C && ldu % 4 == 0, "ldn_rows_chanmask: C %% 4 == 0, ldu >= C, ldu %% 4 == 0 (got C %d, ldu %d)", C, ldu);
+    LDN_REQUIRE(aligned16(u) && aligned16(chan_mask), "ldn_rows_chanmask: u / chan_mask must be 16-byte aligned");
+    if (m_cap == 0) return LDN_OK;
+    const size_t n = (size_t)m_cap * (C / 4);
+    LDN_REQUIRE((n + 255) / 256 <= 0x7fffffffull, "ldn_rows_chanmask: m_cap * C too large");
+    k_rows_chanmask<<<(unsigned)((n + 255) / 256), 256, 0, static_cast<hipStream_t>(stream)>>>(u, ldu, row_prefix, B, chan_mask, m_count, m_cap, C);
+    LDN_CHECK_LAUNCH("k_rows_chanmask");
+    return LDN_OK;
+}
+
+extern "C" size_t ldn_rows_act_bwd_workspace_bytes(int m_cap, int C, int B) {
+    if (m_cap < 0 || C <= 0 || C % 4 || B < 0) return 0;
+    int tiles, splits, rps;
+    act_plan(m_cap, C, &tiles, &splits, &rps);
+    return ((size_t)2 * splits + (B > 0 ? splits + B : 0)) * C * sizeof(float);
+}
+
+extern "C" int ldn_rows_act_bwd(const float* dh, int lddh, const float* u, int ldu, const float* post_sub, const float* scale,
+                                const float* shift, const float* chan_mask, const int32_t* row_prefix, int B, const float* zy, int ldzy,
+                                const int32_t* m_count, int m_cap, int C, float* du, int lddu, float* g_shift, float* g_scale_num,
+                                float* g_mask, float* work, void* stream) {
+    LDN_REQUIRE(dh && u && scale && shift && du && g_shift && g_scale_num && work, "ldn_rows_act_bwd: null pointer");
+    LDN_REQUIRE(m_cap >= 0 && C > 0 && C % 4 == 0, "ldn_rows_act_bwd: m_cap >= 0, C %% 4 == 0 (got %d, %d)", m_cap, C);
+    LDN_REQUIRE(lddh >= C && ldu >= C && lddu >= C && lddh % 4 == 0 && ldu % 4 == 0 && lddu % 4 == 0,
+                "ldn_rows_act_bwd: leading dimensions >= C and multiples of 4 (got %d, %d, %d)", lddh, ldu, lddu);
+    LDN_REQUIRE(!zy || (ldzy >= C && ldzy % 4 == 0), "ldn_rows_act_bwd: ldzy >= C and a multiple of 4 (got %d)", ldzy);
+    LDN_REQUIRE(!(chan_mask || zy) || (row_prefix && B >= 1), "ldn_rows_act_bwd: chan_mask / zy need row_prefix [B + 1] and B >= 1");
+    LDN_REQUIRE((zy != nullptr) == (g_mask != nullptr), "ldn_rows_act_bwd: g_mask [B][C] is the output that goes with zy: give both or neither");
+    LDN_REQUIRE(aligned16(dh) && aligned16(u) && aligned16(post_sub) && aligned16(scale) && aligned16(shift) && aligned16(chan_mask) &&
+                aligned16(zy) && aligned16(du) && aligned16(g_shift) && aligned16(g_scale_num) && aligned16(g_mask) && aligned16(work),
+                "ldn_rows_act_bwd: every float pointer must be 16-byte aligned");
+    ActArgs p;
+    p.dh = dh; p.u = u; p.post_sub = post_sub; p.scale = scale; p.shift = shift; p.chan_mask = chan_mask; p.prefix = row_prefix; p.zy = zy;
+    p.m_count = m_count; p.du = du; p.g_shift = g_shift; p.g_scale = g_scale_num; p.g_mask = g_mask; p.work = work;
+    p.lddh = lddh; p.ldu = ldu; p.ldzy = ldzy; p.lddu = lddu; p.B = (chan_mask || zy) ? B : 0; p.m_cap = m_cap; p.C = C;
+    int tiles;
+    act_plan(m_cap, C, &tiles, &p.splits, &p.rps);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (m_cap > 0) {
+        k_rows_act_bwd<<<dim3((unsigned)tiles, (unsigned)p.splits), ACT_THREADS, 0, st>>>(p);
+        LDN_CHECK_LAUNCH("k_rows_act_bwd");
+    }
+    const int nvec = 2 + (zy ? B : 0);
+    k_act_reduce<<<ceil_div(nvec * (C / 4), 256), 256, 0, st>>>(p, nvec);
+    LDN_CHECK_LAUNCH("k_act_reduce");
+    return LDN_OK;
+}

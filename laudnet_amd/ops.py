@@ -540,7 +540,73 @@ def wgrad_rows(dy2d, a2d, *, a_rows=None, taps=1, m_count=None, m_cap=None, a_va
     return out
 
 
-USE_ROWS_PS = os.environ.get("LDN_ROWS_PS", "1") != "0"      # the pre-split packed path (k_dense<PS / OF> + k_rows3); 0 = round 4's three launches
+def _rows_cap(m_cap, what, *mats):
+    """m_cap of a row kernel over several [rows, ld] matrices: the smallest row count unless given; no matrix may be shorter."""
+    rows = min(t.shape[0] for t in mats if t is not None)
+    m_cap = rows if m_cap is None else int(m_cap)
+    if m_cap < 0 or m_cap > rows:
+        raise L.LdnError(f"{what}: m_cap {m_cap} exceeds a matrix of {rows} rows")
+    return m_cap
+
+
+def rows_chanmask(u2d, row_prefix, chan_mask, m_count=None, m_cap=None):
+    """In place on packed rows (see ldn_rows_chanmask): u2d[r, k] *= chan_mask[img(r), k] for r < count, exact zeros on rows [count, m_cap).
+    u2d [rows, ld >= C] (C = chan_mask.shape[1]); row_prefix [B + 1] int32 = IndexSet.pre1 / pre3 (image b owns rows [prefix[b],
+    prefix[b + 1])): the image of a row is found on the device.  chan_mask [B, C].  Returns u2d."""
+    L.require_device(u2d, row_prefix, chan_mask, m_count)
+    if chan_mask.dim() != 2 or row_prefix.numel() != chan_mask.shape[0] + 1:
+        raise L.LdnError("rows_chanmask: chan_mask must be [B, C] and row_prefix [B + 1]")
+    B, C = chan_mask.shape
+    if C % 4 or u2d.dim() != 2 or u2d.shape[1] < C:
+        raise L.LdnError(f"rows_chanmask: C % 4 == 0 and u2d at least C columns wide (C {C}, u2d {tuple(u2d.shape)})")
+    m_cap = _rows_cap(m_cap, "rows_chanmask", u2d)
+    L.check(L.load().ldn_rows_chanmask(L.ptr(_f32rows(u2d, "u")), u2d.stride(0), L.ptr(_i32c(row_prefix, "row_prefix")), B,
+                                       L.ptr(_f32c(chan_mask, "chan_mask")), L.ptr(_i32c(m_count, "m_count")), m_cap, C,
+                                       L.stream_ptr(u2d)), "ldn_rows_chanmask")
+    return u2d
+
+
+def rows_act_bwd(dh2d, u2d, scale, shift, *, post_sub=None, chan_mask=None, row_prefix=None, zy2d=None, m_count=None, m_cap=None, out=None):
+    """Backward of u = m * (relu(s * y + t) - c) on packed rows (see ldn_rows_act_bwd), given dh2d = d L / d h (h = u + c) and the stored u2d:
+    a = dh where u + c > 0, dz = a * m[img(r)], du = dz * s.  -> (du [m_cap, C], g_shift [C] = sum a, g_scale_num [C] = sum dz * (h - t) -- the
+    caller divides by s --, g_mask [B, C] = sum over the image's rows of a * (zy - t), or None without zy2d).
+    zy2d is the UNMASKED convolution output in its affine form zy = s * y + t (a relu=0 launch of conv_rows with (scale, shift)), so
+    g_mask = sum a * s * y without a division.  chan_mask [B, C] (None = ones) and zy2d need row_prefix [B + 1] (IndexSet.pre1 / pre3).
+    Rows past the device-side count are not read; du is exactly 0 there.  out: a [m_cap, >= C] matrix for du (dh2d itself is allowed).
+    Deterministic: no atomics, a split plan of m_cap and C only, partial sums added in ascending order."""
+    L.require_device(dh2d, u2d, scale, shift, post_sub, chan_mask, row_prefix, zy2d, m_count, out)
+    lib = L.load()
+    C = scale.numel()
+    for name, t in (("dh", dh2d), ("u", u2d), ("zy", zy2d), ("out", out)):
+        if t is not None and (t.dim() != 2 or t.shape[1] < C):
+            raise L.LdnError(f"rows_act_bwd: {name} must be [rows, >= {C}], got {tuple(t.shape)}")
+    if C % 4 or shift.numel() != C or (post_sub is not None and post_sub.numel() != C):
+        raise L.LdnError("rows_act_bwd: scale / shift / post_sub must be [C] with C % 4 == 0")
+    B = 0
+    if chan_mask is not None or zy2d is not None:
+        if row_prefix is None or row_prefix.numel() < 2:
+            raise L.LdnError("rows_act_bwd: chan_mask / zy2d need row_prefix [B + 1]")
+        B = row_prefix.numel() - 1
+        if chan_mask is not None and tuple(chan_mask.shape) != (B, C):
+            raise L.LdnError(f"rows_act_bwd: chan_mask must be [{B}, {C}], got {tuple(chan_mask.shape)}")
+    m_cap = _rows_cap(m_cap, "rows_act_bwd", dh2d, u2d, zy2d, out)
+    dev = dh2d.device
+    if out is None:
+        out = torch.empty(m_cap, C, device=dev, dtype=torch.float32)
+    g_shift = torch.empty(C, device=dev, dtype=torch.float32)
+    g_scale = torch.empty(C, device=dev, dtype=torch.float32)
+    g_mask = torch.empty(B, C, device=dev, dtype=torch.float32) if zy2d is not None else None
+    work = _work(lib.ldn_rows_act_bwd_workspace_bytes(m_cap, C, B if zy2d is not None else 0), dev)
+    L.check(lib.ldn_rows_act_bwd(L.ptr(_f32rows(dh2d, "dh")), dh2d.stride(0), L.ptr(_f32rows(u2d, "u")), u2d.stride(0),
+                                 L.ptr(_f32c(post_sub, "post_sub")), L.ptr(_f32c(scale, "scale")), L.ptr(_f32c(shift, "shift")),
+                                 L.ptr(_f32c(chan_mask, "chan_mask")), L.ptr(_i32c(row_prefix, "row_prefix")), B,
+                                 L.ptr(_f32rows(zy2d, "zy")), zy2d.stride(0) if zy2d is not None else 0, L.ptr(_i32c(m_count, "m_count")),
+                                 m_cap, C, L.ptr(_f32rows(out, "out")), out.stride(0), L.ptr(g_shift), L.ptr(g_scale), L.ptr(g_mask),
+                                 L.ptr(work), L.stream_ptr(out)), "ldn_rows_act_bwd")
+    return out[:m_cap, :C] if tuple(out.shape) != (m_cap, C) else out, g_shift, g_scale, g_mask
+
+
+USE_ROWS_PS = os.environ.get("LDN_ROWS_PS", "1") != "0"     # the pre-split packed path (k_dense<PS / OF> + k_rows3); 0 = round 4's three launches
 
 
 ROWS_PS_MAX_WIDTH = 2048     # = ROWS3_MAX_CIN of csrc/ldn_rows3.hip

@@ -20,6 +20,11 @@ on the library's kernels:
   channel masks (any stride): the row kernels over ALL pixels with the channel mask and the constants of the channel algebra as epilogue
       terms (a masked channel is the constant relu(shift); the library's "dense channel execution").  Correct for every
       gradient, but dense in the channels: the masks save no FLOPs here (stated, not hidden).
+  pixel x channel masks (dyn_mode 'both', the reference's constructor default; any stride): the pixel mask's packed rows with the channel
+      algebra on them -- dense in the channels on those rows: `ops.rows_chanmask` zeroes the masked channels of every packed row (the image
+      of a row comes from the lists' per-image prefix, on the device), and the backward's elementwise chain with ALL its reductions (ReLU
+      gate, channel mask, d scale / d shift, the per-image sums of the channel mask's straight-through term) is `ops.rows_act_bwd`: two
+      launches per layer, no floating-point atomics.  The pixel mask saves its FLOPs in both directions, the channel mask none.
   Weight gradients are the library's own kernel (`ops.wgrad_rows`: dW = sum over the packed rows of dY x A, the nine taps' rows gathered through
   the neighbour table inside the kernel, rows past the device-side count never read, deterministic) wherever `ops.wgrad_rows_ok` holds and
   `USE_WGRAD_KERNEL` is on (the default; env LDN_WGRAD=0 turns it off); otherwise, and for other shapes, the gather + GEMM path; the gradients of BatchNorm's affine parameters come out of the folded
@@ -32,8 +37,8 @@ Entry points: `sparse_block_train(block, x, mask)` (one block, the mask an input
 block signature in training mode: samples its own masks), `train_forward(model, x, temperature)` (a whole LAUD-ResNet -> the reference's
 7-tuple; a `LAD_MMDet_ResNet` -> its (outs, additional, model_configs)), `prepare_for_training(model)` (train mode with BatchNorm statistics
 frozen).  Checked against the oracle's autograd -- blocks on the reference-generated block fixtures, whole models on `det_tiny.pt` /
-`full_tiny.pt` with identical Gumbel noise (tests/test_hip_training.py, plain 1e-3).  Not built: dyn_mode 'both', mask groups > 1, grouped /
-dilated conv2, BatchNorm in batch-statistics mode."""
+`full_tiny.pt` with identical Gumbel noise (tests/test_hip_training.py, tests/test_hip_training_both.py, plain 1e-3).  Not built: mask groups > 1,
+grouped / dilated conv2, BatchNorm in batch-statistics mode, LAD-RegNet."""
 from __future__ import annotations
 
 import os
@@ -139,7 +144,8 @@ class _PixelBranchFn(torch.autograd.Function):
         zW, zC = torch.zeros(W, device=dev), torch.zeros(Cin, device=dev)
         v3, v1 = _rows_valid(ix.cap3, ix.cnt[0], dev), _rows_valid(ix.cap1, ix.cnt[1], dev)
         # conv3^T on the active rows
-        g3 = ops.gather_rows(go, ix.idx3, count=ix.cnt[0:1], cap=ix.cap3) * v3          # d L / d (s3 y3 + t3) at the kept pixels
+        # (the gather leaves the rows past the count unwritten -- recycled memory, possibly NaN: select, do not multiply)
+        g3 = torch.where(v3 > 0, ops.gather_rows(go, ix.idx3, count=ix.cnt[0:1], cap=ix.cap3), zW[:1])          # d L / d (s3 y3 + t3) at the kept pixels
         w3s = w3r * s3.view(-1, 1)
         dh2 = torch.zeros(ix.cap3, W, device=dev)
         ops.conv_rows(g3, w3s.t().reshape(W, 1, cout).contiguous(), None, zW, dh2, taps=1, m_count=ix.cnt[0:1], m_cap=ix.cap3, relu=0)
@@ -181,7 +187,7 @@ class _PixelBranchFn(torch.autograd.Function):
         gt1 = dz1.sum(0) if need[6] else None
         gs2 = (dz2 * (h2 - t2)).sum(0) / safe(s2) if need[7] else None
         gt2 = dz2.sum(0) if need[8] else None
-        y3s = ops.gather_rows(br, ix.idx3, count=ix.cnt[0:1], cap=ix.cap3) - t3       # = s3 * y3 at the kept pixels
+        y3s = torch.where(v3 > 0, ops.gather_rows(br, ix.idx3, count=ix.cnt[0:1], cap=ix.cap3) - t3, zW[:1])       # = s3 * y3 at the kept pixels
         gs3 = (g3 * y3s).sum(0) / safe(s3) if need[9] else None
         gt3 = g3.sum(0) if need[10] else None
         gm = None
@@ -304,6 +310,145 @@ class _ChannelBranchFn(torch.autograd.Function):
         return grad_x, gw1, gw2, gw3, gc, gs1, gt1, gs2, gt2, gs3, gt3, None
 
 
+# ------------------------------------------------------------------------------------------------------------------ pixel x channel masks
+def _conv_const(a2d, w, scale, shift, out2d, *, a_rows, taps, m_count, m_cap, relu, post_sub=None, pix_map=None, geom=None):
+    """A packed-row convolution with the epilogue terms of the channel algebra (post-ReLU constant, border-class shift table): k_dense where the
+    arithmetic mode and the widths put conv_rows there, else the same terms on conv_packed (one image = the whole list).  Rows past the
+    device-side count are not written."""
+    cout, _, cin = w.shape
+    if (ops.dense_kernel_ok() and cin % 32 == 0 and cout % 32 == 0 and taps in ops.DENSE_TAPS and (taps == 1 or ops.DENSE_CHANNEL_3X3)):
+        return ops.conv_rows(a2d, w, scale, shift, out2d, a_rows=a_rows, taps=taps, m_count=m_count, m_cap=m_cap, relu=relu, post_sub=post_sub,
+                             pix_map=pix_map, geom=geom)
+    return ops.conv_packed(a2d, w, scale, shift, out2d, a_map=a_rows, taps=taps, m_count=m_count, m_cap=m_cap, relu=relu, post_sub=post_sub,
+                           pix_map=pix_map, geom=geom)
+
+
+class _BothBranchFn(torch.autograd.Function):
+    """branch = m3 * (s3 * conv3(relu(s2 * (c . conv2(relu(s1 * (c . conv1(x)) + t1))) + t2)) + t3)  (dyn_mode 'both', laud_resnet.py:101-147): the pixel
+    mask's packed rows (the index lists of _PixelBranchFn, any stride) with the channel algebra of _ChannelBranchFn on them.  DENSE in the
+    channels: conv_rows over every channel of the packed rows, u = relu(bn(.)) - relu(shift) stored, the masked channels of each row's image
+    zeroed by ops.rows_chanmask (the image of a packed row comes from the lists' per-image prefix) -- the pixel mask saves its FLOPs in both
+    directions, the channel mask saves none (stated, as for channel mode).  The constants' share of conv2 is the border-class table: every
+    in-map neighbour of a kept pixel is in the dilated list, so a missing neighbour is padding and the table's classes are exact.  The
+    backward's elementwise chain and its reductions (ReLU gate, channel mask, d scale / d shift, the per-image sums of the channel mask's
+    straight-through term) are ops.rows_act_bwd: two launches per layer, deterministic.  Differentiable in x, the three weights, the six
+    folded BatchNorm vectors, the pixel mask and the channel mask."""
+
+    @staticmethod
+    def _chain(x2d, ix, geom, w1r, w2r, w3s, s1, t1, c1, s2, tab, c2, t3c, chm2d, br):
+        """conv1 -> conv2 -> conv3 over the lists of ix, conv3 scattered into br.  -> (u1, u2)"""
+        W = w1r.shape[0]
+        dev = x2d.device
+        u1 = torch.empty(ix.cap1, W, device=dev)
+        _conv_const(x2d, w1r, s1, t1, u1, a_rows=ix.idx1, taps=1, m_count=ix.cnt[1:2], m_cap=ix.cap1, relu=1, post_sub=c1)
+        ops.rows_chanmask(u1, ix.pre1, chm2d, m_count=ix.cnt[1:2], m_cap=ix.cap1)          # (also zeroes the rows past the count)
+        u2 = torch.empty(ix.cap3, W, device=dev)
+        _conv_const(u1, w2r, s2, tab, u2, a_rows=ix.nbr, taps=9, m_count=ix.cnt[0:1], m_cap=ix.cap3, relu=1, post_sub=c2, pix_map=ix.idx3, geom=geom)
+        ops.rows_chanmask(u2, ix.pre3, chm2d, m_count=ix.cnt[0:1], m_cap=ix.cap3)
+        ops.conv_rows(u2, w3s, None, t3c, br, taps=1, m_count=ix.cnt[0:1], m_cap=ix.cap3, relu=0, out_rows=ix.idx3)
+        return u1, u2
+
+    @staticmethod
+    def forward(ctx, x, w1, w2, w3, m3, chm, s1, t1, s2, t2, s3, t3, stride):
+        B, Cin, Hi, Wi = x.shape
+        Ho, Wo = m3.shape[2], m3.shape[3]
+        W, cout = w1.shape[0], w3.shape[0]
+        dev = x.device
+        x2d = ops.as_nhwc(x.detach()).reshape(B * Hi * Wi, Cin)
+        ix = ops.mask_to_index(m3.detach().reshape(B, Ho, Wo).contiguous().float(), Ho, Wo, stride)
+        s1, t1, s2, t2, s3, t3 = (v.detach().float().contiguous() for v in (s1, t1, s2, t2, s3, t3))
+        w2f, w3f = w2.detach().float(), w3.detach().float()
+        c1, c2, tab, t3c = channel_constants(w2f, w3f, s2, t2, t1, s3, t3)
+        w1r = w1.detach().reshape(W, 1, Cin).float().contiguous()
+        w2r = w2f.permute(0, 2, 3, 1).reshape(W, 9, W).contiguous()
+        w3r = w3f.reshape(cout, W)
+        w3s = (w3r * s3.view(-1, 1)).reshape(cout, 1, W).contiguous()
+        chm2d = chm.detach().float().reshape(B, W).contiguous()
+        br = torch.zeros(B * Ho * Wo, cout, device=dev)
+        u1, u2 = _BothBranchFn._chain(x2d, ix, (Hi, Wi, Ho, Wo, stride), w1r, w2r, w3s, s1, t1, c1, s2, tab, c2, t3c, chm2d, br)
+        ctx.save_for_backward(x2d, u1, u2, br, w1r, w2r, w3r, s1, t1, s2, t2, s3, t3, m3.detach().float(), chm2d, c1, c2, tab, t3c)
+        ctx.ix, ctx.shape, ctx.stride = ix, (B, Cin, Hi, Wi, Ho, Wo, W, cout), stride
+        return ops.from_nhwc(br.view(B, Ho, Wo, cout))
+
+    @staticmethod
+    def backward(ctx, g):
+        x2d, u1, u2, br, w1r, w2r, w3r, s1, t1, s2, t2, s3, t3, m3d, chm2d, c1, c2, tab, t3c = ctx.saved_tensors
+        ix, stride = ctx.ix, ctx.stride
+        B, Cin, Hi, Wi, Ho, Wo, W, cout = ctx.shape
+        dev = g.device
+        need = ctx.needs_input_grad
+        geom = (Hi, Wi, Ho, Wo, stride)
+        cnt3, cnt1 = ix.cnt[0:1], ix.cnt[1:2]
+        go = ops.as_nhwc(g.contiguous()).reshape(B * Ho * Wo, cout)
+        zW, zC = torch.zeros(W, device=dev), torch.zeros(Cin, device=dev)
+        v3 = _rows_valid(ix.cap3, ix.cnt[0], dev) > 0
+        zero = torch.zeros((), device=dev)
+        g3 = torch.where(v3, ops.gather_rows(go, ix.idx3, count=cnt3, cap=ix.cap3), zero)     # d L / d (s3 y3 + t3) at the kept pixels (the gather leaves the rows past the count unwritten)
+        w3s = w3r * s3.view(-1, 1)
+        zy1 = zy2 = None
+        if need[5]:
+            # the channel mask's straight-through term needs the UNMASKED conv outputs at the masked channels too: two relu=0 launches on the same
+            # rows, z = s y + t as stored (rows_act_bwd takes that form); conv2 of h1 = u1 + c1, the constants' share in the border-class table
+            zy1 = torch.empty(ix.cap1, W, device=dev)
+            _conv_const(x2d, w1r, s1, t1, zy1, a_rows=ix.idx1, taps=1, m_count=cnt1, m_cap=ix.cap1, relu=0)
+            zy2 = torch.empty(ix.cap3, W, device=dev)
+            _conv_const(u1, w2r, s2, tab, zy2, a_rows=ix.nbr, taps=9, m_count=cnt3, m_cap=ix.cap3, relu=0, pix_map=ix.idx3, geom=geom)
+        # conv3^T on the kept rows, then layer 2's elementwise chain + reductions in one kernel
+        dh2 = torch.empty(ix.cap3, W, device=dev)                     # d L / d h2 at EVERY channel
+        ops.conv_rows(g3, w3s.t().reshape(W, 1, cout).contiguous(), None, zW, dh2, taps=1, m_count=cnt3, m_cap=ix.cap3, relu=0)
+        du2, gt2, gs2n, gm2 = ops.rows_act_bwd(dh2, u2, s2, t2, post_sub=c2, chan_mask=chm2d, row_prefix=ix.pre3, zy2d=zy2, m_count=cnt3,
+                                               m_cap=ix.cap3, out=dh2)
+        # conv2^T: the 3x3 through the transposed neighbour table, then layer 1's chain
+        nbrT = transposed_neighbour_table(ix, B, Hi, Wi, stride, Ho, Wo)
+        dh1 = torch.empty(ix.cap1, W, device=dev)
+        ops.conv_rows(du2, w2r.permute(2, 1, 0).contiguous(), None, zW, dh1, a_rows=nbrT, taps=9, m_count=cnt1, m_cap=ix.cap1, relu=0)
+        du1, gt1, gs1n, gm1 = ops.rows_act_bwd(dh1, u1, s1, t1, post_sub=c1, chan_mask=chm2d, row_prefix=ix.pre1, zy2d=zy1, m_count=cnt1,
+                                               m_cap=ix.cap1, out=dh1)
+        grad_x = None
+        if need[0]:
+            gx = torch.zeros(B * Hi * Wi, Cin, device=dev)
+            ops.conv_rows(du1, w1r.reshape(W, Cin).t().reshape(Cin, 1, W).contiguous(), None, zC, gx, taps=1, m_count=cnt1, m_cap=ix.cap1,
+                          relu=0, out_rows=ix.idx1, residual2d=gx)
+            grad_x = ops.from_nhwc(gx.view(B, Hi, Wi, Cin))
+        # weight gradients: conv3 / conv2 see h = u + c at every channel (the constants of the masked ones included); rows past the counts are
+        # not read by the kernel and carry zero dY on the gather + GEMM path
+        gw1 = gw2 = gw3 = None
+        if need[3]:
+            h2f = u2 + c2
+            if _wgrad_kernel(W, cout, 1):
+                gw3 = (ops.wgrad_rows(g3, h2f, m_count=cnt3, m_cap=ix.cap3).view(cout, W) * s3.view(-1, 1)).reshape(cout, W, 1, 1)
+            else:
+                gw3 = ((g3.t() @ h2f) * s3.view(-1, 1)).reshape(cout, W, 1, 1)
+        if need[2]:
+            h1f = u1 + c1
+            if _wgrad_kernel(W, W, 9):
+                gw2 = ops.wgrad_rows(du2, h1f, a_rows=ix.nbr, taps=9, m_count=cnt3, m_cap=ix.cap3, a_valid=ix.cap1).permute(0, 2, 1).reshape(W, W, 3, 3)
+            else:
+                gw2 = _weight_grad_3x3(du2, h1f, ix.nbr, ix.cap1, ix.cnt[0])
+        if need[1] and _wgrad_kernel(Cin, W, 1):
+            gw1 = ops.wgrad_rows(du1, x2d, a_rows=ix.idx1, taps=1, m_count=cnt1, m_cap=ix.cap1).reshape(W, Cin, 1, 1)
+        elif need[1]:
+            rows1 = torch.where(torch.arange(ix.cap1, device=dev) < ix.cnt[1], ix.idx1.long(), torch.zeros_like(ix.idx1, dtype=torch.long))
+            gw1 = (du1.t() @ x2d[rows1.clamp(0, x2d.shape[0] - 1)]).reshape(W, Cin, 1, 1)
+        safe = lambda s: torch.where(s == 0, torch.ones_like(s), s)
+        gs1 = gs1n / safe(s1) if need[6] else None
+        gs2 = gs2n / safe(s2) if need[8] else None
+        # bn3 sits behind no ReLU: br - t3 = s3 * conv3(h2) at the kept pixels (t3c carries the constants' share)
+        y3s = torch.where(v3, ops.gather_rows(br, ix.idx3, count=cnt3, cap=ix.cap3) - t3, zero)
+        gs3 = (g3 * y3s).sum(0) / safe(s3) if need[10] else None
+        gt3 = g3.sum(0) if need[11] else None
+        gm = None
+        if need[4]:
+            # straight-through term of the pixel mask: the branch at the DROPPED pixels too, WITH the channel mask applied -- the same launches
+            # over the complement's lists
+            cix = ops.mask_to_index((1.0 - m3d).reshape(B, Ho, Wo).contiguous(), Ho, Wo, stride)
+            full = br.clone()
+            _BothBranchFn._chain(x2d, cix, geom, w1r, w2r, w3s.reshape(cout, 1, W).contiguous(), s1, t1, c1, s2, tab, c2, t3c, chm2d, full)
+            gm = (go * full).sum(dim=1).view(B, 1, Ho, Wo)
+        gc = gm1 + gm2 if need[5] else None
+        return grad_x, gw1, gw2, gw3, gm, gc, gs1, gt1 if need[7] else None, gs2, gt2 if need[9] else None, gs3, gt3, None
+
+
 # ------------------------------------------------------------------------------------------------------------------ blocks
 def _fold_live(bn):
     """(scale, shift) of a BatchNorm with FROZEN statistics as differentiable functions of its affine parameters."""
@@ -328,8 +473,9 @@ def _identity(block, x):
 
 def sparse_block_train(block, x, mask):
     """Differentiable forward of ONE Bottleneck under frozen BatchNorm statistics with its hard mask as an input.
-    dyn_mode 'spatial' / 'layer': mask [B, 1, S, S] {0,1};  dyn_mode 'channel': mask [B, G] {0,1}.  The mask may require grad (the hard Gumbel
-    sample of the masker's logits): it receives the straight-through term.  Returns the block's output."""
+    dyn_mode 'spatial' / 'layer': mask [B, 1, S, S] {0,1};  dyn_mode 'channel': mask [B, G] {0,1};  dyn_mode 'both': mask = the pair
+    (spatial [B, 1, S, S], channel [B, G]).  A mask may require grad (the hard Gumbel sample of the masker's logits): it receives the
+    straight-through term.  Returns the block's output."""
     _check_block(block, x)
     bn = _fold_live(block.bn1) + _fold_live(block.bn2) + _fold_live(block.bn3)
     if block.dyn_mode in ("spatial", "layer"):
@@ -345,8 +491,22 @@ def sparse_block_train(block, x, mask):
             raise LdnError("training: channel mask must be [B, G] with G * granularity == width")
         chm = mask.unsqueeze(2).expand(-1, -1, gran).reshape(mask.shape[0], W)            # group j owns channels [j * gran, (j + 1) * gran)
         branch = _ChannelBranchFn.apply(x, block.conv1.weight, block.conv2.weight, block.conv3.weight, chm, *bn, block.stride)
+    elif block.dyn_mode == "both":
+        if not isinstance(mask, (tuple, list)) or len(mask) != 2:
+            raise LdnError("training: a dyn_mode 'both' block takes mask = (spatial [B, 1, S, S], channel [B, G]), not a single tensor")
+        sm, cm = mask
+        W, gran = block.width, block.channel_dyn_granularity
+        if block.masker_spatial.mask_channel_group != 1 or sm.dim() != 4 or sm.shape[1] != 1 or sm.shape[0] != x.shape[0]:
+            raise LdnError("training: one spatial mask group ([B, 1, S, S])")
+        if cm.dim() != 2 or cm.shape[0] != x.shape[0] or cm.shape[1] * gran != W:
+            raise LdnError("training: channel mask must be [B, G] with G * granularity == width")
+        Hi, Wi = x.shape[2], x.shape[3]
+        Ho, Wo = (Hi - 1) // block.stride + 1, (Wi - 1) // block.stride + 1
+        m3 = F.interpolate(sm, size=(Ho, Wo), mode="nearest") if (sm.shape[2], sm.shape[3]) != (Ho, Wo) else sm
+        chm = cm.unsqueeze(2).expand(-1, -1, gran).reshape(cm.shape[0], W)
+        branch = _BothBranchFn.apply(x, block.conv1.weight, block.conv2.weight, block.conv3.weight, m3, chm, *bn, block.stride)
     else:
-        raise LdnError("training: dyn_mode 'spatial', 'layer' and 'channel' (the reference's detection configs); 'both' is not built")
+        raise LdnError(f"training: unknown dyn_mode {block.dyn_mode!r}")
     return F.relu(branch + _identity(block, x))
 
 
@@ -416,8 +576,25 @@ def block_train(block, state, temperature=1.0):
         s2, s1 = st[1], st[2]
         cs = one()
         block.last_spatial_mask = m.detach()
+    elif block.dyn_mode == "both":
+        # the channel mask is drawn FIRST, then the spatial mask: the reference's order of Gumbel noise (laud_resnet.py:102-103)
+        if block.forced_channel_mask is not None:
+            cmask = block.forced_channel_mask.to(x.dtype)
+            cs, c_flops = cmask.mean(), block.masker_channel.flops_for(x)
+        else:
+            cmask, cs, c_flops = sample_channel_mask(block, x, temperature)
+        if block.forced_spatial_mask is not None:
+            m = block.forced_spatial_mask.to(x.dtype)
+            s3, s_flops = m.mean(), block.masker_spatial.flops_for(x)
+        else:
+            m, s3, s_flops = sample_spatial_mask(block, x, temperature)
+        out = sparse_block_train(block, x, (m, cmask))
+        m3 = F.interpolate(m.detach(), size=(Ho, Wo), mode="nearest")
+        st = ops.mask_to_index(m3.reshape(x.shape[0], Ho, Wo).contiguous().float(), Ho, Wo, block.stride).stats
+        s2, s1 = st[1], st[2]
+        block.last_channel_mask, block.last_spatial_mask = cmask.detach(), m.detach()
     else:
-        raise LdnError("training: dyn_mode 'spatial', 'layer' and 'channel'")
+        raise LdnError(f"training: unknown dyn_mode {block.dyn_mode!r}")
     W, cin, cout = block.width, block.conv1.in_channels, block.conv3.out_channels
     macs = (cin * W, W * W * 9, W * cout)
     dense = c_flops + s_flops

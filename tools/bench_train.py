@@ -3,7 +3,10 @@
 kernels (laudnet_amd.training.train_forward) beside the oracle's dense emulation run through PyTorch on the same GPU.  One JSON line per workload;
 it names the weight-gradient path (`wgrad_kernel`: laudnet_amd.training.USE_WGRAD_KERNEL, env LDN_WGRAD=0 | 1) and the peak memory of ONE step on
 the row kernels (`peak_MiB_one_step`: torch.cuda.max_memory_allocated of a step of its own after the timed ones).
-usage: [LDN_WGRAD=0] tools/bench_train.py [--batch 32] [--steps 5] [--warmup 2] [--workloads layer,spatial,channel] [--no-reference]"""
+`both` is the reference's constructor default (pixel x channel masks: spatial S=4-4-2-1 and channel-2222 together), same model, batch and loss
+convention as the other three.  `ms_per_step` is the mean of the timed steps (wall clock over the loop), `ms_per_step_median` the median of the
+steps' own device-event intervals.
+usage: [LDN_WGRAD=0] tools/bench_train.py [--batch 32] [--steps 5] [--warmup 2] [--workloads layer,spatial,channel,both] [--no-reference]"""
 import argparse
 import json
 import os
@@ -32,8 +35,13 @@ ap.add_argument("--no-reference", action="store_true", help="time the row kernel
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
 ops.set_math_mode(args.math)
+WORKLOADS = dict(bench.WORKLOADS)
+WORKLOADS["both"] = dict(name="LAUD-ResNet101 both (spatial S=4-4-2-1 x channel-2222) @224",
+                         kw=dict(dyn_mode=["both"] * 4, mask_spatial_granularity=[4, 4, 2, 1], channel_dyn_granularity=[2, 2, 2, 2],
+                                 channel_masker=["MLP"] * 4, channel_masker_layers=[2, 2, 2, 2], reduction_ratio=[16] * 4),
+                         p_channel=0.62, p_spatial=0.5)
 for w in args.workloads.split(","):
-    wl = bench.WORKLOADS[w]
+    wl = WORKLOADS[w]
     kw = dict(wl["kw"], num_classes=1000, input_size=224)
     hip = laudnet_amd.uni_resnet101(**kw)
     sd = fill_state_dict(hip.state_dict(), 1)
@@ -71,11 +79,16 @@ for w in args.workloads.split(","):
         for _ in range(args.warmup):
             out = step(fwd, model)
         torch.cuda.synchronize()
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        marks[0].record()
+        for i in range(args.steps):
             out = step(fwd, model)
+            marks[i + 1].record()
         torch.cuda.synchronize()
-        res[name] = {"ms_per_step": 1e3 * (time.perf_counter() - t0) / args.steps, "mean_block_flops_ratio": round(float(out[5].detach().mean()), 4)}
+        per_step = sorted(a.elapsed_time(b) for a, b in zip(marks, marks[1:]))
+        res[name] = {"ms_per_step": 1e3 * (time.perf_counter() - t0) / args.steps, "ms_per_step_median": per_step[len(per_step) // 2],
+                     "mean_block_flops_ratio": round(float(out[5].detach().mean()), 4)}
         if name == "hip_row_kernels":      # one more step, alone between a reset and a read of the allocator's high-water mark
             out = None
             for p in model.parameters():
