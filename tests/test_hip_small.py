@@ -1,6 +1,13 @@
 """GPU parity of the one-launch small-map bottleneck (ldn_bottleneck_smallmap: conv1 -> conv2 3x3 -> conv3 + residual of a channel-mode
 block on a map of at most 64 pixels, h1 / h2 in LDS, bf16x3 arithmetic) against the dense-emulation algebra of the reference
-(laud_resnet.py:115-144, channel mask applied before BN).  Tolerance 2e-4 + 1e-4 relative on O(1) activations (north star: 1e-3)."""
+(laud_resnet.py:115-144, channel mask applied before BN) in float32 PyTorch.  Tolerance 2e-4 + 1e-4 relative on O(1) activations (north
+star: 1e-3).
+
+Coverage: eight shapes with cin = cout = 4 * width, each with Bernoulli masks at ONE keep rate plus an empty and a full image.  What a
+workgroup does depends on its image's count, and these draws reach four of the kernel's twelve ring geometries -- (nks2, d2, d3, nf) =
+(1,1,1,4), (1,3,2,3), (2,3,3,1), (2,3,3,2) -- and the counts 0, 330, 356, 512 at 7x7 x 512.  Every geometry, conv1 ring depth, subtile count, conv3
+body, short K loops, cout != 4 * width, residual=None and the 1- and 33-pixel maps, with forced counts and against float64:
+tests/test_hip_small_classes.py."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -42,8 +49,8 @@ def _block_pair(cin, W, gran, Ho):
     return blk, hb.to(DEV)
 
 
-# (B, H, Wd, W, gran, keep): stage 4 of the ResNets (7x7, width 512), every ring shape (keep 1.0 at width 512: single-slot rings; keep
-# 0.75: K16 chunks of conv2), maps of at most 32 pixels (the second pixel tile is empty), 64 pixels, non-square, small widths
+# (B, H, Wd, W, gran, keep): stage 4 of the ResNets (7x7, width 512; keep 1.0 at width 512: single-slot rings; keep 0.75: K16 chunks of
+# conv2 in a ring of three), maps of at most 32 pixels (the second pixel tile is empty), 64 pixels, non-square, small widths
 CASES = [(3, 7, 7, 512, 2, 0.62), (3, 7, 7, 512, 2, 1.0), (3, 7, 7, 512, 4, 0.75), (2, 7, 7, 256, 2, 0.62), (3, 4, 4, 64, 2, 0.62),
          (2, 8, 8, 128, 4, 0.5), (2, 5, 9, 192, 2, 0.62), (9, 7, 7, 384, 2, 0.3)]
 
