@@ -27,11 +27,13 @@ on the library's kernels:
       launches per layer, no floating-point atomics.  The pixel mask saves its FLOPs in both directions, the channel mask none.
   Weight gradients are the library's own kernel (`ops.wgrad_rows`: dW = sum over the packed rows of dY x A, the nine taps' rows gathered through
   the neighbour table inside the kernel, rows past the device-side count never read, deterministic) wherever `ops.wgrad_rows_ok` holds and
-  `USE_WGRAD_KERNEL` is on (the default; env LDN_WGRAD=0 turns it off); otherwise, and for other shapes, the gather + GEMM path; the gradients of BatchNorm's affine parameters come out of the folded
-  (scale, shift) pairs, which stay differentiable functions of (weight, bias); the straight-through terms of the hard masks need the branch at
-  DROPPED units too -- computed by the library's own dense execution (that term is dense in the reference as well).
-  The residual add, the final ReLU, the projection shortcut, the maskers' tiny heads, the static stem and the classifier are plain autograd
-  ops.
+  `USE_WGRAD_KERNEL` is on (the default; env LDN_WGRAD=0 turns it off); otherwise the gather + GEMM path.  BatchNorm's affine gradients come
+  out of the folded (scale, shift) pairs, which stay differentiable functions of (weight, bias); the straight-through terms of the hard masks
+  need the branch at DROPPED units too -- the library's own dense execution (that term is dense in the reference as well).  The residual add,
+  the final ReLU, the projection shortcut, the maskers' tiny heads, the static stem and the classifier are plain autograd ops.
+
+One `autograd.Function` per mask kind; what the three share (operand layouts, transposed convolutions, weight / BatchNorm / pixel-mask gradients,
+every division by a scale: `_safe`) is written once above them.  The index lists are built once per block forward (`_branch`) and handed to the Fn.
 
 Entry points: `sparse_block_train(block, x, mask)` (one block, the mask an input), `block_train(block, state, temperature)` (the reference's
 block signature in training mode: samples its own masks), `train_forward(model, x, temperature)` (a whole LAUD-ResNet -> the reference's
@@ -42,6 +44,7 @@ grouped / dilated conv2, BatchNorm in batch-statistics mode, LAD-RegNet."""
 from __future__ import annotations
 
 import os
+from collections import namedtuple
 
 import torch
 import torch.nn.functional as F
@@ -104,213 +107,29 @@ def _wgrad_kernel(cin, cout, taps):
     return USE_WGRAD_KERNEL and ops.wgrad_rows_ok(cin, cout, taps)
 
 
-# ------------------------------------------------------------------------------------------------------------------ pixel masks
-class _PixelBranchFn(torch.autograd.Function):
-    """branch = m3 * (s3 * conv3(relu(s2 * conv2(relu(s1 * conv1(x) + t1)) + t2)) + t3)  on the packed rows of the kept pixels (NCHW out, zeros at
-    the dropped pixels).  Differentiable in x, the three weights, the six folded BatchNorm vectors and the mask."""
-
-    @staticmethod
-    def forward(ctx, x, w1, w2, w3, m3, s1, t1, s2, t2, s3, t3, stride):
-        B, Cin, Hi, Wi = x.shape
-        Ho, Wo = m3.shape[2], m3.shape[3]
-        W, cout = w1.shape[0], w3.shape[0]
-        dev = x.device
-        xn = ops.as_nhwc(x.detach())
-        x2d = xn.reshape(B * Hi * Wi, Cin)
-        ix = ops.mask_to_index(m3.detach().reshape(B, Ho, Wo).contiguous().float(), Ho, Wo, stride)
-        s1, t1, s2, t2, s3, t3 = (v.detach().float().contiguous() for v in (s1, t1, s2, t2, s3, t3))
-        w1r = w1.detach().reshape(W, 1, Cin).float().contiguous()
-        w2r = w2.detach().permute(0, 2, 3, 1).reshape(W, 9, W).float().contiguous()
-        w3r = w3.detach().reshape(cout, W).float()
-        w3s = (w3r * s3.view(-1, 1)).reshape(cout, 1, W).contiguous()
-        h1 = torch.zeros(ix.cap1, W, device=dev)
-        ops.conv_rows(x2d, w1r, s1, t1, h1, a_rows=ix.idx1, taps=1, m_count=ix.cnt[1:2], m_cap=ix.cap1)
-        h2 = torch.zeros(ix.cap3, W, device=dev)
-        ops.conv_rows(h1, w2r, s2, t2, h2, a_rows=ix.nbr, taps=9, m_count=ix.cnt[0:1], m_cap=ix.cap3)
-        br = torch.zeros(B * Ho * Wo, cout, device=dev)
-        ops.conv_rows(h2, w3s, None, t3, br, taps=1, m_count=ix.cnt[0:1], m_cap=ix.cap3, relu=0, out_rows=ix.idx3)
-        ctx.save_for_backward(x2d, h1, h2, br, w1r, w2r, w3r, s1, t1, s2, t2, s3, t3, m3.detach().float())
-        ctx.ix, ctx.shape, ctx.stride = ix, (B, Cin, Hi, Wi, Ho, Wo, W, cout), stride
-        return ops.from_nhwc(br.view(B, Ho, Wo, cout))
-
-    @staticmethod
-    def backward(ctx, g):
-        x2d, h1, h2, br, w1r, w2r, w3r, s1, t1, s2, t2, s3, t3, m3d = ctx.saved_tensors
-        ix, stride = ctx.ix, ctx.stride
-        B, Cin, Hi, Wi, Ho, Wo, W, cout = ctx.shape
-        dev = g.device
-        need = ctx.needs_input_grad
-        go = ops.as_nhwc(g.contiguous()).reshape(B * Ho * Wo, cout)
-        zW, zC = torch.zeros(W, device=dev), torch.zeros(Cin, device=dev)
-        v3, v1 = _rows_valid(ix.cap3, ix.cnt[0], dev), _rows_valid(ix.cap1, ix.cnt[1], dev)
-        # conv3^T on the active rows
-        # (the gather leaves the rows past the count unwritten -- recycled memory, possibly NaN: select, do not multiply)
-        g3 = torch.where(v3 > 0, ops.gather_rows(go, ix.idx3, count=ix.cnt[0:1], cap=ix.cap3), zW[:1])          # d L / d (s3 y3 + t3) at the kept pixels
-        w3s = w3r * s3.view(-1, 1)
-        dh2 = torch.zeros(ix.cap3, W, device=dev)
-        ops.conv_rows(g3, w3s.t().reshape(W, 1, cout).contiguous(), None, zW, dh2, taps=1, m_count=ix.cnt[0:1], m_cap=ix.cap3, relu=0)
-        dz2 = dh2 * (h2 > 0) * v3                         # through ReLU: d L / d (s2 y2 + t2)
-        du2 = dz2 * s2
-        # conv2^T: the 3x3 through the transposed neighbour table
-        nbrT = transposed_neighbour_table(ix, B, Hi, Wi, stride, Ho, Wo)
-        dh1 = torch.zeros(ix.cap1, W, device=dev)
-        ops.conv_rows(du2, w2r.permute(2, 1, 0).contiguous(), None, zW, dh1, a_rows=nbrT, taps=9, m_count=ix.cnt[1:2], m_cap=ix.cap1, relu=0)
-        dz1 = dh1 * (h1 > 0) * v1
-        du1 = dz1 * s1
-        grad_x = None
-        if need[0]:
-            gx = torch.zeros(B * Hi * Wi, Cin, device=dev)
-            ops.conv_rows(du1, w1r.reshape(W, Cin).t().reshape(Cin, 1, W).contiguous(), None, zC, gx, taps=1, m_count=ix.cnt[1:2], m_cap=ix.cap1,
-                          relu=0, out_rows=ix.idx1, residual2d=gx)
-            grad_x = ops.from_nhwc(gx.view(B, Hi, Wi, Cin))
-        # weight gradients: ldn_wgrad_rows over the packed rows (it reads no row past the counts); shapes outside its predicate keep the
-        # gather + GEMM path (which relies on g3 / du2 / du1 being zero past the counts)
-        gw1 = gw2 = gw3 = None
-        if need[3]:
-            if _wgrad_kernel(W, cout, 1):
-                gw3 = (ops.wgrad_rows(g3, h2, m_count=ix.cnt[0:1], m_cap=ix.cap3).view(cout, W) * s3.view(-1, 1)).reshape(cout, W, 1, 1)
-            else:
-                gw3 = ((g3.t() @ h2) * s3.view(-1, 1)).reshape(cout, W, 1, 1)
-        if need[2]:
-            if _wgrad_kernel(W, W, 9):
-                gw2 = ops.wgrad_rows(du2, h1, a_rows=ix.nbr, taps=9, m_count=ix.cnt[0:1], m_cap=ix.cap3, a_valid=ix.cap1).permute(0, 2, 1).reshape(W, W, 3, 3)
-            else:
-                gw2 = _weight_grad_3x3(du2, h1, ix.nbr, ix.cap1, ix.cnt[0])
-        if need[1] and _wgrad_kernel(Cin, W, 1):
-            gw1 = ops.wgrad_rows(du1, x2d, a_rows=ix.idx1, taps=1, m_count=ix.cnt[1:2], m_cap=ix.cap1).reshape(W, Cin, 1, 1)
-        elif need[1]:
-            rows1 = torch.where(v1.squeeze(1) > 0, ix.idx1.long(), torch.zeros_like(ix.idx1, dtype=torch.long)).clamp(0, x2d.shape[0] - 1)
-            gw1 = (du1.t() @ x2d[rows1]).reshape(W, Cin, 1, 1)      # (list entries past the count are uninitialised: du1 is zero there)
-        # folded BatchNorm vectors: z = s y + t  =>  d t = sum d z,  d s = sum d z * y,  y = (z - t) / s wherever d z != 0 (there z = the stored ReLU output)
-        safe = lambda s: torch.where(s == 0, torch.ones_like(s), s)
-        gs1 = (dz1 * (h1 - t1)).sum(0) / safe(s1) if need[5] else None
-        gt1 = dz1.sum(0) if need[6] else None
-        gs2 = (dz2 * (h2 - t2)).sum(0) / safe(s2) if need[7] else None
-        gt2 = dz2.sum(0) if need[8] else None
-        y3s = torch.where(v3 > 0, ops.gather_rows(br, ix.idx3, count=ix.cnt[0:1], cap=ix.cap3) - t3, zW[:1])       # = s3 * y3 at the kept pixels
-        gs3 = (g3 * y3s).sum(0) / safe(s3) if need[9] else None
-        gt3 = g3.sum(0) if need[10] else None
-        gm = None
-        if need[4]:
-            # straight-through term of the hard mask: d L / d m3[p] = sum_c g[p, c] * (s3 conv3(..) + t3)[p, c] needs the branch at the DROPPED pixels
-            # too (that term is dense in the reference as well).  The kept pixels' branch is `br`; the dropped ones' comes from the same three
-            # launches over the COMPLEMENT's lists -- together one dense execution of the block, of which the forward already paid the kept part.
-            cix = ops.mask_to_index((1.0 - m3d).reshape(B, Ho, Wo).contiguous(), Ho, Wo, stride)
-            d1 = torch.zeros(cix.cap1, W, device=dev)
-            ops.conv_rows(x2d, w1r, s1, t1, d1, a_rows=cix.idx1, taps=1, m_count=cix.cnt[1:2], m_cap=cix.cap1)
-            d2 = torch.zeros(cix.cap3, W, device=dev)
-            ops.conv_rows(d1, w2r, s2, t2, d2, a_rows=cix.nbr, taps=9, m_count=cix.cnt[0:1], m_cap=cix.cap3)
-            full = br.clone()
-            ops.conv_rows(d2, w3s.reshape(cout, 1, W).contiguous(), None, t3, full, taps=1, m_count=cix.cnt[0:1], m_cap=cix.cap3, relu=0, out_rows=cix.idx3)
-            gm = (go * full).sum(dim=1).view(B, 1, Ho, Wo)
-        return grad_x, gw1, gw2, gw3, gm, gs1, gt1, gs2, gt2, gs3, gt3, None
+# ------------------------------------------------------------------------------------------------------------------ shared by the three branch Fns
+_Prep = namedtuple("_Prep", "x2d w1r w2r w3r w3s bn shape")
 
 
-# ------------------------------------------------------------------------------------------------------------------ channel masks
-class _ChannelBranchFn(torch.autograd.Function):
-    """branch = s3 * conv3(relu(s2 * (c . conv2(relu(s1 * (c . conv1(x)) + t1))) + t2)) + t3  with a {0,1} channel mask c [B, W] applied before bn1 / bn2
-    (laud_resnet.py:116-118,124-126), on the row kernels over all pixels: u = relu(bn(.)) - relu(shift) is stored, zeroed on the masked channels
-    of each image (the library's dense channel execution, _shared.dense_channel_convs -- what Bottleneck._run_channel_dense runs)."""
-
-    @staticmethod
-    def forward(ctx, x, w1, w2, w3, chm, s1, t1, s2, t2, s3, t3, stride):
-        B, Cin, Hi, Wi = x.shape
-        Ho, Wo = (Hi - 1) // stride + 1, (Wi - 1) // stride + 1
-        W, cout = w1.shape[0], w3.shape[0]
-        dev = x.device
-        xn = ops.as_nhwc(x.detach())
-        x2d = xn.reshape(B * Hi * Wi, Cin)
-        s1, t1, s2, t2, s3, t3 = (v.detach().float().contiguous() for v in (s1, t1, s2, t2, s3, t3))
-        w2f, w3f = w2.detach().float(), w3.detach().float()
-        c1, c2, tab, t3c = channel_constants(w2f, w3f, s2, t2, t1, s3, t3)
-        w1r = w1.detach().reshape(W, 1, Cin).float().contiguous()
-        w2r = w2f.permute(0, 2, 3, 1).reshape(W, 9, W).contiguous()
-        w3r = w3f.reshape(cout, W)
-        w3s = (w3r * s3.view(-1, 1)).reshape(cout, 1, W).contiguous()
-        chm2d = chm.detach().float().reshape(B, W).contiguous()
-        ix = dense_index(B, Ho, Wo, stride, dev)
-        h1, h2 = dense_channel_convs(x2d, B, (Hi, Wi, Ho, Wo, stride), w1r, w2r, s1, t1, c1, s2, tab, c2, chm2d, ix)
-        br = torch.empty(B * Ho * Wo, cout, device=dev)
-        ops.conv_rows(h2, w3s, None, t3c, br, taps=1, m_cap=ix.cap3, relu=0)
-        ctx.save_for_backward(x2d, h1, h2, br, w1r, w2r, w3r, s1, t1, s2, t2, s3, t3, chm2d, c1, c2, tab)
-        ctx.ix, ctx.shape, ctx.stride = ix, (B, Cin, Hi, Wi, Ho, Wo, W, cout), stride
-        return ops.from_nhwc(br.view(B, Ho, Wo, cout))
-
-    @staticmethod
-    def backward(ctx, g):
-        x2d, u1, u2, br, w1r, w2r, w3r, s1, t1, s2, t2, s3, t3, chm2d, c1, c2, tab = ctx.saved_tensors
-        ix, stride = ctx.ix, ctx.stride
-        B, Cin, Hi, Wi, Ho, Wo, W, cout = ctx.shape
-        dev = g.device
-        need = ctx.needs_input_grad
-        go = ops.as_nhwc(g.contiguous()).reshape(B * Ho * Wo, cout)
-        zW, zC = torch.zeros(W, device=dev), torch.zeros(Cin, device=dev)
-        cm3 = chm2d.view(B, 1, W)
-        per_img = lambda t2d: t2d.view(B, -1, W)
-        # forward values with the masks applied: h = u + c at every channel (a masked channel is the constant c), z > 0 <=> h > 0
-        h1f, h2f = u1 + c1, u2 + c2
-        on1 = (per_img(h1f) > 0).float()
-        on2 = (per_img(h2f) > 0).float()
-        w3s = w3r * s3.view(-1, 1)
-        dh2 = torch.empty(ix.cap3, W, device=dev)                     # d L / d h2 at EVERY channel
-        ops.conv_rows(go, w3s.t().reshape(W, 1, cout).contiguous(), None, zW, dh2, taps=1, m_cap=ix.cap3, relu=0)
-        dz2_all = per_img(dh2) * on2                                  # d L / d z2 (z2 = s2 * (c . y2) + t2)
-        dz2 = (dz2_all * cm3).reshape(-1, W)
-        du2 = dz2 * s2                                                # d L / d y2 on the active channels
-        nbrT = transposed_neighbour_table(ix, B, Hi, Wi, stride, Ho, Wo)
-        dh1 = torch.empty(ix.cap1, W, device=dev)                     # d L / d h1 at every channel
-        ops.conv_rows(du2, w2r.permute(2, 1, 0).contiguous(), None, zW, dh1, a_rows=nbrT, taps=9, m_cap=ix.cap1, relu=0)
-        dz1_all = per_img(dh1) * on1
-        dz1 = (dz1_all * cm3).reshape(-1, W)
-        du1 = dz1 * s1
-        grad_x = None
-        if need[0]:
-            gx = torch.zeros(B * Hi * Wi, Cin, device=dev)
-            ops.conv_rows(du1, w1r.reshape(W, Cin).t().reshape(Cin, 1, W).contiguous(), None, zC, gx, taps=1, m_cap=ix.cap1, relu=0,
-                          out_rows=ix.idx1, residual2d=gx)
-            grad_x = ops.from_nhwc(gx.view(B, Hi, Wi, Cin))
-        gw1 = gw2 = gw3 = None
-        if need[3]:     # conv3 sees h2 = u2 + c2 at every channel (the constants of the masked ones included)
-            if _wgrad_kernel(W, cout, 1):
-                gw3 = (ops.wgrad_rows(go, h2f, m_cap=ix.cap3).view(cout, W) * s3.view(-1, 1)).reshape(cout, W, 1, 1)
-            else:
-                gw3 = ((go.t() @ h2f) * s3.view(-1, 1)).reshape(cout, W, 1, 1)
-        if need[2]:     # conv2 sees h1 = u1 + c1 inside the map, zeros in the padding ring
-            if _wgrad_kernel(W, W, 9):
-                gw2 = ops.wgrad_rows(du2, h1f, a_rows=ix.nbr, taps=9, m_cap=ix.cap3, a_valid=ix.cap1).permute(0, 2, 1).reshape(W, W, 3, 3)
-            else:
-                gw2 = _weight_grad_3x3(du2, h1f, ix.nbr, ix.cap1)
-        if need[1] and _wgrad_kernel(Cin, W, 1):
-            gw1 = ops.wgrad_rows(du1, x2d, a_rows=ix.idx1, taps=1, m_cap=ix.cap1).reshape(W, Cin, 1, 1)
-        elif need[1]:
-            gw1 = (du1.t() @ x2d[ix.idx1.long().clamp(0, x2d.shape[0] - 1)]).reshape(W, Cin, 1, 1)
-        safe = lambda s: torch.where(s == 0, torch.ones_like(s), s)
-        # z = s (c . y) + t: d t sums d z over EVERY channel's pixels (a masked channel's z = t still feeds the ReLU); d s only sees active channels
-        gs1 = (dz1 * (h1f - t1)).sum(0) / safe(s1) if need[5] else None
-        gt1 = dz1_all.reshape(-1, W).sum(0) if need[6] else None
-        gs2 = (dz2 * (h2f - t2)).sum(0) / safe(s2) if need[7] else None
-        gt2 = dz2_all.reshape(-1, W).sum(0) if need[8] else None
-        gs3 = (go * (br - t3)).sum(0) / safe(s3) if need[9] else None
-        gt3 = go.sum(0) if need[10] else None
-        gc = None
-        if need[4]:
-            # straight-through term: d L / d c[b, k] = sum_p d L / d (c . y)[b, k, p] * y[b, k, p] for both masked products, y = the UNMASKED conv
-            # output -- needed at the masked channels too: the library's dense execution without the mask (z = s y + t, no ReLU)
-            r1 = torch.empty(ix.cap1, W, device=dev)
-            ops.conv_rows(x2d, w1r, s1, t1, r1, a_rows=ix.idx1, taps=1, m_cap=ix.cap1, relu=0)
-            y1 = (r1 - t1) / safe(s1)
-            r2 = torch.empty(ix.cap3, W, device=dev)
-            # (conv2 of h1 = u1 + c1: the constants' share is the border-class table)
-            if ops.dense_kernel_ok() and W % 32 == 0 and 9 in ops.DENSE_TAPS and ops.DENSE_CHANNEL_3X3:
-                ops.conv_rows(u1, w2r, s2, tab, r2, a_rows=ix.nbr, taps=9, m_cap=ix.cap3, pix_map=ix.idx3, geom=(Hi, Wi, Ho, Wo, stride), relu=0)
-            else:
-                ops.conv_packed(u1, w2r, s2, tab, r2, a_map=ix.nbr, taps=9, m_cap=ix.cap3, pix_map=ix.idx3, geom=(Hi, Wi, Ho, Wo, stride), relu=0)
-            y2 = (r2 - t2) / safe(s2)
-            gc = (dz1_all * s1 * per_img(y1)).sum(1) + (dz2_all * s2 * per_img(y2)).sum(1)          # [B, W]
-        return grad_x, gw1, gw2, gw3, gc, gs1, gt1, gs2, gt2, gs3, gt3, None
+def _fold_w3(w3r, s3):
+    """conv3's weights with bn3's scale folded in, in conv_rows' layout [cout, 1, W] (recomputed in the backward rather than saved)."""
+    return (w3r * s3.view(-1, 1)).reshape(w3r.shape[0], 1, w3r.shape[1]).contiguous()
 
 
-# ------------------------------------------------------------------------------------------------------------------ pixel x channel masks
+def _prep(x, w1, w2, w3, bn6, stride):
+    """What every branch Fn's forward starts from, detached, fp32, in the row kernels' layouts: x2d [B Hi Wi, Cin] (NHWC rows), w1r [W, 1, Cin],
+    w2r [W, 9, W] (tap-major), w3r [cout, W], w3s = _fold_w3, bn = (s1, t1, s2, t2, s3, t3), shape = (B, Cin, Hi, Wi, Ho, Wo, W, cout)."""
+    B, Cin, Hi, Wi = x.shape
+    Ho, Wo = (Hi - 1) // stride + 1, (Wi - 1) // stride + 1
+    W, cout = w1.shape[0], w3.shape[0]
+    x2d = ops.as_nhwc(x.detach()).reshape(B * Hi * Wi, Cin)
+    bn = tuple(v.detach().float().contiguous() for v in bn6)
+    w1r = w1.detach().reshape(W, 1, Cin).float().contiguous()
+    w2r = w2.detach().float().permute(0, 2, 3, 1).reshape(W, 9, W).contiguous()
+    w3r = w3.detach().float().reshape(cout, W)
+    return _Prep(x2d, w1r, w2r, w3r, _fold_w3(w3r, bn[4]), bn, (B, Cin, Hi, Wi, Ho, Wo, W, cout))
+
+
 def _conv_const(a2d, w, scale, shift, out2d, *, a_rows, taps, m_count, m_cap, relu, post_sub=None, pix_map=None, geom=None):
     """A packed-row convolution with the epilogue terms of the channel algebra (post-ReLU constant, border-class shift table): k_dense where the
     arithmetic mode and the widths put conv_rows there, else the same terms on conv_packed (one image = the whole list).  Rows past the
@@ -323,9 +142,240 @@ def _conv_const(a2d, w, scale, shift, out2d, *, a_rows, taps, m_count, m_cap, re
                            pix_map=pix_map, geom=geom)
 
 
+def _conv3_T(dy, w3s, zW, m_count, m_cap, alloc):
+    """conv3^T: d L / d h2 [m_cap, W] from d L / d (s3 y3 + t3) on the same rows (m_count = None: every row).  alloc = torch.zeros where the rows
+    past the count -- never written -- are multiplied later, torch.empty where they are not read."""
+    cout, _, W = w3s.shape
+    dh2 = alloc(m_cap, W, device=dy.device)
+    ops.conv_rows(dy, w3s.view(cout, W).t().reshape(W, 1, cout).contiguous(), None, zW, dh2, taps=1, m_count=m_count, m_cap=m_cap, relu=0)
+    return dh2
+
+
+def _conv2_T(du2, w2r, zW, ix, shape, stride, m_count, alloc):
+    """conv2^T: d L / d h1 [cap1, W] on the rows of the dilated list, the 3x3 through the transposed neighbour table (m_count, alloc: as _conv3_T)"""
+    B, _, Hi, Wi, Ho, Wo, W, _ = shape
+    nbrT = transposed_neighbour_table(ix, B, Hi, Wi, stride, Ho, Wo)
+    dh1 = alloc(ix.cap1, W, device=du2.device)
+    ops.conv_rows(du2, w2r.permute(2, 1, 0).contiguous(), None, zW, dh1, a_rows=nbrT, taps=9, m_count=m_count, m_cap=ix.cap1, relu=0)
+    return dh1
+
+
+def _grad_x(du1, w1r, ix, m_count, shape):
+    """conv1^T scattered into a zeroed input map -> d L / d x [B, Cin, Hi, Wi].  m_count = None: the dense channel case (every row)."""
+    (B, Cin, Hi, Wi), W, dev = shape[:4], w1r.shape[0], du1.device
+    gx = torch.zeros(B * Hi * Wi, Cin, device=dev)
+    ops.conv_rows(du1, w1r.reshape(W, Cin).t().reshape(Cin, 1, W).contiguous(), None, torch.zeros(Cin, device=dev), gx, taps=1, m_count=m_count,
+                  m_cap=ix.cap1, relu=0, out_rows=ix.idx1, residual2d=gx)
+    return ops.from_nhwc(gx.view(B, Hi, Wi, Cin))
+
+
+def _weight_grads(want1, want2, want3, dy3, h2, du2, h1, du1, x2d, ix, s3, counted, consts=None):
+    """(d W1, d W2, d W3), None where not wanted, from d L / d (conv output) dy3 / du2 / du1 and the convs' inputs h2 / h1 / x2d: ldn_wgrad_rows, or
+    the gather + GEMM path for shapes outside its predicate and with the switch off.  counted: the lists are a pixel mask's -- the kernel gets the
+    device-side counts and reads no row past them; the GEMM path relies on dy3 / du2 / du1 being zero there (select, then clamp: the list entries
+    are uninitialised).  Not counted (the channel Fn's dense lists): every row is live.  consts = (c1, c2) where h1 / h2 are stored as u = h - c
+    (the both Fn): conv2 / conv3 see h at every channel, the constants of the masked ones included."""
+    W, Cin, cout = h1.shape[1], x2d.shape[1], dy3.shape[1]
+    cnt3, cnt1 = (ix.cnt[0:1], ix.cnt[1:2]) if counted else (None, None)
+    gw1 = gw2 = gw3 = None
+    if want3:
+        h2 = h2 if consts is None else h2 + consts[1]
+        if _wgrad_kernel(W, cout, 1):
+            gw3 = (ops.wgrad_rows(dy3, h2, m_count=cnt3, m_cap=ix.cap3).view(cout, W) * s3.view(-1, 1)).reshape(cout, W, 1, 1)
+        else:
+            gw3 = ((dy3.t() @ h2) * s3.view(-1, 1)).reshape(cout, W, 1, 1)
+    if want2:       # conv2 sees h1 inside the map, zeros in the padding ring
+        h1 = h1 if consts is None else h1 + consts[0]
+        if _wgrad_kernel(W, W, 9):
+            gw2 = ops.wgrad_rows(du2, h1, a_rows=ix.nbr, taps=9, m_count=cnt3, m_cap=ix.cap3, a_valid=ix.cap1).permute(0, 2, 1).reshape(W, W, 3, 3)
+        else:
+            gw2 = _weight_grad_3x3(du2, h1, ix.nbr, ix.cap1, ix.cnt[0] if counted else None)
+    if want1:
+        if _wgrad_kernel(Cin, W, 1):
+            gw1 = ops.wgrad_rows(du1, x2d, a_rows=ix.idx1, taps=1, m_count=cnt1, m_cap=ix.cap1).reshape(W, Cin, 1, 1)
+        else:
+            rows1 = ix.idx1.long() if not counted else torch.where(torch.arange(ix.cap1, device=du1.device) < ix.cnt[1], ix.idx1.long(),
+                                                                   torch.zeros_like(ix.idx1, dtype=torch.long))
+            gw1 = (du1.t() @ x2d[rows1.clamp(0, x2d.shape[0] - 1)]).reshape(W, Cin, 1, 1)
+    return gw1, gw2, gw3
+
+
+def _safe(s):
+    """a folded BatchNorm scale as a divisor: 1 where it is 0"""
+    return torch.where(s == 0, torch.ones_like(s), s)
+
+
+def _bn_grads(want_s, want_t, dz, dz_shift, h, s, t):
+    """(d s, d t) of a folded BatchNorm in front of a ReLU, z = s y + t: d t = sum d z, d s = sum d z * y with y = (z - t) / s wherever d z != 0
+    (there z = h, the stored ReLU output).  dz_shift = the d z that d t sums: under a channel mask every channel's, while d s sees the active ones."""
+    return (dz * (h - t)).sum(0) / _safe(s) if want_s else None, dz_shift.sum(0) if want_t else None
+
+
+def _bn3_grads(want_s, want_t, dy3, br, s3, t3, kept=None):
+    """(d s3, d t3): bn3 sits behind no ReLU, br - t3 = s3 * conv3(h2) on the rows that were computed.  dy3 = d L / d (s3 y3 + t3) on the rows of
+    br, or with kept = (ix, valid [cap3, 1] bool, a zero to select) on the packed rows of the kept pixels, whose br rows are gathered."""
+    if kept is None:
+        y3s = br - t3 if want_s else None
+    else:
+        ix, valid, zero = kept
+        y3s = torch.where(valid, ops.gather_rows(br, ix.idx3, count=ix.cnt[0:1], cap=ix.cap3) - t3, zero)
+    return (dy3 * y3s).sum(0) / _safe(s3) if want_s else None, dy3.sum(0) if want_t else None
+
+
+def _pixel_lists(m3, stride):
+    """the packed index lists of a pixel mask m3 [B, 1, Ho, Wo] {0,1} at the block's output size"""
+    B, _, Ho, Wo = m3.shape
+    return ops.mask_to_index(m3.detach().reshape(B, Ho, Wo).contiguous().float(), Ho, Wo, stride)
+
+
+def _pixel_mask_grad(go, br, m3d, stride, run_chain):
+    """Straight-through term of the hard pixel mask: d L / d m3[p] = sum_c g[p, c] * (s3 conv3(..) + t3)[p, c] needs the branch at the DROPPED
+    pixels too (that term is dense in the reference as well).  The kept pixels' branch is `br`; the dropped ones' comes from the Fn's own chain,
+    run_chain(cix, full), over the COMPLEMENT's lists into a copy of br -- together one dense execution of the block, of which the forward
+    already paid the kept part."""
+    B, _, Ho, Wo = m3d.shape
+    cix = ops.mask_to_index((1.0 - m3d).reshape(B, Ho, Wo).contiguous(), Ho, Wo, stride)
+    full = br.clone()
+    run_chain(cix, full)
+    return (go * full).sum(dim=1).view(B, 1, Ho, Wo)
+
+
+# ------------------------------------------------------------------------------------------------------------------ pixel masks
+def _pixel_chain(x2d, ix, w1r, w2r, w3s, s1, t1, s2, t2, t3, br):
+    """conv1 -> conv2 -> conv3 over the lists of ix, conv3 scattered into br.  -> (h1, h2), ZEROED first: the rows past the counts are never
+    written and are multiplied in the backward."""
+    W, dev = w1r.shape[0], x2d.device
+    h1 = torch.zeros(ix.cap1, W, device=dev)
+    ops.conv_rows(x2d, w1r, s1, t1, h1, a_rows=ix.idx1, taps=1, m_count=ix.cnt[1:2], m_cap=ix.cap1)
+    h2 = torch.zeros(ix.cap3, W, device=dev)
+    ops.conv_rows(h1, w2r, s2, t2, h2, a_rows=ix.nbr, taps=9, m_count=ix.cnt[0:1], m_cap=ix.cap3)
+    ops.conv_rows(h2, w3s, None, t3, br, taps=1, m_count=ix.cnt[0:1], m_cap=ix.cap3, relu=0, out_rows=ix.idx3)
+    return h1, h2
+
+
+class _PixelBranchFn(torch.autograd.Function):
+    """branch = m3 * (s3 * conv3(relu(s2 * conv2(relu(s1 * conv1(x) + t1)) + t2)) + t3)  on the packed rows of the kept pixels (NCHW out, zeros at
+    the dropped pixels); ix = _pixel_lists(m3).  Differentiable in x, the three weights, the six folded BatchNorm vectors and the mask."""
+
+    @staticmethod
+    def forward(ctx, x, w1, w2, w3, m3, s1, t1, s2, t2, s3, t3, stride, ix):
+        p = _prep(x, w1, w2, w3, (s1, t1, s2, t2, s3, t3), stride)
+        B, _, _, _, Ho, Wo, _, cout = p.shape
+        s1, t1, s2, t2, s3, t3 = p.bn
+        br = torch.zeros(B * Ho * Wo, cout, device=x.device)
+        h1, h2 = _pixel_chain(p.x2d, ix, p.w1r, p.w2r, p.w3s, s1, t1, s2, t2, t3, br)
+        ctx.save_for_backward(p.x2d, h1, h2, br, p.w1r, p.w2r, p.w3r, *p.bn, m3.detach().float())
+        ctx.ix, ctx.shape, ctx.stride = ix, p.shape, stride
+        return ops.from_nhwc(br.view(B, Ho, Wo, cout))
+
+    @staticmethod
+    def backward(ctx, g):
+        x2d, h1, h2, br, w1r, w2r, w3r, s1, t1, s2, t2, s3, t3, m3d = ctx.saved_tensors
+        ix, shape, stride, need, dev = ctx.ix, ctx.shape, ctx.stride, ctx.needs_input_grad, g.device
+        cnt3, cnt1 = ix.cnt[0:1], ix.cnt[1:2]
+        go = ops.as_nhwc(g.contiguous()).reshape(-1, w3r.shape[0])              # [B Ho Wo, cout]
+        zW = torch.zeros(w1r.shape[0], device=dev)
+        v3, v1 = _rows_valid(ix.cap3, ix.cnt[0], dev), _rows_valid(ix.cap1, ix.cnt[1], dev)
+        # d L / d (s3 y3 + t3) at the kept pixels (the gather leaves the rows past the count unwritten -- recycled memory, possibly NaN: select,
+        # do not multiply)
+        g3 = torch.where(v3 > 0, ops.gather_rows(go, ix.idx3, count=cnt3, cap=ix.cap3), zW[:1])
+        w3s = _fold_w3(w3r, s3)
+        dh2 = _conv3_T(g3, w3s, zW, cnt3, ix.cap3, torch.zeros)
+        dz2 = dh2 * (h2 > 0) * v3                         # through ReLU: d L / d (s2 y2 + t2)
+        du2 = dz2 * s2
+        dh1 = _conv2_T(du2, w2r, zW, ix, shape, stride, cnt1, torch.zeros)
+        dz1 = dh1 * (h1 > 0) * v1
+        du1 = dz1 * s1
+        grad_x = _grad_x(du1, w1r, ix, cnt1, shape) if need[0] else None
+        gw1, gw2, gw3 = _weight_grads(need[1], need[2], need[3], g3, h2, du2, h1, du1, x2d, ix, s3, counted=True)
+        gs1, gt1 = _bn_grads(need[5], need[6], dz1, dz1, h1, s1, t1)
+        gs2, gt2 = _bn_grads(need[7], need[8], dz2, dz2, h2, s2, t2)
+        gs3, gt3 = _bn3_grads(need[9], need[10], g3, br, s3, t3, kept=(ix, v3 > 0, zW[:1]))
+        chain = lambda cix, full: _pixel_chain(x2d, cix, w1r, w2r, w3s, s1, t1, s2, t2, t3, full)
+        gm = _pixel_mask_grad(go, br, m3d, stride, chain) if need[4] else None
+        return grad_x, gw1, gw2, gw3, gm, gs1, gt1, gs2, gt2, gs3, gt3, None, None
+
+
+# ------------------------------------------------------------------------------------------------------------------ channel masks
+class _ChannelBranchFn(torch.autograd.Function):
+    """branch = s3 * conv3(relu(s2 * (c . conv2(relu(s1 * (c . conv1(x)) + t1))) + t2)) + t3  with a {0,1} channel mask c [B, W] applied before bn1 / bn2
+    (laud_resnet.py:116-118,124-126), on the row kernels over all pixels (ix = the cached dense_index): u = relu(bn(.)) - relu(shift) is stored,
+    zeroed on the masked channels of each image (the library's dense channel execution, _shared.dense_channel_convs -- what
+    Bottleneck._run_channel_dense runs)."""
+
+    @staticmethod
+    def forward(ctx, x, w1, w2, w3, chm, s1, t1, s2, t2, s3, t3, stride, ix):
+        p = _prep(x, w1, w2, w3, (s1, t1, s2, t2, s3, t3), stride)
+        B, _, Hi, Wi, Ho, Wo, W, cout = p.shape
+        s1, t1, s2, t2, s3, t3 = p.bn
+        c1, c2, tab, t3c = channel_constants(w2.detach().float(), p.w3r, s2, t2, t1, s3, t3)
+        chm2d = chm.detach().float().reshape(B, W).contiguous()
+        h1, h2 = dense_channel_convs(p.x2d, B, (Hi, Wi, Ho, Wo, stride), p.w1r, p.w2r, s1, t1, c1, s2, tab, c2, chm2d, ix)
+        br = torch.empty(B * Ho * Wo, cout, device=x.device)
+        ops.conv_rows(h2, p.w3s, None, t3c, br, taps=1, m_cap=ix.cap3, relu=0)
+        ctx.save_for_backward(p.x2d, h1, h2, br, p.w1r, p.w2r, p.w3r, *p.bn, chm2d, c1, c2, tab)
+        ctx.ix, ctx.shape, ctx.stride = ix, p.shape, stride
+        return ops.from_nhwc(br.view(B, Ho, Wo, cout))
+
+    @staticmethod
+    def backward(ctx, g):
+        x2d, u1, u2, br, w1r, w2r, w3r, s1, t1, s2, t2, s3, t3, chm2d, c1, c2, tab = ctx.saved_tensors
+        ix, shape, stride, need, dev = ctx.ix, ctx.shape, ctx.stride, ctx.needs_input_grad, g.device
+        B, _, Hi, Wi, Ho, Wo, W, _ = shape
+        go = ops.as_nhwc(g.contiguous()).reshape(-1, w3r.shape[0])              # [B Ho Wo, cout]
+        zW = torch.zeros(W, device=dev)
+        cm3 = chm2d.view(B, 1, W)
+        per_img = lambda t2d: t2d.view(B, -1, W)
+        # forward values with the masks applied: h = u + c at every channel (a masked channel is the constant c), z > 0 <=> h > 0
+        h1f, h2f = u1 + c1, u2 + c2
+        on1 = (per_img(h1f) > 0).float()
+        on2 = (per_img(h2f) > 0).float()
+        dh2 = _conv3_T(go, _fold_w3(w3r, s3), zW, None, ix.cap3, torch.empty)
+        dz2_all = per_img(dh2) * on2                                  # d L / d z2 (z2 = s2 * (c . y2) + t2)
+        dz2 = (dz2_all * cm3).reshape(-1, W)
+        du2 = dz2 * s2                                                # d L / d y2 on the active channels
+        dh1 = _conv2_T(du2, w2r, zW, ix, shape, stride, None, torch.empty)
+        dz1_all = per_img(dh1) * on1
+        dz1 = (dz1_all * cm3).reshape(-1, W)
+        du1 = dz1 * s1
+        grad_x = _grad_x(du1, w1r, ix, None, shape) if need[0] else None
+        gw1, gw2, gw3 = _weight_grads(need[1], need[2], need[3], go, h2f, du2, h1f, du1, x2d, ix, s3, counted=False)
+        # z = s (c . y) + t: d t sums d z over EVERY channel's pixels (a masked channel's z = t still feeds the ReLU); d s only sees active channels
+        gs1, gt1 = _bn_grads(need[5], need[6], dz1, dz1_all.reshape(-1, W), h1f, s1, t1)
+        gs2, gt2 = _bn_grads(need[7], need[8], dz2, dz2_all.reshape(-1, W), h2f, s2, t2)
+        gs3, gt3 = _bn3_grads(need[9], need[10], go, br, s3, t3)
+        gc = None
+        if need[4]:
+            # straight-through term: d L / d c[b, k] = sum_p d L / d (c . y)[b, k, p] * y[b, k, p] for both masked products, y = the UNMASKED conv
+            # output -- needed at the masked channels too: the library's dense execution without the mask (z = s y + t, no ReLU)
+            r1 = torch.empty(ix.cap1, W, device=dev)
+            ops.conv_rows(x2d, w1r, s1, t1, r1, a_rows=ix.idx1, taps=1, m_cap=ix.cap1, relu=0)
+            y1 = (r1 - t1) / _safe(s1)
+            r2 = torch.empty(ix.cap3, W, device=dev)
+            # (conv2 of h1 = u1 + c1: the constants' share is the border-class table)
+            _conv_const(u1, w2r, s2, tab, r2, a_rows=ix.nbr, taps=9, m_count=None, m_cap=ix.cap3, relu=0, pix_map=ix.idx3, geom=(Hi, Wi, Ho, Wo, stride))
+            y2 = (r2 - t2) / _safe(s2)
+            gc = (dz1_all * s1 * per_img(y1)).sum(1) + (dz2_all * s2 * per_img(y2)).sum(1)          # [B, W]
+        return grad_x, gw1, gw2, gw3, gc, gs1, gt1, gs2, gt2, gs3, gt3, None, None
+
+
+# ------------------------------------------------------------------------------------------------------------------ pixel x channel masks
+def _both_chain(x2d, ix, geom, w1r, w2r, w3s, s1, t1, c1, s2, tab, c2, t3c, chm2d, br):
+    """conv1 -> conv2 -> conv3 over the lists of ix with the channel mask applied, conv3 scattered into br.  -> (u1, u2)"""
+    W, dev = w1r.shape[0], x2d.device
+    u1 = torch.empty(ix.cap1, W, device=dev)
+    _conv_const(x2d, w1r, s1, t1, u1, a_rows=ix.idx1, taps=1, m_count=ix.cnt[1:2], m_cap=ix.cap1, relu=1, post_sub=c1)
+    ops.rows_chanmask(u1, ix.pre1, chm2d, m_count=ix.cnt[1:2], m_cap=ix.cap1)          # (also zeroes the rows past the count)
+    u2 = torch.empty(ix.cap3, W, device=dev)
+    _conv_const(u1, w2r, s2, tab, u2, a_rows=ix.nbr, taps=9, m_count=ix.cnt[0:1], m_cap=ix.cap3, relu=1, post_sub=c2, pix_map=ix.idx3, geom=geom)
+    ops.rows_chanmask(u2, ix.pre3, chm2d, m_count=ix.cnt[0:1], m_cap=ix.cap3)
+    ops.conv_rows(u2, w3s, None, t3c, br, taps=1, m_count=ix.cnt[0:1], m_cap=ix.cap3, relu=0, out_rows=ix.idx3)
+    return u1, u2
+
+
 class _BothBranchFn(torch.autograd.Function):
     """branch = m3 * (s3 * conv3(relu(s2 * (c . conv2(relu(s1 * (c . conv1(x)) + t1))) + t2)) + t3)  (dyn_mode 'both', laud_resnet.py:101-147): the pixel
-    mask's packed rows (the index lists of _PixelBranchFn, any stride) with the channel algebra of _ChannelBranchFn on them.  DENSE in the
+    mask's packed rows (ix = _pixel_lists(m3), any stride) with the channel algebra of _ChannelBranchFn on them.  DENSE in the
     channels: conv_rows over every channel of the packed rows, u = relu(bn(.)) - relu(shift) stored, the masked channels of each row's image
     zeroed by ops.rows_chanmask (the image of a packed row comes from the lists' per-image prefix) -- the pixel mask saves its FLOPs in both
     directions, the channel mask saves none (stated, as for channel mode).  The constants' share of conv2 is the border-class table: every
@@ -335,56 +385,33 @@ class _BothBranchFn(torch.autograd.Function):
     folded BatchNorm vectors, the pixel mask and the channel mask."""
 
     @staticmethod
-    def _chain(x2d, ix, geom, w1r, w2r, w3s, s1, t1, c1, s2, tab, c2, t3c, chm2d, br):
-        """conv1 -> conv2 -> conv3 over the lists of ix, conv3 scattered into br.  -> (u1, u2)"""
-        W = w1r.shape[0]
-        dev = x2d.device
-        u1 = torch.empty(ix.cap1, W, device=dev)
-        _conv_const(x2d, w1r, s1, t1, u1, a_rows=ix.idx1, taps=1, m_count=ix.cnt[1:2], m_cap=ix.cap1, relu=1, post_sub=c1)
-        ops.rows_chanmask(u1, ix.pre1, chm2d, m_count=ix.cnt[1:2], m_cap=ix.cap1)          # (also zeroes the rows past the count)
-        u2 = torch.empty(ix.cap3, W, device=dev)
-        _conv_const(u1, w2r, s2, tab, u2, a_rows=ix.nbr, taps=9, m_count=ix.cnt[0:1], m_cap=ix.cap3, relu=1, post_sub=c2, pix_map=ix.idx3, geom=geom)
-        ops.rows_chanmask(u2, ix.pre3, chm2d, m_count=ix.cnt[0:1], m_cap=ix.cap3)
-        ops.conv_rows(u2, w3s, None, t3c, br, taps=1, m_count=ix.cnt[0:1], m_cap=ix.cap3, relu=0, out_rows=ix.idx3)
-        return u1, u2
-
-    @staticmethod
-    def forward(ctx, x, w1, w2, w3, m3, chm, s1, t1, s2, t2, s3, t3, stride):
-        B, Cin, Hi, Wi = x.shape
-        Ho, Wo = m3.shape[2], m3.shape[3]
-        W, cout = w1.shape[0], w3.shape[0]
-        dev = x.device
-        x2d = ops.as_nhwc(x.detach()).reshape(B * Hi * Wi, Cin)
-        ix = ops.mask_to_index(m3.detach().reshape(B, Ho, Wo).contiguous().float(), Ho, Wo, stride)
-        s1, t1, s2, t2, s3, t3 = (v.detach().float().contiguous() for v in (s1, t1, s2, t2, s3, t3))
-        w2f, w3f = w2.detach().float(), w3.detach().float()
-        c1, c2, tab, t3c = channel_constants(w2f, w3f, s2, t2, t1, s3, t3)
-        w1r = w1.detach().reshape(W, 1, Cin).float().contiguous()
-        w2r = w2f.permute(0, 2, 3, 1).reshape(W, 9, W).contiguous()
-        w3r = w3f.reshape(cout, W)
-        w3s = (w3r * s3.view(-1, 1)).reshape(cout, 1, W).contiguous()
+    def forward(ctx, x, w1, w2, w3, m3, chm, s1, t1, s2, t2, s3, t3, stride, ix):
+        p = _prep(x, w1, w2, w3, (s1, t1, s2, t2, s3, t3), stride)
+        B, _, Hi, Wi, Ho, Wo, W, cout = p.shape
+        s1, t1, s2, t2, s3, t3 = p.bn
+        c1, c2, tab, t3c = channel_constants(w2.detach().float(), p.w3r, s2, t2, t1, s3, t3)
         chm2d = chm.detach().float().reshape(B, W).contiguous()
-        br = torch.zeros(B * Ho * Wo, cout, device=dev)
-        u1, u2 = _BothBranchFn._chain(x2d, ix, (Hi, Wi, Ho, Wo, stride), w1r, w2r, w3s, s1, t1, c1, s2, tab, c2, t3c, chm2d, br)
-        ctx.save_for_backward(x2d, u1, u2, br, w1r, w2r, w3r, s1, t1, s2, t2, s3, t3, m3.detach().float(), chm2d, c1, c2, tab, t3c)
-        ctx.ix, ctx.shape, ctx.stride = ix, (B, Cin, Hi, Wi, Ho, Wo, W, cout), stride
+        br = torch.zeros(B * Ho * Wo, cout, device=x.device)
+        u1, u2 = _both_chain(p.x2d, ix, (Hi, Wi, Ho, Wo, stride), p.w1r, p.w2r, p.w3s, s1, t1, c1, s2, tab, c2, t3c, chm2d, br)
+        ctx.save_for_backward(p.x2d, u1, u2, br, p.w1r, p.w2r, p.w3r, *p.bn, m3.detach().float(), chm2d, c1, c2, tab, t3c)
+        ctx.ix, ctx.shape, ctx.stride = ix, p.shape, stride
         return ops.from_nhwc(br.view(B, Ho, Wo, cout))
 
     @staticmethod
     def backward(ctx, g):
         x2d, u1, u2, br, w1r, w2r, w3r, s1, t1, s2, t2, s3, t3, m3d, chm2d, c1, c2, tab, t3c = ctx.saved_tensors
-        ix, stride = ctx.ix, ctx.stride
-        B, Cin, Hi, Wi, Ho, Wo, W, cout = ctx.shape
+        ix, shape, stride = ctx.ix, ctx.shape, ctx.stride
+        _, _, Hi, Wi, Ho, Wo, W, _ = shape
         dev = g.device
-        need = ctx.needs_input_grad
+        need = ctx.needs_input_grad          # (x, w1, w2, w3, m3, chm, s1, t1, s2, t2, s3, t3): one further along than the other two Fns from chm on
         geom = (Hi, Wi, Ho, Wo, stride)
         cnt3, cnt1 = ix.cnt[0:1], ix.cnt[1:2]
-        go = ops.as_nhwc(g.contiguous()).reshape(B * Ho * Wo, cout)
-        zW, zC = torch.zeros(W, device=dev), torch.zeros(Cin, device=dev)
+        go = ops.as_nhwc(g.contiguous()).reshape(-1, w3r.shape[0])              # [B Ho Wo, cout]
+        zW = torch.zeros(W, device=dev)
         v3 = _rows_valid(ix.cap3, ix.cnt[0], dev) > 0
         zero = torch.zeros((), device=dev)
-        g3 = torch.where(v3, ops.gather_rows(go, ix.idx3, count=cnt3, cap=ix.cap3), zero)     # d L / d (s3 y3 + t3) at the kept pixels (the gather leaves the rows past the count unwritten)
-        w3s = w3r * s3.view(-1, 1)
+        g3 = torch.where(v3, ops.gather_rows(go, ix.idx3, count=cnt3, cap=ix.cap3), zero)     # d L / d (s3 y3 + t3) at the kept pixels (as in _PixelBranchFn)
+        w3s = _fold_w3(w3r, s3)
         zy1 = zy2 = None
         if need[5]:
             # the channel mask's straight-through term needs the UNMASKED conv outputs at the masked channels too: two relu=0 launches on the same
@@ -393,60 +420,22 @@ class _BothBranchFn(torch.autograd.Function):
             _conv_const(x2d, w1r, s1, t1, zy1, a_rows=ix.idx1, taps=1, m_count=cnt1, m_cap=ix.cap1, relu=0)
             zy2 = torch.empty(ix.cap3, W, device=dev)
             _conv_const(u1, w2r, s2, tab, zy2, a_rows=ix.nbr, taps=9, m_count=cnt3, m_cap=ix.cap3, relu=0, pix_map=ix.idx3, geom=geom)
-        # conv3^T on the kept rows, then layer 2's elementwise chain + reductions in one kernel
-        dh2 = torch.empty(ix.cap3, W, device=dev)                     # d L / d h2 at EVERY channel
-        ops.conv_rows(g3, w3s.t().reshape(W, 1, cout).contiguous(), None, zW, dh2, taps=1, m_count=cnt3, m_cap=ix.cap3, relu=0)
+        # conv3^T on the kept rows, then layer 2's elementwise chain + reductions in one kernel; likewise conv2^T and layer 1's
+        dh2 = _conv3_T(g3, w3s, zW, cnt3, ix.cap3, torch.empty)
         du2, gt2, gs2n, gm2 = ops.rows_act_bwd(dh2, u2, s2, t2, post_sub=c2, chan_mask=chm2d, row_prefix=ix.pre3, zy2d=zy2, m_count=cnt3,
                                                m_cap=ix.cap3, out=dh2)
-        # conv2^T: the 3x3 through the transposed neighbour table, then layer 1's chain
-        nbrT = transposed_neighbour_table(ix, B, Hi, Wi, stride, Ho, Wo)
-        dh1 = torch.empty(ix.cap1, W, device=dev)
-        ops.conv_rows(du2, w2r.permute(2, 1, 0).contiguous(), None, zW, dh1, a_rows=nbrT, taps=9, m_count=cnt1, m_cap=ix.cap1, relu=0)
+        dh1 = _conv2_T(du2, w2r, zW, ix, shape, stride, cnt1, torch.empty)
         du1, gt1, gs1n, gm1 = ops.rows_act_bwd(dh1, u1, s1, t1, post_sub=c1, chan_mask=chm2d, row_prefix=ix.pre1, zy2d=zy1, m_count=cnt1,
                                                m_cap=ix.cap1, out=dh1)
-        grad_x = None
-        if need[0]:
-            gx = torch.zeros(B * Hi * Wi, Cin, device=dev)
-            ops.conv_rows(du1, w1r.reshape(W, Cin).t().reshape(Cin, 1, W).contiguous(), None, zC, gx, taps=1, m_count=cnt1, m_cap=ix.cap1,
-                          relu=0, out_rows=ix.idx1, residual2d=gx)
-            grad_x = ops.from_nhwc(gx.view(B, Hi, Wi, Cin))
-        # weight gradients: conv3 / conv2 see h = u + c at every channel (the constants of the masked ones included); rows past the counts are
-        # not read by the kernel and carry zero dY on the gather + GEMM path
-        gw1 = gw2 = gw3 = None
-        if need[3]:
-            h2f = u2 + c2
-            if _wgrad_kernel(W, cout, 1):
-                gw3 = (ops.wgrad_rows(g3, h2f, m_count=cnt3, m_cap=ix.cap3).view(cout, W) * s3.view(-1, 1)).reshape(cout, W, 1, 1)
-            else:
-                gw3 = ((g3.t() @ h2f) * s3.view(-1, 1)).reshape(cout, W, 1, 1)
-        if need[2]:
-            h1f = u1 + c1
-            if _wgrad_kernel(W, W, 9):
-                gw2 = ops.wgrad_rows(du2, h1f, a_rows=ix.nbr, taps=9, m_count=cnt3, m_cap=ix.cap3, a_valid=ix.cap1).permute(0, 2, 1).reshape(W, W, 3, 3)
-            else:
-                gw2 = _weight_grad_3x3(du2, h1f, ix.nbr, ix.cap1, ix.cnt[0])
-        if need[1] and _wgrad_kernel(Cin, W, 1):
-            gw1 = ops.wgrad_rows(du1, x2d, a_rows=ix.idx1, taps=1, m_count=cnt1, m_cap=ix.cap1).reshape(W, Cin, 1, 1)
-        elif need[1]:
-            rows1 = torch.where(torch.arange(ix.cap1, device=dev) < ix.cnt[1], ix.idx1.long(), torch.zeros_like(ix.idx1, dtype=torch.long))
-            gw1 = (du1.t() @ x2d[rows1.clamp(0, x2d.shape[0] - 1)]).reshape(W, Cin, 1, 1)
-        safe = lambda s: torch.where(s == 0, torch.ones_like(s), s)
-        gs1 = gs1n / safe(s1) if need[6] else None
-        gs2 = gs2n / safe(s2) if need[8] else None
-        # bn3 sits behind no ReLU: br - t3 = s3 * conv3(h2) at the kept pixels (t3c carries the constants' share)
-        y3s = torch.where(v3, ops.gather_rows(br, ix.idx3, count=cnt3, cap=ix.cap3) - t3, zero)
-        gs3 = (g3 * y3s).sum(0) / safe(s3) if need[10] else None
-        gt3 = g3.sum(0) if need[11] else None
-        gm = None
-        if need[4]:
-            # straight-through term of the pixel mask: the branch at the DROPPED pixels too, WITH the channel mask applied -- the same launches
-            # over the complement's lists
-            cix = ops.mask_to_index((1.0 - m3d).reshape(B, Ho, Wo).contiguous(), Ho, Wo, stride)
-            full = br.clone()
-            _BothBranchFn._chain(x2d, cix, geom, w1r, w2r, w3s.reshape(cout, 1, W).contiguous(), s1, t1, c1, s2, tab, c2, t3c, chm2d, full)
-            gm = (go * full).sum(dim=1).view(B, 1, Ho, Wo)
+        grad_x = _grad_x(du1, w1r, ix, cnt1, shape) if need[0] else None
+        gw1, gw2, gw3 = _weight_grads(need[1], need[2], need[3], g3, u2, du2, u1, du1, x2d, ix, s3, counted=True, consts=(c1, c2))
+        gs1 = gs1n / _safe(s1) if need[6] else None
+        gs2 = gs2n / _safe(s2) if need[8] else None
+        gs3, gt3 = _bn3_grads(need[10], need[11], g3, br, s3, t3, kept=(ix, v3, zero))        # (t3c carries the constants' share)
+        chain = lambda cix, full: _both_chain(x2d, cix, geom, w1r, w2r, w3s, s1, t1, c1, s2, tab, c2, t3c, chm2d, full)     # WITH the channel mask
+        gm = _pixel_mask_grad(go, br, m3d, stride, chain) if need[4] else None
         gc = gm1 + gm2 if need[5] else None
-        return grad_x, gw1, gw2, gw3, gm, gc, gs1, gt1 if need[7] else None, gs2, gt2 if need[9] else None, gs3, gt3, None
+        return grad_x, gw1, gw2, gw3, gm, gc, gs1, gt1 if need[7] else None, gs2, gt2 if need[9] else None, gs3, gt3, None, None
 
 
 # ------------------------------------------------------------------------------------------------------------------ blocks
@@ -471,43 +460,57 @@ def _identity(block, x):
     return x if block.downsample is None else block.downsample(x)      # (conv 1x1 stride s + BatchNorm on frozen statistics: plain autograd)
 
 
+def _out_size(block, x):
+    return (x.shape[2] - 1) // block.stride + 1, (x.shape[3] - 1) // block.stride + 1
+
+
+def _spatial_m3(block, x, mask):
+    """a block's spatial mask [B, 1, S, S], checked, at the size of the block's output (nearest, laud_resnet.py:106)"""
+    if block.masker_spatial.mask_channel_group != 1 or mask.dim() != 4 or mask.shape[1] != 1 or mask.shape[0] != x.shape[0]:
+        raise LdnError("training: one spatial mask group ([B, 1, S, S])")
+    size = _out_size(block, x)
+    return F.interpolate(mask, size=size, mode="nearest") if (mask.shape[2], mask.shape[3]) != size else mask
+
+
+def _expand_channel_mask(block, x, mask):
+    """a block's channel mask [B, G], checked, per channel [B, W]: group j owns channels [j * gran, (j + 1) * gran)"""
+    W, gran = block.width, block.channel_dyn_granularity
+    if mask.dim() != 2 or mask.shape[0] != x.shape[0] or mask.shape[1] * gran != W:
+        raise LdnError("training: channel mask must be [B, G] with G * granularity == width")
+    return mask.unsqueeze(2).expand(-1, -1, gran).reshape(mask.shape[0], W)
+
+
+def _branch(block, x, mask):
+    """sparse_block_train -> (out, ix): ix = the index lists the block ran on, built ONCE per forward -- the Fn gets them as an argument and
+    block_train reads the dilated masks' means off the same object."""
+    _check_block(block, x)
+    bn = _fold_live(block.bn1) + _fold_live(block.bn2) + _fold_live(block.bn3)
+    w = (block.conv1.weight, block.conv2.weight, block.conv3.weight)
+    if block.dyn_mode in ("spatial", "layer"):
+        m3 = _spatial_m3(block, x, mask)
+        ix = _pixel_lists(m3, block.stride)
+        branch = _PixelBranchFn.apply(x, *w, m3, *bn, block.stride, ix)
+    elif block.dyn_mode == "channel":
+        chm = _expand_channel_mask(block, x, mask)
+        ix = dense_index(x.shape[0], *_out_size(block, x), block.stride, x.device)
+        branch = _ChannelBranchFn.apply(x, *w, chm, *bn, block.stride, ix)
+    elif block.dyn_mode == "both":
+        if not isinstance(mask, (tuple, list)) or len(mask) != 2:
+            raise LdnError("training: a dyn_mode 'both' block takes mask = (spatial [B, 1, S, S], channel [B, G]), not a single tensor")
+        m3, chm = _spatial_m3(block, x, mask[0]), _expand_channel_mask(block, x, mask[1])
+        ix = _pixel_lists(m3, block.stride)
+        branch = _BothBranchFn.apply(x, *w, m3, chm, *bn, block.stride, ix)
+    else:
+        raise LdnError(f"training: unknown dyn_mode {block.dyn_mode!r}")
+    return F.relu(branch + _identity(block, x)), ix
+
+
 def sparse_block_train(block, x, mask):
     """Differentiable forward of ONE Bottleneck under frozen BatchNorm statistics with its hard mask as an input.
     dyn_mode 'spatial' / 'layer': mask [B, 1, S, S] {0,1};  dyn_mode 'channel': mask [B, G] {0,1};  dyn_mode 'both': mask = the pair
     (spatial [B, 1, S, S], channel [B, G]).  A mask may require grad (the hard Gumbel sample of the masker's logits): it receives the
     straight-through term.  Returns the block's output."""
-    _check_block(block, x)
-    bn = _fold_live(block.bn1) + _fold_live(block.bn2) + _fold_live(block.bn3)
-    if block.dyn_mode in ("spatial", "layer"):
-        if block.masker_spatial.mask_channel_group != 1 or mask.dim() != 4 or mask.shape[1] != 1:
-            raise LdnError("training: one spatial mask group ([B, 1, S, S])")
-        Hi, Wi = x.shape[2], x.shape[3]
-        Ho, Wo = (Hi - 1) // block.stride + 1, (Wi - 1) // block.stride + 1
-        m3 = F.interpolate(mask, size=(Ho, Wo), mode="nearest") if (mask.shape[2], mask.shape[3]) != (Ho, Wo) else mask     # laud_resnet.py:106
-        branch = _PixelBranchFn.apply(x, block.conv1.weight, block.conv2.weight, block.conv3.weight, m3, *bn, block.stride)
-    elif block.dyn_mode == "channel":
-        W, gran = block.width, block.channel_dyn_granularity
-        if mask.dim() != 2 or mask.shape[1] * gran != W:
-            raise LdnError("training: channel mask must be [B, G] with G * granularity == width")
-        chm = mask.unsqueeze(2).expand(-1, -1, gran).reshape(mask.shape[0], W)            # group j owns channels [j * gran, (j + 1) * gran)
-        branch = _ChannelBranchFn.apply(x, block.conv1.weight, block.conv2.weight, block.conv3.weight, chm, *bn, block.stride)
-    elif block.dyn_mode == "both":
-        if not isinstance(mask, (tuple, list)) or len(mask) != 2:
-            raise LdnError("training: a dyn_mode 'both' block takes mask = (spatial [B, 1, S, S], channel [B, G]), not a single tensor")
-        sm, cm = mask
-        W, gran = block.width, block.channel_dyn_granularity
-        if block.masker_spatial.mask_channel_group != 1 or sm.dim() != 4 or sm.shape[1] != 1 or sm.shape[0] != x.shape[0]:
-            raise LdnError("training: one spatial mask group ([B, 1, S, S])")
-        if cm.dim() != 2 or cm.shape[0] != x.shape[0] or cm.shape[1] * gran != W:
-            raise LdnError("training: channel mask must be [B, G] with G * granularity == width")
-        Hi, Wi = x.shape[2], x.shape[3]
-        Ho, Wo = (Hi - 1) // block.stride + 1, (Wi - 1) // block.stride + 1
-        m3 = F.interpolate(sm, size=(Ho, Wo), mode="nearest") if (sm.shape[2], sm.shape[3]) != (Ho, Wo) else sm
-        chm = cm.unsqueeze(2).expand(-1, -1, gran).reshape(cm.shape[0], W)
-        branch = _BothBranchFn.apply(x, block.conv1.weight, block.conv2.weight, block.conv3.weight, m3, chm, *bn, block.stride)
-    else:
-        raise LdnError(f"training: unknown dyn_mode {block.dyn_mode!r}")
-    return F.relu(branch + _identity(block, x))
+    return _branch(block, x, mask)[0]
 
 
 def _gumbel_hard(logits2, temperature):
@@ -543,55 +546,49 @@ def sample_channel_mask(block, x, temperature):
     return mask, mask.mean(), flops
 
 
+def _draw_channel(block, x, temperature):
+    """the block's channel mask -- forced_channel_mask, else a hard Gumbel sample of its masker -> (mask [B, G], sparsity, flops)"""
+    if block.forced_channel_mask is None:
+        return sample_channel_mask(block, x, temperature)
+    mask = block.forced_channel_mask.to(x.dtype)
+    return mask, mask.mean(), block.masker_channel.flops_for(x)
+
+
+def _draw_spatial(block, x, temperature):
+    """the block's spatial mask, likewise -> (mask [B, 1, S, S], sparsity, flops)"""
+    if block.forced_spatial_mask is None:
+        return sample_spatial_mask(block, x, temperature)
+    mask = block.forced_spatial_mask.to(x.dtype)
+    return mask, mask.mean(), block.masker_spatial.flops_for(x)
+
+
 def block_train(block, state, temperature=1.0):
     """Bottleneck.forward of the reference in TRAINING mode (laud_resnet.py:88-165) under frozen BatchNorm statistics: samples the block's hard
     masks from its maskers' logits (forced_*_mask is honoured), runs the convolutions on the row kernels and keeps the reference's bookkeeping
     (sparsity lists, FLOPs ratio, running FLOPs) differentiable where the reference's is (channel sparsity, conv3's spatial sparsity)."""
     x, s3l, s2l, s1l, csl, percl, flops = state
-    dev = x.device
-    one = lambda: torch.tensor(1.0, device=dev)
+    one = lambda: torch.tensor(1.0, device=x.device)
     c_flops = s_flops = 0
     Hi, Wi = x.shape[2], x.shape[3]
-    Ho, Wo = (Hi - 1) // block.stride + 1, (Wi - 1) // block.stride + 1
-    s1 = s2 = s3 = cs = None
+    Ho, Wo = _out_size(block, x)
     if block.dyn_mode == "channel":
-        if block.forced_channel_mask is not None:
-            cmask = block.forced_channel_mask.to(x.dtype)
-            cs, c_flops = cmask.mean(), block.masker_channel.flops_for(x)
-        else:
-            cmask, cs, c_flops = sample_channel_mask(block, x, temperature)
-        out = sparse_block_train(block, x, cmask)
+        cmask, cs, c_flops = _draw_channel(block, x, temperature)
+        out, _ = _branch(block, x, cmask)
         s1, s2, s3 = one(), one(), one()
         block.last_channel_mask = cmask.detach()
     elif block.dyn_mode in ("spatial", "layer"):
-        if block.forced_spatial_mask is not None:
-            m = block.forced_spatial_mask.to(x.dtype)
-            s3, s_flops = m.mean(), block.masker_spatial.flops_for(x)
-        else:
-            m, s3, s_flops = sample_spatial_mask(block, x, temperature)
-        out = sparse_block_train(block, x, m)
-        # the dilated masks' means (ExpandMask, laud_resnet.py:107-110: thresholded, no gradient) come out of the list build
-        m3 = F.interpolate(m.detach(), size=(Ho, Wo), mode="nearest")
-        st = ops.mask_to_index(m3.reshape(x.shape[0], Ho, Wo).contiguous().float(), Ho, Wo, block.stride).stats
-        s2, s1 = st[1], st[2]
+        m, s3, s_flops = _draw_spatial(block, x, temperature)
+        out, ix = _branch(block, x, m)
+        # the dilated masks' means (ExpandMask, laud_resnet.py:107-110: thresholded, no gradient) come out of the block's own list build
+        s2, s1 = ix.stats[1], ix.stats[2]
         cs = one()
         block.last_spatial_mask = m.detach()
     elif block.dyn_mode == "both":
         # the channel mask is drawn FIRST, then the spatial mask: the reference's order of Gumbel noise (laud_resnet.py:102-103)
-        if block.forced_channel_mask is not None:
-            cmask = block.forced_channel_mask.to(x.dtype)
-            cs, c_flops = cmask.mean(), block.masker_channel.flops_for(x)
-        else:
-            cmask, cs, c_flops = sample_channel_mask(block, x, temperature)
-        if block.forced_spatial_mask is not None:
-            m = block.forced_spatial_mask.to(x.dtype)
-            s3, s_flops = m.mean(), block.masker_spatial.flops_for(x)
-        else:
-            m, s3, s_flops = sample_spatial_mask(block, x, temperature)
-        out = sparse_block_train(block, x, (m, cmask))
-        m3 = F.interpolate(m.detach(), size=(Ho, Wo), mode="nearest")
-        st = ops.mask_to_index(m3.reshape(x.shape[0], Ho, Wo).contiguous().float(), Ho, Wo, block.stride).stats
-        s2, s1 = st[1], st[2]
+        cmask, cs, c_flops = _draw_channel(block, x, temperature)
+        m, s3, s_flops = _draw_spatial(block, x, temperature)
+        out, ix = _branch(block, x, (m, cmask))
+        s2, s1 = ix.stats[1], ix.stats[2]
         block.last_channel_mask, block.last_spatial_mask = cmask.detach(), m.detach()
     else:
         raise LdnError(f"training: unknown dyn_mode {block.dyn_mode!r}")

@@ -120,6 +120,57 @@ def test_training_scope_is_enforced():
         sparse_block_train(make_block(Bottleneck, fx), block_input(fx), fx["channel_mask"].float())
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("mask_grad", [True, False], ids=["mask_grad", "mask_const"])
+@pytest.mark.parametrize("name", ["spatial_g1_s1", "layer_s2", "both_s2", "channel_g2_s2"])
+def test_block_train_builds_the_pixel_lists_once(name, mask_grad, monkeypatch):
+    """block_train builds a block's pixel lists ONCE per forward (the branch Fn runs on them and the dilated masks' means s2 / s1 are read off
+    the same object), once more in the backward -- the complement's lists -- iff the pixel mask requires grad, and for a channel block never:
+    its all-active lists are _shared.dense_index's, cached per shape (built here before the count starts).  A wrapper around ops.mask_to_index
+    counts.  s2, s1 must equal the statistics of a list build made directly from the same mask."""
+    import torch.nn.functional as F
+    from laudnet_amd import ops
+    from laudnet_amd._shared import dense_index
+    from laudnet_amd.laud_resnet import Bottleneck
+    from laudnet_amd.training import block_train
+    fx = BLOCKS[name]
+    mode, stride = fx["kw"]["dyn_mode"], fx["kw"]["stride"]
+    blk = make_block(Bottleneck, fx).to(DEV)
+    x = block_input(fx).to(DEV).requires_grad_(True)
+    B, Ho, Wo = x.shape[0], (x.shape[2] - 1) // stride + 1, (x.shape[3] - 1) // stride + 1
+    want = None
+    if mode in ("channel", "both"):
+        blk.forced_channel_mask = fx["channel_mask"].float().to(DEV)
+        dense_index(B, Ho, Wo, stride, x.device)
+    if mode != "channel":
+        sm = fx["spatial_mask"].float().to(DEV).clone()
+        assert (sm < 0.5).any(), "the fixture must drop pixels"
+        m3 = F.interpolate(sm, size=(Ho, Wo), mode="nearest")
+        want = ops.mask_to_index(m3.reshape(B, Ho, Wo).contiguous(), Ho, Wo, stride).stats[1:3].clone()
+        blk.forced_spatial_mask = sm.requires_grad_(mask_grad)
+    real, calls = ops.mask_to_index, []
+
+    def counted(*args, **kwargs):
+        calls.append(args[1:])
+        return real(*args, **kwargs)
+
+    monkeypatch.setattr(ops, "mask_to_index", counted)
+    res = block_train(blk, _start(x), 1.0)
+    built = 0 if mode == "channel" else 1
+    assert len(calls) == built, f"{len(calls)} list builds in the forward, expected {built}: {calls}"
+    res[0].backward(seeded_randn(tuple(res[0].shape), 77).to(DEV))
+    torch.cuda.synchronize()
+    more = 1 if (mode != "channel" and mask_grad) else 0
+    assert len(calls) == built + more, f"{len(calls) - built} list builds in the backward, expected {more}: {calls}"
+    assert x.grad is not None and bool(torch.isfinite(x.grad).all())
+    s2, s1 = res[2][-1].detach(), res[3][-1].detach()
+    if mode == "channel":
+        assert s2.item() == 1.0 and s1.item() == 1.0
+    else:
+        assert torch.equal(torch.stack((s2, s1)), want), (s2, s1, want)
+        assert (blk.forced_spatial_mask.grad is not None) == mask_grad
+
+
 def _freeze_bn_train(model):
     model.train()
     for m in model.modules():

@@ -4,7 +4,7 @@ channel modes, stride 1 (identity shortcut, 28 x 28 out) and stride 2 with a pro
 
 For every block the gradients of conv1 / conv2 / conv3 (and of everything else: input, BatchNorm affine terms, the mask's straight-through
 term) come from `sparse_block_train` with the kernel ON, with it OFF (the gather + PyTorch GEMM path) and from the oracle's autograd
-(oracle.torch_ref.BottleneckRef, BatchNorm in eval mode = frozen statistics).  Bounds, restated from tests/test_hip_training.py:
+(oracle.torch_ref.BottleneckRef, BatchNorm in eval mode = frozen statistics).  Bounds, those of tests/test_hip_training.py::_close (imported):
     fp32 arithmetic:   every element within 1e-3 of max(1, max |want|);
     bf16x3 arithmetic: a pre-activation within the 1e-5-class forward error of zero takes the other side of its ReLU and ONE flipped unit moves
                        a 3x3 neighbourhood of d x and one filter of the weight gradients by O(1): at most 8 % of the elements outside that
@@ -20,26 +20,10 @@ import torch
 
 from fill import seeded_bernoulli, seeded_randn
 from helpers import apply_math_mode, block_input, make_block  # noqa: F401  (apply_math_mode: autouse)
+from test_hip_training import _close, _err, _start
 
 DEV = "cuda:0"
 CASES = [("spatial", 1), ("layer", 1), ("channel", 1), ("spatial", 2), ("layer", 2), ("channel", 2)]
-
-
-def _err(got, want):
-    """max |got - want|, in units of max(1, max |want|): plain absolute error for O(1) tensors"""
-    return (got - want).abs().max().item() / max(1.0, want.abs().max().item())
-
-
-def _close(got, want, math_mode, what):
-    if math_mode != "bf16x3":
-        assert _err(got, want) < 1e-3, f"{what}: {_err(got, want):.2e} (scale {want.abs().max().item():.2e})"
-        return
-    d = (got - want).abs()
-    tol = 1e-3 * max(1.0, want.abs().max().item())
-    frac = (d > tol).float().mean().item()
-    fro = (d.norm() / want.norm().clamp(min=1e-12)).item()
-    few = got.numel() < 2000
-    assert (few or frac <= 0.08) and fro < 0.05, f"{what}: {100 * frac:.2f} % of the elements outside 1e-3, relative Frobenius error {fro:.2e}"
 
 
 def _fixture(mode, stride):
@@ -57,10 +41,6 @@ def _fixture(mode, stride):
     else:
         fx["mask"] = seeded_bernoulli((batch, planes // 2), 0.6, seed + 3)
     return fx
-
-
-def _start(x):
-    return (x, None, None, None, None, None, torch.tensor(0.0, device=x.device))
 
 
 @pytest.mark.gpu
