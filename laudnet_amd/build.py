@@ -9,14 +9,19 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libldn_hip.so")
 SOURCES = ["ldn_conv_image.hip", "ldn_index.hip", "ldn_regnet.hip", "ldn_tail.hip", "ldn_dense.hip", "ldn_stem.hip", "ldn_attn.hip", "ldn_grouped.hip", "ldn_small.hip", "ldn_rows3.hip", "ldn_wgrad.hip", "ldn_train_rows.hip"]
-HEADERS = [os.path.join(CSRC, "ldn_common.h"), os.path.join(os.path.dirname(PKG), "include", "ldn_hip.h")]
+PUBLIC_HEADER = os.path.join(os.path.dirname(PKG), "include", "ldn_hip.h")
+
+
+def _headers() -> list:
+    """Every header a translation unit may include: the public one and every csrc/*.h (ldn_common.h, ldn_prims.h, ldn_mlp.h, ldn_chain_ld.h ...)."""
+    return [PUBLIC_HEADER] + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
 
 
 def needs_build() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + HEADERS
+    deps = [os.path.join(CSRC, s) for s in SOURCES] + _headers()
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 
@@ -29,8 +34,7 @@ def _compile_and_link(lib: str, tag: str, extra: list, force: bool, verbose: boo
     """One object per translation unit (compiled in parallel, only when its source or a header is newer), then one link."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(OBJ_DIR, exist_ok=True)
-    hdrs = HEADERS + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]      # (every internal header: ldn_mlp.h, ldn_se_head.h ...)
-    hdr_t = max(os.path.getmtime(h) for h in hdrs if os.path.exists(h))
+    hdr_t = max(os.path.getmtime(h) for h in _headers() if os.path.exists(h))
     objs, jobs = [], []
     for src in SOURCES:
         sp = os.path.join(CSRC, src)

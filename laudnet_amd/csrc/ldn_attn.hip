@@ -14,8 +14,6 @@
 
 namespace ldn {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int A_D = 64;                 // head dimension
 constexpr int A_KS = 68;                // row stride of K in LDS (floats): 16-byte aligned, 4 banks of shift per row
 constexpr int A_MAXTOK = 256;
@@ -30,16 +28,6 @@ struct MhaArgs {
     int vs;                             // row stride of V^T in LDS (floats): multiple of 4, = 4 mod 32
     const float* head_keep;             // optional [B][heads] {0,1}: head skipping (simulate_adavit.py:81-88) -- a dropped head's output is 0
 };
-
-__device__ __forceinline__ void split8(const f32x4 a, const f32x4 b, bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float v = e < 4 ? a[e] : b[e - 4];
-        const __bf16 hb = (__bf16)v;
-        hi[e] = hb;
-        lo[e] = (__bf16)(v - (float)hb);
-    }
-}
 
 __global__ __launch_bounds__(512, 2) void k_packed_mha(const MhaArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];

@@ -15,8 +15,10 @@
 // (tests/test_hip_chain.py).  Every spin is bounded: a wait that runs into its bound is counted (ldn_plan_timeouts) and poisons nothing but the
 // values -- the launch always terminates.
 //
-// Included by ldn_tail.hip behind head_body / tail_body (their DMA / fragment helpers are used as they are).
+// Included by ldn_tail.hip behind head_body / tail_body: it uses that file's argument records (HeadArgs, TailArgs, ChainArgs), its LDS layout
+// constants, its fragment helpers and its ablatable group DMA (dma16_pieces_abl); the device primitives come from ldn_prims.h.
 #pragma once
+#include "ldn_common.h"
 
 namespace ldn {
 
@@ -142,20 +144,9 @@ __device__ __forceinline__ void ld_publish(LdSync* sy, unsigned landed) {
     asm volatile("" ::: "memory");
 }
 
-// counted wait with a run-time, wave-uniform count (0 .. 63: the counter has six bits)
-__device__ __forceinline__ void wait_vm_rt63(int n) {
-#define LDN_WV(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-    switch (n) {
-        LDN_WV(0) LDN_WV(1) LDN_WV(2) LDN_WV(3) LDN_WV(4) LDN_WV(5) LDN_WV(6) LDN_WV(7) LDN_WV(8) LDN_WV(9) LDN_WV(10) LDN_WV(11) LDN_WV(12)
-        LDN_WV(13) LDN_WV(14) LDN_WV(15) LDN_WV(16) LDN_WV(17) LDN_WV(18) LDN_WV(19) LDN_WV(20) LDN_WV(21) LDN_WV(22) LDN_WV(23) LDN_WV(24)
-        LDN_WV(25) LDN_WV(26) LDN_WV(27) LDN_WV(28) LDN_WV(29) LDN_WV(30) LDN_WV(31) LDN_WV(32) LDN_WV(33) LDN_WV(34) LDN_WV(35) LDN_WV(36)
-        LDN_WV(37) LDN_WV(38) LDN_WV(39) LDN_WV(40) LDN_WV(41) LDN_WV(42) LDN_WV(43) LDN_WV(44) LDN_WV(45) LDN_WV(46) LDN_WV(47) LDN_WV(48)
-        LDN_WV(49) LDN_WV(50) LDN_WV(51) LDN_WV(52) LDN_WV(53) LDN_WV(54) LDN_WV(55) LDN_WV(56) LDN_WV(57) LDN_WV(58) LDN_WV(59) LDN_WV(60)
-        LDN_WV(61) LDN_WV(62)
-        default: asm volatile("s_waitcnt vmcnt(63)" ::: "memory"); break;
-    }
-#undef LDN_WV
-}
+// The loader's run-time counted waits are wait_vm_rt<62, 63>: exact up to 62, 63 for every other count.  Its counts are the pieces of ONE chunk
+// (nwp, P2 <= 32; P2 plus at most five h1 pieces <= 37), so the clamp is never reached.  head_ld's consumers wait for their own x rows with the
+// tail's wait_vm_rt<15, 16>: 4 (DX - 2) is 0 or 4.
 
 // 16 bytes from sbase (wave-uniform) + off (per lane): a GLOBAL load in the saddr + 32-bit offset form (left as a generic pointer, hipcc emits
 // flat loads behind 64-bit address arithmetic -- two address registers per load, 64 of them in a staged tile)
@@ -169,24 +160,18 @@ __device__ __forceinline__ f32x4 ld_global_f4(const float* ptr) {
     return *(gptr)(ptr);
 }
 
-// One LDS-DMA piece (1 KB: 16 bytes per lane) from sbase (wave-uniform) + vo (per-lane byte offset) to LDS lds_base + lane * 16.
-__device__ __forceinline__ void ld_dma1(unsigned vo, const void* sbase, unsigned lds_base) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(vo), "s"(sbase), "s"(lds_base) : "memory");
-}
 // n (wave-uniform, a multiple of 4, <= MAXP) consecutive 1 KB pieces of a slot: piece i from sbase + vo[i] to lds_base + i * 1024.  Groups of four
 // share one M0 set-up (dma16_pieces: the instruction offset moves source AND destination, so vo[i] carries the bias (3 - i % 4) * 1024 against
 // sbase - 3072: ld_bias()).  All indices are compile-time: the offsets stay in registers.
 __device__ __forceinline__ unsigned ld_bias(int i) { return (unsigned)(3 - (i & 3)) * 1024u; }
 template <int MAXP>
 __device__ __forceinline__ void ld_dma_run(const unsigned (&vo)[MAXP], int n, const unsigned char* sbase, unsigned lds_base) {
-    const void* sb = uniform_cptr(sbase - 3072);
+    const void* sb = uniform_ptr(sbase - 3072);
 #pragma unroll
     for (int g = 0; g < MAXP / 4; ++g) {
         if (4 * g >= n) break;
         const unsigned v4[4] = {vo[4 * g], vo[4 * g + 1], vo[4 * g + 2], vo[4 * g + 3]};
-        dma16_pieces<4>(v4, sb, (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_base + (unsigned)g * 4096u)));
+        dma16_pieces_abl<4>(v4, sb, (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_base + (unsigned)g * 4096u)));
     }
 }
 
@@ -255,9 +240,9 @@ __device__ __forceinline__ void head_ld(const HeadArgs& p, const int b, unsigned
             if (c >= RW) LD_TIMED(5, ld_wait_done(sy, ncomp, base + (unsigned)(c - RW + 1), dead))
             ld_dma_run<MAXP>(wo, nwp, p.w1s + (long)c * 128, lds_w + (unsigned)slot * (unsigned)wslot);
             slot = slot + 1 == RW ? 0 : slot + 1;
-            if (c > 0) { wait_vm_rt63(nwp); ld_publish(sy, base + (unsigned)c); }      // chunks < c have landed
+            if (c > 0) { wait_vm_rt<62, 63>(nwp); ld_publish(sy, base + (unsigned)c); }      // chunks < c have landed
         }
-        wait_vm_n<0>();
+        wait_vm<0>();
         ld_publish(sy, base + (unsigned)nchunks);
         LT(tb)
         LD_SPAN(0, ta, tb)
@@ -278,7 +263,7 @@ __device__ __forceinline__ void head_ld(const HeadArgs& p, const int b, unsigned
     const unsigned char* const xbase = reinterpret_cast<const unsigned char*>(p.x + row0 * p.ldx) - 3072;
     auto dma_x = [&](int c, int xs) {      // chunk c (beyond the K range: the last one again -- keeps the counted wait's arithmetic constant) into x slot xs
         const int cc = min(c, nchunks - 1);
-        dma16_pieces<4>(xo, uniform_cptr(xbase + (long)cc * 128), (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_x + (unsigned)xs * 4096u)));
+        dma16_pieces_abl<4>(xo, uniform_ptr(xbase + (long)cc * 128), (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_x + (unsigned)xs * 4096u)));
     };
 
     f32x16 acc[NS];
@@ -293,7 +278,7 @@ __device__ __forceinline__ void head_ld(const HeadArgs& p, const int b, unsigned
     bf16x8 bh[2], bl[2];
     int xs = 0, ws_i = 0;                   // x slot / weight slot of chunk c
     for (int c = 0; c < nchunks; ++c) {
-        wait_vm_rt(4 * (DX - 2));           // this wave's x rows of chunk c have landed
+        wait_vm_rt<15, 16>(4 * (DX - 2));           // this wave's x rows of chunk c have landed
         {   // B operands of both K16 steps (the wave's 32 pixels), split once for all of the image's n-subtiles
             const unsigned char* xsl = my_x + xs * 4096 + l31 * 128;
 #pragma unroll
@@ -367,7 +352,7 @@ __device__ __forceinline__ void head_ld(const HeadArgs& p, const int b, unsigned
         xs = xs + 1 == DX ? 0 : xs + 1;
         ws_i = ws_i + 1 == RW ? 0 : ws_i + 1;
     }
-    wait_vm_n<0>();      // no LDS-DMA of this wave may be in flight when the phase's LDS is handed on
+    wait_vm<0>();      // no LDS-DMA of this wave may be in flight when the phase's LDS is handed on
     LT(tb)
     LD_SPAN(0, ta, tb)
 
@@ -383,7 +368,6 @@ __device__ __forceinline__ void head_ld(const HeadArgs& p, const int b, unsigned
             const f32x4 sc = *reinterpret_cast<const f32x4*>(s_tab + n0);
             const f32x4 sh = *reinterpret_cast<const f32x4*>(s_tab + W + n0);
             const f32x4 ps = *reinterpret_cast<const f32x4*>(s_tab + 2 * W + n0);
-            typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
             unsigned hi2[2], lo2[2];
 #pragma unroll
             for (int d = 0; d < 2; ++d) {
@@ -509,7 +493,7 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
         };
         u32x4 LA[NH][4], LB[NH][4];                   // the two halves' pieces
         auto load_half = [&](int t_, int hf, u32x4 (&L_)[NH][4]) {
-            const unsigned char* src = reinterpret_cast<const unsigned char*>(uniform_cptr(p.w2p + (long)t_ * ((W / 2) * (W / 2) * 16)));
+            const unsigned char* src = reinterpret_cast<const unsigned char*>(uniform_ptr(p.w2p + (long)t_ * ((W / 2) * (W / 2) * 16)));
 #pragma unroll
             for (int i = 0; i < NH; ++i)
                 if (i < nhi)
@@ -535,10 +519,10 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
         auto h1_piece = [&](int i, const void* sb, unsigned dst) {
             const int r = 8 * i + (lane >> 3);
             const unsigned o = (unsigned)(min(r, NR - 1) * (int)p.h1_row_bytes + (((lane & 7) ^ ((r >> 1) & 7)) << 4));
-            ld_dma1(o, sb, (unsigned)__builtin_amdgcn_readfirstlane((int)(dst + (unsigned)i * 1024u)));
+            dma16_pieces<1>({o}, sb, (unsigned)__builtin_amdgcn_readfirstlane((int)(dst + (unsigned)i * 1024u)));
         };
         if (nchunks > 0) {
-            const void* sb0 = uniform_cptr(h1b);
+            const void* sb0 = uniform_ptr(h1b);
             for (int i = 0; i < nq; ++i) h1_piece(i, sb0, lds_h1);       // slice 0 -> slot 0
             slice_rows(0);
             load_half(0, 0, LA);
@@ -550,7 +534,7 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
             const int sc = c / 9, tc = c - 9 * sc;
             const bool nxt = c + 1 < nchunks;
             if (c >= R2) LD_TIMED(6, ld_wait_done(sy, ncomp, base2 + (unsigned)(c - R2 + 1), dead))
-            if (tc == 0) wait_vm_n<0>();              // slice sc has landed (its pieces went out with taps TMIN .. 8 of the slice before)
+            if (tc == 0) wait_vm<0>();              // slice sc has landed (its pieces went out with taps TMIN .. 8 of the slice before)
             unsigned char* const slotp = s_w2 + slot * slot2;
             slot = slot + 1 == R2 ? 0 : slot + 1;
             store_half(slotp, 0, LA);                 // (waits for half 0's pieces only: half 1's and nothing younger may still fly)
@@ -562,7 +546,7 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
             ld_publish(sy, base2 + (unsigned)c + 1u);                  // (LDS executes this wave's writes in order: the word lands behind the quads)
             if (nxt) load_half(tn, 1, LB);
             if (tc >= TMIN && sc + 1 < nsub) {        // slice sc + 1: piece i goes out with tap TMIN + i % 6 (every reader has left slice sc - 1 by then: R2 <= 4)
-                const void* hsb = uniform_cptr(h1b + (long)(sc + 1) * 128);
+                const void* hsb = uniform_ptr(h1b + (long)(sc + 1) * 128);
                 const unsigned hdst = lds_h1 + (unsigned)((sc + 1) & 1) * (unsigned)p.slice_bytes;
                 for (int i = tc - TMIN; i < nq; i += 6) h1_piece(i, hsb, hdst);
             }
@@ -592,7 +576,7 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
         if (nchunks > 0) {
 #pragma unroll
             for (int i = 0; i < MAXH; ++i)
-                if (i < nq) ld_dma1(ho[i], uniform_cptr(h1b), (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_h1 + (unsigned)i * 1024u)));      // slice 0 -> slot 0
+                if (i < nq) dma16_pieces<1>({ho[i]}, uniform_ptr(h1b), (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_h1 + (unsigned)i * 1024u)));      // slice 0 -> slot 0
         }
         int slot = 0;
         for (int s = 0; s < nsub; ++s) {
@@ -612,8 +596,8 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
                 slot = slot + 1 == R2 ? 0 : slot + 1;
                 int pieces = P2;
                 if (t >= TMIN && more) {
-                    const void* hsb = uniform_cptr(hsrc);
-#define LDN_LD_H1(I) if ((I) < nq) { ld_dma1(ho[(I)], hsb, (unsigned)__builtin_amdgcn_readfirstlane((int)(hdst + (unsigned)(I) * 1024u))); ++pieces; }
+                    const void* hsb = uniform_ptr(hsrc);
+#define LDN_LD_H1(I) if ((I) < nq) { dma16_pieces<1>({ho[(I)]}, hsb, (unsigned)__builtin_amdgcn_readfirstlane((int)(hdst + (unsigned)(I) * 1024u))); ++pieces; }
                     switch (t) {      // piece i goes out with tap TMIN + i % NT
                         case 3: LDN_LD_H1(0) LDN_LD_H1(6) LDN_LD_H1(12) LDN_LD_H1(18) LDN_LD_H1(24) break;
                         case 4: LDN_LD_H1(1) LDN_LD_H1(7) LDN_LD_H1(13) LDN_LD_H1(19) LDN_LD_H1(25) break;
@@ -624,11 +608,11 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
                     }
 #undef LDN_LD_H1
                 }
-                if (c > 0) { wait_vm_rt63(pieces); ld_publish(sy, base2 + (unsigned)c); }      // chunks < c (and every slice piece issued with them) have landed
+                if (c > 0) { wait_vm_rt<62, 63>(pieces); ld_publish(sy, base2 + (unsigned)c); }      // chunks < c (and every slice piece issued with them) have landed
             }
         }
 #endif
-        wait_vm_n<0>();
+        wait_vm<0>();
         ld_publish(sy, base2 + (unsigned)nchunks);
         LT(tb)
         LD_SPAN(2, ta, tb)
@@ -654,7 +638,7 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
             }
         u32x4 L[NS][4];
         auto load_chunk = [&](int cc) {
-            const unsigned char* src = reinterpret_cast<const unsigned char*>(uniform_cptr(p.w3p + (long)cc * (LD_CW * 8)));
+            const unsigned char* src = reinterpret_cast<const unsigned char*>(uniform_ptr(p.w3p + (long)cc * (LD_CW * 8)));
 #pragma unroll
             for (int i = 0; i < NS; ++i)
                 if (i < nsub)
@@ -701,10 +685,10 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
                 if (cc >= R3) LD_TIMED(7, ld_wait_done(sy, ncomp, base3 + (unsigned)(cc - R3 + 1), dead))
                 ld_dma_run<MAXP>(w3o, P2, p.w3p + (long)cc * (LD_CW * 8), lds_w3 + (unsigned)slot3i * (unsigned)slot3);
                 slot3i = slot3i + 1 == R3 ? 0 : slot3i + 1;
-                wait_vm_rt63(P2);
+                wait_vm_rt<62, 63>(P2);
                 ld_publish(sy, base3 + (unsigned)cc);
             }
-            wait_vm_n<0>();
+            wait_vm<0>();
         }
 #endif
         ld_publish(sy, base3 + (unsigned)nchunk3);
@@ -980,7 +964,6 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
     if (!consumer) return;
 
     // In place: the 16 fp32 accumulators of n-subtile j become 16 dwords of bf16 pairs (tail_body's conversion, same values)
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
     for (int j = 0; j < NS; ++j) {
         float v[16];

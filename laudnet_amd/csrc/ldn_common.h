@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "../../include/ldn_hip.h"
+#include "ldn_prims.h"
 
 namespace ldn {
 
@@ -69,9 +70,6 @@ int tu_chain_stalls(unsigned* count, int reset);      // csrc/ldn_tail.hip
 int* fault_word_host();
 int* fault_word_dev();
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // lane ^ 1 exchange (DPP quad_perm [1,0,3,2]).  Inline asm on purpose: hipcc 7.2 merges several __builtin_amdgcn_update_dpp calls
 // of one unrolled loop into ONE v_mov_b32_dpp of the first operand and uses its result for all of them (seen in the pre-split
 // epilogues of round 5: every lane got its partner's element 0 four times).  The s_nop covers the VALU-write -> DPP-read wait states.
@@ -85,25 +83,23 @@ __device__ __forceinline__ float dpp_swap_pair(float v) {
 // Each lane splits its OWN quad (hi = bf16(x), lo = bf16(x - hi), both round-to-nearest-even: the in-loop split of the un-split kernels),
 // then the pair exchanges what the other one stores: the even lane stores the octet's 8 hi (its own 4 + the partner's), the odd lane the
 // 8 lo (the partner's 4 + its own).  Two DPP moves of packed pairs per lane.
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x4_t presplit_store_quad(const f32x4 x, bool odd) {
+__device__ __forceinline__ u32x4 presplit_store_quad(const f32x4 x, bool odd) {
 #ifdef LDN_OF_NOP     // tuning only (wrong values): what the conversion itself costs
-    return __builtin_bit_cast(u32x4_t, x);
+    return __builtin_bit_cast(u32x4, x);
 #endif
     unsigned hi[2], lo[2];
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
         const __bf16 h0 = (__bf16)x[2 * q], h1 = (__bf16)x[2 * q + 1];
-        const bf16x2_t hp = {h0, h1};
-        const bf16x2_t lp = {(__bf16)(x[2 * q] - (float)h0), (__bf16)(x[2 * q + 1] - (float)h1)};
+        const bf16x2 hp = {h0, h1};
+        const bf16x2 lp = {(__bf16)(x[2 * q] - (float)h0), (__bf16)(x[2 * q + 1] - (float)h1)};
         hi[q] = __builtin_bit_cast(unsigned, hp);
         lo[q] = __builtin_bit_cast(unsigned, lp);
     }
     const float r0 = dpp_swap_pair(__builtin_bit_cast(float, odd ? hi[0] : lo[0]));     // even sends its lo, odd sends its hi
     const float r1 = dpp_swap_pair(__builtin_bit_cast(float, odd ? hi[1] : lo[1]));
     const unsigned p0 = __builtin_bit_cast(unsigned, r0), p1 = __builtin_bit_cast(unsigned, r1);
-    return odd ? u32x4_t{p0, p1, lo[0], lo[1]} : u32x4_t{hi[0], hi[1], p0, p1};
+    return odd ? u32x4{p0, p1, lo[0], lo[1]} : u32x4{hi[0], hi[1], p0, p1};
 }
 
 // x[l] + x[l ^ 8] + x[l ^ 16] + ... : the sum over lane bits 3, 4, 5 (the eight row groups of a (row = lane >> 3, quad = lane & 7) epilogue layout), in every

@@ -97,13 +97,8 @@ __device__ __forceinline__ void block_sync() {
     asm volatile("" ::: "memory");
 }
 
-// consumer-side form: consumers never use LDS-DMA, and their only outstanding global loads (residual tiles requested
-// straight into the accumulators) are waited for by the compiler where the accumulators are first used
-__device__ __forceinline__ void block_sync_lds() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
+// (the consumers use lds_barrier, which leaves vmcnt alone: they never use LDS-DMA, and their only outstanding global loads -- residual
+// tiles requested straight into the accumulators -- are waited for by the compiler where the accumulators are first used)
 
 // per-block geometry and the LDS tables behind the two staging buffers (built by tile_setup)
 struct Tile {
@@ -756,18 +751,6 @@ __global__ __launch_bounds__(512, MINW) void k_conv_image(const ImgArgs p) {
 //   * the ACTIVATION tile still lands as raw fp32 through LDS-DMA; each consumer wave owns whole m-subtiles (wave grid
 //     WM x 4/WM over the block's subtiles), splits its A fragments once per K16 step and reuses them against every
 //     n-subtile it owns -- register blocking that keeps both the VALU work and the LDS reads per MFMA low.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void split_bf16(const f32x4& x0, const f32x4& x1, bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float v = e < 4 ? x0[e] : x1[e - 4];
-        const __bf16 hb = (__bf16)v;
-        hi[e] = hb;
-        lo[e] = (__bf16)(v - (float)hb);
-    }
-}
-
 template <int MS, int NS, int WM, int BMODE, bool KSKIP, int MINW>
 __global__ __launch_bounds__(512, MINW) void k_conv_bf3(const ImgArgs p) {
     static_assert(MS >= 1 && MS + NS <= 18 && NS % 2 == 0 && (WM == 1 || WM == 2 || WM == 4), "tile shape");
@@ -803,7 +786,7 @@ __global__ __launch_bounds__(512, MINW) void k_conv_bf3(const ImgArgs p) {
         // the consumers gather the epilogue tables while the producers' first loads are in flight; one extra
         // workgroup barrier (matched in the producer prologue) publishes them
         tile_tables<NS>(p, t, tid, 256);
-        block_sync_lds();
+        lds_barrier();
     }
 
     if (wave8 >= 4) {
@@ -982,7 +965,7 @@ __global__ __launch_bounds__(512, MINW) void k_conv_bf3(const ImgArgs p) {
                         const f32x4 x0 = {f[e], f[2 + e], f[4 + e], f[6 + e]};
                         const f32x4 x1 = {f[8 + e], f[10 + e], f[12 + e], f[14 + e]};
                         bf16x8 hi, lo;
-                        split_bf16(x0, x1, hi, lo);
+                        split8<const f32x4&>(x0, x1, hi, lo);
                         const int row = pr_col + e, sw = (pr_col >> 1) & 7;
                         *reinterpret_cast<bf16x8*>(bt + row * BK + ((2 * pr_oct) ^ sw) * 4) = hi;
                         *reinterpret_cast<bf16x8*>(bt + row * BK + ((2 * pr_oct + 1) ^ sw) * 4) = lo;
@@ -996,7 +979,7 @@ __global__ __launch_bounds__(512, MINW) void k_conv_bf3(const ImgArgs p) {
                     const int row = (wave + 4 * u) * 16 + rl;
                     if (row < nsub * 32) {
                         bf16x8 hi, lo;
-                        split_bf16(rb[u][0], rb[u][1], hi, lo);
+                        split8<const f32x4&>(rb[u][0], rb[u][1], hi, lo);
                         const int sw = lane & 7;                                    // (row >> 1) & 7
                         *reinterpret_cast<bf16x8*>(bt + row * BK + ((2 * oct_nk) ^ sw) * 4) = hi;
                         *reinterpret_cast<bf16x8*>(bt + row * BK + ((2 * oct_nk + 1) ^ sw) * 4) = lo;
@@ -1007,7 +990,7 @@ __global__ __launch_bounds__(512, MINW) void k_conv_bf3(const ImgArgs p) {
                         const f32x4 x0 = {rb[u][0][e], rb[u][1][e], rb[u][2][e], rb[u][3][e]};
                         const f32x4 x1 = {rb[u][4][e], rb[u][5][e], rb[u][6][e], rb[u][7][e]};
                         bf16x8 hi, lo;
-                        split_bf16(x0, x1, hi, lo);
+                        split8<const f32x4&>(x0, x1, hi, lo);
                         const int row = cq[u] * 4 + e, sw = (row >> 1) & 7;
                         *reinterpret_cast<bf16x8*>(bt + row * BK + ((2 * oct_kn[u]) ^ sw) * 4) = hi;
                         *reinterpret_cast<bf16x8*>(bt + row * BK + ((2 * oct_kn[u] + 1) ^ sw) * 4) = lo;
@@ -1143,7 +1126,7 @@ __global__ __launch_bounds__(512, MINW) void k_conv_bf3(const ImgArgs p) {
             const int buf = ch & 1;
             const int kgroups = ceil_div(min(Ktot - ch * BK, BK), 8);   // octets of this chunk that lie inside K (only the last chunk is partial)
             LDN_TRACE_T(tr_a)
-            block_sync_lds();                  // barrier(ch)
+            lds_barrier();                  // barrier(ch)
             LDN_TRACE_T(tr_b)
             LDN_TRACE_ADD(tr_bar, tr_a, tr_b)
 #ifdef LDN_TRACE
@@ -1168,7 +1151,7 @@ __global__ __launch_bounds__(512, MINW) void k_conv_bf3(const ImgArgs p) {
                 if (KSKIP && 2 * ks >= kgroups) break;
                 bf16x8 ah[AM], al[AM];
 #pragma unroll
-                for (int a = 0; a < AM; ++a) split_bf16(ar[a][0], ar[a][1], ah[a], al[a]);
+                for (int a = 0; a < AM; ++a) split8<const f32x4&>(ar[a][0], ar[a][1], ah[a], al[a]);
                 if (ks + 1 < BK / 16) {
 #pragma unroll
                     for (int a = 0; a < AM; ++a) {
@@ -1204,7 +1187,7 @@ __global__ __launch_bounds__(512, MINW) void k_conv_bf3(const ImgArgs p) {
             LDN_TRACE_T(tr_a)
             LDN_TRACE_ADD(tr_mma, tr_b, tr_a)
         }
-        block_sync_lds();   // every consumer is done with both buffers before buffer 0 becomes the epilogue scratch
+        lds_barrier();   // every consumer is done with both buffers before buffer 0 becomes the epilogue scratch
     }
     LDN_TRACE_T(tr_epi)
 
@@ -1269,17 +1252,6 @@ constexpr int ST_LDS_FLOATS = ST_OFF_CB + 2 * ST_TILE;    // 9 slots = 144 KiB
 constexpr int ST_MAXROWS = 1024;                          // rows per workgroup (8 M blocks)
 constexpr int ST_ROW_RELU = 1 << 30;
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    static_assert(N == 0 || N == 8, "add the immediate");
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-}
-__device__ __forceinline__ unsigned lds_addr(const void* ptr) {
-    return (unsigned)(size_t)(const __attribute__((address_space(3))) void*)ptr;
-}
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void lds_write16(unsigned addr, const bf16x8& v) {
     asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory");
 }
@@ -1367,7 +1339,7 @@ __global__ __launch_bounds__(512, 2) void k_conv1x1_stream(const ImgArgs p) {
 #define LDN_STREAM_PRIO 2
 #endif
         __builtin_amdgcn_s_setprio(LDN_STREAM_PRIO);
-        const unsigned lds_arow = lds_addr(s_arow), lds_kidx = lds_addr(s_kidx), lds0 = lds_addr(smem);
+        const unsigned lds_arow = lds_off(s_arow), lds_kidx = lds_off(s_kidx), lds0 = lds_off(smem);
         // every load address is "base + (valid ? offset : offset of the zero line)": one instruction per slot, never a branch
         const long zoff_a = g_zero16 - p.a, zoff_w = g_zero16 - p.w;
         // ---- A (and the n-major weight tile): one wave instruction = 8 rows x 128 B; this lane moves physical slot
@@ -1441,7 +1413,7 @@ __global__ __launch_bounds__(512, 2) void k_conv1x1_stream(const ImgArgs p) {
                     const f32x4 x0 = {f[0][e], f[1][e], f[2][e], f[3][e]};
                     const f32x4 x1 = {f[4][e], f[5][e], f[6][e], f[7][e]};
                     bf16x8 hi, lo;
-                    split_bf16(x0, x1, hi, lo);
+                    split8<const f32x4&>(x0, x1, hi, lo);
                     const int row = 2 * lane + e;     // (row >> 1) & 7 == lane & 7
                     lds_write16(cb + 4u * (unsigned)(row * BK + ((2 * wave) ^ sw) * 4), hi);
                     lds_write16(cb + 4u * (unsigned)(row * BK + ((2 * wave + 1) ^ sw) * 4), lo);
@@ -1455,7 +1427,7 @@ __global__ __launch_bounds__(512, 2) void k_conv1x1_stream(const ImgArgs p) {
                     lds_read2x16_wait(raw + 4u * (unsigned)(row * BK + ((2 * oct_nk) ^ sw) * 4),
                                       raw + 4u * (unsigned)(row * BK + ((2 * oct_nk + 1) ^ sw) * 4), x0, x1);
                     bf16x8 hi, lo;
-                    split_bf16(x0, x1, hi, lo);
+                    split8<const f32x4&>(x0, x1, hi, lo);
                     lds_write16(cb + 4u * (unsigned)(row * BK + ((2 * oct_nk) ^ sw) * 4), hi);
                     lds_write16(cb + 4u * (unsigned)(row * BK + ((2 * oct_nk + 1) ^ sw) * 4), lo);
                 }
@@ -1469,9 +1441,9 @@ __global__ __launch_bounds__(512, 2) void k_conv1x1_stream(const ImgArgs p) {
         for (int i = -3; i < G; ++i) {
             if (i >= 0) { __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); }
 #ifdef LDN_STREAM_SAFE
-            wait_vmcnt<0>();
+            wait_vm<0>();
 #else
-            wait_vmcnt<8>();      // the 8 DMA instructions of iteration i-1 (chunk i+2) may still fly; chunk i+1 is in
+            wait_vm<8>();      // the 8 DMA instructions of iteration i-1 (chunk i+2) may still fly; chunk i+1 is in
 #endif
 #if !(LDN_ABLATE & 8)
             if (i >= -1 && i + 1 < G) convert((i + 1) % ST_B_SLOTS, (i + 1) & 1);
@@ -1484,7 +1456,7 @@ __global__ __launch_bounds__(512, 2) void k_conv1x1_stream(const ImgArgs p) {
                 asm volatile("" ::: "memory");
             }
         }
-        wait_vmcnt<0>();     // no LDS-DMA may be in flight when the workgroup's LDS is released
+        wait_vm<0>();     // no LDS-DMA may be in flight when the workgroup's LDS is released
         return;
     }
 
@@ -1568,7 +1540,7 @@ __global__ __launch_bounds__(512, 2) void k_conv1x1_stream(const ImgArgs p) {
                     if (ks == 1 && krem <= 16) break;
                     bf16x8 ah[2], al[2];
 #pragma unroll
-                    for (int a = 0; a < 2; ++a) split_bf16(ar[a][0], ar[a][1], ah[a], al[a]);
+                    for (int a = 0; a < 2; ++a) split8<const f32x4&>(ar[a][0], ar[a][1], ah[a], al[a]);
                     if (ks == 0) {
 #pragma unroll
                         for (int a = 0; a < 2; ++a) {

@@ -13,9 +13,6 @@
 
 namespace ldn {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 struct DenseArgs {
     const float* a; int lda;
     const int32_t* a_rows; const int32_t* m_count; int m_cap;
@@ -50,36 +47,16 @@ __device__ unsigned long long* g_dense_trace = nullptr;
 #ifndef LDN_DENSE_ABLATE
 #define LDN_DENSE_ABLATE 0   // tuning only (results are wrong): 1 = no LDS-DMA at all, 2 = every DMA reads the zero line, 4 = no MFMA, 8 = no weight-fragment reads
 #endif
-__device__ __forceinline__ void d_dma16(const void* gsrc, unsigned lds_base) {
+// Run-time counted waits are wait_vm_rt<16, 0>: exact up to 16, and every other count waits for EVERYTHING, which is always safe (the callers
+// of own_landed clamp to 0 themselves above 16).
+__device__ __forceinline__ void dma16_abl(const void* gsrc, unsigned lds_base) {     // every LDS-DMA of this file, behind its ablation switches
 #if LDN_DENSE_ABLATE & 1
     return;
 #endif
 #if LDN_DENSE_ABLATE & 2
     gsrc = g_dense_zero;
 #endif
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_base) : "memory");
-}
-template <int N> __device__ __forceinline__ void d_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void d_wait_vm_rt(int n) {
-    switch (n) {
-        case 1: d_wait_vm<1>(); break;   case 2: d_wait_vm<2>(); break;   case 3: d_wait_vm<3>(); break;
-        case 4: d_wait_vm<4>(); break;   case 5: d_wait_vm<5>(); break;   case 6: d_wait_vm<6>(); break;
-        case 7: d_wait_vm<7>(); break;   case 8: d_wait_vm<8>(); break;   case 9: d_wait_vm<9>(); break;
-        case 10: d_wait_vm<10>(); break; case 11: d_wait_vm<11>(); break; case 12: d_wait_vm<12>(); break;
-        case 13: d_wait_vm<13>(); break; case 14: d_wait_vm<14>(); break; case 15: d_wait_vm<15>(); break;
-        case 16: d_wait_vm<16>(); break;
-        default: d_wait_vm<0>(); break;   // 0, and anything unexpected: wait for everything (always safe)
-    }
-}
-__device__ __forceinline__ void d_lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ unsigned d_lds_off(const void* ptr) {
-    return (unsigned)(size_t)(const __attribute__((address_space(3))) void*)ptr;
+    dma16(gsrc, lds_base);
 }
 
 constexpr int D_ROWS_MAX = 256;
@@ -182,7 +159,7 @@ __device__ __forceinline__ void dense_epilogue(const DenseArgs& p, f32x16 (&acc)
                 // pre-split rows: lanes tc = 2 q and 2 q + 1 hold channels 0-3 and 4-7 of octet 4 j + q (+ n0 / 8); they exchange their
                 // quads (DPP quad_perm [1,0,3,2]); the even lane stores the octet's 8 hi, the odd lane its 8 lo (16 bytes each, adjacent)
                 const bool odd = tc & 1;
-                const u32x4_t o = presplit_store_quad(x, odd);
+                const u32x4 o = presplit_store_quad(x, odd);
                 if (orw[it] >= 0 && cok)
                     store16(reinterpret_cast<unsigned char*>(p.out) + ((size_t)(orw[it] & (D_ROW_RELU - 1)) * p.ldo + n0 + 32 * j + (tc & ~1) * 4) * 4 + (odd ? 16 : 0), o);
             } else {
@@ -315,7 +292,7 @@ __global__ __launch_bounds__(2 * R, 2) void k_dense(const DenseArgs p) {
     const int cpt = ceil_div(p.cin, 32);                         // chunks per tap (cin % 32 != 0: the tail of a tap's last chunk is zero-filled)
     const int wrow = (T9 ? 9 : 1) * (p.cin / 8);                 // octets per weight row
     const int nchunks = (T9 ? 9 : 1) * cpt;
-    const unsigned lds_ring = d_lds_off(s_ring);
+    const unsigned lds_ring = lds_off(s_ring);
     // ... of which this wave issues nwi: with NT = 160 (NSUB 5) the last instruction only exists for the waves whose 8 rows are inside the tile
     const int nwi = (NT % WR == 0 || (NWI - 1) * WR + wave * 8 < NT) ? NWI : NWI - 1;
     const int per_chunk = (active ? 4 : 0) + nwi;
@@ -339,7 +316,7 @@ __global__ __launch_bounds__(2 * R, 2) void k_dense(const DenseArgs p) {
                     off = ar >= 0 ? (long)ar * p.lda : -1;
                 }
                 const float* src = (off >= 0 && ck * 32 + ls * 4 < p.cin) ? p.a + off + ck * 32 + ls * 4 : g_dense_zero;
-                d_dma16(src, slot + (wave * 32 + i * 8) * 128);
+                dma16_abl(src, slot + (wave * 32 + i * 8) * 128);
             }
         }
 #pragma unroll
@@ -351,12 +328,12 @@ __global__ __launch_bounds__(2 * R, 2) void k_dense(const DenseArgs p) {
             const unsigned char* src = (r < NT && n < p.cout && ck * 8 + ls < p.cin / 4)
                                            ? p.ws + ((long)n * wrow + tap * (p.cin / 8) + ck * 4) * 32 + ls * 16
                                                                : reinterpret_cast<const unsigned char*>(g_dense_zero);
-            d_dma16(src, slot + (D_ROWS + i * WR + wave * 8) * 128);      // (i < nwi: the wave's 8 rows are inside the tile)
+            dma16_abl(src, slot + (D_ROWS + i * WR + wave * 8) * 128);      // (i < nwi: the wave's 8 rows are inside the tile)
         }
     };
     auto dma_dummy = [&](int c) {
         const unsigned slot = lds_ring + (c % D) * SLOT;
-        for (int i = 0; i < per_chunk; ++i) d_dma16(g_dense_zero, slot + (D_ROWS + wave * 8) * 128);
+        for (int i = 0; i < per_chunk; ++i) dma16_abl(g_dense_zero, slot + (D_ROWS + wave * 8) * 128);
     };
     // instruction k (0 .. 3: this wave's x rows, 4 ..: its weight rows) of chunk c, for ACTIVE waves; a chunk beyond the K range
     // gets a dummy so that the per-iteration count the vmcnt waits rely on stays constant
@@ -384,7 +361,7 @@ __global__ __launch_bounds__(2 * R, 2) void k_dense(const DenseArgs p) {
             if (real && r < NT && n < p.cout && ck * 8 + ls < p.cin / 4) src = p.ws + ((long)n * wrow + tap * (p.cin / 8) + ck * 4) * 32 + ls * 16;
             if (real && i * WR + wave * 8 < NT) dst = slot + (D_ROWS + i * WR + wave * 8) * 128;
         }
-        d_dma16(src, (unsigned)__builtin_amdgcn_readfirstlane((int)dst));
+        dma16_abl(src, (unsigned)__builtin_amdgcn_readfirstlane((int)dst));
     };
 
     f32x16 acc[NSUB];
@@ -433,14 +410,14 @@ __global__ __launch_bounds__(2 * R, 2) void k_dense(const DenseArgs p) {
     // own rows of a chunk = the first four DMA instructions of that chunk: landed once at most (chunks in flight) x per_chunk - 4 are outstanding
     const int own_landed = per_chunk * (D - 1) - 4;
     if (PRE && active && nchunks > 0) {
-        d_wait_vm_rt(own_landed <= 16 ? own_landed : 0);
+        wait_vm_rt<16, 0>(own_landed <= 16 ? own_landed : 0);
         load_b(0);
     }
     for (int c = 0; c < nchunks; ++c) {
         DT(d0)
-        d_wait_vm_rt(per_chunk * (D - 2));
+        wait_vm_rt<16, 0>(per_chunk * (D - 2));
         DT(d1)
-        d_lds_barrier();
+        lds_barrier();
         DT(d2)
         // full tiles, computing waves: the DMA instructions of chunk c + D - 1 are issued one per MFMA step below (the texture
         // addresser takes 16 cycles per 1-KB instruction: issued in a burst after the barrier they cost every wave ~800 cycles during
@@ -502,7 +479,7 @@ __global__ __launch_bounds__(2 * R, 2) void k_dense(const DenseArgs p) {
             for (int k = 2 * NSUB; k < 4 + NWI; ++k)
                 if (k < 4 + nwi) dma_one(c + D - 1, k);   // (64-column tiles: five instructions, four steps)
             if (PRE && c + 1 < nchunks) {              // the next chunk's rows: landed (own DMA), read and split behind this chunk's MFMAs
-                d_wait_vm_rt(own_landed <= 16 ? own_landed : 0);
+                wait_vm_rt<16, 0>(own_landed <= 16 ? own_landed : 0);
                 load_b(c + 1);
             }
         } else {
@@ -528,8 +505,8 @@ __global__ __launch_bounds__(2 * R, 2) void k_dense(const DenseArgs p) {
 #ifdef LDN_TRACE
     DT(d_loop)
 #endif
-    d_wait_vm<0>();
-    d_lds_barrier();       // every wave is out of the ring: it becomes the per-wave 32 x 32 transpose scratch
+    wait_vm<0>();
+    lds_barrier();       // every wave is out of the ring: it becomes the per-wave 32 x 32 transpose scratch
     if (!active) return;
 
     // ---- epilogue
@@ -642,7 +619,7 @@ __global__ __launch_bounds__(512, 2) void k_dense2(const DenseArgs p) {
     const int nsubc = (T9 ? 9 : 1) * cpt, nstep = RAG ? ceil_div(nsubc, SPS) : nsubc / SPS;
     const int nsub_t = RAG ? min(NSUB, ceil_div(p.cout - n0, 32)) : NSUB;      // n-subtiles of this column tile
     const long wrow = (long)(T9 ? 9 : 1) * p.cin * 4;     // bytes per weight row
-    const unsigned lds_w = d_lds_off(s_w), lds_r = d_lds_off(s_r) + (unsigned)wave * 2u * RSLOT;
+    const unsigned lds_w = lds_off(s_w), lds_r = lds_off(s_r) + (unsigned)wave * 2u * RSLOT;
     unsigned char* const my_r = s_r + wave * 2 * RSLOT;
     const unsigned char* const zrow = reinterpret_cast<const unsigned char*>(g_dense_zero);
 
@@ -661,7 +638,7 @@ __global__ __launch_bounds__(512, 2) void k_dense2(const DenseArgs p) {
         const bool pad = NT % (8 * RPI) != 0 && 8 * RPI * k + RPI * wave >= NT;       // (wave-uniform: a padding instruction of a 160-column tile)
         const int Sc = min(S, nstep - 1);
         const bool ktail = RAG && Sc * KS + wku[k] >= p.cin;                          // (per lane) this unit lies beyond K: zero
-        d_dma16(ktail ? zrow : wsrc[k] + (pad || wsrc[k] == zrow ? 0l : (long)Sc * WROWB),
+        dma16_abl(ktail ? zrow : wsrc[k] + (pad || wsrc[k] == zrow ? 0l : (long)Sc * WROWB),
                 (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_w + (unsigned)(S & 1) * WSLOT + (unsigned)(8 * RPI * k + RPI * wave) * WROWB)));
     };
     const unsigned char* rsrc[4];
@@ -680,9 +657,9 @@ __global__ __launch_bounds__(512, 2) void k_dense2(const DenseArgs p) {
         if constexpr (RAG) {
             const int r = 8 * k + (lane >> 3);
             const int ku = ((lane & 7) ^ ((r >> 1) & 7)) * 4;
-            d_dma16(ck_r * 32 + ku < p.cin ? rsrc[k] + ck_r * 128 : zrow, dst);
+            dma16_abl(ck_r * 32 + ku < p.cin ? rsrc[k] + ck_r * 128 : zrow, dst);
         } else {
-            d_dma16(rsrc[k] + ck_r * 128, dst);
+            dma16_abl(rsrc[k] + ck_r * 128, dst);
         }
     };
     auto next_r = [&]() {
@@ -699,11 +676,11 @@ __global__ __launch_bounds__(512, 2) void k_dense2(const DenseArgs p) {
     if (!active) {
         for (int k = 0; k < NWI; ++k) dma_w(0, k);
         for (int S = 0; S < nstep; ++S) {
-            d_wait_vm<0>();
-            d_lds_barrier();
+            wait_vm<0>();
+            lds_barrier();
             for (int k = 0; k < NWI; ++k) dma_w(S + 1, k);
         }
-        d_wait_vm<0>();
+        wait_vm<0>();
         return;
     }
 
@@ -763,7 +740,7 @@ __global__ __launch_bounds__(512, 2) void k_dense2(const DenseArgs p) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) dma_r(1, k);
     next_r();
-    d_wait_vm<4>();
+    wait_vm<4>();
     read_b(0, bh[0], bl[0]);
     split_b(0, bh[0], bl[0]);
     split_b(1, bh[0], bl[0]);
@@ -772,15 +749,15 @@ __global__ __launch_bounds__(512, 2) void k_dense2(const DenseArgs p) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) dma_r(2, k);
     next_r();
-    if constexpr (SPS == 1) d_wait_vm<4>();         // (one sub-chunk per step: R(1) has landed before the loop's counted waits start)
+    if constexpr (SPS == 1) wait_vm<4>();         // (one sub-chunk per step: R(1) has landed before the loop's counted waits start)
 
     // in-order completion: what may still be outstanding at each wait (see k_rows3):
     //   two sub-chunks per step:  W(S): vmcnt(8);  R(s + 1): vmcnt(4 + NWI)        one per step:  W(S): vmcnt(4);  R(s + 1): vmcnt(4 + 2 NWI)
     // one weight step: barrier, then its SPS sub-chunks; CUR0 = register set of its first sub-chunk (compile-time)
     auto step = [&](int S, auto cur0_c) {
         constexpr int CUR0 = decltype(cur0_c)::value;
-        d_wait_vm<SPS == 2 ? 8 : 4>();
-        d_lds_barrier();
+        wait_vm<SPS == 2 ? 8 : 4>();
+        lds_barrier();
         const unsigned char* wsl = s_w + (S & 1) * WSLOT + l31 * WROWB;
         // the body of one sub-chunk with B set CUR: MFMA steps with, between them, W(S + 1) (first sub-chunk of the step), the read (+ split) of
         // sub-chunk s + 1 into the other set, and R(s + 3)
@@ -814,7 +791,7 @@ __global__ __launch_bounds__(512, 2) void k_dense2(const DenseArgs p) {
                 } else if (st == rd_at) {
                     if (sub == 0)
                         while (w_done < NWI) dma_w(S + 1, w_done++);
-                    d_wait_vm<SPS == 2 ? 4 + NWI : 4 + 2 * NWI>();
+                    wait_vm<SPS == 2 ? 4 + NWI : 4 + 2 * NWI>();
                     read_b(s + 1, bh[CUR ^ 1], bl[CUR ^ 1]);
                 } else if (sp_done < 2) {
                     split_b(sp_done++, bh[CUR ^ 1], bl[CUR ^ 1]);      // (waits for the raw reads: they were issued a whole MFMA step ago)
@@ -841,7 +818,7 @@ __global__ __launch_bounds__(512, 2) void k_dense2(const DenseArgs p) {
             if (!RAG || S + 1 < nstep) step(S + 1, std::integral_constant<int, 1>{});
         }
     }
-    d_wait_vm<0>();        // the trailing re-reads have landed: this wave's row slots become its 32 x 32 transpose scratch (private: no barrier)
+    wait_vm<0>();        // the trailing re-reads have landed: this wave's row slots become its 32 x 32 transpose scratch (private: no barrier)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     dense_epilogue<NSUB, T9, !RAG, OF, FEAT || T9>(p, acc, s_arow, s_orow, s_cls, reinterpret_cast<float*>(my_r), wave, lane, n0, nsub_t);
 }

@@ -12,8 +12,6 @@
 
 namespace ldn {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int GM_STEPS = 5;                 // nine taps in pairs: the second half of step 4 has zero weights
 constexpr int GM_FRAG = GM_STEPS * 64 * 32; // bytes of one group's fragments: [5][64 lanes][8 hi | 8 lo] bf16
 constexpr int GM_MAXG = 12;                 // groups per workgroup (120 KB of LDS)
@@ -101,7 +99,6 @@ __global__ __launch_bounds__(512, 2) void k_grouped16_mfma(const GmArgs p) {
         }
     }
 }
-
 
 // ------------------------------------------------------------------------------------------------------------------------
 // k_grouped16_img -- the same convolution when the packed rows are WHOLE IMAGES (layer skip: image k of the kept ones owns the

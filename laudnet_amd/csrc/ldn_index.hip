@@ -612,7 +612,7 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan(const PlanArgs a) {
                 atomicAdd(&g_plan_timeouts, 1u);
                 if (g_fault_dev) __hip_atomic_store(g_fault_dev, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // loud: the caller's next check() raises
             }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm<0>();
             poison();
         }
         leave();
@@ -687,7 +687,7 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan(const PlanArgs a) {
     }
     // 6. end check (wave 0, behind the acknowledgement of its own stores): did ANY workgroup of this launch fail its prefix wait?
     if (wave == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
         if (__hip_atomic_load(&a.sync[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) poison();
     }
     leave();

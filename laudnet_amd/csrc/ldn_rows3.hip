@@ -17,8 +17,6 @@
 
 namespace ldn {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 struct Rows3Args {
     const unsigned char* a; long lda;                 // pre-split rows, lda in BYTES (>= 4 cin)
     const int32_t* nbr;                               // [m_cap][9] packed h1 row of every tap, -1 = zero row
@@ -39,24 +37,12 @@ __device__ unsigned long long* g_rows3_trace = nullptr;
 #define RT(x)
 #endif
 
-__device__ __forceinline__ void r3_dma16(const void* gsrc, unsigned lds_base) {
+__device__ __forceinline__ void dma16_m0(const void* gsrc, unsigned lds_base) {
 #ifdef R3_M0_CLOBBER     // tuning: M0 declared clobbered instead of saved / restored around every DMA (two scalar instructions fewer)
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(gsrc), "s"(lds_base) : "memory", "m0");
 #else
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_base) : "memory");
+    dma16(gsrc, lds_base);
 #endif
-}
-template <int N> __device__ __forceinline__ void r3_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void r3_wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void r3_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ unsigned r3_lds_off(const void* ptr) {
-    return (unsigned)(size_t)(const __attribute__((address_space(3))) void*)ptr;
 }
 
 constexpr int R3_ROWS = 256;
@@ -108,7 +94,7 @@ __global__ __launch_bounds__(512, 2) void k_rows3(const Rows3Args p) {
     const int cpt = p.cin >> 5;                       // K32 sub-chunks per tap
     const int nsub = 9 * cpt, nsup = nsub >> 1;       // (cin % 64 == 0: a K64 step never straddles two taps' weight rows)
     const long wrow = (long)9 * p.cin * 4;            // bytes per weight row
-    const unsigned lds_w = r3_lds_off(s_w), lds_r = r3_lds_off(s_r) + (unsigned)wave * 2u * RSLOT;
+    const unsigned lds_w = lds_off(s_w), lds_r = lds_off(s_r) + (unsigned)wave * 2u * RSLOT;
     unsigned char* const my_r = s_r + wave * 2 * RSLOT;
 
     // per-lane sources.  Weights: instruction k (0 .. NWI - 1) of a K64 step covers LDS rows 32 k + 4 wave .. + 3, lane = (row in quad, 16-byte
@@ -120,7 +106,7 @@ __global__ __launch_bounds__(512, 2) void k_rows3(const Rows3Args p) {
         wsrc[k] = p.ws + (long)(n0 + rr) * wrow + (((lane & 15) ^ (rr & 15)) << 4);
     }
     auto dma_w = [&](int S, int k) {
-        r3_dma16(wsrc[k] + (long)min(S, nsup - 1) * 256,
+        dma16_m0(wsrc[k] + (long)min(S, nsup - 1) * 256,
                  (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_w + (unsigned)(S & 1) * WSLOT + (unsigned)(32 * k + 4 * wave) * 256u)));
     };
     // Rows: instruction k (0 .. 3) of a K32 sub-chunk covers the wave's rows 8 k .. 8 k + 7, lane = (row in octet, unit).  rsrc[k] = this lane's
@@ -138,7 +124,7 @@ __global__ __launch_bounds__(512, 2) void k_rows3(const Rows3Args p) {
         }
     };
     auto dma_r = [&](int s, int k) {      // (s only selects the slot: the source position is (tap_r, ck_r))
-        r3_dma16(rsrc[k] + ck_r * 128, (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_r + (unsigned)(s & 1) * RSLOT + (unsigned)k * 1024u)));
+        dma16_m0(rsrc[k] + ck_r * 128, (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_r + (unsigned)(s & 1) * RSLOT + (unsigned)k * 1024u)));
     };
     auto next_r = [&]() {
         if (++ck_r == cpt) {
@@ -151,11 +137,11 @@ __global__ __launch_bounds__(512, 2) void k_rows3(const Rows3Args p) {
     if (!active) {      // a wave without rows (ragged last tile) only stages its share of the weights
         for (int k = 0; k < NWI; ++k) dma_w(0, k);
         for (int S = 0; S < nsup; ++S) {
-            r3_wait_vm<0>();
-            r3_barrier();
+            wait_vm<0>();
+            lds_barrier();
             for (int k = 0; k < NWI; ++k) dma_w(S + 1, k);
         }
-        r3_wait_vm<0>();
+        wait_vm<0>();
         return;
     }
 
@@ -191,9 +177,9 @@ __global__ __launch_bounds__(512, 2) void k_rows3(const Rows3Args p) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) dma_r(1, k);
     next_r();
-    r3_wait_vm<4>();
+    wait_vm<4>();
     load_b(0, bh[0], bl[0]);
-    r3_wait_lgkm0();
+    wait_lgkm0();
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int k = 0; k < 4; ++k) dma_r(2, k);
@@ -208,9 +194,9 @@ __global__ __launch_bounds__(512, 2) void k_rows3(const Rows3Args p) {
     //                                                     sub 2S+1: [wait R(2S+2): vmcnt(4 + NWI)] read B(2S+2), R(2S+4)
     for (int S = 0; S < nsup; ++S) {
         RT(t0)
-        r3_wait_vm<8>();
+        wait_vm<8>();
         RT(t1)
-        r3_barrier();
+        lds_barrier();
         RT(t2)
         const unsigned char* wsl = s_w + (S & 1) * WSLOT + l31 * 256;
 #pragma unroll
@@ -246,15 +232,15 @@ __global__ __launch_bounds__(512, 2) void k_rows3(const Rows3Args p) {
                 } else if (st == rd_at) {
                     if (sub == 0)
                         while (w_done < NWI) dma_w(S + 1, w_done++);       // (narrow tiles: fewer steps than instructions)
-                    r3_wait_vm<4 + NWI>();
+                    wait_vm<4 + NWI>();
                     load_b(s + 1, bh[sub ^ 1], bl[sub ^ 1]);
                 } else {
-                    if (r_done == 0) r3_wait_lgkm0();                      // B(s+1) is in registers: its slot may be refilled
+                    if (r_done == 0) wait_lgkm0();                      // B(s+1) is in registers: its slot may be refilled
                     if (r_done < 4) dma_r(s + 3, r_done++);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if (r_done == 0) r3_wait_lgkm0();
+            if (r_done == 0) wait_lgkm0();
             while (r_done < 4) dma_r(s + 3, r_done++);
             next_r();
             __builtin_amdgcn_sched_barrier(0);
@@ -268,8 +254,8 @@ __global__ __launch_bounds__(512, 2) void k_rows3(const Rows3Args p) {
 #ifdef LDN_TRACE
     RT(t_loop)
 #endif
-    r3_wait_vm<0>();        // the trailing dummy DMAs have landed: this wave's row slots become its 32 x 32 transpose scratch (private: no barrier)
-    r3_wait_lgkm0();
+    wait_vm<0>();        // the trailing dummy DMAs have landed: this wave's row slots become its 32 x 32 transpose scratch (private: no barrier)
+    wait_lgkm0();
 
     // ---- epilogue: per n-subtile, C layout (lane = row, register = channel) -> rows of 32 channels, 16-byte accesses
     float* const scr = reinterpret_cast<float*>(my_r);
@@ -284,7 +270,7 @@ __global__ __launch_bounds__(512, 2) void k_rows3(const Rows3Args p) {
             const f32x4 v = {acc[j][4 * q4], acc[j][4 * q4 + 1], acc[j][4 * q4 + 2], acc[j][4 * q4 + 3]};
             *reinterpret_cast<f32x4*>(scr + l31 * 32 + (((2 * q4 + h) ^ (l31 & 7)) << 2)) = v;
         }
-        r3_wait_lgkm0();
+        wait_lgkm0();
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
@@ -299,13 +285,13 @@ __global__ __launch_bounds__(512, 2) void k_rows3(const Rows3Args p) {
             unsigned char* orow = p.out + (size_t)(m0 + wave * 32 + row) * p.ldo;
             if constexpr (OF) {     // pre-split rows: see k_dense's OF epilogue (csrc/ldn_dense.hip) -- same pairing, same conversions
                 const bool odd = tc & 1;
-                const u32x4_t o = presplit_store_quad(x, odd);
+                const u32x4 o = presplit_store_quad(x, odd);
                 if (ok) store16(orow + (size_t)(n0 + 32 * j + (tc & ~1) * 4) * 4 + (odd ? 16 : 0), o);
             } else {
                 if (ok) store16(orow + (size_t)cb * 4, x);
             }
         }
-        r3_wait_lgkm0();
+        wait_lgkm0();
         __builtin_amdgcn_wave_barrier();
     }
 #ifdef LDN_TRACE

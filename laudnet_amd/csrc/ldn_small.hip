@@ -21,11 +21,6 @@
 
 namespace ldn {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 struct SmallArgs {
     const float* x; int ldx;
     int B, H, Wd, HW, cin, W, cout;
@@ -65,77 +60,28 @@ constexpr int S_ZERO_OFF = S_KIDX_BYTES;              // one all-zero row of 128
 constexpr int S_ACT_OFF = S_KIDX_BYTES + 128;         // h1, then h2: [K slice][pixel][128 B]
 constexpr int S_TAB1_BYTES = 3 * 512 * 4;             // conv1's epilogue tables at the END of the LDS
 
-__device__ __forceinline__ void dma16(const void* gsrc, unsigned lds_base) {   // 16 B per lane, LDS = lds_base + lane * 16
-    unsigned keep;
-    lds_base = __builtin_amdgcn_readfirstlane(lds_base);    // wave-uniform by construction; a copy when it already is a scalar register
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_base) : "memory");
-}
+// The LDS bases this file hands to dma16 / dma16_pieces are wave-uniform by construction, but the compiler cannot always prove it and then keeps
+// them in VGPRs: every such call site applies readfirstlane itself (a copy where the value already is a scalar register).
+// Run-time counted waits are wait_vm_rt<14, 15>: exact up to 14, 15 for every other count.  Counts are instructions per chunk x (D - 1 or D - 2)
+// with D >= 2 where they are used, so never negative; a count above 15 over-waits, which is safe.
+
 // four consecutive 1 KB pieces of one row: source = sbase (wave-uniform) + voff (per-lane byte offset) + f * 1024, LDS = lds_base + lane * 16
 // + f * 1024 -- the instruction offset moves BOTH addresses (measured: tools/experiments/dma_offset.hip), so one M0 set-up and one address
 // serve the row
 __device__ __forceinline__ void dma16x4_row(unsigned voff, const void* sbase, unsigned lds_base) {
     unsigned keep;
     lds_base = __builtin_amdgcn_readfirstlane(lds_base);
-    {
-        const unsigned long long u = reinterpret_cast<unsigned long long>(sbase);
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-        sbase = reinterpret_cast<const void*>(((unsigned long long)hi << 32) | lo);
-    }
+    sbase = uniform_ptr(sbase);
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
                  "global_load_lds_dwordx4 %1, %2\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\t"
                  "global_load_lds_dwordx4 %1, %2 offset:2048\n\tglobal_load_lds_dwordx4 %1, %2 offset:3072\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_base) : "memory");
-}
-// NF gathered 1 KB pieces of one staged row: piece f = sbase (wave-uniform) + vo[f] (per-lane byte offset, biased by the caller so that the
-// instruction offset f * 1024 is part of it) -> LDS lds_base + f * 1024 + lane * 16; one M0 set-up for the row
-template <int NF> __device__ __forceinline__ void dma16_gather_row(const unsigned (&vo)[4], const void* sbase, unsigned lds_base) {
-    unsigned keep;
-    lds_base = __builtin_amdgcn_readfirstlane(lds_base);
-    if constexpr (NF == 1)
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(vo[0]), "s"(sbase), "s"(lds_base) : "memory");
-    else if constexpr (NF == 2)
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\tglobal_load_lds_dwordx4 %2, %3 offset:1024\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(vo[0]), "v"(vo[1]), "s"(sbase), "s"(lds_base) : "memory");
-    else if constexpr (NF == 3)
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %4\n\tglobal_load_lds_dwordx4 %2, %4 offset:1024\n\t"
-                     "global_load_lds_dwordx4 %3, %4 offset:2048\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(vo[0]), "v"(vo[1]), "v"(vo[2]), "s"(sbase), "s"(lds_base) : "memory");
-    else
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %5\n\tglobal_load_lds_dwordx4 %2, %5 offset:1024\n\t"
-                     "global_load_lds_dwordx4 %3, %5 offset:2048\n\tglobal_load_lds_dwordx4 %4, %5 offset:3072\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(vo[0]), "v"(vo[1]), "v"(vo[2]), "v"(vo[3]), "s"(sbase), "s"(lds_base) : "memory");
 }
 // piece F (1 KB) of a row whose scalar base / lane offset / LDS row base were prepared by row_prepare (same addressing as dma16x4_row)
 template <int F> __device__ __forceinline__ void dma16_row_piece(unsigned voff, const void* sbase, unsigned lds_base) {
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:%4\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_base), "n"(F * 1024) : "memory");
-}
-__device__ __forceinline__ const void* uniform_ptr(const void* v) {
-    const unsigned long long u = reinterpret_cast<unsigned long long>(v);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-    return reinterpret_cast<const void*>(((unsigned long long)hi << 32) | lo);
-}
-template <int N> __device__ __forceinline__ void wait_vm_n() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void wait_vm_rt(int n) {   // counted wait with a run-time (wave-uniform) count; more than 15: 15 (over-waits)
-    switch (n) {
-        case 0: wait_vm_n<0>(); break;   case 1: wait_vm_n<1>(); break;   case 2: wait_vm_n<2>(); break;
-        case 3: wait_vm_n<3>(); break;   case 4: wait_vm_n<4>(); break;   case 5: wait_vm_n<5>(); break;
-        case 6: wait_vm_n<6>(); break;   case 7: wait_vm_n<7>(); break;   case 8: wait_vm_n<8>(); break;
-        case 9: wait_vm_n<9>(); break;   case 10: wait_vm_n<10>(); break; case 11: wait_vm_n<11>(); break;
-        case 12: wait_vm_n<12>(); break; case 13: wait_vm_n<13>(); break; case 14: wait_vm_n<14>(); break;
-        default: wait_vm_n<15>(); break;
-    }
-}
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ unsigned lds_off(const void* ptr) {
-    return (unsigned)(size_t)(const __attribute__((address_space(3))) void*)ptr;
 }
 
 // LDS geometry of an image with nsub K slices on a map of HW pixels (shared by the kernel and the host-side fit check)
@@ -239,7 +185,7 @@ __global__ __launch_bounds__(512, 2) void k_smallmap(const SmallArgs p) {
         // ==================================================================================================== conv1 (1x1)
         // ring slot = [64 x rows | wrows weight rows] x 128 B over everything behind the channel list (h1 does not exist yet).  The weight
         // rows are staged WAVE-MAJOR: piece i (rows 64 i + 8 w .. + 7 of the image's list) of wave w lies at 1 KB block w * nw + i, so that a
-        // wave's pieces are consecutive kilobytes and up to four of them share one address set-up (dma16_gather_row).  Software pipeline
+        // wave's pieces are consecutive kilobytes and up to four of them share one address set-up (dma16_pieces).  Software pipeline
         // over the K16 steps as in conv2 / conv3: the raw fragments of step u + 1 are read while the MFMAs of step u run.
         {
             const int wrows = round_up(Kb, 64);
@@ -268,16 +214,16 @@ __global__ __launch_bounds__(512, 2) void k_smallmap(const SmallArgs p) {
             }
             unsigned foff = 0; int fc = 0;
             auto gather = [&](int nf, const unsigned (&vo)[4], const void* sbase, unsigned lds) {
-                if (nf >= 4) dma16_gather_row<4>(vo, sbase, lds);
-                else if (nf == 3) dma16_gather_row<3>(vo, sbase, lds);
-                else if (nf == 2) dma16_gather_row<2>(vo, sbase, lds);
-                else if (nf == 1) dma16_gather_row<1>(vo, sbase, lds);
+                if (nf >= 4) dma16_pieces<4>(vo, sbase, __builtin_amdgcn_readfirstlane(lds));
+                else if (nf == 3) dma16_pieces<3>(vo, sbase, __builtin_amdgcn_readfirstlane(lds));
+                else if (nf == 2) dma16_pieces<2>(vo, sbase, __builtin_amdgcn_readfirstlane(lds));
+                else if (nf == 1) dma16_pieces<1>(vo, sbase, __builtin_amdgcn_readfirstlane(lds));
             };
             const unsigned wa4[4] = {wo[0], wo[1], wo[2], wo[3]}, wb4[4] = {wo[4], wo[5], wo[6], wo[7]};
             auto issue = [&]() {
                 const int c = min(fc, nchunks - 1);             // chunks beyond the K loop: the last one again (keeps the per-chunk count)
                 const unsigned slot = ring1 + foff;
-                if (xw) dma16_gather_row<1>(xo, uniform_ptr(p.x + c * 32), slot + 8 * wave * 128);
+                if (xw) dma16_pieces<1>(xo, uniform_ptr(p.x + c * 32), __builtin_amdgcn_readfirstlane(slot + 8 * wave * 128));
                 const void* wb = uniform_ptr(p.w1s + (long)c * 128 - 3072);
                 gather(min(nw, 4), wa4, wb, slot + (64 * 128) + (wave * nw) * 1024);
                 if (nw > 4) gather(nw - 4, wb4, wb, slot + (64 * 128) + (wave * nw + 4) * 1024);
@@ -330,7 +276,7 @@ __global__ __launch_bounds__(512, 2) void k_smallmap(const SmallArgs p) {
                     }
                 };
                 Frag f0, f1;
-                wait_vm_rt(ipc * (D - 1));                       // chunk 0
+                wait_vm_rt<14, 15>(ipc * (D - 1));                       // chunk 0
                 lds_barrier();
                 load_frag(f0, 0);
 #pragma unroll 1
@@ -338,7 +284,7 @@ __global__ __launch_bounds__(512, 2) void k_smallmap(const SmallArgs p) {
                     load_frag(f1, 1);
                     mfma_frag(f0);
                     ST(ta)
-                    wait_vm_rt(ipc * (D - 2));                   // chunk c + 1 has landed ...
+                    wait_vm_rt<14, 15>(ipc * (D - 2));                   // chunk c + 1 has landed ...
                     lds_barrier();                               // ... for every wave; every wave has read chunk c
                     ST(tb)
                     ST_ADD(wt[0], ta, tb)
@@ -355,7 +301,7 @@ __global__ __launch_bounds__(512, 2) void k_smallmap(const SmallArgs p) {
                 case 3: run(std::integral_constant<int, 3>{}); break;
                 default: run(std::integral_constant<int, 4>{}); break;
             }
-            wait_vm_n<0>();
+            wait_vm<0>();
             lds_barrier();                                     // the ring is dead: its place is h1's
             ST(ts[1])
         }
@@ -442,10 +388,10 @@ __global__ __launch_bounds__(512, 2) void k_smallmap(const SmallArgs p) {
                 };
                 load_rb();
                 auto row_dma = [&](const void* sbase, unsigned lds) {
-                    if (nf == 3) dma16_gather_row<3>(vo, sbase, lds);
-                    else if (nf == 4) dma16_gather_row<4>(vo, sbase, lds);
-                    else if (nf == 2) dma16_gather_row<2>(vo, sbase, lds);
-                    else dma16_gather_row<1>(vo, sbase, lds);
+                    if (nf == 3) dma16_pieces<3>(vo, sbase, __builtin_amdgcn_readfirstlane(lds));
+                    else if (nf == 4) dma16_pieces<4>(vo, sbase, __builtin_amdgcn_readfirstlane(lds));
+                    else if (nf == 2) dma16_pieces<2>(vo, sbase, __builtin_amdgcn_readfirstlane(lds));
+                    else dma16_pieces<1>(vo, sbase, __builtin_amdgcn_readfirstlane(lds));
                 };
                 auto issue = [&]() {
                     const unsigned char* tapbase = p.w2p + (long)itp * tapstride - 3072;
@@ -509,7 +455,7 @@ __global__ __launch_bounds__(512, 2) void k_smallmap(const SmallArgs p) {
                     };
                     auto sync_issue = [&]() {          // the next chunk has landed for every wave; every wave has read the current one
                         ST(ta)
-                        wait_vm_rt(ipc * (D - 2));
+                        wait_vm_rt<14, 15>(ipc * (D - 2));
                         lds_barrier();
                         ST(tb)
                         ST_ADD(wt[1], ta, tb)
@@ -517,7 +463,7 @@ __global__ __launch_bounds__(512, 2) void k_smallmap(const SmallArgs p) {
                         coff += slotB; if (coff == ring_bytes) coff = 0;
                     };
                     Frag f0, f1;
-                    wait_vm_rt(ipc * (D - 1));                   // chunk 0
+                    wait_vm_rt<14, 15>(ipc * (D - 1));                   // chunk 0
                     lds_barrier();
                     load_frag(f0, 0, 0, 0, 0);
 #pragma unroll 1
@@ -563,7 +509,7 @@ __global__ __launch_bounds__(512, 2) void k_smallmap(const SmallArgs p) {
                     const int rowoff = (itp * (W / 2) + (kch >> 1)) * (W / 2) * 16;
                     const int np = f == 0 ? npo[0] : f == 1 ? npo[1] : f == 2 ? npo[2] : npo[3];
                     const unsigned char* src = (kch >= 0 && np >= 0) ? p.w2p + rowoff + np : reinterpret_cast<const unsigned char*>(g_small_zero);
-                    dma16(src, slot + u * W2ROW + f * 1024);
+                    dma16(src, __builtin_amdgcn_readfirstlane(slot + u * W2ROW + f * 1024));
                 }
             };
             auto issue_advance = [&]() {
@@ -595,8 +541,8 @@ __global__ __launch_bounds__(512, 2) void k_smallmap(const SmallArgs p) {
 #pragma unroll 1
                     for (int hf = 0; hf < per; ++hf, ++c) {
                         ST(ta)
-                        if (D == 1) { lds_barrier(); issue(); wait_vm_n<0>(); }
-                        else wait_vm_rt(ipc * (D - 2));
+                        if (D == 1) { lds_barrier(); issue(); wait_vm<0>(); }
+                        else wait_vm_rt<14, 15>(ipc * (D - 2));
                         lds_barrier();
                         ST(tb)
                         ST_ADD(wt[1], ta, tb)
@@ -664,7 +610,7 @@ __global__ __launch_bounds__(512, 2) void k_smallmap(const SmallArgs p) {
                 }
             }
             }
-            wait_vm_n<0>();
+            wait_vm<0>();
             lds_barrier();                                     // every wave has left h1 and the W2 ring
             ST(ts[3])
             // ---- epilogue 2: h2 = relu(sc2 * conv2 + sh2[class]) - c2 over h1's place; tables in the dead ring
@@ -720,7 +666,7 @@ __global__ __launch_bounds__(512, 2) void k_smallmap(const SmallArgs p) {
         auto issue_part = [&](int f) {
             const unsigned slot = lds_ring + ioff;
             const unsigned char* src = (i3base && 512 * ig + 128 * f < p.cout) ? i3base + f * 1024 : reinterpret_cast<const unsigned char*>(g_small_zero);
-            dma16(src, slot + wave * 4096 + f * 1024);
+            dma16(src, __builtin_amdgcn_readfirstlane(slot + wave * 4096 + f * 1024));
         };
         auto issue_advance = [&]() {
             ioff += 32768; if (ioff == D * 32768) ioff = 0;
@@ -835,7 +781,7 @@ __global__ __launch_bounds__(512, 2) void k_smallmap(const SmallArgs p) {
             // (the four DMA instructions as ONE burst right after the barrier: spread between the MFMAs of the step they measured 10 % slower)
             auto sync_issue = [&]() {          // the next chunk has landed for every wave; every wave has read the current one
                 ST(tb)
-                if (D == 2) wait_vm_n<0>(); else wait_vm_n<4>();
+                if (D == 2) wait_vm<0>(); else wait_vm<4>();
                 ST(ta)
                 ST_ADD(x3[0], tb, ta)
                 lds_barrier();
@@ -850,7 +796,7 @@ __global__ __launch_bounds__(512, 2) void k_smallmap(const SmallArgs p) {
                 ST_ADD(x3[2], tb, ta)
             };
             Frag f0, f1;
-            if (D == 2) wait_vm_n<4>(); else wait_vm_n<8>();   // chunk 0
+            if (D == 2) wait_vm<4>(); else wait_vm<8>();   // chunk 0
             lds_barrier();
             load_frag(f0, s_act, bo[0]);
 #pragma unroll 1
@@ -882,8 +828,8 @@ __global__ __launch_bounds__(512, 2) void k_smallmap(const SmallArgs p) {
                 for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
 #pragma unroll 1
             for (int ks = 0; ks < nk16; ++ks, ++c) {
-                if (D == 1) { lds_barrier(); issue(); wait_vm_n<0>(); }
-                else wait_vm_rt(4 * (D - 2));
+                if (D == 1) { lds_barrier(); issue(); wait_vm<0>(); }
+                else wait_vm_rt<14, 15>(4 * (D - 2));
                 lds_barrier();
                 const unsigned char* ws = smem + G.ring_off + coff;
                 coff += 32768; if (coff == D * 32768) coff = 0;
@@ -915,7 +861,7 @@ __global__ __launch_bounds__(512, 2) void k_smallmap(const SmallArgs p) {
             if (active) group_epilogue(g);
         }
         }
-        wait_vm_n<0>();      // no LDS-DMA may be in flight when the workgroup's LDS is released
+        wait_vm<0>();      // no LDS-DMA may be in flight when the workgroup's LDS is released
 #ifdef LDN_TRACE
         ST(ts[5])
         if (g_small_trace && lane == 0) {

@@ -22,8 +22,6 @@
 
 namespace ldn {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 #ifndef LDN_STEM_ABLATE
 #define LDN_STEM_ABLATE 0   // tuning only (results are wrong): 1 = no MFMA loop, 2 = no pooling phase, 4 = no patch fetch, 8 = no conv-tile write
 #endif
@@ -147,8 +145,7 @@ __global__ __launch_bounds__(512, 2) void k_stem(const StemArgs p) {
             for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
         // software-pipelined over the 11 K16 steps (schedule pinned): the 8 patch floats and the weight fragments of step s + 1 are
         // requested before the MFMAs of step s and split into bf16 hi / lo after them
-        typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
-        u32x4s rawh[2], rawl[2];
+        u32x4 rawh[2], rawl[2];
         bf16x8 fh[2][NSUB], fl[2][NSUB];
         auto request = [&](int s, int buf) {
             const int q = 2 * s + h;                   // this lane's k8 group: patch row q / 3, values 8 (q % 3) .. + 7 of the row window
@@ -259,7 +256,6 @@ __global__ __launch_bounds__(512, 2) void k_stem(const StemArgs p) {
     }
 }
 
-
 template <int NSUB>
 static int launch_stem(const StemArgs& a, int cus, hipStream_t st) {
     constexpr int C = 32 * NSUB;
@@ -272,7 +268,6 @@ static int launch_stem(const StemArgs& a, int cus, hipStream_t st) {
     LDN_CHECK_LAUNCH("k_stem");
     return LDN_OK;
 }
-
 
 // ------------------------------------------------------------------------------------------------------------------------
 // k_stem3 -- the static stem of the LAD-RegNets as one kernel: conv 3x3 stride 2 pad 1 (3 -> C channels, the BN's scale folded into

@@ -26,10 +26,6 @@
 
 namespace ldn {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 struct TailArgs {
     const unsigned char* h1; long h1_row_bytes;       // pre-split h1: row of pixel q at h1 + q * h1_row_bytes
     int B, Hi, Wi, Ho, Wo, W, cout;                   // stride 1: Hi == Ho, Wi == Wo
@@ -74,42 +70,21 @@ template <typename A, typename B, typename C> __device__ __forceinline__ C t_mfm
 #define t_mfma_bf16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
 #endif
 
-// LDS-DMA of 16 bytes per lane: LDS destination = lds_base (wave-uniform byte address) + lane * 16, source per lane.
-// Inline asm: the compiler neither counts it nor waits for it (cdna_hip_programming.md 5.7) -- every wait is explicit below.
-__device__ __forceinline__ void dma16(const void* gsrc, unsigned lds_base) {
+// This file's LDS-DMA goes through two wrappers, so that LDN_TAIL_ABLATE & 1 can take all of it out (ldn_chain_ld.h, part of this translation
+// unit, uses them for the same reason).
+// Its run-time counted waits are wait_vm_rt<15, 16>: exact up to 15, 16 for every other count.  A larger count (up to 9 per chunk x 3 chunks
+// in flight) over-waits, which is safe; a negative one is only own_landed of a wave without pixels, which has no rows of its own to wait for.
+__device__ __forceinline__ void dma16_abl(const void* gsrc, unsigned lds_base) {
 #if LDN_TAIL_ABLATE & 1
     return;
 #endif
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_base) : "memory");
+    dma16(gsrc, lds_base);
 }
-// L2 prefetch (round 5): 4 bytes per lane through the LDS-DMA path into a scratch word -- no VGPR result to keep alive, counted in vmcnt like
-// every other DMA instruction.  What it buys is the LINE in the XCD's L2 ahead of the 16-byte DMA that will fetch it for real.
-__device__ __forceinline__ void dma4_touch(const void* gsrc, unsigned lds_base) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_base) : "memory");
-}
-template <int N> __device__ __forceinline__ void wait_vm() {
-    static_assert(N == 0 || N == 1 || N == 2 || N == 4, "add the immediate");
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-}
-__device__ __forceinline__ void lds_barrier() {   // LDS traffic of this wave retired, then the workgroup barrier (no vmcnt)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ unsigned lds_off(const void* ptr) {
-    return (unsigned)(size_t)(const __attribute__((address_space(3))) void*)ptr;
-}
-
-__device__ __forceinline__ void split2(float v, __bf16& hi, __bf16& lo) {
-    hi = (__bf16)v;
-    lo = (__bf16)(v - (float)hi);
+template <int NF> __device__ __forceinline__ void dma16_pieces_abl(const unsigned (&vo)[4], const void* sbase, unsigned lds_base) {
+#if LDN_TAIL_ABLATE & 1
+    return;
+#endif
+    dma16_pieces<NF>(vo, sbase, lds_base);
 }
 
 // One K16 step of a 32 x 32 tile.  bf16x3: three v_mfma_f32_32x32x16_bf16 of the hi / lo halves (AH_ / AL_ = 8 hi | 8 lo of the A rows,
@@ -279,7 +254,7 @@ __device__ __forceinline__ void tail_body(const TailArgs& p, const int b, const 
         const int lslot = (lane & 7) ^ ((r >> 1) & 7);
         const unsigned char* src = r < NR ? p.h1 + (in_row0 + r) * p.h1_row_bytes + slice * 128 + lslot * 16
                                           : reinterpret_cast<const unsigned char*>(g_tail_zero);
-        dma16(src, lds_h1 + (slice % SLICE_BUFS) * p.slice_bytes + q * 1024);
+        dma16_abl(src, lds_h1 + (slice % SLICE_BUFS) * p.slice_bytes + q * 1024);
     };
     // W2 chunk (slice s, tap t): 16 k-pair rows x (Kp / 2) n-pair pieces of 16 B.  Wave w stages rows 2w and 2w + 1.
     //   NS == 2: one instruction covers both rows (lanes 0-31 / 32-63); NS == 4: one instruction per row;
@@ -301,7 +276,7 @@ __device__ __forceinline__ void tail_body(const TailArgs& p, const int b, const 
         const long pix = (long)b * p.Hi * p.Wi + (long)(2 * (plo[g] + pr) + (g >> 1)) * p.Wi + 2 * (clo[g] + pc) + (g & 1);
         const unsigned char* src = r < pn[g] ? p.h1 + pix * p.h1_row_bytes + slice * 128 + lslot * 16
                                              : reinterpret_cast<const unsigned char*>(g_tail_zero);
-        dma16(src, lds_h1 + buf * p.slice_bytes + q * 1024);
+        dma16_abl(src, lds_h1 + buf * p.slice_bytes + q * 1024);
     };
     // W2 chunk c (W2 slot c % 3) = tap t of K slice s; e = 0 / 1: this wave's first / second k-pair row (the two halves of its share)
     auto dma_w2e = [&](int c, int s, int t, int e) {
@@ -312,16 +287,16 @@ __device__ __forceinline__ void tail_body(const TailArgs& p, const int b, const 
         if (NS == 2) {
             if (e == 1) return;
             const unsigned char* src = (kch >= 0 && npo[0] >= 0) ? p.w2p + rowoff + npo[0] : reinterpret_cast<const unsigned char*>(g_tail_zero);
-            dma16(src, slot + 2 * wave * W2_ROW);
+            dma16_abl(src, slot + 2 * wave * W2_ROW);
         } else if (NS == 4) {
             const unsigned char* src = (kch >= 0 && npo[0] >= 0) ? p.w2p + rowoff + npo[0] : reinterpret_cast<const unsigned char*>(g_tail_zero);
-            dma16(src, slot + u * W2_ROW);
+            dma16_abl(src, slot + u * W2_ROW);
         } else {
 #pragma unroll
             for (int f = 0; f < 2; ++f) {
                 if (f == 1 && Kp <= 128) break;
                 const unsigned char* src = (kch >= 0 && npo[f] >= 0) ? p.w2p + rowoff + npo[f] : reinterpret_cast<const unsigned char*>(g_tail_zero);
-                dma16(src, slot + u * W2_ROW + f * 1024);
+                dma16_abl(src, slot + u * W2_ROW + f * 1024);
             }
         }
     };
@@ -329,7 +304,7 @@ __device__ __forceinline__ void tail_body(const TailArgs& p, const int b, const 
     // the dummies that stand in for half e of a W2 tile beyond the K range (they keep the counted wait's arithmetic constant)
     auto dma_w2_dummy = [&](int c, int e) {
         const int n = NS == 2 ? (e == 0 ? 1 : 0) : (NS == 4 ? 1 : (Kp > 128 ? 2 : 1));
-        for (int i = 0; i < n; ++i) dma16(g_tail_zero, lds_w2 + (c % T_W2_SLOTS) * W2_SLOT + (2 * wave) * W2_ROW);
+        for (int i = 0; i < n; ++i) dma16_abl(g_tail_zero, lds_w2 + (c % T_W2_SLOTS) * W2_SLOT + (2 * wave) * W2_ROW);
     };
     auto dma_w2 = [&](int c) { dma_w2x(c, c / 9, c % 9); };   // stride 1: taps in order
     auto wait_chunk = [&]() {   // everything but this wave's last n_w2 DMA instructions (= the W2 pieces of the NEXT chunk) has landed
@@ -387,7 +362,7 @@ __device__ __forceinline__ void tail_body(const TailArgs& p, const int b, const 
                     // issue: this chunk's share of the next plane first, then the W2 tile of chunk c + 2 (the counted wait relies on the order)
                     for (int q = i * 8 + wave; q < npn; q += 8 * NTP[o]) dma_plane(sn, gn, (u + 1) & 1, q);
                     if (c + 2 < nchunks) dma_w2x(c + 2, (c + 2) / 9, tap_of(c + 2));
-                    else { for (int e = 0; e < n_w2; ++e) dma16(g_tail_zero, lds_w2 + ((c + 2) % T_W2_SLOTS) * W2_SLOT + (2 * wave) * W2_ROW); }
+                    else { for (int e = 0; e < n_w2; ++e) dma16_abl(g_tail_zero, lds_w2 + ((c + 2) % T_W2_SLOTS) * W2_SLOT + (2 * wave) * W2_ROW); }
                     if (active) LDN_TAIL_CHUNK_MFMA(s_w2 + (c % T_W2_SLOTS) * W2_SLOT, hs, trow[TAPS[o][i]])
                     ++c;
                 }
@@ -487,7 +462,7 @@ __device__ __forceinline__ void tail_body(const TailArgs& p, const int b, const 
 #endif
             if (SLICE_BUFS == 2 && s + 1 < nsub) { const int q = t * 8 + wave; if (q < nq) dma_h1(s + 1, q); }
             if (c + 2 < nchunks) dma_w2(c + 2);
-            else { for (int e = 0; e < n_w2; ++e) dma16(g_tail_zero, lds_w2 + ((t + 2) % T_W2_SLOTS) * W2_SLOT + (2 * wave) * W2_ROW); }   // keeps the count
+            else { for (int e = 0; e < n_w2; ++e) dma16_abl(g_tail_zero, lds_w2 + ((t + 2) % T_W2_SLOTS) * W2_SLOT + (2 * wave) * W2_ROW); }   // keeps the count
 #if LDN_TAIL_PRIO == 2
             __builtin_amdgcn_s_setprio(0);
 #endif
@@ -526,7 +501,7 @@ __device__ __forceinline__ void tail_body(const TailArgs& p, const int b, const 
             const int kch = s_kidx[2 * u];
             const unsigned char* src = kch >= 0 ? p.w3p + ((long)(kch >> 1) * p.cout + cc * CW + 2 * (lane % LPR)) * 8
                                                 : reinterpret_cast<const unsigned char*>(g_tail_zero);
-            dma16(src, slot + i * 1024);
+            dma16_abl(src, slot + i * 1024);
         }
         if constexpr (PROJ) {
             // Wd's k-pair rows behind the image's Kp / 2 rows of W3.  Staged row 8 s + r of K16 step s holds source pair 8 s + PI[r]:
@@ -536,7 +511,7 @@ __device__ __forceinline__ void tail_body(const TailArgs& p, const int b, const 
                 const int u = RPI * i + lane / LPR;
                 const int r = u & 7;
                 const int sp = (u & ~7) | ((r & 1) | ((r & 2) << 1) | ((r & 4) >> 1));
-                dma16(p.pw + ((long)sp * p.cout + cc * CW + 2 * (lane % LPR)) * 8, slot + (Kp / (2 * RPI) + i) * 1024);
+                dma16_abl(p.pw + ((long)sp * p.cout + cc * CW + 2 * (lane % LPR)) * 8, slot + (Kp / (2 * RPI) + i) * 1024);
             }
         }
     };
@@ -571,7 +546,6 @@ __device__ __forceinline__ void tail_body(const TailArgs& p, const int b, const 
     // In place: the 16 fp32 accumulators of n-subtile j become 16 dwords of bf16 pairs -- for each K16 step t of conv3
     // [8t .. 8t+3] = the 8 hi halves, [8t+4 .. 8t+7] = the 8 lo halves of the lane's h2 values (k-slot e = 4 qq + i <->
     // accumulator register 8t + 4 qq + i).  No second register array: h2 of the widest layer alone takes 128 registers.
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
     for (int j = 0; j < NS; ++j) {
         float v[16];
@@ -975,49 +949,6 @@ struct HeadArgs {
     unsigned char* xs;                                // optional: x itself written pre-split in 32-pixel tiles (ldn_bottleneck_head_split) for a folded projection
 };
 
-template <int N> __device__ __forceinline__ void wait_vm_n() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void wait_vm_rt(int n) {   // counted wait with a run-time (wave-uniform) count, 0..16
-    switch (n) {
-        case 0: wait_vm_n<0>(); break;   case 1: wait_vm_n<1>(); break;   case 2: wait_vm_n<2>(); break;
-        case 3: wait_vm_n<3>(); break;   case 4: wait_vm_n<4>(); break;   case 5: wait_vm_n<5>(); break;
-        case 6: wait_vm_n<6>(); break;   case 7: wait_vm_n<7>(); break;   case 8: wait_vm_n<8>(); break;
-        case 9: wait_vm_n<9>(); break;   case 10: wait_vm_n<10>(); break; case 11: wait_vm_n<11>(); break;
-        case 12: wait_vm_n<12>(); break; case 13: wait_vm_n<13>(); break; case 14: wait_vm_n<14>(); break;
-        case 15: wait_vm_n<15>(); break; default: wait_vm_n<16>(); break;
-    }
-}
-
-// NF consecutive 1 KB pieces of a ring slot with ONE address set-up: piece f = sbase (wave-uniform) + vo[f] (per-lane byte offset, biased by
-// the caller with (3 - f) * 1024 against sbase - 3072) -> LDS lds_base + f * 1024 + lane * 16.  The instruction offset of
-// global_load_lds_dwordx4 moves the LDS destination as well as the global source (tools/experiments/dma_offset.hip).
-template <int NF> __device__ __forceinline__ void dma16_pieces(const unsigned (&vo)[4], const void* sbase, unsigned lds_base) {
-#if LDN_TAIL_ABLATE & 1
-    return;
-#endif
-    unsigned keep;
-    if constexpr (NF == 1)
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(vo[0]), "s"(sbase), "s"(lds_base) : "memory");
-    else if constexpr (NF == 2)
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\tglobal_load_lds_dwordx4 %2, %3 offset:1024\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(vo[0]), "v"(vo[1]), "s"(sbase), "s"(lds_base) : "memory");
-    else if constexpr (NF == 3)
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %4\n\tglobal_load_lds_dwordx4 %2, %4 offset:1024\n\t"
-                     "global_load_lds_dwordx4 %3, %4 offset:2048\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(vo[0]), "v"(vo[1]), "v"(vo[2]), "s"(sbase), "s"(lds_base) : "memory");
-    else
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %5\n\tglobal_load_lds_dwordx4 %2, %5 offset:1024\n\t"
-                     "global_load_lds_dwordx4 %3, %5 offset:2048\n\tglobal_load_lds_dwordx4 %4, %5 offset:3072\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(vo[0]), "v"(vo[1]), "v"(vo[2]), "v"(vo[3]), "s"(sbase), "s"(lds_base) : "memory");
-}
-__device__ __forceinline__ const void* uniform_cptr(const void* v) {
-    const unsigned long long u = reinterpret_cast<unsigned long long>(v);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-    return reinterpret_cast<const void*>(((unsigned long long)hi << 32) | lo);
-}
-
 constexpr int H_XROWS = 256;                          // rows of the x tile of a ring slot (pixels of the block, padded)
 
 template <int NS, bool F32 = false, bool PRE_ROWS = false>
@@ -1086,7 +1017,7 @@ __device__ __forceinline__ void head_body(const HeadArgs& p, const int b, const 
     auto dma_chunk = [&](int c) {
         const unsigned slot = lds_ring + (c % D) * slot_bytes;
         const int cc = min(c, nchunks - 1);              // chunks beyond the K loop: the last one again (keeps the per-iteration DMA count constant)
-        if (active) dma16_pieces<4>(xo, uniform_cptr(xbase + (long)cc * 128), __builtin_amdgcn_readfirstlane(slot + wave * 32 * 128));
+        if (active) dma16_pieces_abl<4>(xo, uniform_ptr(xbase + (long)cc * 128), __builtin_amdgcn_readfirstlane(slot + wave * 32 * 128));
         if (PF && active) {
             // L2 prefetch of this wave's x rows two and three chunks beyond the ring (round 5): the phase is bound by bytes in
             // flight / HBM latency at one workgroup per CU; a touched line waits in the XCD's L2 when its 16-byte DMA comes (lanes 0-31: chunk
@@ -1095,12 +1026,12 @@ __device__ __forceinline__ void head_body(const HeadArgs& p, const int b, const 
             dma4_touch(reinterpret_cast<const unsigned char*>(p.x + (row0 + min(wave * 32 + l31, npix - 1)) * p.ldx) + (long)pc * 128,
                        __builtin_amdgcn_readfirstlane((unsigned)(lds_ring + (unsigned)avail)));
         }
-        const void* wb = uniform_cptr(wbase + (long)cc * 128);
+        const void* wb = uniform_ptr(wbase + (long)cc * 128);
         const unsigned wl = __builtin_amdgcn_readfirstlane(slot + (xrows + wave * nw * 8) * 128);
-        if (nw == 1) dma16_pieces<1>(wo, wb, wl);
-        else if (nw == 2) dma16_pieces<2>(wo, wb, wl);
-        else if (nw == 3) dma16_pieces<3>(wo, wb, wl);
-        else dma16_pieces<4>(wo, wb, wl);
+        if (nw == 1) dma16_pieces_abl<1>(wo, wb, wl);
+        else if (nw == 2) dma16_pieces_abl<2>(wo, wb, wl);
+        else if (nw == 3) dma16_pieces_abl<3>(wo, wb, wl);
+        else dma16_pieces_abl<4>(wo, wb, wl);
     };
     auto dma_dummy = [&](int c) { dma_chunk(c); };
 
@@ -1163,12 +1094,12 @@ __device__ __forceinline__ void head_body(const HeadArgs& p, const int b, const 
     constexpr bool PRE = PRE_ROWS;
     const int own_landed = per_chunk * (D - 1) - 4;      // own rows of the oldest chunk in flight = its first four pieces
     if (PRE && active && nchunks > 0) {
-        wait_vm_rt(own_landed);
+        wait_vm_rt<15, 16>(own_landed);
         load_b(0);
     }
     for (int c = 0; c < nchunks; ++c) {
         TT(h0)
-        wait_vm_rt(per_chunk * (D - 2));     // chunk c has landed; the D - 2 chunks issued after it may still fly
+        wait_vm_rt<15, 16>(per_chunk * (D - 2));     // chunk c has landed; the D - 2 chunks issued after it may still fly
         TT(h1)
         lds_barrier();                       // ... for every wave; every wave has left chunk c - 1
         TT(h2)
@@ -1242,7 +1173,7 @@ __device__ __forceinline__ void head_body(const HeadArgs& p, const int b, const 
         }
 #undef LDN_HEAD_STEP
         if (PRE && c + 1 < nchunks) {
-            wait_vm_rt(own_landed);
+            wait_vm_rt<15, 16>(own_landed);
             load_b(c + 1);
         }
 #ifdef LDN_TRACE
@@ -1259,7 +1190,7 @@ __device__ __forceinline__ void head_body(const HeadArgs& p, const int b, const 
         r[0] = hw; r[1] = hb; r[2] = hi_; r[3] = hs; r[4] = hm; r[5] = hend - hstart; r[6] = nchunks; r[7] = nsub;
     }
 #endif
-    wait_vm_n<0>();      // no LDS-DMA may be in flight when the workgroup's LDS is released
+    wait_vm<0>();      // no LDS-DMA may be in flight when the workgroup's LDS is released
 
     // ---- epilogue: bn1 + ReLU - c1, split, pair the half-waves, 16-byte stores of [8 hi] (lanes 0-31) / [8 lo] (lanes 32-63)
     const int pm = wave * 32 + l31;
@@ -1281,7 +1212,6 @@ __device__ __forceinline__ void head_body(const HeadArgs& p, const int b, const 
                 if (pm < npix) *reinterpret_cast<f32x4*>(orow + (4 * j + q4) * 32 + h * 16) = v4;
                 continue;
             }
-            typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
             unsigned hi2[2], lo2[2];
 #pragma unroll
             for (int d = 0; d < 2; ++d) {
@@ -1363,7 +1293,7 @@ __device__ __forceinline__ void head_body2(const HeadArgs& p, const int b, const
         rsrc[k] = reinterpret_cast<const unsigned char*>(p.x + (row0 + min(wave * 32 + r, npix - 1)) * p.ldx) + (((lane & 7) ^ ((r >> 1) & 7)) << 4);
     }
     auto dma_w = [&](int S, int k) {
-        dma16(wsrc[k] + (long)min(S, nstep - 1) * 128, (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_w + (unsigned)(S & 1) * WSLOT + (unsigned)(64 * k + 8 * wave) * 128u)));
+        dma16_abl(wsrc[k] + (long)min(S, nstep - 1) * 128, (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_w + (unsigned)(S & 1) * WSLOT + (unsigned)(64 * k + 8 * wave) * 128u)));
     };
     auto dma_w_all = [&](int S) {
 #pragma unroll
@@ -1371,17 +1301,17 @@ __device__ __forceinline__ void head_body2(const HeadArgs& p, const int b, const
             if (k < nw) dma_w(S, k);
     };
     auto dma_r = [&](int s, int k) {
-        dma16(rsrc[k] + (long)min(s, nstep - 1) * 128, (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_r + (unsigned)(s & 1) * RSLOT + (unsigned)k * 1024u)));
+        dma16_abl(rsrc[k] + (long)min(s, nstep - 1) * 128, (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_r + (unsigned)(s & 1) * RSLOT + (unsigned)k * 1024u)));
     };
 
     if (!active) {      // a wave without pixels only stages its share of the weights
         dma_w_all(0);
         for (int S = 0; S < nstep; ++S) {
-            wait_vm_n<0>();
+            wait_vm<0>();
             lds_barrier();
             dma_w_all(S + 1);
         }
-        wait_vm_n<0>();
+        wait_vm<0>();
         return;
     }
 
@@ -1419,7 +1349,7 @@ __device__ __forceinline__ void head_body2(const HeadArgs& p, const int b, const
     for (int k = 0; k < 4; ++k) dma_r(0, k);
 #pragma unroll
     for (int k = 0; k < 4; ++k) dma_r(1, k);
-    wait_vm_n<4>();
+    wait_vm<4>();
     read_raw(0);
     split_b(0, bh[0], bl[0]);
     split_b(1, bh[0], bl[0]);
@@ -1427,19 +1357,19 @@ __device__ __forceinline__ void head_body2(const HeadArgs& p, const int b, const
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int k = 0; k < 4; ++k) dma_r(2, k);
-    wait_vm_n<4>();
+    wait_vm<4>();
 
     // one step with B register set CUR: [W(S) landed: vmcnt(4)] barrier | MFMA steps (K16 half 0 of every n-subtile, then half 1) with, behind
     // the first ones, W(S + 1), the raw read of x(S + 1) [x(S + 1) landed: vmcnt(4 + 2 nw)], its split into the other set, and R(S + 3)
     auto step = [&](int S, auto cur_c) {
         constexpr int CUR = decltype(cur_c)::value;
-        wait_vm_n<4>();
+        wait_vm<4>();
         lds_barrier();
         const unsigned char* wsl = s_w + (S & 1) * WSLOT + l31 * 128;
         int stage = 0;      // what has gone out of: 0 W(S + 1), 1 read, 2 split 0, 3 split 1, 4 R(S + 3)
         auto extra = [&]() {
             if (stage == 0) dma_w_all(S + 1);
-            else if (stage == 1) { wait_vm_rt(4 + 2 * nw); read_raw(S + 1); }
+            else if (stage == 1) { wait_vm_rt<15, 16>(4 + 2 * nw); read_raw(S + 1); }
             else if (stage == 2) split_b(0, bh[CUR ^ 1], bl[CUR ^ 1]);
             else if (stage == 3) split_b(1, bh[CUR ^ 1], bl[CUR ^ 1]);
             else if (stage == 4) {
@@ -1474,7 +1404,7 @@ __device__ __forceinline__ void head_body2(const HeadArgs& p, const int b, const
         step(S, std::integral_constant<int, 0>{});
         step(S + 1, std::integral_constant<int, 1>{});
     }
-    wait_vm_n<0>();      // no LDS-DMA may be in flight when the workgroup's LDS is released
+    wait_vm<0>();      // no LDS-DMA may be in flight when the workgroup's LDS is released
 
     // ---- epilogue (as head_body): bn1 + ReLU - c1, split, pair the half-waves, 16-byte stores of [8 hi] (lanes 0-31) / [8 lo] (lanes 32-63)
     const int pm = wave * 32 + l31;
@@ -1488,7 +1418,6 @@ __device__ __forceinline__ void head_body2(const HeadArgs& p, const int b, const
             const f32x4 sc = *reinterpret_cast<const f32x4*>(s_tab + n0);
             const f32x4 sh = *reinterpret_cast<const f32x4*>(s_tab + W + n0);
             const f32x4 ps = *reinterpret_cast<const f32x4*>(s_tab + 2 * W + n0);
-            typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
             unsigned hi2[2], lo2[2];
 #pragma unroll
             for (int d = 0; d < 2; ++d) {
@@ -1644,12 +1573,6 @@ __device__ __forceinline__ int opaque_tid() {
     int t = threadIdx.x;
     asm volatile("" : "+v"(t));
     return t;
-}
-
-template <typename T> __device__ __forceinline__ T uniform_ptr(T v) {
-    const unsigned long long u = reinterpret_cast<unsigned long long>(v);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-    return reinterpret_cast<T>(((unsigned long long)hi << 32) | lo);
 }
 
 #ifdef LDN_TRACE   // tuning only: per-image cycles of the masker / conv1 / conv2+conv3 phases and of the fences, summed over the run

@@ -20,8 +20,6 @@
 
 namespace ldn {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int WG_KT = 128;        // tile columns over the flattened (tap, channel) axis
 constexpr int WG_CHUNK = 32;      // rows per staged chunk = two K16 steps
 constexpr int WG_PITCH = 144;     // bytes per column record of the LDS image (128 + 16 pad)

@@ -44,7 +44,7 @@ def ops():
 
 
 # ------------------------------------------------------------------ the dispatch rule and the LDS predicate, restated
-T_KIDX_BYTES = 1280      # csrc/ldn_tail.hip:132
+T_KIDX_BYTES = 1280      # csrc/ldn_tail.hip:107
 T_W2_SLOTS = 3           # :133
 LDS_BYTES = 160 * 1024
 
@@ -54,7 +54,7 @@ def _round_up(a, b):
 
 
 def chain_fits(H, Wd, C, width, hidden, G):
-    """ldn_bottleneck_chain_fits (csrc/ldn_tail.hip:1811-1814) with chain_fits (:1732-1743): do the masker, conv1, conv2 and conv3 phases of a
+    """ldn_bottleneck_chain_fits (csrc/ldn_tail.hip:1734-1737) with chain_fits (:1655-1666): do the masker, conv1, conv2 and conv3 phases of a
     chained block fit the workgroup's 160 KiB of LDS, and the map the 72-piece slice pipeline?"""
     if H < 1 or Wd < 1 or H * Wd > 256 or C < 1 or G < 1 or hidden < 0 or width not in (64, 128, 256):
         return False
@@ -69,7 +69,7 @@ def chain_fits(H, Wd, C, width, hidden, G):
 
 
 def expected_chain_kernel(H, Wd, width, f32):
-    """The instantiation launch_chain runs (csrc/ldn_tail.hip:1745-1779, LDN_CHAIN_LD at its default): the loader / consumer form serves
+    """The instantiation launch_chain runs (csrc/ldn_tail.hip:1668-1702, LDN_CHAIN_LD at its default): the loader / consumer form serves
     bf16x3 at widths 128 / 256 on maps that leave the eighth wave without pixels (at most 224), the plain body everything else."""
     NS = width // 32
     if not f32 and NS >= 4 and H * Wd <= 224:

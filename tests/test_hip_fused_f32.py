@@ -6,7 +6,7 @@ tests/test_hip_tail.py pins bf16x3, compares with float32 PyTorch and runs squar
 csrc/ldn_tail.hip (LDN_K16's fragment shuffles, the epilogue stores, the A-operand load); a wrong k-slot pairing there was visible only
 through a model-level logit tolerance.
 
-`tail_rows_per_block` / `tail_splits` restate the row split of the tail (csrc/ldn_tail.hip:771-810, 849-854) in Python; non-GPU tests compare
+`tail_rows_per_block` / `tail_splits` restate the row split of the tail (csrc/ldn_tail.hip:745-784, 823-828) in Python; non-GPU tests compare
 them with ldn_bottleneck_tail_splits over a grid and prove that the case table reaches NS in {2, 4, 8} x stride in {1, 2}, each with one
 workgroup per image, several workgroups with an even split and several with a shorter last one.
 
@@ -36,7 +36,7 @@ def ops():
 
 
 # ------------------------------------------------------------------ the row split of the tail, restated
-T_KIDX_BYTES = 1280      # csrc/ldn_tail.hip:132
+T_KIDX_BYTES = 1280      # csrc/ldn_tail.hip:107
 T_W2_SLOTS = 3           # :133
 LDS_BYTES = 160 * 1024
 

@@ -6,7 +6,7 @@ A1  The three launches of Bottleneck._run_both -- conv1 on the dilated pixel lis
     float64 (helpers.bottleneck_stages_f64).  The model-level checks see these kernels only through a global average pool.
 A2  The options of the entry point that _run_both never combines, as literal-contract tests of include/ldn_hip.h:285-308,447-462.
 
-`expected_variant` restates the dispatch of csrc/ldn_conv_image.hip:1690-1797 in Python; the non-GPU test
+`expected_variant` restates the dispatch of csrc/ldn_conv_image.hip:1662-1769 in Python; the non-GPU test
 test_case_table_reaches_every_variant proves from it that the case table runs every tile shape, weight-staging mode and kernel a
 packed launch with channel lists can reach, in both arithmetic modes.
 
@@ -605,7 +605,7 @@ def test_border_class_shift_table(ops, B, Hi, Wi, stride, math_mode):
 
 @gpu
 def test_argument_checks_refuse_before_any_launch(ops):
-    """The checks of ldn_conv_packed (csrc/ldn_conv_image.hip:1861-1879): an error code, and the output is not touched."""
+    """The checks of ldn_conv_packed (csrc/ldn_conv_image.hip:1833-1851): an error code, and the output is not touched."""
     from laudnet_amd import LdnError
     rows, cin, cout, B = 64, 32, 32, 2
     a = torch.zeros(rows, cin, device=DEV)

@@ -40,7 +40,7 @@ def ops():
 
 
 # ------------------------------------------------------------------ the per-image dispatch of k_smallmap, restated
-S_LDS = 160 * 1024                   # csrc/ldn_small.hip:62
+S_LDS = 160 * 1024                   # csrc/ldn_small.hip:57
 S_KIDX_BYTES = 2304                  # :63
 S_ACT_OFF = S_KIDX_BYTES + 128       # :65
 S_TAB1_BYTES = 3 * 512 * 4           # :66
