@@ -237,6 +237,27 @@ size_t ldn_wgrad_rows_workspace_bytes(int m_cap, int cin, int cout, int taps);
 int ldn_wgrad_rows(const float* dy, int lddy, const float* a, int lda, int a_valid, const int32_t* a_rows, int taps,
                    const int32_t* m_count, int m_cap, int cin, int cout, float* dw, float* work, int math_mode, void* stream);
 
+/* ---- the WEIGHT GRADIENT of ldn_grouped_conv3x3_rows (LAD-RegNet's conv b; csrc/ldn_wgrad_grouped.hip): per group a gw x 9 gw tile reduced
+ * over the packed rows
+ *   dW[c, t, j] = sum_{r < count} dY[r, c] * A[nbr[r * 9 + t], (c / gw) * gw + j]          for c < C, t < 9, j < gw
+ *   an entry of nbr < 0 or >= a_valid is a ZERO row (a missing 3x3 neighbour)
+ *   count = m_count ? clamp(*m_count, 0, m_cap) : m_cap, read on the device (no host read, no synchronisation)
+ * dY [m_cap][lddy >= C] fp32, A [a_valid][lda >= C] fp32, nbr [m_cap][9] (the neighbour table of ldn_mask_to_index).  Rows r >= count are
+ * NOT READ -- neither dY nor nbr: they may hold anything, NaN included.
+ * dW [C][9][gw] fp32 = the weight layout of ldn_grouped_conv3x3_rows, fully overwritten (count == 0: zeros).
+ * math_mode is validated as for ldn_wgrad_rows; BOTH modes run the same fp32 form (fp32 products and fp32 accumulation on the VALU: there is
+ * no three-product MFMA form of this kernel).
+ * Deterministic: the rows are split over workgroups -- how many ways is a function of m_cap and the shapes only, never of *m_count, so the
+ * launch can be captured into a graph -- the partial results go to `work` (ldn_wgrad_grouped_rows_workspace_bytes = splits * C * 9 * gw * 4
+ * bytes, 0 when the rows are not split; `work` may be NULL then) and are added in ascending order by a second small launch.  No
+ * floating-point atomics: two runs are bit-identical.
+ * Shapes (ldn_wgrad_grouped_rows_ok): gw 8 | 16 | 24, C % gw == 0, C <= 2048; lddy, lda % 4 == 0, 16-byte aligned pointers.  Anything else is
+ * LDN_EINVAL -- there is no fallback inside the library.  LDN_DEBUG build: nbr entries below -1 are counted (code 611). */
+int ldn_wgrad_grouped_rows_ok(int C, int gw);
+size_t ldn_wgrad_grouped_rows_workspace_bytes(int m_cap, int C, int gw);
+int ldn_wgrad_grouped_rows(const float* dy, int lddy, const float* a, int lda, int a_valid, const int32_t* nbr, const int32_t* m_count,
+                           int m_cap, int C, int gw, float* dw, float* work, int math_mode, void* stream);
+
 /* ---- the ELEMENTWISE backward chain of training on packed rows (csrc/ldn_train_rows.hip).  Both are bandwidth-bound row kernels over
  * [m_cap][ld >= C] fp32 matrices, C % 4 == 0, ld % 4 == 0, 16-byte aligned pointers, every access 16 bytes wide.
  *   count  = m_count ? clamp(*m_count, 0, m_cap) : m_cap, read on the device (no host read, no synchronisation)

@@ -32,15 +32,23 @@ on the library's kernels:
   need the branch at DROPPED units too -- the library's own dense execution (that term is dense in the reference as well).  The residual add,
   the final ReLU, the projection shortcut, the maskers' tiny heads, the static stem and the classifier are plain autograd ops.
 
-One `autograd.Function` per mask kind; what the three share (operand layouts, transposed convolutions, weight / BatchNorm / pixel-mask gradients,
+One `autograd.Function` per mask kind; what they share (operand layouts, transposed convolutions, weight / BatchNorm / pixel-mask gradients,
 every division by a scale: `_safe`) is written once above them.  The index lists are built once per block forward (`_branch`) and handed to the Fn.
 
 Entry points: `sparse_block_train(block, x, mask)` (one block, the mask an input), `block_train(block, state, temperature)` (the reference's
 block signature in training mode: samples its own masks), `train_forward(model, x, temperature)` (a whole LAUD-ResNet -> the reference's
 7-tuple; a `LAD_MMDet_ResNet` -> its (outs, additional, model_configs)), `prepare_for_training(model)` (train mode with BatchNorm statistics
 frozen).  Checked against the oracle's autograd -- blocks on the reference-generated block fixtures, whole models on `det_tiny.pt` /
-`full_tiny.pt` with identical Gumbel noise (tests/test_hip_training.py, tests/test_hip_training_both.py, plain 1e-3).  Not built: mask groups > 1,
-grouped / dilated conv2, BatchNorm in batch-statistics mode, LAD-RegNet."""
+`full_tiny.pt` with identical Gumbel noise (tests/test_hip_training.py, tests/test_hip_training_both.py, plain 1e-3).
+
+LAD-RegNet (`laud_regnet.ResBottleneckBlock`) trains in its LAYER-SKIP form -- dyn_mode 'spatial' with one keep / skip bit per image, SE present, stride
+1 and 2, with and without `proj`: a kept image runs a -> grouped b -> SE -> c on packed rows in both directions (`_RegNetSkipBranchFn`: the grouped
+3x3's adjoint is its forward kernel over the transposed neighbour table with per-group transposed weights, its weight gradient `ops.wgrad_grouped_rows`,
+the squeeze / excite and their backward tensor ops on the [slots, Ho Wo, C] view of the rows); the same three entry points take it and a whole
+`LAD_RegNet` (tests/test_hip_training_regnet.py).
+
+Not built: mask groups > 1, dilated conv2, grouped conv2 outside that block, BatchNorm in batch-statistics mode, LAD-RegNet 'channel' / 'both' /
+patch-mask (mask_size > 1) training."""
 from __future__ import annotations
 
 import os
@@ -52,9 +60,11 @@ import torch.nn.functional as F
 from . import ops
 from ._lib import LdnError
 from ._shared import channel_constants, dense_channel_convs, dense_index
+from .laud_regnet import LAD_RegNet, ResBottleneckBlock, _conv_b_rows
 
-# weight gradients on ldn_wgrad_rows; LDN_WGRAD=0 = the gather + PyTorch GEMM path.  On by default: the median step is shorter with the kernel for
-# all three full-width workloads at batch 32 and 128 (profiles/train_step_wgrad.jsonl)
+# weight gradients on ldn_wgrad_rows / ldn_wgrad_grouped_rows; LDN_WGRAD=0 = the gather + PyTorch GEMM / bmm path.  On by default: the median step is shorter with the kernel for
+# all three full-width workloads at batch 32 and 128 (profiles/train_step_wgrad.jsonl), and for LAD-RegNetY-800MF layer skip with the grouped
+# kernel (profiles/train_step_regnet.jsonl)
 USE_WGRAD_KERNEL = os.environ.get("LDN_WGRAD", "1") != "0"
 
 
@@ -107,7 +117,35 @@ def _wgrad_kernel(cin, cout, taps):
     return USE_WGRAD_KERNEL and ops.wgrad_rows_ok(cin, cout, taps)
 
 
-# ------------------------------------------------------------------------------------------------------------------ shared by the three branch Fns
+def _weight_grad_grouped_3x3(du2, h1, nbr, cap1, gw, count3=None):
+    """d W_b [C, gw, 3, 3] of a GROUPED 3x3 (group width gw): the gather of _weight_grad_3x3 reshaped per group, then one bmm -- the path
+    without ldn_wgrad_grouped_rows (LDN_WGRAD=0, or a shape outside ops.wgrad_grouped_rows_ok)."""
+    C, G = du2.shape[1], du2.shape[1] // gw
+    h1z = torch.cat((h1, torch.zeros(1, C, device=h1.device)))
+    nb = nbr.view(-1, 9)
+    if count3 is not None:
+        nb = torch.where((torch.arange(nb.shape[0], device=nb.device) < count3).unsqueeze(1), nb, torch.full_like(nb, -1))
+    nb = torch.where(nb < cap1, nb, torch.full_like(nb, -1)).long()
+    nb = torch.where(nb >= 0, nb, torch.full_like(nb, cap1))
+    R = nb.shape[0]
+    cols = h1z[nb.reshape(-1)].view(R, 9, G, gw).permute(2, 0, 1, 3).reshape(G, R, 9 * gw)      # [G, rows, 9 gw]: the group's nine taps side by side
+    dw = torch.bmm(du2.view(R, G, gw).permute(1, 2, 0), cols)                                   # [G, gw, 9 gw]
+    return dw.view(C, 9, gw).permute(0, 2, 1).reshape(C, gw, 3, 3)
+
+
+def _wgrad_grouped_kernel(C, gw):
+    """Does the grouped weight gradient run on ldn_wgrad_grouped_rows (the same module switch, that kernel's shape predicate)?"""
+    return USE_WGRAD_KERNEL and ops.wgrad_grouped_rows_ok(C, gw)
+
+
+def grouped_weight_T(wbr, gw):
+    """The adjoint of the grouped 3x3 is the same kernel over the transposed neighbour table with per-group transposed weights
+    (ldn_grouped_conv3x3_rows' layout [C, 9, gw]: out channel, tap, in channel of the group):  wT[g gw + j, t, i] = w[g gw + i, t, j]."""
+    C = wbr.shape[0]
+    return wbr.view(C // gw, gw, 9, gw).permute(0, 3, 2, 1).reshape(C, 9, gw).contiguous()
+
+
+# ------------------------------------------------------------------------------------------------------------------ shared by the branch Fns
 _Prep = namedtuple("_Prep", "x2d w1r w2r w3r w3s bn shape")
 
 
@@ -118,14 +156,14 @@ def _fold_w3(w3r, s3):
 
 def _prep(x, w1, w2, w3, bn6, stride):
     """What every branch Fn's forward starts from, detached, fp32, in the row kernels' layouts: x2d [B Hi Wi, Cin] (NHWC rows), w1r [W, 1, Cin],
-    w2r [W, 9, W] (tap-major), w3r [cout, W], w3s = _fold_w3, bn = (s1, t1, s2, t2, s3, t3), shape = (B, Cin, Hi, Wi, Ho, Wo, W, cout)."""
+    w2r [W, 9, W] (tap-major; a grouped conv2: [W, 9, gw]), w3r [cout, W], w3s = _fold_w3, bn = (s1, t1, s2, t2, s3, t3), shape = (B, Cin, Hi, Wi, Ho, Wo, W, cout)."""
     B, Cin, Hi, Wi = x.shape
     Ho, Wo = (Hi - 1) // stride + 1, (Wi - 1) // stride + 1
     W, cout = w1.shape[0], w3.shape[0]
     x2d = ops.as_nhwc(x.detach()).reshape(B * Hi * Wi, Cin)
     bn = tuple(v.detach().float().contiguous() for v in bn6)
     w1r = w1.detach().reshape(W, 1, Cin).float().contiguous()
-    w2r = w2.detach().float().permute(0, 2, 3, 1).reshape(W, 9, W).contiguous()
+    w2r = w2.detach().float().permute(0, 2, 3, 1).reshape(W, 9, w2.shape[1]).contiguous()
     w3r = w3.detach().float().reshape(cout, W)
     return _Prep(x2d, w1r, w2r, w3r, _fold_w3(w3r, bn[4]), bn, (B, Cin, Hi, Wi, Ho, Wo, W, cout))
 
@@ -438,6 +476,114 @@ class _BothBranchFn(torch.autograd.Function):
         return grad_x, gw1, gw2, gw3, gm, gc, gs1, gt1 if need[7] else None, gs2, gt2 if need[9] else None, gs3, gt3, None, None
 
 
+# ------------------------------------------------------------------------------------------------------------------ LAD-RegNet, layer skip
+def _se_gate(sq, w1, b1, w2, b2):
+    """the excite MLP on the squeezed rows sq [slots, C] -> (u = fc1's output in front of its ReLU, gate = sigmoid(fc2(relu(u))))"""
+    u = sq @ w1.t() + b1
+    return u, torch.sigmoid(torch.relu(u) @ w2.t() + b2)
+
+
+def _conv_b_params(wbr, sb, tb, gw):
+    """what laud_regnet._conv_b_rows reads of a prepared block, from the live weights (the matrix-core form's fragments only where it runs)"""
+    pb = {"wb": wbr, "sb": sb, "tb": tb}
+    if gw == 16 and wbr.shape[0] % 16 == 0 and ops.get_math_mode() == "bf16x3":
+        pb["wb_frag"] = ops.pack_grouped16_weights(wbr)
+    return pb
+
+
+def _regnet_chain(x2d, ix, P, f, war, wbr, wcs, sa, ta, sb, tb, tc, se, br):
+    """a -> grouped b -> SE -> c over the lists of ix (WHOLE images in list order: the j-th listed image owns rows [j P, (j + 1) P), P = Ho Wo),
+    c scattered into br.  -> (h_a, h_b in front of the gate, gate [slots, C]); h_a / h_b ZEROED first, as _pixel_chain's: a slot past the count
+    squeezes to zero and its gate multiplies zero rows."""
+    W, dev = war.shape[0], x2d.device
+    h_a = torch.zeros(ix.cap1, W, device=dev)
+    ops.conv_rows(x2d, war, sa, ta, h_a, a_rows=ix.idx1, taps=1, m_count=ix.cnt[1:2], m_cap=ix.cap1)
+    h_b = torch.zeros(ix.cap3, W, device=dev)
+    _conv_b_rows(_conv_b_params(wbr, sb, tb, f.group_width), f, h_a, ix.nbr, h_b, ix.cnt[0:1], ix.cap3)
+    hbv = h_b.view(-1, P, W)
+    gate = _se_gate(hbv.mean(1), *se)[1]
+    z = (hbv * gate.unsqueeze(1)).view(ix.cap3, W)
+    ops.conv_rows(z, wcs, None, tc, br, taps=1, m_count=ix.cnt[0:1], m_cap=ix.cap3, relu=0, out_rows=ix.idx3)
+    return h_a, h_b, gate
+
+
+class _RegNetSkipBranchFn(torch.autograd.Function):
+    """branch = m3 * (sc * c(gate . h_b) + tc),  h_b = relu(sb * b(relu(sa * a(x) + ta)) + tb),  gate = sigmoid(fc2(relu(fc1(mean_pixels h_b))))
+    (laud_regnet.py:179-200 in its layer-skip form: one keep / skip bit per image, m3 constant over an image) on the packed rows of the KEPT
+    images: a and c on conv_rows, the grouped 3x3 b on ldn_grouped_conv3x3_rows -- its adjoint the same kernel over the transposed neighbour
+    table with per-group transposed weights, its weight gradient ops.wgrad_grouped_rows -- and the squeeze / excite as tensor ops on the
+    [slots, Ho Wo, C] view of the rows.  A dropped image costs nothing in either direction.  Differentiable in x, the three weights, the six
+    folded BatchNorm vectors, the four SE tensors and the mask."""
+
+    @staticmethod
+    def forward(ctx, x, wa, wb, wc, m3, sa, ta, sb, tb, sc, tc, w1, b1, w2, b2, stride, f, ix):
+        p = _prep(x, wa, wb, wc, (sa, ta, sb, tb, sc, tc), stride)
+        B, _, _, _, Ho, Wo, W, cout = p.shape
+        sa, ta, sb, tb, sc, tc = p.bn
+        se = (w1.detach().float().reshape(-1, W).contiguous(), b1.detach().float().contiguous(),
+              w2.detach().float().reshape(W, -1).contiguous(), b2.detach().float().contiguous())
+        br = torch.zeros(B * Ho * Wo, cout, device=x.device)
+        h_a, h_b, gate = _regnet_chain(p.x2d, ix, Ho * Wo, f, p.w1r, p.w2r, p.w3s, sa, ta, sb, tb, tc, se, br)
+        ctx.save_for_backward(p.x2d, h_a, h_b, gate, br, p.w1r, p.w2r, p.w3r, *p.bn, *se, m3.detach().float())
+        ctx.ix, ctx.shape, ctx.stride, ctx.f, ctx.se_shapes = ix, p.shape, stride, f, (w1.shape, w2.shape)
+        return ops.from_nhwc(br.view(B, Ho, Wo, cout))
+
+    @staticmethod
+    def backward(ctx, g):
+        x2d, h_a, h_b, gate, br, war, wbr, wcr, sa, ta, sb, tb, sc, tc, w1, b1, w2, b2, m3d = ctx.saved_tensors
+        ix, shape, stride, f, need, dev = ctx.ix, ctx.shape, ctx.stride, ctx.f, ctx.needs_input_grad, g.device
+        B, _, Hi, Wi, Ho, Wo, W, cout = shape
+        P, gw = Ho * Wo, f.group_width
+        cnt3, cnt1 = ix.cnt[0:1], ix.cnt[1:2]
+        go = ops.as_nhwc(g.contiguous()).reshape(-1, cout)                       # [B Ho Wo, cout]
+        zW = torch.zeros(W, device=dev)
+        v3, v1 = _rows_valid(ix.cap3, ix.cnt[0], dev), _rows_valid(ix.cap1, ix.cnt[1], dev)
+        g3 = torch.where(v3 > 0, ops.gather_rows(go, ix.idx3, count=cnt3, cap=ix.cap3), zW[:1])     # d L / d (sc y_c + tc) at the kept pixels (as in _PixelBranchFn)
+        wcs = _fold_w3(wcr, sc)
+        dz = _conv3_T(g3, wcs, zW, cnt3, ix.cap3, torch.zeros)                   # d L / d (gate . h_b); zero rows past the count
+        # squeeze-excitation: two per-image reductions over the [slots, P, C] view and the excite MLP by hand on [slots, C] tensors.  A slot past
+        # the count holds zero rows in dz and h_b alike: d gate is selected to zero there, so nothing of it reaches d fc1 / d fc2
+        dzv, hbv = dz.view(-1, P, W), h_b.view(-1, P, W)
+        slot_on = (torch.arange(dzv.shape[0], device=dev) * P < ix.cnt[0]).unsqueeze(1)
+        sq = hbv.mean(1)
+        u = sq @ w1.t() + b1
+        r = torch.relu(u)
+        dv = torch.where(slot_on, (dzv * hbv).sum(1), zW[:1]) * gate * (1.0 - gate)      # through the sigmoid
+        du = (dv @ w2) * (u > 0)
+        dsq = du @ w1
+        gw1s = (du.t() @ sq).reshape(ctx.se_shapes[0]) if need[11] else None
+        gb1s = du.sum(0) if need[12] else None
+        gw2s = (dv.t() @ r).reshape(ctx.se_shapes[1]) if need[13] else None
+        gb2s = dv.sum(0) if need[14] else None
+        dhb = (dzv * gate.unsqueeze(1) + dsq.unsqueeze(1) / P).view(ix.cap3, W)
+        dzb = dhb * (h_b > 0) * v3                        # through ReLU: d L / d (sb y_b + tb)
+        dub = dzb * sb
+        # b^T: the forward kernel over the transposed neighbour table with per-group transposed weights, scale 1, shift 0, no ReLU
+        nbrT = transposed_neighbour_table(ix, B, Hi, Wi, stride, Ho, Wo)
+        dha = torch.zeros(ix.cap1, W, device=dev)
+        ops.grouped_conv3x3_rows(dub, nbrT, grouped_weight_T(wbr, gw), gw, torch.ones(W, device=dev), zW, dha, m_count=cnt1, m_cap=ix.cap1, relu=0)
+        dza = dha * (h_a > 0) * v1
+        dua = dza * sa
+        grad_x = _grad_x(dua, war, ix, cnt1, shape) if need[0] else None
+        z = (hbv * gate.unsqueeze(1)).view(ix.cap3, W) if need[3] else None       # conv c's input
+        gwa, _, gwc = _weight_grads(need[1], False, need[3], g3, z, None, h_a, dua, x2d, ix, sc, counted=True)
+        gwb = None
+        if need[2]:       # conv b sees h_a inside the map, zeros in the padding ring
+            if _wgrad_grouped_kernel(W, gw):
+                gwb = ops.wgrad_grouped_rows(dub, h_a, ix.nbr, gw, m_count=cnt3, m_cap=ix.cap3, a_valid=ix.cap1).permute(0, 2, 1).reshape(W, gw, 3, 3)
+            else:
+                gwb = _weight_grad_grouped_3x3(dub, h_a, ix.nbr, ix.cap1, gw, ix.cnt[0])
+        gsa, gta = _bn_grads(need[5], need[6], dza, dza, h_a, sa, ta)
+        gsb, gtb = _bn_grads(need[7], need[8], dzb, dzb, h_b, sb, tb)
+        gsc, gtc = _bn3_grads(need[9], need[10], g3, br, sc, tc, kept=(ix, v3 > 0, zW[:1]))
+        # the straight-through term needs the branch of the DROPPED images: this Fn's own chain over the complement's lists (their SE squeezes
+        # their own rows -- what the dense reference computes)
+        se = (w1, b1, w2, b2)
+        chain = lambda cix, full: _regnet_chain(x2d, cix, P, f, war, wbr, wcs, sa, ta, sb, tb, tc, se, full)
+        gm = _pixel_mask_grad(go, br, m3d, stride, chain) if need[4] else None
+        return grad_x, gwa, gwb, gwc, gm, gsa, gta, gsb, gtb, gsc, gtc, gw1s, gb1s, gw2s, gb2s, None, None, None
+
+
 # ------------------------------------------------------------------------------------------------------------------ blocks
 def _fold_live(bn):
     """(scale, shift) of a BatchNorm with FROZEN statistics as differentiable functions of its affine parameters."""
@@ -480,9 +626,47 @@ def _expand_channel_mask(block, x, mask):
     return mask.unsqueeze(2).expand(-1, -1, gran).reshape(mask.shape[0], W)
 
 
+def _check_regnet_block(block, x):
+    """what of LAD-RegNet trains: the layer-skip form run_dynamic executes itself (one keep / skip bit per image, one mask group, SE present)"""
+    f = block.f
+    if f.dyn_mode != "spatial":
+        raise LdnError(f"training: LAD-RegNet dyn_mode {f.dyn_mode!r} is not built (layer skip only: dyn_mode 'spatial' with one mask bit per image)")
+    if f.mask_size != 1:
+        raise LdnError("training: LAD-RegNet patch masks (mask_size > 1) are not built (layer skip only)")
+    if f.masker_spatial.mask_channel_group != 1:
+        raise LdnError("training: LAD-RegNet spatial mask groups > 1 are not built")
+    if not f.has_se:
+        raise LdnError("training: LAD-RegNet without squeeze-excitation (RegNet-X) is not built")
+    if not x.is_cuda:
+        raise LdnError("laudnet_amd ops need tensors on a HIP device (cuda:N); there is no CPU path")
+    if x.shape[2] != f.output_size * block.stride or x.shape[3] != f.output_size * block.stride:
+        raise LdnError(f"training: input {x.shape[2]}x{x.shape[3]} does not match output_size {f.output_size} * stride {block.stride}")
+    for bn in (f.a[1], f.b[1], f.c[1]) + (() if block.proj is None else (block.proj[1],)):
+        if bn.training:
+            raise LdnError("training: BatchNorm must run on its frozen statistics (norm_eval; call prepare_for_training(model)) -- the "
+                           "batch-statistics recipe is dense by construction and not built")
+
+
+def _branch_regnet(block, x, mask):
+    """_branch for a laud_regnet.ResBottleneckBlock in its layer-skip form (mask [B, 1, 1, 1])"""
+    _check_regnet_block(block, x)
+    f = block.f
+    if isinstance(mask, (tuple, list)) or mask.dim() != 4 or tuple(mask.shape[1:]) != (1, 1, 1) or mask.shape[0] != x.shape[0]:
+        raise LdnError("training: a LAD-RegNet layer-skip block takes one keep / skip bit per image (mask [B, 1, 1, 1])")
+    m3 = F.interpolate(mask, size=(f.output_size, f.output_size), mode="nearest")      # laud_regnet.py:173
+    ix = _pixel_lists(m3, block.stride)
+    bn = _fold_live(f.a[1]) + _fold_live(f.b[1]) + _fold_live(f.c[1])
+    branch = _RegNetSkipBranchFn.apply(x, f.a[0].weight, f.b[0].weight, f.c[0].weight, m3, *bn, f.se.fc1.weight, f.se.fc1.bias,
+                                       f.se.fc2.weight, f.se.fc2.bias, block.stride, f, ix)
+    identity = x if block.proj is None else block.proj(x)      # (conv 1x1 stride s + BatchNorm on frozen statistics: plain autograd)
+    return F.relu(branch + identity), ix
+
+
 def _branch(block, x, mask):
     """sparse_block_train -> (out, ix): ix = the index lists the block ran on, built ONCE per forward -- the Fn gets them as an argument and
     block_train reads the dilated masks' means off the same object."""
+    if isinstance(block, ResBottleneckBlock):
+        return _branch_regnet(block, x, mask)
     _check_block(block, x)
     bn = _fold_live(block.bn1) + _fold_live(block.bn2) + _fold_live(block.bn3)
     w = (block.conv1.weight, block.conv2.weight, block.conv3.weight)
@@ -509,7 +693,8 @@ def sparse_block_train(block, x, mask):
     """Differentiable forward of ONE Bottleneck under frozen BatchNorm statistics with its hard mask as an input.
     dyn_mode 'spatial' / 'layer': mask [B, 1, S, S] {0,1};  dyn_mode 'channel': mask [B, G] {0,1};  dyn_mode 'both': mask = the pair
     (spatial [B, 1, S, S], channel [B, G]).  A mask may require grad (the hard Gumbel sample of the masker's logits): it receives the
-    straight-through term.  Returns the block's output."""
+    straight-through term.  A `laud_regnet.ResBottleneckBlock` in its layer-skip form (dyn_mode 'spatial', one mask bit per image, SE present):
+    mask [B, 1, 1, 1]; every other LAD-RegNet form raises LdnError.  Returns the block's output."""
     return _branch(block, x, mask)[0]
 
 
@@ -566,6 +751,8 @@ def block_train(block, state, temperature=1.0):
     """Bottleneck.forward of the reference in TRAINING mode (laud_resnet.py:88-165) under frozen BatchNorm statistics: samples the block's hard
     masks from its maskers' logits (forced_*_mask is honoured), runs the convolutions on the row kernels and keeps the reference's bookkeeping
     (sparsity lists, FLOPs ratio, running FLOPs) differentiable where the reference's is (channel sparsity, conv3's spatial sparsity)."""
+    if isinstance(block, ResBottleneckBlock):
+        return _regnet_block_train(block, state, temperature)
     x, s3l, s2l, s1l, csl, percl, flops = state
     one = lambda: torch.tensor(1.0, device=x.device)
     c_flops = s_flops = 0
@@ -615,6 +802,33 @@ def block_train(block, state, temperature=1.0):
     return out, push(s3l, s3), push(s2l, s2), push(s1l, s1), push(csl, cs), push(percl, perc), flops
 
 
+def _regnet_block_train(block, state, temperature):
+    """ResBottleneckBlock.forward of the reference in TRAINING mode (laud_regnet.py:157-217,272-292), layer skip: the keep / skip bits are a hard
+    Gumbel sample of the block's masker (forced_spatial_mask is honoured); the bookkeeping of ResBottleneckBlock.forward, differentiable where
+    the reference's is (conv c's sparsity s3; the dilated masks' means come out of the list build, channel sparsity 1)."""
+    x, s3l, s2l, s1l, csl, percl, flops = state
+    f = block.f
+    _check_regnet_block(block, x)
+    m, s3, s_flops = _draw_spatial(f, x, temperature)
+    out, ix = _branch_regnet(block, x, m)
+    s2, s1 = ix.stats[1], ix.stats[2]
+    cs = torch.tensor(1.0, device=x.device)
+    f.last_spatial_mask = m.detach()
+    _, c1, c2, c3, proj, se = block.flops_terms(x.shape)
+    dense = s_flops + c1 + c2 + c3 + proj
+    sparse = s_flops + c1 * cs * s1
+    sparse = sparse + c2 * cs ** 2 * s2
+    sparse = sparse + c3 * cs * s3
+    sparse = sparse + proj
+    flops = flops + se + sparse
+    perc = sparse / dense
+
+    def push(lst, v):
+        v = v.reshape(1)
+        return v if lst is None else torch.cat((lst, v))
+    return out, push(s3l, s3), push(s2l, s2), push(s1l, s1), push(csl, cs), push(percl, perc), flops
+
+
 # ------------------------------------------------------------------------------------------------------------------ models
 def prepare_for_training(model):
     """Train mode with the BatchNorm STATISTICS frozen (mmdet's norm_eval=True, lad_mmdet_resnet.py:753-758): every BatchNorm runs on its
@@ -630,6 +844,28 @@ def _stem(model, x):
     return model.maxpool(model.relu(model.bn1(model.conv1(x))))          # static stem, laud_resnet.py:316-326 (BatchNorm on frozen statistics)
 
 
+def _regnet_train_forward(model, x, temperature):
+    """LAD_RegNet.forward in training mode (laud_regnet.py:573-611): the stem and the head are plain module calls under autograd"""
+    cin = x.shape[1]
+    h = model.stem(x)
+    k = model.stem[0].kernel_size[0]
+    flops = torch.tensor(float(cin * h.shape[1] * h.shape[2] * h.shape[3] * k * k), device=x.device)
+    percl = None
+    stage_stats = []
+    for stage in model.trunk_output.children():
+        state = (h, None, None, None, None, percl, flops)              # sparsity lists restart per stage, the FLOPs ratios and FLOPs run on
+        for blk in stage.children():
+            state = block_train(blk, state, temperature)
+        h, s3l, s2l, s1l, csl, percl, flops = state
+        stage_stats.append((s3l, s2l, s1l, csl))
+    h = model.avgpool(h)
+    flops = flops + float(h.shape[1] * h.shape[2] * h.shape[3])
+    h = h.flatten(start_dim=1)
+    flops = flops + float(h.shape[1] * model.fc.out_features)
+    s3, s2, s1, cs = ([st[i] for st in stage_stats] for i in range(4))
+    return model.fc(h), s3, s2, s1, cs, percl, flops
+
+
 def train_forward(model, x, temperature=1.0):
     """The reference's forward in training mode on the row kernels.  LAUD-ResNet (`laudnet_amd.ResNet`): -> the 7-tuple (logits, spatial
     sparsity lists of conv3 / conv2 / conv1 per stage, channel sparsity per stage, per-block FLOPs ratios, FLOPs), `laud_resnet.py:312-363`;
@@ -637,6 +873,8 @@ def train_forward(model, x, temperature=1.0):
     `laudnet_amd.sparsity_loss` / the detector's loss as the reference does (`train/main.py:527-604`, `single_stage.py:44-90`)."""
     if not x.is_cuda:
         raise LdnError("laudnet_amd ops need tensors on a HIP device (cuda:N); there is no CPU path")
+    if isinstance(model, LAD_RegNet):
+        return _regnet_train_forward(model, x, temperature)
     is_det = not hasattr(model, "fc")
     h = _stem(model, x)
     # static terms of the FLOPs count (stem conv + its map; the classifier): the module's own shape-only table

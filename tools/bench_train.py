@@ -4,9 +4,12 @@ kernels (laudnet_amd.training.train_forward) beside the oracle's dense emulation
 it names the weight-gradient path (`wgrad_kernel`: laudnet_amd.training.USE_WGRAD_KERNEL, env LDN_WGRAD=0 | 1) and the peak memory of ONE step on
 the row kernels (`peak_MiB_one_step`: torch.cuda.max_memory_allocated of a step of its own after the timed ones).
 `both` is the reference's constructor default (pixel x channel masks: spatial S=4-4-2-1 and channel-2222 together), same model, batch and loss
-convention as the other three.  `ms_per_step` is the mean of the timed steps (wall clock over the loop), `ms_per_step_median` the median of the
+convention as the other three.  `regnet` is the full-width LAD-RegNetY-800MF in its layer-skip form (bench.py's workload, keep 0.5) beside
+oracle/regnet_ref.py's dense emulation.  `--ab-wgrad` adds `wgrad_ab`: further steps of the row-kernel leg with the weight-gradient kernels
+(training.USE_WGRAD_KERNEL) off and on ALTERNATING step by step in this one process, the median of each setting's device-event intervals.
+`ms_per_step` is the mean of the timed steps (wall clock over the loop), `ms_per_step_median` the median of the
 steps' own device-event intervals.
-usage: [LDN_WGRAD=0] tools/bench_train.py [--batch 32] [--steps 5] [--warmup 2] [--workloads layer,spatial,channel,both] [--no-reference]"""
+usage: [LDN_WGRAD=0] tools/bench_train.py [--batch 32] [--steps 5] [--warmup 2] [--workloads layer,spatial,channel,both,regnet] [--no-reference] [--ab-wgrad]"""
 import argparse
 import json
 import os
@@ -20,9 +23,10 @@ import torch  # noqa: E402
 
 import bench  # noqa: E402
 import laudnet_amd  # noqa: E402
-from fill import fill_state_dict, seeded_randn  # noqa: E402
+from fill import damp_residual_branches, fill_state_dict, seeded_randn  # noqa: E402
 from laudnet_amd import ops, training  # noqa: E402
 from laudnet_amd.training import prepare_for_training, train_forward  # noqa: E402
+from oracle import regnet_ref as RR  # noqa: E402
 from oracle import torch_ref as TR  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -32,6 +36,7 @@ ap.add_argument("--workloads", default="layer,spatial,channel")
 ap.add_argument("--math", default="bf16x3")
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--no-reference", action="store_true", help="time the row kernels only (no dense emulation through PyTorch, no speedup)")
+ap.add_argument("--ab-wgrad", action="store_true", help="also time the row-kernel leg with the weight-gradient kernels off / on, alternating per step")
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
 ops.set_math_mode(args.math)
@@ -43,17 +48,14 @@ WORKLOADS["both"] = dict(name="LAUD-ResNet101 both (spatial S=4-4-2-1 x channel-
 for w in args.workloads.split(","):
     wl = WORKLOADS[w]
     kw = dict(wl["kw"], num_classes=1000, input_size=224)
-    hip = laudnet_amd.uni_resnet101(**kw)
-    sd = fill_state_dict(hip.state_dict(), 1)
-    for k in sd:
-        if k.endswith("bn3.weight"):
-            sd[k] = sd[k] * 0.3
-    hip.load_state_dict(sd)
+    arch = wl.get("arch", "uni_resnet101")
+    hip = getattr(laudnet_amd, arch)(**kw)
+    hip.load_state_dict(damp_residual_branches(fill_state_dict(hip.state_dict(), 1)))      # (the last BatchNorm of every residual branch x 0.3)
     hip = hip.to(dev).eval()
     x = seeded_randn((args.batch, 3, 224, 224), 1000).to(dev).contiguous(memory_format=torch.channels_last)
     bench.calibrate_maskers(hip, x, wl["p_channel"], wl["p_spatial"])
     sd = {k: v.detach().clone() for k, v in hip.state_dict().items()}
-    ref = TR.resnet101_ref(**kw)
+    ref = RR.regnet_y_ref(arch, **kw) if arch.startswith("lad_regnet") else TR.resnet101_ref(**kw)
     ref.load_state_dict(sd)
     ref = ref.to(dev).train()
     for m in ref.modules():
@@ -97,6 +99,23 @@ for w in args.workloads.split(","):
             step(fwd, model)
             torch.cuda.synchronize()
             res[name]["peak_MiB_one_step"] = round(torch.cuda.max_memory_allocated() / 2 ** 20, 1)
+    if args.ab_wgrad:
+        # the A/B of the weight-gradient kernels on this workload: off and on alternate step by step behind a warm-up step of each, same process
+        shipped = training.USE_WGRAD_KERNEL
+        fwd, times = legs[0][1], {False: [], True: []}
+        torch.manual_seed(3)
+        for k in range(2 * (args.steps + 1)):
+            training.USE_WGRAD_KERNEL = on = bool(k % 2)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            step(fwd, hip)
+            b.record()
+            torch.cuda.synchronize()
+            if k >= 2:
+                times[on].append(a.elapsed_time(b))
+        training.USE_WGRAD_KERNEL = shipped
+        med = lambda v: sorted(v)[len(v) // 2]
+        res["wgrad_ab"] = {"steps_each": args.steps, "ms_per_step_median_wgrad_off": med(times[False]), "ms_per_step_median_wgrad_on": med(times[True])}
     if not args.no_reference:
         res["speedup"] = res["dense_emulation_pytorch"]["ms_per_step"] / res["hip_row_kernels"]["ms_per_step"]
     print(json.dumps({"workload": wl["name"], "batch": args.batch, "steps": args.steps, "math": args.math, "wgrad_kernel": training.USE_WGRAD_KERNEL,
