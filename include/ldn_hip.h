@@ -600,8 +600,11 @@ int ldn_conv_rows_gated(const float* a, int lda, const int32_t* m_count, int m_c
  * dense masked attention written for the purpose (oracle/adavit_ref.py).
  * qkv [rows][ld_qkv] fp32: per token row q | k | v, each [heads][64].  tok_rows [N]: flat row of every kept token, image-major and
  * ascending (ldn_mask_to_index of the [B, L, 1] keep mask gives it as idx3); img_prefix [B + 1]: exclusive prefix of kept tokens per
- * image (at most max_tokens <= 256 each).  out [N][ldo]: row n = softmax(scale * q_n K_b^T) V_b over the kept tokens of n's image,
- * heads concatenated.  bf16x3 products, fp32 softmax. */
+ * image (at most max_tokens each; tokens of an image beyond max_tokens are neither attended to nor written).  out [N][ldo]: row n =
+ * softmax(scale * q_n K_b^T) V_b over the kept tokens of n's image, heads concatenated.  bf16x3 products, fp32 softmax.
+ * max_tokens <= 256: one workgroup per (image, head), the image's keys in LDS at once.  256 < max_tokens <= 65535 * 256: one workgroup
+ * per (image, head, tile of 256 queries), the keys streamed through LDS in tiles of 256 with a running softmax (the bound is the
+ * grid's second dimension); an image with <= 256 kept tokens gets bit-identical rows either way. */
 int ldn_packed_mha(const float* qkv, int ld_qkv, const int32_t* tok_rows, const int32_t* img_prefix, int B, int heads,
                    int head_dim, int max_tokens, float scale, float* out, int ldo, void* stream);
 /* ... with HEAD skipping (simulate_adavit.py:81-88: attention over the selected heads of every image): head_keep [B][heads] {0,1}; the

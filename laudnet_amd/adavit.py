@@ -6,7 +6,8 @@ MLP / residual updates on the selected tokens only (the latency model prices q /
 query nor key, so they are computed for the attending tokens only -- TokenSkipBlock.qkv_kept_only).  This module executes that operator list on PACKED token lists with the
 kernels of libldn_hip.so: the keep mask becomes a row list (ldn_mask_to_index on a [B, L, 1] mask), the linears are the packed-row
 1x1 kernel (k_dense: gather rows in, scatter-add rows out, fused bias + residual), the attention is ldn_packed_mha (one workgroup
-per image and head over the image's kept tokens).  HEAD skipping (a per-image head mask: q / k / v masked in the linear's epilogue, the
+per image and head over the image's kept tokens; beyond 256 tokens per image, e.g. the 577 of a 384 px input, one workgroup per image,
+head and tile of 256 queries, the keys streamed through LDS 256 at a time -- any sequence length).  HEAD skipping (a per-image head mask: q / k / v masked in the linear's epilogue, the
 dropped heads' attention workgroups compute nothing) and LAYER skipping (per-image decisions for the attention and the MLP sub-block: the
 image has no tokens in that sub-block's list) of simulate_adavit.py:81-88,140-182 ride on the same lists.  LayerNorm and GELU are epilogue terms of the linears (ldn_row_stats + the ln_* / relu-mode-3 arguments of ldn_conv_rows_split).  Parity is UNPINNED (there is
 nothing in the reference to pin it to): tests compare against oracle/adavit_ref.py, a dense masked restatement of the same operator
@@ -130,10 +131,8 @@ class TokenSkipBlock(nn.Module):
 
     def forward(self, x, keep, head_keep=None, attn_keep=None, mlp_keep=None):
         """x [B, L, dim], keep [B, L] {0,1} -> new [B, L, dim] (kept tokens updated, the others passed through).  head_keep [B, heads],
-        attn_keep / mlp_keep [B]: head and layer skipping (see run_packed)."""
+        attn_keep / mlp_keep [B]: head and layer skipping (see run_packed).  Any L: ldn_packed_mha tiles sequences beyond 256 tokens."""
         B, Lt, D = x.shape
-        if Lt > 256:    # ldn_packed_mha holds at most 256 kept tokens of an image in LDS: more would be dropped silently
-            raise LdnError("TokenSkipBlock: at most 256 tokens per image (ldn_packed_mha)")
         x2d = x.reshape(B * Lt, D).clone()
         (tok_rows, prefix, count), m_list, q_rows = self.skip_lists(keep, attn_keep, mlp_keep)
         self.run_packed(x2d, tok_rows, prefix, count, B, Lt, head_keep=head_keep, mlp_lists=m_list, qkv_rows=q_rows)
@@ -141,8 +140,8 @@ class TokenSkipBlock(nn.Module):
 
 
 class TokenSkipViT(nn.Module):
-    """A trunk of token-skipping blocks (DeiT-S: depth 12, dim 384, 6 heads, MLP x4; 197 tokens).  forward(x, keeps): keeps[i] is the
-    [B, L] keep mask of block i (the CLS token must be kept).  The residual stream is one [B*L, dim] buffer updated in place."""
+    """A trunk of token-skipping blocks (DeiT-S: depth 12, dim 384, 6 heads, MLP x4; 197 tokens at 224 px, 577 at 384 px -- the
+    sequence length is free).  forward(x, keeps): keeps[i] is the [B, L] keep mask of block i (the CLS token must be kept).  The residual stream is one [B*L, dim] buffer updated in place."""
 
     def __init__(self, depth=12, dim=384, heads=6, mlp_ratio=4.0):
         super().__init__()
@@ -156,8 +155,6 @@ class TokenSkipViT(nn.Module):
     def forward(self, x, keeps, head_keeps=None, attn_keeps=None, mlp_keeps=None):
         """keeps[i] [B, L]; optional per-block head_keeps[i] [B, heads], attn_keeps[i] / mlp_keeps[i] [B] (head / layer skipping)."""
         B, Lt, D = x.shape
-        if Lt > 256:
-            raise LdnError("TokenSkipViT: at most 256 tokens per image (ldn_packed_mha)")
         x2d = x.reshape(B * Lt, D).clone()
         pick = lambda seq, i: None if seq is None else seq[i]
         for i, (blk, keep) in enumerate(zip(self.blocks, keeps)):

@@ -1277,7 +1277,10 @@ def token_lists(keep):
 
 def packed_mha(qkv2d, tok_rows, prefix, B, heads, max_tokens, scale=None, head_keep=None):
     """Multi-head attention among the kept tokens of every image (see ldn_packed_mha).  qkv2d [B*L, 3*dim]; returns the packed
-    rows [B*L (capacity), dim]: row n belongs to token tok_rows[n].  head_keep [B, heads] {0,1}: head skipping (ldn_packed_mha_heads)."""
+    rows [B*L (capacity), dim]: row n belongs to token tok_rows[n].  head_keep [B, heads] {0,1}: head skipping (ldn_packed_mha_heads).
+    max_tokens bounds the kept tokens of one image (usually L) and picks the kernel: up to 256 the image's keys sit in LDS at once
+    (k_packed_mha); beyond, queries and keys are tiled by 256 (k_packed_mha_long) -- the same floats for an image with <= 256 kept
+    tokens.  Tokens of an image past max_tokens are neither attended to nor written."""
     L.require_device(qkv2d, tok_rows, prefix)
     lib = L.load()
     rows, three_dim = qkv2d.shape
