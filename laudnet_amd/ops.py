@@ -2,6 +2,7 @@
 memory and the current stream; every computation below runs in libldn_hip.so.  No fallbacks."""
 from __future__ import annotations
 
+import contextlib
 import os
 import threading
 import weakref
@@ -53,6 +54,18 @@ def get_math_mode():
         m = L.load().ldn_default_math_mode()
         mode = next(k for k, v in MATH_MODES.items() if v == m)
     return mode
+
+
+@contextlib.contextmanager
+def math_mode(mode):
+    """`with ops.math_mode(m):` -- set_math_mode(m) for the block; the thread's previous default comes back after it.  The default is PER THREAD:
+    code that runs on another thread than its caller's (an autograd backward) carries the mode over with this."""
+    prev = getattr(_math, "mode", None)
+    set_math_mode(mode)
+    try:
+        yield
+    finally:
+        _math.mode = prev
 
 
 def _mm(math=None):

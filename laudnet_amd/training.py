@@ -39,7 +39,9 @@ Entry points: `sparse_block_train(block, x, mask)` (one block, the mask an input
 block signature in training mode: samples its own masks), `train_forward(model, x, temperature)` (a whole LAUD-ResNet -> the reference's
 7-tuple; a `LAD_MMDet_ResNet` -> its (outs, additional, model_configs)), `prepare_for_training(model)` (train mode with BatchNorm statistics
 frozen).  Checked against the oracle's autograd -- blocks on the reference-generated block fixtures, whole models on `det_tiny.pt` /
-`full_tiny.pt` with identical Gumbel noise (tests/test_hip_training.py, tests/test_hip_training_both.py, plain 1e-3).
+`full_tiny.pt` with identical Gumbel noise (tests/test_hip_training.py, tests/test_hip_training_both.py, plain 1e-3; bf16x3 with a flip
+allowance) -- and, element by element to 1e-3 of each gradient's own maximum in both arithmetic modes, against a float64 restatement on inputs
+where no ReLU can flip (tests/test_hip_training_f64.py, tests/train_ref.py).
 
 LAD-RegNet (`laud_regnet.ResBottleneckBlock`) trains in its LAYER-SKIP form -- dyn_mode 'spatial' with one keep / skip bit per image, SE present, stride
 1 and 2, with and without `proj`: a kept image runs a -> grouped b -> SE -> c on packed rows in both directions (`_RegNetSkipBranchFn`: the grouped
@@ -51,6 +53,7 @@ Not built: mask groups > 1, dilated conv2, grouped conv2 outside that block, Bat
 patch-mask (mask_size > 1) training."""
 from __future__ import annotations
 
+import functools
 import os
 from collections import namedtuple
 
@@ -147,6 +150,18 @@ def grouped_weight_T(wbr, gw):
 
 # ------------------------------------------------------------------------------------------------------------------ shared by the branch Fns
 _Prep = namedtuple("_Prep", "x2d w1r w2r w3r w3s bn shape")
+
+
+def _in_forward_mode(backward):
+    """A branch Fn's backward under the arithmetic mode its forward ran in (ctx.math_mode).  ops.set_math_mode is a PER-THREAD default and autograd
+    runs the backward of a GPU graph on a thread of its own, where that default is unset: without this the whole backward -- transposed
+    convolutions, weight gradients, the dense re-execution of the straight-through terms and the kernel choice of _conv_const -- ran in the
+    process default (fp32) whatever mode the caller had selected."""
+    @functools.wraps(backward)
+    def run(ctx, *grads):
+        with ops.math_mode(ctx.math_mode):
+            return backward(ctx, *grads)
+    return run
 
 
 def _fold_w3(w3r, s3):
@@ -304,9 +319,11 @@ class _PixelBranchFn(torch.autograd.Function):
         h1, h2 = _pixel_chain(p.x2d, ix, p.w1r, p.w2r, p.w3s, s1, t1, s2, t2, t3, br)
         ctx.save_for_backward(p.x2d, h1, h2, br, p.w1r, p.w2r, p.w3r, *p.bn, m3.detach().float())
         ctx.ix, ctx.shape, ctx.stride = ix, p.shape, stride
+        ctx.math_mode = ops.get_math_mode()
         return ops.from_nhwc(br.view(B, Ho, Wo, cout))
 
     @staticmethod
+    @_in_forward_mode
     def backward(ctx, g):
         x2d, h1, h2, br, w1r, w2r, w3r, s1, t1, s2, t2, s3, t3, m3d = ctx.saved_tensors
         ix, shape, stride, need, dev = ctx.ix, ctx.shape, ctx.stride, ctx.needs_input_grad, g.device
@@ -353,9 +370,11 @@ class _ChannelBranchFn(torch.autograd.Function):
         ops.conv_rows(h2, p.w3s, None, t3c, br, taps=1, m_cap=ix.cap3, relu=0)
         ctx.save_for_backward(p.x2d, h1, h2, br, p.w1r, p.w2r, p.w3r, *p.bn, chm2d, c1, c2, tab)
         ctx.ix, ctx.shape, ctx.stride = ix, p.shape, stride
+        ctx.math_mode = ops.get_math_mode()
         return ops.from_nhwc(br.view(B, Ho, Wo, cout))
 
     @staticmethod
+    @_in_forward_mode
     def backward(ctx, g):
         x2d, u1, u2, br, w1r, w2r, w3r, s1, t1, s2, t2, s3, t3, chm2d, c1, c2, tab = ctx.saved_tensors
         ix, shape, stride, need, dev = ctx.ix, ctx.shape, ctx.stride, ctx.needs_input_grad, g.device
@@ -433,9 +452,11 @@ class _BothBranchFn(torch.autograd.Function):
         u1, u2 = _both_chain(p.x2d, ix, (Hi, Wi, Ho, Wo, stride), p.w1r, p.w2r, p.w3s, s1, t1, c1, s2, tab, c2, t3c, chm2d, br)
         ctx.save_for_backward(p.x2d, u1, u2, br, p.w1r, p.w2r, p.w3r, *p.bn, m3.detach().float(), chm2d, c1, c2, tab, t3c)
         ctx.ix, ctx.shape, ctx.stride = ix, p.shape, stride
+        ctx.math_mode = ops.get_math_mode()
         return ops.from_nhwc(br.view(B, Ho, Wo, cout))
 
     @staticmethod
+    @_in_forward_mode
     def backward(ctx, g):
         x2d, u1, u2, br, w1r, w2r, w3r, s1, t1, s2, t2, s3, t3, m3d, chm2d, c1, c2, tab, t3c = ctx.saved_tensors
         ix, shape, stride = ctx.ix, ctx.shape, ctx.stride
@@ -526,9 +547,11 @@ class _RegNetSkipBranchFn(torch.autograd.Function):
         h_a, h_b, gate = _regnet_chain(p.x2d, ix, Ho * Wo, f, p.w1r, p.w2r, p.w3s, sa, ta, sb, tb, tc, se, br)
         ctx.save_for_backward(p.x2d, h_a, h_b, gate, br, p.w1r, p.w2r, p.w3r, *p.bn, *se, m3.detach().float())
         ctx.ix, ctx.shape, ctx.stride, ctx.f, ctx.se_shapes = ix, p.shape, stride, f, (w1.shape, w2.shape)
+        ctx.math_mode = ops.get_math_mode()
         return ops.from_nhwc(br.view(B, Ho, Wo, cout))
 
     @staticmethod
+    @_in_forward_mode
     def backward(ctx, g):
         x2d, h_a, h_b, gate, br, war, wbr, wcr, sa, ta, sb, tb, sc, tc, w1, b1, w2, b2, m3d = ctx.saved_tensors
         ix, shape, stride, f, need, dev = ctx.ix, ctx.shape, ctx.stride, ctx.f, ctx.needs_input_grad, g.device

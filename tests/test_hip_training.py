@@ -6,12 +6,19 @@ autograd (oracle/torch_ref.py: the reference's dense emulation, BatchNorm in eva
 fixtures of `blocks_s1.pt` / `blocks_s2.pt`, both arithmetic modes; whole models (`det_tiny.pt::channel_r50`, `::layer_r50` -- the shipped
 detection configs -- and two classifiers of `full_tiny.pt`) in training mode with IDENTICAL Gumbel noise: outputs, statistics and the gradient of
 every parameter (models/utils.py:56-58; lad_mmdet_resnet.py:753-758).  Tolerance: plain 1e-3 on values of scale <= 1, 1e-3 of the tensor's
-scale above (the assert says which).  CPU: the transposed neighbour table against a brute-force adjoint, stride 1 and 2."""
+scale above (the assert says which); for the whole models additionally 1e-3 of the tensor's OWN scale, however small, on every gradient on
+which the oracle's CPU and GPU steps agree to a quarter of that (_relative_param_grads).  The strict per-element statement for single blocks,
+without the bf16x3 flip allowance of _close, is tests/test_hip_training_f64.py.  CPU: the transposed neighbour table against a brute-force
+adjoint, stride 1 and 2."""
+import contextlib
+import copy
+
 import pytest
 import torch
+import torch.nn.functional as F
 
 from fill import fill_state_dict, seeded_bernoulli, seeded_randn
-from helpers import block_input, load_golden, make_block
+from helpers import assert_close, block_input, load_golden, make_block
 
 DEV = "cuda:0"
 BLOCKS = dict(load_golden("blocks_s1.pt"))
@@ -29,7 +36,10 @@ def _close(got, want, math_mode, what):
     """fp32 arithmetic: every element within 1e-3 (of max(1, scale)).  bf16x3 arithmetic (1e-5-class forward error): a pre-activation that sits
     within that error of zero takes the other side of its ReLU, and ONE flipped unit moves a 3x3 neighbourhood of d x (all channels) and one
     filter of the weight gradients by O(1) -- exactly what happens to the masker decisions of the inference path at near-ties.  There the
-    bar is: at most 8 % of the elements outside the tolerance (one or two flipped units: a 16-filter 3x3 layer loses 6 % to one), relative Frobenius error below 5 %."""
+    bar is: at most 8 % of the elements outside the tolerance (one or two flipped units: a 16-filter 3x3 layer loses 6 % to one), relative Frobenius error below 5 %.
+    This allowance is for inputs WITH near-ties (the reference-generated fixtures, the 28 x 28 blocks) and cannot tell a flipped unit from a wrong
+    kernel; the strict statement -- every element of every gradient within 1e-3 of the tensor's own maximum, both modes, against float64, on
+    inputs where no ReLU can flip -- lives in tests/test_hip_training_f64.py."""
     if math_mode != "bf16x3":
         assert _err(got, want) < 1e-3, f"{what}: {_err(got, want):.2e} (scale {want.abs().max().item():.2e})"
         return
@@ -179,7 +189,106 @@ def _freeze_bn_train(model):
     return model
 
 
-def _compare_param_grads(hip, ref, math_mode="fp32"):
+class GumbelTape:
+    """The Gumbel noise of one training forward, so that the SAME step can be run on another device.  record(): every F.gumbel_softmax call
+    runs unchanged (same generator draws, same result) and the exponential sample it drew is regenerated from the generator state in front of
+    the call and kept.  replay(): F.gumbel_softmax is torch's own formula on the recorded samples, in order.
+    Depends on torch's implementation: gumbel_softmax draws exactly ONE empty_like(logits).exponential_() from the device generator and nothing
+    else.  Should that change, the replayed step no longer matches the GPU's masks, every tensor becomes ineligible and the
+    half-of-the-small-tensors assertion of _relative_param_grads fails loudly; the recorded run itself is untouched either way."""
+
+    def __init__(self):
+        self.noise = []
+
+    @contextlib.contextmanager
+    def record(self):
+        real = F.gumbel_softmax
+
+        def recording(logits, tau=1, hard=False, eps=1e-10, dim=-1):
+            dev = logits.device
+            before = torch.cuda.get_rng_state(dev)
+            ret = real(logits, tau=tau, hard=hard, dim=dim)
+            after = torch.cuda.get_rng_state(dev)
+            torch.cuda.set_rng_state(before, dev)
+            self.noise.append(torch.empty_like(logits, memory_format=torch.legacy_contiguous_format).exponential_().cpu())
+            torch.cuda.set_rng_state(after, dev)
+            return ret
+
+        F.gumbel_softmax = recording
+        try:
+            yield self
+        finally:
+            F.gumbel_softmax = real
+
+    @contextlib.contextmanager
+    def replay(self):
+        real, todo = F.gumbel_softmax, list(self.noise)
+
+        def replaying(logits, tau=1, hard=False, eps=1e-10, dim=-1):
+            e = todo.pop(0).to(logits.device)
+            assert e.shape == logits.shape, (e.shape, logits.shape)
+            y_soft = ((logits - e.log()) / tau).softmax(dim)
+            if not hard:
+                return y_soft
+            y_hard = torch.zeros_like(logits).scatter_(dim, y_soft.max(dim, keepdim=True)[1], 1.0)
+            return y_hard - y_soft.detach() + y_soft
+
+        F.gumbel_softmax = replaying
+        try:
+            yield self
+            assert not todo, f"{len(todo)} recorded Gumbel samples were not used"
+        finally:
+            F.gumbel_softmax = real
+
+
+def oracle_cpu_grads(ref, tape, step):
+    """The oracle's own training step once more on the CPU: a copy of `ref`, the recorded Gumbel noise, step(model, "cpu") = forward + loss + backward
+    -> {parameter name: gradient}.  Two fp32 evaluations of the same reference: where they agree to a quarter of a bound, HIP may be held to it."""
+    cpu = copy.deepcopy(ref).cpu()
+    for p_ in cpu.parameters():
+        p_.grad = None
+    with tape.replay():
+        step(cpu, "cpu")
+    return {n: p_.grad for n, p_ in cpu.named_parameters()}
+
+
+RELATIVE_RECORDS = {}       # test id -> {tensor: {"scale", "eligible", "oracle_cpu_vs_gpu", "rel_err"}} (tools/train_parity_f64.py writes them out)
+
+
+def _relative_param_grads(hip, ref, cpu_grads, what):
+    """The scale-relative statement the absolute floor of _err hides (45 of det_tiny.pt::channel_r50's 223 gradients have max |g| < 1, the smallest
+    1.4e-3: plain 1e-3 is a 1 - 70 % bound there).  A tensor is ELIGIBLE where the oracle's CPU step agrees with its GPU step within 2.5e-4 of the
+    tensor's scale; every eligible tensor must hold max |got - want| <= 1e-3 max |want|.  The others keep _close alone and are listed by name.
+    At least half of the tensors with max |want| < 1 must be eligible, masker tensors among them (at least half of those as well): otherwise
+    this check is empty."""
+    want = dict(ref.named_parameters())
+    rec = RELATIVE_RECORDS.setdefault(what, {})
+    small, small_ok, maskers, maskers_ok, left = 0, 0, 0, 0, []
+    for name, p_ in hip.named_parameters():
+        w = want[name].grad
+        if w is None or w.abs().max().item() == 0:
+            continue
+        scale = w.abs().max().item()
+        agree = (cpu_grads[name].to(w.device) - w).abs().max().item() / scale
+        eligible = agree <= 2.5e-4
+        rel = (p_.grad - w).abs().max().item() / scale
+        rec[name] = dict(scale=scale, eligible=eligible, oracle_cpu_vs_gpu=agree, rel_err=rel)
+        small += scale < 1
+        small_ok += scale < 1 and eligible
+        maskers += "masker" in name
+        maskers_ok += "masker" in name and eligible
+        if not eligible:
+            left.append(f"{name} (scale {scale:.2e}, oracle CPU vs GPU {agree:.1e})")
+    print(f"{what}: {len(rec) - len(left)} of {len(rec)} gradients eligible for the relative check ({small_ok} of {small} with scale < 1, "
+          f"{maskers_ok} of {maskers} masker tensors); absolute check only: {left}")
+    for name, p_ in hip.named_parameters():
+        if name in rec and rec[name]["eligible"]:
+            assert_close(p_.grad, want[name].grad, 1e-3 * rec[name]["scale"], 0, f"{what}: d {name} relative to its scale {rec[name]['scale']:.2e}")
+    assert small == 0 or 2 * small_ok >= small, f"{what}: only {small_ok} of {small} gradients with scale < 1 are eligible"
+    assert maskers == 0 or (maskers_ok > 0 and 2 * maskers_ok >= maskers), f"{what}: only {maskers_ok} of {maskers} masker gradients are eligible"
+
+
+def _compare_param_grads(hip, ref, math_mode="fp32", cpu_grads=None, what=""):
     want = dict(ref.named_parameters())
     n = 0
     for name, p_ in hip.named_parameters():
@@ -189,6 +298,8 @@ def _compare_param_grads(hip, ref, math_mode="fp32"):
         assert (w is None) == (p_.grad is None), f"{name}: gradient present on one side only"
         _close(p_.grad, w, math_mode, f"d {name}")
         n += 1
+    if cpu_grads is not None:
+        _relative_param_grads(hip, ref, cpu_grads, what)
     return n
 
 
@@ -219,10 +330,12 @@ def test_detection_backbone_train_step_vs_oracle(case):
             outs, add, _ = res
             if gs is None:
                 gs = [seeded_randn(tuple(o.shape), 500 + i).to(DEV) for i, o in enumerate(outs)]
-            return sum((o * g).sum() for o, g in zip(outs, gs)) / 100.0 + 10.0 * (add["flops"] / add["dense_flops"] - 0.5) ** 2
+            return sum((o * g.to(o.device)).sum() for o, g in zip(outs, gs)) / 100.0 + 10.0 * (add["flops"] / add["dense_flops"] - 0.5) ** 2
 
+        tape = GumbelTape()
         torch.manual_seed(1234)
-        res_r = ref(x)
+        with tape.record():
+            res_r = ref(x)
         loss_of(res_r).backward()
         torch.manual_seed(1234)
         res_h = train_forward(hip, x)
@@ -236,7 +349,8 @@ def test_detection_backbone_train_step_vs_oracle(case):
         assert torch.allclose(res_h[1]["flops_perc_list"].detach(), res_r[1]["flops_perc_list"].detach(), atol=1e-5)
         assert abs(float(res_h[1]["flops"].detach()) - float(res_r[1]["flops"].detach())) <= 1e-5 * float(res_r[1]["flops"].detach())
         assert abs(float(res_h[1]["dense_flops"]) - float(res_r[1]["dense_flops"])) <= 1e-6 * float(res_r[1]["dense_flops"])
-        n = _compare_param_grads(hip, ref)
+        cpu_grads = oracle_cpu_grads(ref, tape, lambda m, dev: loss_of(m(x.to(dev))).backward())
+        n = _compare_param_grads(hip, ref, cpu_grads=cpu_grads, what=f"det_tiny.pt::{case}")
         assert n >= 100, n
         drops = sum(float((1 - v).sum()) for k in ("spatial_sparsity_conv3", "channel_sparsity") for v in res_r[1][k])
         assert drops > 0, "the sampled masks must drop something"
@@ -268,10 +382,12 @@ def test_classifier_train_step_vs_oracle(case):
     g = seeded_randn((fx["batch"], fx["kw"].get("num_classes", 1000)), 9).to(DEV)
 
     def loss_of(out):
-        return (out[0] * g).sum() / 10.0 + 10.0 * (out[5].mean() - 0.5) ** 2 + 1e-18 * out[6] ** 2
+        return (out[0] * g.to(out[0].device)).sum() / 10.0 + 10.0 * (out[5].mean() - 0.5) ** 2 + 1e-18 * out[6] ** 2
 
+    tape = GumbelTape()
     torch.manual_seed(77)
-    out_r = ref(x, 1.0)
+    with tape.record():
+        out_r = ref(x, 1.0)
     loss_of(out_r).backward()
     torch.manual_seed(77)
     out_h = train_forward(hip, x, 1.0)
@@ -283,7 +399,8 @@ def test_classifier_train_step_vs_oracle(case):
             assert torch.allclose(a.detach().float(), b.detach().float(), atol=1e-6), i
     assert torch.allclose(out_h[5].detach(), out_r[5].detach(), atol=1e-5)
     assert abs(float(out_h[6]) - float(out_r[6])) <= 1e-5 * float(out_r[6])
-    n = _compare_param_grads(hip, ref)
+    cpu_grads = oracle_cpu_grads(ref, tape, lambda m, dev: loss_of(m(x.to(dev), 1.0)).backward())
+    n = _compare_param_grads(hip, ref, cpu_grads=cpu_grads, what=f"full_tiny.pt::{case}")
     assert n >= 200, n
 
 

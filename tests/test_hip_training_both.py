@@ -12,7 +12,7 @@ import torch
 
 from fill import fill_state_dict, seeded_bernoulli, seeded_randn
 from helpers import block_input, load_golden, make_block
-from test_hip_training import BLOCKS, _close, _compare_param_grads, _err, _freeze_bn_train, _start
+from test_hip_training import BLOCKS, GumbelTape, _close, _compare_param_grads, _err, _freeze_bn_train, _start, oracle_cpu_grads
 
 DEV = "cuda:0"
 
@@ -114,10 +114,12 @@ def test_both_classifier_train_step_vs_oracle(case):
     g = seeded_randn((fx["batch"], fx["kw"].get("num_classes", 1000)), 9).to(DEV)
 
     def loss_of(out):
-        return (out[0] * g).sum() / 10.0 + 10.0 * (out[5].mean() - 0.5) ** 2 + 1e-18 * out[6] ** 2
+        return (out[0] * g.to(out[0].device)).sum() / 10.0 + 10.0 * (out[5].mean() - 0.5) ** 2 + 1e-18 * out[6] ** 2
 
+    tape = GumbelTape()
     torch.manual_seed(77)
-    out_r = ref(x, 1.0)
+    with tape.record():
+        out_r = ref(x, 1.0)
     loss_of(out_r).backward()
     torch.manual_seed(77)
     out_h = train_forward(hip, x, 1.0)
@@ -129,7 +131,8 @@ def test_both_classifier_train_step_vs_oracle(case):
             assert torch.allclose(a.detach().float(), b.detach().float(), atol=1e-6), i
     assert torch.allclose(out_h[5].detach(), out_r[5].detach(), atol=1e-5)
     assert abs(float(out_h[6]) - float(out_r[6])) <= 1e-5 * float(out_r[6])
-    n = _compare_param_grads(hip, ref)
+    cpu_grads = oracle_cpu_grads(ref, tape, lambda m, dev: loss_of(m(x.to(dev), 1.0)).backward())
+    n = _compare_param_grads(hip, ref, cpu_grads=cpu_grads, what=f"full_tiny.pt::{case}")
     assert n >= 200, n
     both = [b for s in (1, 2, 3, 4) for b in getattr(hip, f"layer{s}") if b.dyn_mode == "both"]
     assert both and all(getattr(b, "last_channel_mask", None) is not None and getattr(b, "last_spatial_mask", None) is not None for b in both)

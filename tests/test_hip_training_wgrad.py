@@ -43,6 +43,27 @@ def _fixture(mode, stride):
     return fx
 
 
+def poisoning_wgrad_rows(real, calls, poisoned):
+    """A stand-in for ops.wgrad_rows that counts the call (calls += (taps, dY shape, A shape, counted?)) and POISONS every row the kernel may not
+    read: where a device-side count is passed, the rows of dY past it become NaN and the rows of a_rows past it out-of-range indices.  The
+    poisoned copies are appended to `poisoned`: the caller zeroes them once the backward is over (a recycled NaN block would otherwise surface
+    in the next torch.empty of some (uninitialised * 0) product).  Shared with tests/test_hip_training_f64.py."""
+    def counted(dy2d, a2d, *, a_rows=None, taps=1, m_count=None, m_cap=None, a_valid=None, out=None, math=None):
+        if m_count is not None:
+            cap = m_cap if m_cap is not None else dy2d.shape[0]
+            dead = torch.arange(dy2d.shape[0], device=dy2d.device) >= m_count.long()
+            dy2d = dy2d.clone().masked_fill_(dead.unsqueeze(1), float("nan"))        # (in place on the copy: no temporary NaN block)
+            if a_rows is not None:
+                t = a_rows.view(-1, taps)
+                dead_t = torch.arange(t.shape[0], device=t.device) >= m_count.long()
+                a_rows = torch.where(dead_t.unsqueeze(1), torch.full_like(t, 1 << 30), t).reshape(a_rows.shape).contiguous()
+            assert cap <= dy2d.shape[0]
+            poisoned.append(dy2d)
+        calls.append((taps, tuple(dy2d.shape), tuple(a2d.shape), m_count is not None))
+        return real(dy2d, a2d, a_rows=a_rows, taps=taps, m_count=m_count, m_cap=m_cap, a_valid=a_valid, out=out, math=math)
+    return counted
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode,stride", CASES, ids=[f"{m}_s{s}" for m, s in CASES])
 def test_full_width_block_weight_gradients(mode, stride, math_mode, monkeypatch):
@@ -69,25 +90,8 @@ def test_full_width_block_weight_gradients(mode, stride, math_mode, monkeypatch)
     out_r.backward(gout)
     want = {n: p_.grad for n, p_ in ref.named_parameters()}
 
-    real = ops.wgrad_rows
-    calls, poisoned = [], []      # the poisoned copies stay alive until the backward is over and are zeroed before they go back to the caching
-                                  # allocator: a recycled NaN block would otherwise surface in the next torch.empty of some (uninitialised * 0) product
-
-    def counted(dy2d, a2d, *, a_rows=None, taps=1, m_count=None, m_cap=None, a_valid=None, out=None, math=None):
-        """counts the call and poisons every row the kernel may not read"""
-        if m_count is not None:
-            cap = m_cap if m_cap is not None else dy2d.shape[0]
-            dead = torch.arange(dy2d.shape[0], device=dy2d.device) >= m_count.long()
-            dy2d = dy2d.clone().masked_fill_(dead.unsqueeze(1), float("nan"))        # (in place on the copy: no temporary NaN block)
-            if a_rows is not None:
-                t = a_rows.view(-1, taps)
-                dead_t = torch.arange(t.shape[0], device=t.device) >= m_count.long()
-                a_rows = torch.where(dead_t.unsqueeze(1), torch.full_like(t, 1 << 30), t).reshape(a_rows.shape).contiguous()
-            assert cap <= dy2d.shape[0]
-            poisoned.append(dy2d)
-        calls.append((taps, tuple(dy2d.shape), tuple(a2d.shape), m_count is not None))
-        return real(dy2d, a2d, a_rows=a_rows, taps=taps, m_count=m_count, m_cap=m_cap, a_valid=a_valid, out=out, math=math)
-
+    calls, poisoned = [], []
+    counted = poisoning_wgrad_rows(ops.wgrad_rows, calls, poisoned)
     monkeypatch.setattr(ops, "wgrad_rows", counted)
     grads = {}
     for on in (True, False):
