@@ -290,6 +290,23 @@ int ldn_rows_act_bwd(const float* dh, int lddh, const float* u, int ldu, const f
                      int m_cap, int C, float* du, int lddu, float* g_shift, float* g_scale_num, float* g_mask, float* work,
                      void* stream);
 
+/* ldn_rows_ln_bwd: the LayerNorm backward on LISTED rows (a token-skip block's norm1 / norm2 in training).  For every list entry r < count
+ * (count = clamp(*count, 0, m_cap), read on the device; list NULL: the rows 0 .. m_cap - 1 themselves), src = list[r]:
+ *   x^ = (x[src] - mean) * rstd        {mean, rstd} = stats[src] (ldn_row_stats / ldn_row_stats_list; formed from the difference, so a row with
+ *                                      |mean| >> std keeps its digits)
+ *   g  = dy[r] * gamma                 dy [m_cap][lddy] PACKED: d L / d (the LayerNorm's output on row src)
+ *   dx[src] += rstd * (g - mean_k(g) - x^ * mean_k(g x^))       ADDED into dx [rows][lddx] (the residual stream's gradient); the list entries
+ *                                      must be distinct; an entry outside [0, rows) is skipped
+ *   d_gamma[k] = sum_r dy[r][k] x^[k]      d_beta[k] = sum_r dy[r][k]      over the entries below the count (zeros for an empty list)
+ *   xhat [m_cap][ldxh] (nullable): x^ of every entry below the count, packed -- the input of the weight gradient of the linear behind the norm.
+ * Entries at and past the count are not read, and nothing is written for them.  C % 4 == 0, C <= 2048, leading dimensions % 4 == 0, 16-byte
+ * aligned pointers (stats excepted).  Deterministic: one wave per row, the split plan a function of m_cap only (graph-capturable), partial sums
+ * to `work` (ldn_rows_ln_bwd_workspace_bytes(m_cap, C); never NULL), a second small launch adds them in ascending order.  No atomics. */
+size_t ldn_rows_ln_bwd_workspace_bytes(int m_cap, int C);
+int ldn_rows_ln_bwd(const float* x, int ldx, int rows, const float* stats, const float* gamma, const int32_t* list, const int32_t* count,
+                    int m_cap, int C, const float* dy, int lddy, float* dx, int lddx, float* d_gamma, float* d_beta, float* xhat, int ldxh,
+                    float* work, void* stream);
+
 /* ldn_conv_rows_split / ldn_conv_rows_f32 with taps == 1, plus a by-product: pool [B][S*Sx][cout] receives, for every patch
  * this launch writes, the MEAN of the final output (after residual and ReLU) over the patch's Ho/S x Wo/Sx pixels (4 or 16) --
  * the pooled means the next block's spatial masker needs (adaptive_avg_pool2d of models/utils.py:48-52 on an even grid), so
@@ -611,6 +628,19 @@ int ldn_packed_mha(const float* qkv, int ld_qkv, const int32_t* tok_rows, const 
  * workgroup of a dropped (image, head) writes zeros to its 64 output columns and computes nothing. */
 int ldn_packed_mha_heads(const float* qkv, int ld_qkv, const int32_t* tok_rows, const int32_t* img_prefix, int B, int heads,
                          int head_dim, int max_tokens, float scale, const float* head_keep, float* out, int ldo, void* stream);
+
+/* The BACKWARD of ldn_packed_mha / ldn_packed_mha_heads for max_tokens <= 256 (csrc/ldn_attn_bwd.hip): d_out [N][ldo] = d L / d (the packed
+ * rows of `out`) -> d_qkv [rows][ld_dqkv] = d L / d qkv in the dense token-row layout of qkv: the gradient of kept token n goes to row
+ * tok_rows[n] (dq | dk | dv, each [heads][64]).  With P = softmax(scale Q K^T) per (image, head): dV = P^T dO, dP = dO V^T,
+ * D_i = sum_j P_ij dP_ij, dS = P o (dP - D), dQ = scale dS K, dK = scale dS^T Q; P is recomputed from qkv (bf16x3 products, fp32 softmax).
+ * Only rows of kept tokens are written, all 3 * 64 columns of every head of them; a head dropped by head_keep [B][heads] (nullable) gets
+ * exact zeros in its 3 * 64 columns and its workgroup does nothing else; an image without listed tokens is not touched; tokens of an image
+ * past max_tokens are neither read nor written.  max_tokens > 256 is an error (the tiled form has no backward).  One workgroup per
+ * (image, head), dK / dV summed inside it in a fixed order: no atomics, two runs are bit-identical; the launch depends on B, heads and
+ * max_tokens only. */
+int ldn_packed_mha_bwd(const float* qkv, int ld_qkv, const int32_t* tok_rows, const int32_t* img_prefix, int B, int heads, int head_dim,
+                       int max_tokens, float scale, const float* head_keep, const float* d_out, int ldo, float* d_qkv, int ld_dqkv,
+                       void* stream);
 
 #ifdef __cplusplus
 }

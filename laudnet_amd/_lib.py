@@ -50,6 +50,8 @@ SIGNATURES = {
     "ldn_rows_chanmask": ([_P, _I, _P, _I, _P, _P, _I, _I, _P], _I),
     "ldn_rows_act_bwd_workspace_bytes": ([_I, _I, _I], C.c_size_t),
     "ldn_rows_act_bwd": ([_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P], _I),
+    "ldn_rows_ln_bwd_workspace_bytes": ([_I, _I], C.c_size_t),
+    "ldn_rows_ln_bwd": ([_P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _I, _P, _I, _P, _P, _P, _I, _P, _P], _I),
     "ldn_row_stats": ([_P, _I, _I, _I, C.c_float, _P, _P], _I),
     "ldn_row_stats_list": ([_P, _I, _I, _I, C.c_float, _P, _P, _P, _P], _I),
     "ldn_channel_masker_splits": ([_I], _I),
@@ -91,6 +93,7 @@ SIGNATURES = {
     "ldn_stem3_conv": ([_P, _I, _I, _I, _P, _P, _I, _I, _P, _I, _I, _P], _I),
     "ldn_packed_mha": ([_P, _I, _P, _P, _I, _I, _I, _I, C.c_float, _P, _I, _P], _I),
     "ldn_packed_mha_heads": ([_P, _I, _P, _P, _I, _I, _I, _I, C.c_float, _P, _P, _I, _P], _I),
+    "ldn_packed_mha_bwd": ([_P, _I, _P, _P, _I, _I, _I, _I, C.c_float, _P, _P, _I, _P, _I, _P], _I),
     "ldn_bottleneck_chain_fits": ([_I, _I, _I, _I, _I, _I], _I),
     "ldn_bottleneck_smallmap_fits": ([_I, _I, _I, _I, _I], _I),
     "ldn_bottleneck_smallmap": ([_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P], _I),

@@ -11,13 +11,21 @@ head and tile of 256 queries, the keys streamed through LDS 256 at a time -- any
 dropped heads' attention workgroups compute nothing) and LAYER skipping (per-image decisions for the attention and the MLP sub-block: the
 image has no tokens in that sub-block's list) of simulate_adavit.py:81-88,140-182 ride on the same lists.  LayerNorm and GELU are epilogue terms of the linears (ldn_row_stats + the ln_* / relu-mode-3 arguments of ldn_conv_rows_split).  Parity is UNPINNED (there is
 nothing in the reference to pin it to): tests compare against oracle/adavit_ref.py, a dense masked restatement of the same operator
-list.  Inference only; no CPU fallback."""
+list.  The modules are eval-only; no CPU fallback.
+
+TRAINING goes through block_train / train_forward below (forward + backward on the same packed lists, one autograd.Function per block): the
+forward runs the inference kernels and keeps each sub-block's input rows, the backward is ldn_packed_mha_bwd (attention), ldn_rows_ln_bwd (both
+LayerNorms), the transposed linears on ldn_conv_rows (gather in, scatter out) and the weight gradients on ldn_wgrad_rows.  A dropped token's
+gradient passes through untouched.  Not built (LdnError): more than 256 kept tokens per image, gradients of the keep masks, q / k / v of
+unattending tokens (qkv_kept_only = False), dropout / drop-path."""
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import ops
+from . import training as _tr
 from ._lib import LdnError
 
 
@@ -161,3 +169,140 @@ class TokenSkipViT(nn.Module):
             (tok_rows, prefix, count), m_list, q_rows = blk.skip_lists(keep, pick(attn_keeps, i), pick(mlp_keeps, i))
             blk.run_packed(x2d, tok_rows, prefix, count, B, Lt, head_keep=pick(head_keeps, i), mlp_lists=m_list, qkv_rows=q_rows)
         return x2d.view(B, Lt, D)
+
+
+# ------------------------------------------------------------------------------------------------------------------ training
+BWD_MAX_TOKENS = 256      # kept tokens per image ldn_packed_mha_bwd takes
+
+
+def _wgrad_T(dy, a2d, a_rows, count, cap, valid):
+    """sum_{r < count} dy[r, n] * a2d[src(r), k] -> [n, k] (src = a_rows[r], or r): ldn_wgrad_rows, or the gather + GEMM path for shapes outside its
+    predicate and with training.USE_WGRAD_KERNEL off.  dy [cap, n] packed; rows past the device-side count may hold recycled memory: the
+    kernel does not read them, the GEMM path selects them away (valid [cap, 1] bool)."""
+    n, k = dy.shape[1], a2d.shape[1]
+    if _tr.USE_WGRAD_KERNEL and ops.wgrad_rows_ok(k, n, 1):
+        return ops.wgrad_rows(dy, a2d, a_rows=a_rows, taps=1, m_count=count, m_cap=cap).view(n, k)
+    zero = dy.new_zeros(1)
+    if a_rows is not None:
+        src = torch.where(valid.view(-1), a_rows[:cap].long(), torch.zeros_like(a_rows[:cap], dtype=torch.long)).clamp(0, a2d.shape[0] - 1)
+        a2d = a2d[src]
+    return torch.where(valid, dy[:cap], zero).t() @ torch.where(valid, a2d[:cap], zero)
+
+
+def _linear_T(dy, lin_weight, out_cols, *, a_rows=None, count, cap):
+    """The transposed linear on listed rows: out[r] = dy[src(r)] . W for r < count (W = the nn.Linear weight [cols of dy, out_cols]), packed."""
+    out = torch.empty(cap, out_cols, device=dy.device, dtype=torch.float32)
+    wT = lin_weight.t().reshape(out_cols, 1, lin_weight.shape[0]).contiguous()
+    ops.conv_rows(dy, wT, None, torch.zeros(out_cols, device=dy.device), out, a_rows=a_rows, taps=1, m_count=count, m_cap=cap, relu=0)
+    return out
+
+
+class _TokenSkipBlockFn(torch.autograd.Function):
+    """One token-skipping block on packed lists (TokenSkipBlock.run_packed with the sub-blocks' inputs kept): differentiable in x and the
+    block's twelve parameter tensors.  lists = TokenSkipBlock.skip_lists(...); ka / km [B * L, 1] bool = the rows of the two lists."""
+
+    @staticmethod
+    def forward(ctx, x, n1w, n1b, qw, qb, pw, pb, n2w, n2b, f1w, f1b, f2w, f2b, block, lists, head_keep, ka, km):
+        B, Lt, D = x.shape
+        dev, rows = x.device, B * Lt
+        (wq, bq, cq), (wp, bp), (w1, b1, c1), (w2, b2) = block._weights(dev)
+        (a_rows, prefix, a_count), m_list, _ = lists
+        m_rows, _, m_count = m_list if m_list is not None else (a_rows, prefix, a_count)
+        x0 = x.detach().reshape(rows, D).float().contiguous()
+        hk = hk3 = None
+        if head_keep is not None:
+            hk = head_keep.detach().float().reshape(B, block.heads).contiguous()
+            hk3 = hk.repeat_interleave(D // block.heads, dim=1).repeat(1, 3).contiguous()
+        st1 = ops.row_stats(x0, block.norm1.eps, rows=a_rows, count=a_count)
+        qkv = torch.empty(rows, 3 * D, device=dev, dtype=torch.float32)
+        ops.conv_rows(x0, wq, None, bq, qkv, a_rows=a_rows, out_rows=a_rows, taps=1, m_count=a_count, m_cap=rows, relu=0, ln_stats=st1, ln_c1=cq,
+                      chan_mask=hk3, rows_per_image=Lt if hk3 is not None else 0)
+        att = ops.packed_mha(qkv, a_rows, prefix, B, block.heads, Lt, head_keep=hk)                      # [capacity, dim], packed
+        x1 = x0.clone()                                            # the MLP sub-block's input: x0 stays what norm1's backward reads
+        ops.conv_rows(att, wp, None, bp, x1, taps=1, m_count=a_count, m_cap=rows, relu=0, out_rows=a_rows, residual2d=x0)
+        st2 = ops.row_stats(x1, block.norm2.eps, rows=m_rows, count=m_count)
+        pre = torch.empty(rows, w1.shape[0], device=dev, dtype=torch.float32)                       # fc1 WITHOUT the GELU epilogue: the backward needs z
+        ops.conv_rows(x1, w1, None, b1, pre, a_rows=m_rows, taps=1, m_count=m_count, m_cap=rows, relu=0, ln_stats=st2, ln_c1=c1)
+        hid = F.gelu(pre)                                          # rows past the count hold recycled memory on both sides; fc2 does not read them
+        x2 = x1.clone()
+        ops.conv_rows(hid, w2, None, b2, x2, taps=1, m_count=m_count, m_cap=rows, relu=0, out_rows=m_rows, residual2d=x1)
+        f32 = lambda t: t.detach().float().contiguous()
+        ctx.save_for_backward(x0, x1, st1, st2, qkv, att, pre, a_rows, prefix, a_count, m_rows, m_count, ka, km,
+                              f32(n1w), f32(n1b), f32(qw), f32(pw), f32(n2w), f32(n2b), f32(f1w), f32(f2w))
+        ctx.hk, ctx.geom, ctx.heads = hk, (B, Lt, D), block.heads
+        ctx.math_mode = ops.get_math_mode()
+        return x2.view(B, Lt, D)
+
+    @staticmethod
+    @_tr._in_forward_mode
+    def backward(ctx, g):
+        (x0, x1, st1, st2, qkv, att, pre, a_rows, prefix, a_count, m_rows, m_count, ka, km,
+         n1w, n1b, qw, pw, n2w, n2b, f1w, f2w) = ctx.saved_tensors
+        B, Lt, D = ctx.geom
+        dev, rows, H = g.device, B * Lt, f1w.shape[0]
+        zero = torch.zeros(1, device=dev)
+        ar = torch.arange(rows, device=dev).unsqueeze(1)
+        va, vm = ar < a_count, ar < m_count                        # [rows, 1] bool: the packed rows in front of each device-side count
+        gx = g.detach().reshape(rows, D).float().clone()           # d L / d (residual stream), walked backwards in place: dropped tokens keep g
+
+        # ---- MLP sub-block: x2 = x1 + fc2(gelu(fc1(norm2(x1)))) on the rows of the MLP list
+        g_f2b = torch.where(km, gx, zero).sum(0)
+        g_f2w = _wgrad_T(F.gelu(pre), gx, m_rows, m_count, rows, vm).t()                                    # [dim, hidden]
+        dhid = _linear_T(gx, f2w, H, a_rows=m_rows, count=m_count, cap=rows)                       # [capacity, hidden], packed
+        z = pre
+        dgelu = 0.5 * (1.0 + torch.erf(z * 0.7071067811865476)) + z * torch.exp(-0.5 * z * z) * 0.3989422804014327
+        dpre = torch.where(vm, dhid * dgelu, zero)                 # select, do not multiply: rows past the count are recycled memory
+        g_f1b = dpre.sum(0)
+        dyln = _linear_T(dpre, f1w, D, count=m_count, cap=rows)                                     # d L / d norm2(x1), packed
+        g_n2w, g_n2b, xh = ops.rows_ln_bwd(x1, st2, n2w, dyln, gx, rows=m_rows, count=m_count, m_cap=rows, want_xhat=True)   # gx += : now d L / d x1
+        g_f1w = _wgrad_T(dpre, xh, None, m_count, rows, vm) * n2w.view(1, -1) + g_f1b.view(-1, 1) * n2b.view(1, -1)
+
+        # ---- attention sub-block: x1 = x0 + proj(mha(qkv(norm1(x0)))) on the rows of the attention list
+        g_pb = torch.where(ka, gx, zero).sum(0)
+        g_pw = _wgrad_T(att, gx, a_rows, a_count, rows, va).t()
+        datt = _linear_T(gx, pw, D, a_rows=a_rows, count=a_count, cap=rows)                        # packed
+        dqkv = ops.packed_mha_bwd(qkv, a_rows, prefix, B, ctx.heads, Lt, datt, head_keep=ctx.hk)   # dense rows, zeros off the list
+        g_qb = dqkv.sum(0)
+        dyln = _linear_T(dqkv, qw, D, a_rows=a_rows, count=a_count, cap=rows)                      # d L / d norm1(x0), packed
+        g_n1w, g_n1b, xh = ops.rows_ln_bwd(x0, st1, n1w, dyln, gx, rows=a_rows, count=a_count, m_cap=rows, want_xhat=True)   # gx += : now d L / d x0
+        g_qw = _wgrad_T(xh, dqkv, a_rows, a_count, rows, va).t() * n1w.view(1, -1) + g_qb.view(-1, 1) * n1b.view(1, -1)
+        return (gx.view(B, Lt, D), g_n1w, g_n1b, g_qw, g_qb, g_pw, g_pb, g_n2w, g_n2b, g_f1w, g_f1b, g_f2w, g_f2b, None, None, None, None, None)
+
+
+def block_train(block, x, keep, head_keep=None, attn_keep=None, mlp_keep=None):
+    """A TokenSkipBlock's forward with a backward: x [B, L, dim], keep [B, L] {0,1} (head_keep [B, heads], attn_keep / mlp_keep [B] as in
+    TokenSkipBlock.forward) -> [B, L, dim], differentiable in x and the block's twelve parameter tensors.  The masks are inputs, not
+    variables: their straight-through gradients need the sub-blocks' outputs at dropped tokens and heads -- a dense execution."""
+    if not isinstance(block, TokenSkipBlock):
+        raise LdnError("block_train: expected a TokenSkipBlock")
+    if ops.get_math_mode() != "bf16x3":
+        raise LdnError("TokenSkipBlock runs in the bf16x3 arithmetic mode (ops.set_math_mode('bf16x3'))")
+    for name, m in (("keep", keep), ("head_keep", head_keep), ("attn_keep", attn_keep), ("mlp_keep", mlp_keep)):
+        if m is not None and m.requires_grad:
+            raise LdnError(f"block_train: the gradient of {name} (a straight-through term of a dense execution) is not built")
+    if not block.qkv_kept_only:
+        raise LdnError("block_train: q / k / v of unattending tokens (qkv_kept_only = False) are not built for training")
+    if x.dim() != 3 or x.shape[2] != block.dim or tuple(keep.shape) != tuple(x.shape[:2]):
+        raise LdnError(f"block_train: x must be [B, L, {block.dim}] and keep [B, L], got {tuple(x.shape)} and {tuple(keep.shape)}")
+    B, Lt, _ = x.shape
+    if Lt > BWD_MAX_TOKENS:
+        raise LdnError(f"block_train: the attention backward for more than {BWD_MAX_TOKENS} kept tokens per image is not built (L = {Lt})")
+    keep = keep.detach()
+    lists = block.skip_lists(keep, attn_keep, mlp_keep)
+    row_mask = lambda k: (k.reshape(B * Lt, 1) > 0.5)
+    ka = row_mask(keep if attn_keep is None else keep * attn_keep.detach().view(B, 1).to(keep.dtype))
+    km = row_mask(keep if mlp_keep is None else keep * mlp_keep.detach().view(B, 1).to(keep.dtype))
+    return _TokenSkipBlockFn.apply(x, block.norm1.weight, block.norm1.bias, block.qkv.weight, block.qkv.bias, block.proj.weight, block.proj.bias,
+                                   block.norm2.weight, block.norm2.bias, block.fc1.weight, block.fc1.bias, block.fc2.weight, block.fc2.bias,
+                                   block, lists, head_keep, ka, km)
+
+
+def train_forward(trunk, x, keeps, head_keeps=None, attn_keeps=None, mlp_keeps=None):
+    """TokenSkipViT.forward with a backward: block_train over the trunk's blocks (keeps[i] [B, L]; optional per-block head_keeps[i],
+    attn_keeps[i], mlp_keeps[i])."""
+    if not isinstance(trunk, TokenSkipViT):
+        raise LdnError("train_forward: expected a TokenSkipViT")
+    pick = lambda seq, i: None if seq is None else seq[i]
+    for i, (blk, keep) in enumerate(zip(trunk.blocks, keeps)):
+        x = block_train(blk, x, keep, pick(head_keeps, i), pick(attn_keeps, i), pick(mlp_keeps, i))
+    return x

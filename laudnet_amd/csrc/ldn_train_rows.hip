@@ -1,6 +1,7 @@
-// ldn_train_rows.hip -- the elementwise backward chain of training on packed rows (ldn_rows_chanmask, ldn_rows_act_bwd; include/ldn_hip.h).
+// ldn_train_rows.hip -- the elementwise backward chain of training on packed rows (ldn_rows_chanmask, ldn_rows_act_bwd; include/ldn_hip.h), and the
+// LayerNorm backward on listed rows (ldn_rows_ln_bwd, further down with its own notes).
 //
-// Both are bandwidth-bound row kernels over [m_cap, C] fp32 matrices with a leading dimension: C % 4 == 0, every access 16 bytes wide, a wave
+// The first two are bandwidth-bound row kernels over [m_cap, C] fp32 matrices with a leading dimension: C % 4 == 0, every access 16 bytes wide, a wave
 // reads consecutive quads of a row.  The count is read on the device; rows r >= count are never read and are written as exact zeros.
 //
 // The image of a packed row comes from the per-image row prefix ([B + 1]: image b owns rows [prefix[b], prefix[b + 1])) inside the kernel --
@@ -200,6 +201,122 @@ static void act_plan(int m_cap, int C, int* tiles, int* splits, int* rps) {
 
 static bool aligned16(const void* ptr) { return (uintptr_t)ptr % 16 == 0; }
 
+// ---- ldn_rows_ln_bwd: the LayerNorm backward on listed rows.  One WAVE per row (the row sums are wave reductions: lane l owns the quads l, l + 64, ...
+// of the row, at most LN_MAXQ of them); a workgroup of four waves owns the list entries [split * rps, + rps), wave w every fourth of them.  The lanes'
+// column sums (d_gamma, d_beta) over the wave's rows stay in registers, the four waves' are added in wave order through the LDS, and the
+// workgroup writes them to work[split]; k_ln_reduce adds the splits in ascending order.
+constexpr int LN_THREADS = 256;
+constexpr int LN_WAVES = LN_THREADS / 64;
+constexpr int LN_MAXQ = 8;             // quads per lane: C <= 2048 (= ldn_row_stats)
+constexpr int LN_MIN_SPLIT_ROWS = 32;
+constexpr int LN_MAX_SPLITS = 512;
+
+struct LnArgs {
+    const float* x; const float* stats; const float* gamma; const int32_t* list; const int32_t* count; const float* dy;
+    float* dx; float* d_gamma; float* d_beta; float* xhat; float* work;
+    int ldx, lddy, lddx, ldxh, rows, m_cap, C, splits, rps;
+};
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(LN_THREADS) void k_rows_ln_bwd(const LnArgs p) {
+    __shared__ f32x4 s_red[LN_WAVES][2][64];
+    const int Q = p.C >> 2;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int split = blockIdx.x;
+    const int count = rows_count(p.count, p.m_cap);
+    const int r_begin = split * p.rps;
+    const int r_end = min(count, min(p.m_cap, r_begin + p.rps));
+    if (r_begin >= r_end) return;          // (uniform) no rows: k_ln_reduce does not read this split's partials
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    const float inv_c = 1.f / (float)p.C;
+    f32x4 gam[LN_MAXQ], g_ga[LN_MAXQ], g_be[LN_MAXQ];
+#pragma unroll
+    for (int i = 0; i < LN_MAXQ; ++i) {
+        const int q = lane + 64 * i;
+        gam[i] = q < Q ? *reinterpret_cast<const f32x4*>(p.gamma + 4 * q) : zero;
+        g_ga[i] = g_be[i] = zero;
+    }
+    for (int r = r_begin + wave; r < r_end; r += LN_WAVES) {
+        const int src = p.list ? p.list[r] : r;
+        if (src < 0 || src >= p.rows) continue;                           // (wave-uniform) a list entry outside the matrix is skipped, never followed
+        const float mean = p.stats[2 * (size_t)src], rstd = p.stats[2 * (size_t)src + 1];
+        f32x4 xh[LN_MAXQ], g[LN_MAXQ];
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < LN_MAXQ; ++i) {
+            const int q = lane + 64 * i;
+            xh[i] = g[i] = zero;
+            if (q < Q) {
+                const f32x4 xv = *reinterpret_cast<const f32x4*>(p.x + (size_t)src * p.ldx + 4 * q);
+                const f32x4 dy = *reinterpret_cast<const f32x4*>(p.dy + (size_t)r * p.lddy + 4 * q);
+                xh[i] = (xv - mean) * rstd;                               // x^ from the difference: a row with |mean| >> std keeps its digits
+                g[i] = dy * gam[i];
+                g_be[i] += dy;
+                g_ga[i] += dy * xh[i];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    s1 += g[i][e];
+                    s2 += g[i][e] * xh[i][e];
+                }
+            }
+        }
+        const float c1 = wave_sum(s1) * inv_c, c2 = wave_sum(s2) * inv_c;
+#pragma unroll
+        for (int i = 0; i < LN_MAXQ; ++i) {
+            const int q = lane + 64 * i;
+            if (q < Q) {
+                float* dst = p.dx + (size_t)src * p.lddx + 4 * q;
+                const f32x4 v = *reinterpret_cast<const f32x4*>(dst) + (g[i] - c1 - xh[i] * c2) * rstd;
+                store16(dst, v);
+                if (p.xhat) store16(p.xhat + (size_t)r * p.ldxh + 4 * q, xh[i]);
+            }
+        }
+    }
+    // the four waves' column sums in wave order (the trip count depends on C only: uniform barriers)
+    const int npass = ceil_div(Q, 64);
+#pragma unroll
+    for (int i = 0; i < LN_MAXQ; ++i) {
+        if (i >= npass) break;
+        s_red[wave][0][lane] = g_ga[i];
+        s_red[wave][1][lane] = g_be[i];
+        __syncthreads();
+        const int q = lane + 64 * i;
+        if (wave < 2 && q < Q) {
+            f32x4 s = zero;
+            for (int w = 0; w < LN_WAVES; ++w) s += s_red[w][wave][lane];
+            *reinterpret_cast<f32x4*>(p.work + ((size_t)(2 * split + wave)) * p.C + 4 * q) = s;
+        }
+        __syncthreads();
+    }
+}
+
+// one thread per quad of d_gamma (j == 0) and d_beta (j == 1): the partials of the splits that hold rows, in ascending order
+__global__ __launch_bounds__(256) void k_ln_reduce(const LnArgs p) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int Q = p.C >> 2;
+    if (i >= 2 * Q) return;
+    const int j = i / Q, k = 4 * (i - j * Q);
+    const int count = rows_count(p.count, p.m_cap);
+    const int live = min(p.splits, ceil_div(count, p.rps));
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < live; ++t) s += *reinterpret_cast<const f32x4*>(p.work + ((size_t)(2 * t + j)) * p.C + k);
+    *reinterpret_cast<f32x4*>((j == 0 ? p.d_gamma : p.d_beta) + k) = s;
+}
+
+// the launch plan: a function of m_cap ONLY
+static void ln_plan(int m_cap, int* splits, int* rps) {
+    int s = m_cap / LN_MIN_SPLIT_ROWS;
+    if (s > LN_MAX_SPLITS) s = LN_MAX_SPLITS;
+    if (s < 1) s = 1;
+    *rps = ceil_div(m_cap > 0 ? m_cap : 1, s);
+    *splits = ceil_div(m_cap > 0 ? m_cap : 1, *rps);
+}
+
 }  // namespace ldn
 
 using namespace ldn;
@@ -253,5 +370,38 @@ extern "C" int ldn_rows_act_bwd(const float* dh, int lddh, const float* u, int l
     const int nvec = 2 + (zy ? B : 0);
     k_act_reduce<<<ceil_div(nvec * (C / 4), 256), 256, 0, st>>>(p, nvec);
     LDN_CHECK_LAUNCH("k_act_reduce");
+    return LDN_OK;
+}
+
+extern "C" size_t ldn_rows_ln_bwd_workspace_bytes(int m_cap, int C) {
+    if (m_cap < 0 || C <= 0 || C % 4) return 0;
+    int splits, rps;
+    ln_plan(m_cap, &splits, &rps);
+    return (size_t)2 * splits * C * sizeof(float);
+}
+
+extern "C" int ldn_rows_ln_bwd(const float* x, int ldx, int rows, const float* stats, const float* gamma, const int32_t* list,
+                               const int32_t* count, int m_cap, int C, const float* dy, int lddy, float* dx, int lddx, float* d_gamma,
+                               float* d_beta, float* xhat, int ldxh, float* work, void* stream) {
+    LDN_REQUIRE(x && stats && gamma && dy && dx && d_gamma && d_beta && work, "ldn_rows_ln_bwd: null pointer");
+    LDN_REQUIRE(rows >= 0 && m_cap >= 0 && C > 0 && C % 4 == 0 && C <= 256 * LN_MAXQ,
+                "ldn_rows_ln_bwd: rows >= 0, m_cap >= 0, C %% 4 == 0, C <= %d (got %d, %d, %d)", 256 * LN_MAXQ, rows, m_cap, C);
+    LDN_REQUIRE(list || m_cap <= rows, "ldn_rows_ln_bwd: without a list the rows are 0 .. m_cap - 1: m_cap %d exceeds %d rows", m_cap, rows);
+    LDN_REQUIRE(ldx >= C && lddy >= C && lddx >= C && ldx % 4 == 0 && lddy % 4 == 0 && lddx % 4 == 0,
+                "ldn_rows_ln_bwd: leading dimensions >= C and multiples of 4 (got %d, %d, %d)", ldx, lddy, lddx);
+    LDN_REQUIRE(!xhat || (ldxh >= C && ldxh % 4 == 0), "ldn_rows_ln_bwd: ldxh >= C and a multiple of 4 (got %d)", ldxh);
+    LDN_REQUIRE(aligned16(x) && aligned16(gamma) && aligned16(dy) && aligned16(dx) && aligned16(d_gamma) && aligned16(d_beta) && aligned16(xhat) &&
+                aligned16(work), "ldn_rows_ln_bwd: every float pointer except stats must be 16-byte aligned");
+    LnArgs p;
+    p.x = x; p.stats = stats; p.gamma = gamma; p.list = list; p.count = count; p.dy = dy; p.dx = dx; p.d_gamma = d_gamma; p.d_beta = d_beta;
+    p.xhat = xhat; p.work = work; p.ldx = ldx; p.lddy = lddy; p.lddx = lddx; p.ldxh = ldxh; p.rows = rows; p.m_cap = m_cap; p.C = C;
+    ln_plan(m_cap, &p.splits, &p.rps);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (m_cap > 0) {
+        k_rows_ln_bwd<<<(unsigned)p.splits, LN_THREADS, 0, st>>>(p);
+        LDN_CHECK_LAUNCH("k_rows_ln_bwd");
+    }
+    k_ln_reduce<<<ceil_div(2 * (C / 4), 256), 256, 0, st>>>(p);
+    LDN_CHECK_LAUNCH("k_ln_reduce");
     return LDN_OK;
 }

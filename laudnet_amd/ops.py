@@ -1313,3 +1313,75 @@ def packed_mha(qkv2d, tok_rows, prefix, B, heads, max_tokens, scale=None, head_k
                                d, max_tokens, float(scale if scale is not None else d ** -0.5), L.ptr(out), dim, L.stream_ptr(out)),
             "ldn_packed_mha")
     return out
+
+
+def packed_mha_bwd(qkv2d, tok_rows, prefix, B, heads, max_tokens, d_out, scale=None, head_keep=None, out=None):
+    """Backward of packed_mha for images with at most 256 kept tokens (see ldn_packed_mha_bwd).  qkv2d [B*L, 3*dim] and the lists as in the
+    forward; d_out [capacity, dim]: the gradient of the forward's packed rows.  Returns d_qkv [B*L, 3*dim] in qkv2d's dense row layout: the
+    gradient of kept token n is row tok_rows[n].  ONLY the rows of kept tokens are written (out: a buffer to write into; by default a zeroed
+    one), a head dropped by head_keep [B, heads] gets exact zeros, an image without listed tokens is not touched.  max_tokens > 256 raises
+    LdnError: the tiled form has no backward.  Deterministic (no atomics)."""
+    L.require_device(qkv2d, tok_rows, prefix, d_out, head_keep, out)
+    lib = L.load()
+    if qkv2d.dim() != 2 or qkv2d.dtype != torch.float32 or qkv2d.stride(1) != 1:
+        raise L.LdnError("packed_mha_bwd: qkv must be fp32 [rows, 3 * heads * head_dim] with contiguous rows")
+    rows, three_dim = qkv2d.shape
+    dim = three_dim // 3
+    d = dim // max(int(heads), 1)
+    if heads <= 0 or three_dim != 3 * dim or dim != heads * d:
+        raise L.LdnError("packed_mha_bwd: qkv must be fp32 [rows, 3 * heads * head_dim]")
+    if max_tokens > 256:
+        raise L.LdnError(f"packed_mha_bwd: more than 256 kept tokens per image are not built (max_tokens {max_tokens}): the tiled form of "
+                         "packed_mha has no backward")
+    if d_out.dim() != 2 or d_out.shape[1] != dim or d_out.dtype != torch.float32 or d_out.stride(1) != 1:
+        raise L.LdnError(f"packed_mha_bwd: d_out must be fp32 [capacity, {dim}] with contiguous rows, got {d_out.dtype} {tuple(d_out.shape)}")
+    if prefix.numel() != B + 1:
+        raise L.LdnError(f"packed_mha_bwd: prefix must be [B + 1] = [{B + 1}], got {prefix.numel()} entries")
+    if d_out.shape[0] < tok_rows.numel():
+        raise L.LdnError(f"packed_mha_bwd: d_out has {d_out.shape[0]} rows, the token list {tok_rows.numel()} (the capacity of packed_mha's rows)")
+    if head_keep is not None and tuple(head_keep.shape) != (B, heads):
+        raise L.LdnError("packed_mha_bwd: head_keep must be [B, heads]")
+    if out is None:
+        out = torch.zeros(rows, three_dim, device=qkv2d.device, dtype=torch.float32)
+    elif tuple(out.shape) != (rows, three_dim):
+        raise L.LdnError(f"packed_mha_bwd: out must be [{rows}, {three_dim}], got {tuple(out.shape)}")
+    L.check(lib.ldn_packed_mha_bwd(L.ptr(_f32rows(qkv2d, "qkv")), qkv2d.stride(0), L.ptr(_i32c(tok_rows, "tok_rows")), L.ptr(_i32c(prefix, "prefix")),
+                                   B, heads, d, max_tokens, float(scale if scale is not None else d ** -0.5), L.ptr(_f32c(head_keep, "head_keep")),
+                                   L.ptr(_f32rows(d_out, "d_out")), d_out.stride(0), L.ptr(_f32rows(out, "out")), out.stride(0),
+                                   L.stream_ptr(out)), "ldn_packed_mha_bwd")
+    return out
+
+
+def rows_ln_bwd(x2d, stats, gamma, dy2d, dx2d, *, rows=None, count=None, m_cap=None, want_xhat=False):
+    """LayerNorm backward on listed rows (see ldn_rows_ln_bwd).  x2d [R, C] and its stats [R, 2] (row_stats), gamma [C]; rows: int32 list of
+    DISTINCT rows of x2d with its device-side count (None: the rows 0 .. m_cap - 1); dy2d [m_cap, C] PACKED: the gradient of the LayerNorm's
+    output on row rows[r].  dx is ADDED into dx2d [R, C] at the listed rows (the other rows are untouched).
+    -> (d_gamma [C], d_beta [C], xhat [m_cap, C] packed or None): sums over the entries below the count; xhat = the normalised rows (before
+    gamma / beta), written below the count only.  Entries past the count are not read.  Deterministic (no atomics)."""
+    L.require_device(x2d, stats, gamma, dy2d, dx2d, rows, count)
+    lib = L.load()
+    if x2d.dim() != 2 or dx2d.dim() != 2 or dy2d.dim() != 2:
+        raise L.LdnError("rows_ln_bwd: x, dy and dx must be matrices")
+    R, C = x2d.shape
+    if C % 4 or C > 2048 or gamma.numel() != C:
+        raise L.LdnError(f"rows_ln_bwd: C % 4 == 0, C <= 2048 and gamma [C] (C {C}, gamma {tuple(gamma.shape)})")
+    if tuple(stats.shape) != (R, 2):
+        raise L.LdnError(f"rows_ln_bwd: stats must be [{R}, 2] (row_stats of x), got {tuple(stats.shape)}")
+    if tuple(dx2d.shape) != (R, C) or dy2d.shape[1] != C:
+        raise L.LdnError(f"rows_ln_bwd: dx must be [{R}, {C}] and dy [m_cap, {C}], got {tuple(dx2d.shape)} and {tuple(dy2d.shape)}")
+    if rows is None and count is not None:
+        raise L.LdnError("rows_ln_bwd: a count needs its row list")
+    if m_cap is None:
+        m_cap = min(dy2d.shape[0], rows.numel() if rows is not None else R)
+    if m_cap < 0 or m_cap > dy2d.shape[0] or (rows is not None and m_cap > rows.numel()) or (rows is None and m_cap > R):
+        raise L.LdnError(f"rows_ln_bwd: m_cap {m_cap} exceeds dy ({dy2d.shape[0]} rows), the row list or x ({R} rows)")
+    dev = x2d.device
+    d_gamma = torch.empty(C, device=dev, dtype=torch.float32)
+    d_beta = torch.empty(C, device=dev, dtype=torch.float32)
+    xhat = torch.empty(m_cap, C, device=dev, dtype=torch.float32) if want_xhat else None
+    work = _work(max(lib.ldn_rows_ln_bwd_workspace_bytes(m_cap, C), 16), dev)
+    L.check(lib.ldn_rows_ln_bwd(L.ptr(_f32rows(x2d, "x")), x2d.stride(0), R, L.ptr(_f32c(stats, "stats")), L.ptr(_f32c(gamma, "gamma")),
+                                L.ptr(_i32c(rows, "rows")), L.ptr(_i32c(count, "count")), m_cap, C, L.ptr(_f32rows(dy2d, "dy")), dy2d.stride(0),
+                                L.ptr(_f32rows(dx2d, "dx")), dx2d.stride(0), L.ptr(d_gamma), L.ptr(d_beta), L.ptr(xhat), C, L.ptr(work),
+                                L.stream_ptr(dx2d)), "ldn_rows_ln_bwd")
+    return d_gamma, d_beta, xhat
