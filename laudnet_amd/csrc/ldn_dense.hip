@@ -9,6 +9,7 @@
 // source address) and are split by the one wave that owns the 32 rows; no producer waves -- every wave issues its share of the
 // DMA (inline asm) with counted vmcnt over a ring of 2-3 slots.  One workgroup = 256 rows x NT columns (NT = 64 / 128 / 256).
 #include "ldn_common.h"
+#include "ldn_dense_plan.h"
 #include <type_traits>
 
 namespace ldn {
@@ -862,46 +863,39 @@ __global__ __launch_bounds__(256) void k_row_stats(const float* __restrict__ x, 
 
 LDN_DEFINE_TU_VIOLATIONS(tu_violations_dense)
 
-template <int NSUB, bool T9, bool FULL, bool F32 = false, int R = 256, bool PS = false, bool OF = false>
-static int launch_dense_f(DenseArgs& a, hipStream_t st) {
-    constexpr int NT = NSUB * 32;
-    constexpr int D = (NSUB >= 6 || R == 128) ? 2 : 3;
-    const size_t lds = (size_t)(T9 ? 12 : 2) * R * 4 + (size_t)D * (R + NT) * 128;
-    a.ntn = ceil_div(a.cout, NT);
-    a.mtn = ceil_div(a.m_cap, R);
-    LDN_REQUIRE(allow_dynamic_lds(reinterpret_cast<const void*>(&k_dense<NSUB, T9, FULL, F32, R, PS, OF>), lds), "k_dense: cannot reserve %zu B of LDS", lds);
-    const unsigned grid = (unsigned)round_up(a.mtn, 8) * a.ntn;
-    hipLaunchKernelGGL((k_dense<NSUB, T9, FULL, F32, R, PS, OF>), dim3(grid), dim3(2 * R), lds, st, a);
-    LDN_CHECK_LAUNCH("k_dense");
+// One launch of either family: mtn x ntn tiles of r rows x nt columns (the grid rounds mtn up to the 8 XCDs), `threads` per workgroup.
+static int launch_rows(void (*kernel)(const DenseArgs), const char* name, int r, int nt, unsigned threads, size_t lds, DenseArgs& a, hipStream_t st) {
+    a.ntn = ceil_div(a.cout, nt);
+    a.mtn = ceil_div(a.m_cap, r);
+    LDN_REQUIRE(allow_dynamic_lds(reinterpret_cast<const void*>(kernel), lds), "%s: cannot reserve %zu B of LDS", name, lds);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)round_up(a.mtn, 8) * a.ntn), dim3(threads), lds, st, a);
+    LDN_CHECK_LAUNCH(name);
     return LDN_OK;
 }
 
-template <int NSUB, bool T9, bool PS, bool OF, bool FEAT = false, bool RAG = false, bool AG = false>
+template <int NSUB, bool T9, bool FULL, bool F32, int R, bool PS, bool OF>
+static int launch_dense_f(DenseArgs& a, hipStream_t st) {
+    constexpr int NT = NSUB * 32, D = (NSUB >= 6 || R == 128) ? 2 : 3;
+    return launch_rows(&k_dense<NSUB, T9, FULL, F32, R, PS, OF>, "k_dense", R, NT, 2 * R, (size_t)(T9 ? 12 : 2) * R * 4 + (size_t)D * (R + NT) * 128, a, st);
+}
+
+template <int NSUB, bool T9, bool PS, bool OF, bool FEAT, bool RAG, bool AG>
 static int launch_dense2(DenseArgs& a, hipStream_t st) {
-    if constexpr (!FEAT && !T9 && !PS && !OF && !RAG) {       // the plain 1x1 form has a second instantiation with the rarely used epilogue terms (T9: always in)
-        if (a.relu == 3 || a.ln_stats || a.chmask || a.post_sub) return launch_dense2<NSUB, T9, PS, OF, true>(a, st);
-    }
     constexpr int NT = NSUB * 32, KS = NSUB <= 4 ? 64 : 32, WROWB = KS * 4, RPI = 1024 / WROWB, NWI = (NT + 8 * RPI - 1) / (8 * RPI);
     const size_t lds = (size_t)(T9 ? 12 : 2) * 256 * 4 + 2 * (size_t)NWI * 8 * 1024 + 8 * 2 * (size_t)32 * 128 +
-                       (AG ? (size_t)(255 / a.gate_rows + 2) * round_up(a.cin, 32) * 4 : 0);      // (AG: the gate vectors of the images a tile touches)
-    a.ntn = ceil_div(a.cout, NT);
-    a.mtn = ceil_div(a.m_cap, 256);
-    LDN_REQUIRE(allow_dynamic_lds(reinterpret_cast<const void*>(&k_dense2<NSUB, T9, PS, OF, FEAT, RAG, AG>), lds), "k_dense2: cannot reserve %zu B of LDS", lds);
-    const unsigned grid = (unsigned)round_up(a.mtn, 8) * a.ntn;
-    hipLaunchKernelGGL((k_dense2<NSUB, T9, PS, OF, FEAT, RAG, AG>), dim3(grid), dim3(512), lds, st, a);
-    LDN_CHECK_LAUNCH("k_dense2");
-    return LDN_OK;
-}
-// can k_dense2 run this launch with tiles of ns * 32 columns?  (whole column tiles, cin a multiple of the tile's K step, a zero row of cin floats)
-static bool dense2_ok(int ns, int taps, int cin, int cout) {
-    static const bool on = !(getenv("LDN_DENSE_V2") && atoi(getenv("LDN_DENSE_V2")) == 0);
-    static const int max_ns = getenv("LDN_DENSE_V2_MAXNS") ? atoi(getenv("LDN_DENSE_V2_MAXNS")) : 8;      // (tuning: widest tile that takes k_dense2)
-    return on && ns <= max_ns && cout % (ns * 32) == 0 && cin % 64 == 0 && cin <= 2048 && (taps == 1 || ns <= 4);
+                       (AG ? (size_t)dense_gate_bytes(a.gate_rows, a.cin) : 0);      // (AG: the gate vectors of the images a tile touches)
+    return launch_rows(&k_dense2<NSUB, T9, PS, OF, FEAT, RAG, AG>, "k_dense2", 256, NT, 512, lds, a, st);
 }
 
-template <int NSUB, bool T9, bool F32 = false>
-static int launch_dense(DenseArgs& a, hipStream_t st) {
-    return a.cout % (NSUB * 32) == 0 ? launch_dense_f<NSUB, T9, true, F32>(a, st) : launch_dense_f<NSUB, T9, false, F32>(a, st);
+// Launches the row of LDN_DENSE_KERNELS (csrc/ldn_dense_plan.h) that the plan is -- the only place that instantiates k_dense / k_dense2.
+// A plan that is no row is refused: it never falls through to a neighbouring kernel.
+static int launch_dense_plan(const DensePlan& plan, DenseArgs& a, hipStream_t st) {
+#define LDN_D1(...) if (plan == LDN_DENSE_ROW1(__VA_ARGS__)) return launch_dense_f<__VA_ARGS__>(a, st);
+#define LDN_D2(...) if (plan == LDN_DENSE_ROW2(__VA_ARGS__)) return launch_dense2<__VA_ARGS__>(a, st);
+    LDN_DENSE_KERNELS(LDN_D1, LDN_D2)
+#undef LDN_D1
+#undef LDN_D2
+    LDN_REQUIRE(false, "ldn_conv_rows: %s is not built (taps %d, cin %d, cout %d, m_cap %d)", dense_plan_name(plan).c_str(), a.taps, a.cin, a.cout, a.m_cap);
 }
 
 }  // namespace ldn
@@ -915,18 +909,57 @@ extern "C" int ldn_debug_set_dense_trace(void* buf) {
 }
 #endif
 
-static int conv_rows_dense_impl(const float* a, int lda, const int32_t* a_rows, int taps, const int32_t* m_count, int m_cap,
-                                const void* w_split, int cin, int cout, const float* scale, const float* shift, int relu,
-                                const int32_t* relu_if_neg, const int32_t* out_rows, const float* residual, int ldr,
-                                float* out, int ldo, const float* post_sub, const float* chan_mask, int rows_per_image,
-                                int shift_classes, const int32_t* pix_map, int Hi, int Wi, int Ho, int Wo, int stride,
-                                const float* ln_stats, const float* ln_c1, bool f32, void* stream, float* pool = nullptr, int pool_S = 0,
-                                int pool_Sx = 0, bool ps = false, bool of = false);
-
 // Advisory: about how many rows the NEXT ldn_conv_rows_split / _pool call of this thread will find in its device-side count (which the
 // host cannot read without a synchronisation) -- e.g. the count of the previous forward.  Used to choose the tile width only.
 static thread_local long g_rows_hint = -1;
 extern "C" int ldn_hint_rows(int rows) { g_rows_hint = rows; return LDN_OK; }
+
+// What an entry point adds to its DenseArgs: the arithmetic, the pre-split sides, and the patch grid of the pooled means (S x pool_Sx patches
+// of the Ho x Wo map).  The gated form is a.a_gate.
+struct DenseForm { bool f32, ps, of; int pool_S; };
+
+// Every shared-weight row convolution: validates the launch, consumes the rows hint, chooses the kernel (dense_plan) and launches it.
+// Ho / Wo / rows_per_img <= 0 mean "not given" (1 in the kernel's arguments, like gate_rows without a gate).
+static int conv_rows_dense(DenseArgs d, const DenseForm& f, void* stream) {
+    const long hint = g_rows_hint;      // (consumed by this call whatever path it takes)
+    g_rows_hint = -1;
+    LDN_REQUIRE(d.a && d.ws && d.shift && d.out, "ldn_conv_rows_split: null pointer");
+    if (d.pool) {
+        LDN_REQUIRE(d.taps == 1 && d.cout % 128 == 0 && !d.post_sub && !d.chmask && !d.ln_stats && (uintptr_t)d.pool % 16 == 0,
+                    "ldn_conv_rows_pool: 1x1 only, cout a multiple of 128, no post_sub / chan_mask / LayerNorm terms");
+        LDN_REQUIRE(f.pool_S > 0 && d.pool_Sx > 0 && d.Ho > 0 && d.Wo > 0 && d.Ho % f.pool_S == 0 && d.Wo % d.pool_Sx == 0,
+                    "ldn_conv_rows_pool: the %dx%d map must split evenly into %dx%d patches", d.Ho, d.Wo, f.pool_S, d.pool_Sx);
+        d.pool_gy = d.Ho / f.pool_S; d.pool_gx = d.Wo / d.pool_Sx;
+        LDN_REQUIRE(d.pool_gy * d.pool_gx == 4 || d.pool_gy * d.pool_gx == 16, "ldn_conv_rows_pool: patches of 4 or 16 pixels (got %dx%d)", d.pool_gy, d.pool_gx);
+    }
+    LDN_REQUIRE((d.ln_stats == nullptr) == (d.ln_c1 == nullptr) && (!d.ln_stats || d.taps == 1), "ldn_conv_rows_split: ln_stats and ln_c1 go together (1x1 only)");
+    LDN_REQUIRE((uintptr_t)d.ln_stats % 8 == 0 && (uintptr_t)d.ln_c1 % 16 == 0, "ldn_conv_rows_split: ln_stats / ln_c1 must be 8 / 16-byte aligned");
+    LDN_REQUIRE(d.cin > 0 && d.cin % 8 == 0 && d.cout > 0 && d.cout % 4 == 0, "ldn_conv_rows_split: cin must be a multiple of 8 and cout of 4 (got %d, %d)", d.cin, d.cout);
+    LDN_REQUIRE(d.lda % 4 == 0 && d.lda >= d.cin && d.ldo % 4 == 0 && d.ldo >= d.cout && (!d.residual || (d.ldr % 4 == 0 && d.ldr >= d.cout)),
+                "ldn_conv_rows_split: strides must be multiples of 4 and cover the row");
+    LDN_REQUIRE(d.relu >= 0 && d.relu <= 3 && (d.relu != 2 || d.relu_if_neg), "ldn_conv_rows_split: bad relu mode (0 none, 1 ReLU, 2 ReLU on the rows with relu_if_neg < 0, 3 GELU)");
+    LDN_REQUIRE((uintptr_t)d.a % 16 == 0 && (uintptr_t)d.ws % 16 == 0 && (uintptr_t)d.out % 16 == 0 && (uintptr_t)d.residual % 16 == 0 &&
+                (uintptr_t)d.shift % 16 == 0 && (uintptr_t)d.scale % 16 == 0, "ldn_conv_rows_split: pointers must be 16-byte aligned");
+    LDN_REQUIRE(d.taps == 1 || (d.taps == 9 && d.a_rows), "ldn_conv_rows_split: taps must be 1, or 9 with a neighbour table");
+    LDN_REQUIRE(d.shift_classes == 1 || (d.shift_classes == 16 && d.taps == 9 && d.pix_map && d.Ho > 0 && d.Wo > 0 && d.Hi > 0 && d.Wi > 0 && d.stride >= 1),
+                "ldn_conv_rows_split: shift_classes 16 needs pix_map and the layer geometry");
+    LDN_REQUIRE(!d.chmask || d.rows_per_img > 0, "ldn_conv_rows_split: chan_mask needs rows_per_image");
+    LDN_REQUIRE((uintptr_t)d.post_sub % 16 == 0 && (uintptr_t)d.chmask % 16 == 0, "ldn_conv_rows_split: post_sub / chan_mask must be 16-byte aligned");
+    if (d.m_cap <= 0) return LDN_OK;
+    // (the bf16x3 forms: every fp32 form runs k_dense, whose epilogue carries every term)
+    LDN_REQUIRE(f.f32 || !((f.ps || f.of || d.taps == 9) && d.relu == 3), "ldn_conv_rows_split: the GELU epilogue exists on the plain 1x1 form only");
+    LDN_REQUIRE(!((f.ps || f.of) && (d.post_sub || d.chmask || d.ln_stats)), "ldn_conv_rows_ps: no post_sub / chan_mask / LayerNorm terms on the pre-split forms");
+    LDN_REQUIRE(!(f.ps && f.of), "ldn_conv_rows_ps: pre-split on both sides is not built");
+    d.Ho = d.Ho > 0 ? d.Ho : 1; d.Wo = d.Wo > 0 ? d.Wo : 1; d.rows_per_img = d.rows_per_img > 0 ? d.rows_per_img : 1;
+    if (!d.a_gate) d.gate_rows = 1;
+    DenseShape s{};
+    s.taps = d.taps; s.cin = d.cin; s.cout = d.cout; s.m_cap = d.m_cap;
+    s.rows_known = dense_rows_known(d.m_cap, d.m_count != nullptr, hint);
+    s.f32 = f.f32; s.ps = f.ps; s.of = f.of; s.pool = d.pool != nullptr;
+    s.feat = d.post_sub || d.chmask || d.ln_stats || d.relu == 3;
+    s.gated = d.a_gate != nullptr; s.gate_bytes = s.gated ? dense_gate_bytes(d.gate_rows, d.cin) : 0;
+    return launch_dense_plan(dense_plan(s), d, static_cast<hipStream_t>(stream));
+}
 
 extern "C" int ldn_conv_rows_split(const float* a, int lda, const int32_t* a_rows, int taps, const int32_t* m_count, int m_cap,
                                    const void* w_split, int cin, int cout, const float* scale, const float* shift, int relu,
@@ -934,8 +967,14 @@ extern "C" int ldn_conv_rows_split(const float* a, int lda, const int32_t* a_row
                                    float* out, int ldo, const float* post_sub, const float* chan_mask, int rows_per_image,
                                    int shift_classes, const int32_t* pix_map, int Hi, int Wi, int Ho, int Wo, int stride,
                                    const float* ln_stats, const float* ln_c1, void* stream) {
-    return conv_rows_dense_impl(a, lda, a_rows, taps, m_count, m_cap, w_split, cin, cout, scale, shift, relu, relu_if_neg, out_rows, residual, ldr,
-                                out, ldo, post_sub, chan_mask, rows_per_image, shift_classes, pix_map, Hi, Wi, Ho, Wo, stride, ln_stats, ln_c1, false, stream);
+    DenseArgs d{};
+    d.a = a; d.lda = lda; d.a_rows = a_rows; d.taps = taps; d.m_count = m_count; d.m_cap = m_cap;
+    d.ws = static_cast<const unsigned char*>(w_split); d.cin = cin; d.cout = cout;
+    d.scale = scale; d.shift = shift; d.relu = relu; d.relu_if_neg = relu_if_neg;
+    d.out_rows = out_rows; d.residual = residual; d.ldr = ldr; d.out = out; d.ldo = ldo;
+    d.post_sub = post_sub; d.chmask = chan_mask; d.rows_per_img = rows_per_image; d.ln_stats = ln_stats; d.ln_c1 = ln_c1;
+    d.shift_classes = shift_classes; d.pix_map = pix_map; d.Hi = Hi; d.Wi = Wi; d.Ho = Ho; d.Wo = Wo; d.stride = stride;
+    return conv_rows_dense(d, DenseForm{}, stream);
 }
 
 extern "C" int ldn_conv_rows_f32(const float* a, int lda, const int32_t* a_rows, int taps, const int32_t* m_count, int m_cap,
@@ -944,8 +983,16 @@ extern "C" int ldn_conv_rows_f32(const float* a, int lda, const int32_t* a_rows,
                                  float* out, int ldo, const float* post_sub, const float* chan_mask, int rows_per_image,
                                  int shift_classes, const int32_t* pix_map, int Hi, int Wi, int Ho, int Wo, int stride,
                                  const float* ln_stats, const float* ln_c1, void* stream) {
-    return conv_rows_dense_impl(a, lda, a_rows, taps, m_count, m_cap, w, cin, cout, scale, shift, relu, relu_if_neg, out_rows, residual, ldr,
-                                out, ldo, post_sub, chan_mask, rows_per_image, shift_classes, pix_map, Hi, Wi, Ho, Wo, stride, ln_stats, ln_c1, true, stream);
+    DenseArgs d{};
+    d.a = a; d.lda = lda; d.a_rows = a_rows; d.taps = taps; d.m_count = m_count; d.m_cap = m_cap;
+    d.ws = reinterpret_cast<const unsigned char*>(w); d.cin = cin; d.cout = cout;
+    d.scale = scale; d.shift = shift; d.relu = relu; d.relu_if_neg = relu_if_neg;
+    d.out_rows = out_rows; d.residual = residual; d.ldr = ldr; d.out = out; d.ldo = ldo;
+    d.post_sub = post_sub; d.chmask = chan_mask; d.rows_per_img = rows_per_image; d.ln_stats = ln_stats; d.ln_c1 = ln_c1;
+    d.shift_classes = shift_classes; d.pix_map = pix_map; d.Hi = Hi; d.Wi = Wi; d.Ho = Ho; d.Wo = Wo; d.stride = stride;
+    DenseForm f{};
+    f.f32 = true;
+    return conv_rows_dense(d, f, stream);
 }
 
 // The 1x1 form with the pooled patch means of its output as a by-product (the fused spatial masker): `pool`
@@ -959,8 +1006,16 @@ extern "C" int ldn_conv_rows_pool(const float* a, int lda, const int32_t* a_rows
                                   int Sx, int Ho, int Wo, int math_mode, void* stream) {
     LDN_REQUIRE(pool, "ldn_conv_rows_pool: null pool");
     LDN_REQUIRE(math_mode == 0 || math_mode == 1, "ldn_conv_rows_pool: math_mode must be 0 (fp32) or 1 (bf16x3)");
-    return conv_rows_dense_impl(a, lda, a_rows, 1, m_count, m_cap, w, cin, cout, scale, shift, relu, relu_if_neg, out_rows, residual, ldr,
-                                out, ldo, nullptr, nullptr, 0, 1, nullptr, 0, 0, Ho, Wo, 1, nullptr, nullptr, math_mode == 0, stream, pool, S, Sx);
+    DenseArgs d{};
+    d.a = a; d.lda = lda; d.a_rows = a_rows; d.taps = 1; d.m_count = m_count; d.m_cap = m_cap;
+    d.ws = static_cast<const unsigned char*>(w); d.cin = cin; d.cout = cout;
+    d.scale = scale; d.shift = shift; d.relu = relu; d.relu_if_neg = relu_if_neg;
+    d.out_rows = out_rows; d.residual = residual; d.ldr = ldr; d.out = out; d.ldo = ldo;
+    d.shift_classes = 1; d.stride = 1;
+    d.Ho = Ho; d.Wo = Wo; d.pool = pool; d.pool_Sx = Sx;
+    DenseForm f{};
+    f.f32 = math_mode == 0; f.pool_S = S;
+    return conv_rows_dense(d, f, stream);
 }
 
 // The 1x1 form on PRE-SPLIT rows (round 5: the packed spatial / layer path keeps h1 and h2 pre-split between its three launches, so no
@@ -975,9 +1030,16 @@ extern "C" int ldn_conv_rows_ps(const float* a, int lda, int a_presplit, const i
     LDN_REQUIRE(a_presplit || out_presplit, "ldn_conv_rows_ps: neither side is pre-split (use ldn_conv_rows_split)");
     LDN_REQUIRE(cin % 32 == 0 && cout % 64 == 0, "ldn_conv_rows_ps: cin must be a multiple of 32 and cout of 64 (got %d, %d)", cin, cout);
     LDN_REQUIRE(!out_presplit || (!residual && !pool && !out_rows), "ldn_conv_rows_ps: a pre-split output takes no residual, scatter or pooled means");
-    return conv_rows_dense_impl(a, lda, a_rows, 1, m_count, m_cap, w_split, cin, cout, scale, shift, relu, relu_if_neg, out_rows, residual, ldr,
-                                out, ldo, nullptr, nullptr, 0, 1, nullptr, 0, 0, Ho, Wo, 1, nullptr, nullptr, false, stream, pool, S, Sx,
-                                a_presplit != 0, out_presplit != 0);
+    DenseArgs d{};
+    d.a = a; d.lda = lda; d.a_rows = a_rows; d.taps = 1; d.m_count = m_count; d.m_cap = m_cap;
+    d.ws = static_cast<const unsigned char*>(w_split); d.cin = cin; d.cout = cout;
+    d.scale = scale; d.shift = shift; d.relu = relu; d.relu_if_neg = relu_if_neg;
+    d.out_rows = out_rows; d.residual = residual; d.ldr = ldr; d.out = out; d.ldo = ldo;
+    d.shift_classes = 1; d.stride = 1;
+    d.Ho = Ho; d.Wo = Wo; d.pool = pool; d.pool_Sx = Sx;
+    DenseForm f{};
+    f.ps = a_presplit != 0; f.of = out_presplit != 0; f.pool_S = S;
+    return conv_rows_dense(d, f, stream);
 }
 
 // The 1x1 form with a per-image GATE on its input rows (the excitation of an SE block folded into the conv that follows it,
@@ -997,192 +1059,36 @@ extern "C" int ldn_conv_rows_gated(const float* a, int lda, const int32_t* m_cou
     LDN_REQUIRE((uintptr_t)a % 16 == 0 && (uintptr_t)w_split % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)residual % 16 == 0 &&
                 (uintptr_t)shift % 16 == 0 && (uintptr_t)scale % 16 == 0 && (uintptr_t)gate % 16 == 0, "ldn_conv_rows_gated: pointers must be 16-byte aligned");
     if (m_cap <= 0) return LDN_OK;
-    DenseArgs d{a, lda, nullptr, m_count, m_cap, static_cast<const unsigned char*>(w_split), cin, cout, scale, shift, relu,
-                relu_if_neg, out_rows, residual, ldr, out, ldo, 1, 1, nullptr, 0, 0, 1, 1, 1, nullptr, nullptr, 1, 0, 0, nullptr, nullptr, nullptr, 0, 0, 0,
-                gate, gate_rows};
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    g_rows_hint = -1;
     // the gate vectors of every image a 256-row tile can touch sit in LDS behind the staging buffers (98 - 114 KB): small images x wide layers do not fit
-    LDN_REQUIRE((size_t)(255 / gate_rows + 2) * round_up(cin, 32) * 4 <= 44 * 1024,
+    // (the 128-column tiles stage 130 KB, so wider gates take the 160-column tiles -- dense_plan -- whose 46 KB cover this bound)
+    LDN_REQUIRE(dense_gate_bytes(gate_rows, cin) <= 44 * 1024,
                 "ldn_conv_rows_gated: the gate vectors of the %d images a 256-row tile touches (%d channels each) exceed the 44 KB of LDS left for them "
                 "(scale the rows first and use ldn_conv_rows_split)", 255 / gate_rows + 2, cin);
-    //  the 128-column tiles stage 130 KB: only 30 KB are left for the gate vectors there -- wider gates take the 160-column
-    // tiles (114 KB of staging, ragged last tile), whose 46 KB cover the 44 KB bound above
-    const size_t gate_bytes = (size_t)(255 / gate_rows + 2) * round_up(cin, 32) * 4;
-    if ((cout % 128 == 0 || (cout > 64 && cout <= 128)) && gate_bytes <= 30 * 1024) return launch_dense2<4, false, false, false, true, true, true>(d, st);
-    if (cout <= 64) return launch_dense2<2, false, false, false, true, true, true>(d, st);
-    return launch_dense2<5, false, false, false, true, true, true>(d, st);
+    DenseArgs d{};
+    d.a = a; d.lda = lda; d.taps = 1; d.m_count = m_count; d.m_cap = m_cap;
+    d.ws = static_cast<const unsigned char*>(w_split); d.cin = cin; d.cout = cout;
+    d.scale = scale; d.shift = shift; d.relu = relu; d.relu_if_neg = relu_if_neg;
+    d.out_rows = out_rows; d.residual = residual; d.ldr = ldr; d.out = out; d.ldo = ldo;
+    d.shift_classes = 1; d.stride = 1;
+    d.a_gate = gate; d.gate_rows = gate_rows;
+    return conv_rows_dense(d, DenseForm{}, stream);
 }
 
-static int conv_rows_dense_impl(const float* a, int lda, const int32_t* a_rows, int taps, const int32_t* m_count, int m_cap,
-                                const void* w_split, int cin, int cout, const float* scale, const float* shift, int relu,
-                                const int32_t* relu_if_neg, const int32_t* out_rows, const float* residual, int ldr,
-                                float* out, int ldo, const float* post_sub, const float* chan_mask, int rows_per_image,
-                                int shift_classes, const int32_t* pix_map, int Hi, int Wi, int Ho, int Wo, int stride,
-                                const float* ln_stats, const float* ln_c1, bool f32, void* stream, float* pool, int pool_S, int pool_Sx,
-                                bool ps, bool of) {
-    const long hint = g_rows_hint;      // (consumed by this call whatever path it takes)
-    g_rows_hint = -1;
-    LDN_REQUIRE(a && w_split && shift && out, "ldn_conv_rows_split: null pointer");
-    int pool_gy = 0, pool_gx = 0;
-    if (pool) {
-        LDN_REQUIRE(taps == 1 && cout % 128 == 0 && !post_sub && !chan_mask && !ln_stats && (uintptr_t)pool % 16 == 0,
-                    "ldn_conv_rows_pool: 1x1 only, cout a multiple of 128, no post_sub / chan_mask / LayerNorm terms");
-        LDN_REQUIRE(pool_S > 0 && pool_Sx > 0 && Ho > 0 && Wo > 0 && Ho % pool_S == 0 && Wo % pool_Sx == 0,
-                    "ldn_conv_rows_pool: the %dx%d map must split evenly into %dx%d patches", Ho, Wo, pool_S, pool_Sx);
-        pool_gy = Ho / pool_S; pool_gx = Wo / pool_Sx;
-        LDN_REQUIRE(pool_gy * pool_gx == 4 || pool_gy * pool_gx == 16, "ldn_conv_rows_pool: patches of 4 or 16 pixels (got %dx%d)", pool_gy, pool_gx);
-    }
-    LDN_REQUIRE((ln_stats == nullptr) == (ln_c1 == nullptr) && (!ln_stats || taps == 1), "ldn_conv_rows_split: ln_stats and ln_c1 go together (1x1 only)");
-    LDN_REQUIRE((uintptr_t)ln_stats % 8 == 0 && (uintptr_t)ln_c1 % 16 == 0, "ldn_conv_rows_split: ln_stats / ln_c1 must be 8 / 16-byte aligned");
-    LDN_REQUIRE(cin > 0 && cin % 8 == 0 && cout > 0 && cout % 4 == 0, "ldn_conv_rows_split: cin must be a multiple of 8 and cout of 4 (got %d, %d)", cin, cout);
-    LDN_REQUIRE(lda % 4 == 0 && lda >= cin && ldo % 4 == 0 && ldo >= cout && (!residual || (ldr % 4 == 0 && ldr >= cout)),
-                "ldn_conv_rows_split: strides must be multiples of 4 and cover the row");
-    LDN_REQUIRE(relu >= 0 && relu <= 3 && (relu != 2 || relu_if_neg), "ldn_conv_rows_split: bad relu mode (0 none, 1 ReLU, 2 ReLU on the rows with relu_if_neg < 0, 3 GELU)");
-    LDN_REQUIRE((uintptr_t)a % 16 == 0 && (uintptr_t)w_split % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)residual % 16 == 0 &&
-                (uintptr_t)shift % 16 == 0 && (uintptr_t)scale % 16 == 0, "ldn_conv_rows_split: pointers must be 16-byte aligned");
-    LDN_REQUIRE(taps == 1 || (taps == 9 && a_rows), "ldn_conv_rows_split: taps must be 1, or 9 with a neighbour table");
-    LDN_REQUIRE(shift_classes == 1 || (shift_classes == 16 && taps == 9 && pix_map && Ho > 0 && Wo > 0 && Hi > 0 && Wi > 0 && stride >= 1),
-                "ldn_conv_rows_split: shift_classes 16 needs pix_map and the layer geometry");
-    LDN_REQUIRE(!chan_mask || rows_per_image > 0, "ldn_conv_rows_split: chan_mask needs rows_per_image");
-    LDN_REQUIRE((uintptr_t)post_sub % 16 == 0 && (uintptr_t)chan_mask % 16 == 0, "ldn_conv_rows_split: post_sub / chan_mask must be 16-byte aligned");
-    if (m_cap <= 0) return LDN_OK;
-    DenseArgs d{a, lda, a_rows, m_count, m_cap, static_cast<const unsigned char*>(w_split), cin, cout, scale, shift, relu,
-                relu_if_neg, out_rows, residual, ldr, out, ldo, taps, shift_classes, pix_map, Hi, Wi, Ho > 0 ? Ho : 1, Wo > 0 ? Wo : 1,
-                stride, post_sub, chan_mask, rows_per_image > 0 ? rows_per_image : 1, 0, 0, ln_stats, ln_c1, pool, pool_gy, pool_gx, pool_Sx, nullptr, 1};
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    // columns per workgroup: as wide as the layer allows (fewer passes over the activation rows) while the grid still fills the chip
-    const int mt = ceil_div(m_cap, D_ROWS_MAX);
-    if (f32) {   // true-fp32 MFMA: the same tile rules (the matrix time per tile is 5.3x longer, the staging the same)
-        if (taps == 9) return (cout % 128 == 0 || cout > 64) ? launch_dense<4, true, true>(d, st) : launch_dense<2, true, true>(d, st);
-        if (cout % 256 == 0 && (long)mt * (cout / 256) >= 384) return launch_dense<8, false, true>(d, st);
-        if (cout % 128 == 0) return launch_dense<4, false, true>(d, st);
-        if (cout <= 64) return launch_dense<2, false, true>(d, st);
-        if (cout % 160 == 0 || (cout % 32 != 0 && cout > 128)) return launch_dense<5, false, true>(d, st);
-        return launch_dense<4, false, true>(d, st);
-    }
-    // 128-row tiles (four waves, two workgroups per CU) where the grid of 256-row tiles is at most one round of the chip's 512
-    // workgroup slots (the workgroups that survive the device-side row count sit alone on their CUs).  MEASURED SLOWER
-    // (round 4: channel 12.07 -> 12.30 ms, layer 12.92 -> 13.11, spatial 13.98 -> 14.28: a third more L2 -> LDS bytes per product
-    // outweighs the second resident workgroup), so it is off; LDN_DENSE_R128=1 (or a workgroup-count threshold) switches it on for A/B
-    static const int r128 = getenv("LDN_DENSE_R128") ? atoi(getenv("LDN_DENSE_R128")) : 0;
-    const bool small_grid = r128 && cout % 128 == 0 && (long)mt * (cout / 128) <= (r128 > 1 ? r128 : 512);
-    // Tile width by a cost model when the number of rows is KNOWN (no device-side count) or HINTED (ldn_hint_rows: the host cannot see
-    // a device-side count, the caller passes what the previous forward's count was): the time of a launch is rounds x tile time
-    // (DESIGN.md 4n / 4t), rounds = ceil(live workgroups / 256) (one workgroup per CU: 115-159 KB of LDS), tile time = chunks x (1700 + 500
-    // NSUB) + 12000 NSUB cycles (the per-chunk law of 4r; the second constant, fitted: epilogue + pipeline fill per 32-column subtile).  Results do not depend on the choice.
-    static const bool use_model = !(getenv("LDN_DENSE_MODEL") && atoi(getenv("LDN_DENSE_MODEL")) == 0);
-    // the ragged form of k_dense2 (any cin % 8 == 0, ragged last column tile; 64- and 160-column tiles: LAD-RegNet's widths)
-    static const bool rag2 = !(getenv("LDN_DENSE_V2") && atoi(getenv("LDN_DENSE_V2")) == 0) && !getenv("LDN_DENSE_NO_RAG");
-    const long rows_known = !m_count ? (long)m_cap : (hint >= 0 ? (hint < m_cap ? hint : (long)m_cap) : -1);
-    static long mc[3] = {1700, 500, 12000};   // LDN_DENSE_MODEL_C="a,b,c" overrides (tuning)
-    static const bool mc_env = [] { const char* e = getenv("LDN_DENSE_MODEL_C"); if (e) sscanf(e, "%ld,%ld,%ld", &mc[0], &mc[1], &mc[2]); return e != nullptr; }();
-    (void)mc_env;
-    auto tile_cost = [&](int ns) {
-        const long mtl = (rows_known + D_ROWS_MAX - 1) / D_ROWS_MAX;
-        const long chunks = (long)taps * ((cin + 31) / 32);
-        const long wgs = mtl * (cout / (ns * 32));
-        return (double)((wgs + 255) / 256) * (double)(chunks * (mc[0] + mc[1] * ns) + mc[2] * ns);
-    };
-    LDN_REQUIRE(!((ps || of || taps == 9) && relu == 3), "ldn_conv_rows_split: the GELU epilogue exists on the plain 1x1 form only");
-    LDN_REQUIRE(!((ps || of) && (post_sub || chan_mask || ln_stats)), "ldn_conv_rows_ps: no post_sub / chan_mask / LayerNorm terms on the pre-split forms");
-    if (ps || of) {      // pre-split rows on one or both sides: 1x1, whole column tiles of 256 / 128 / 64
-        int best = 0;
-        double best_cost = 0.0;
-        if (use_model && rows_known > 0) {
-            for (int ns : {8, 4, 2}) {
-                if (cout % (ns * 32) != 0) continue;
-                const double cost = tile_cost(ns);
-                if (!best || cost < best_cost) { best = ns; best_cost = cost; }
-            }
-        }
-        if (!best) best = (cout % 256 == 0 && (long)mt * (cout / 256) >= 384) ? 8 : (cout % 128 == 0 ? 4 : 2);
-        const bool v2 = dense2_ok(best, 1, cin, cout);
-        if (ps && !of) {
-            switch (best) {
-                case 8: return v2 ? launch_dense2<8, false, true, false>(d, st) : launch_dense_f<8, false, true, false, 256, true, false>(d, st);
-                case 4: return v2 ? launch_dense2<4, false, true, false>(d, st) : launch_dense_f<4, false, true, false, 256, true, false>(d, st);
-                default: return v2 ? launch_dense2<2, false, true, false>(d, st) : launch_dense_f<2, false, true, false, 256, true, false>(d, st);
-            }
-        }
-        LDN_REQUIRE(!ps, "ldn_conv_rows_ps: pre-split on both sides is not built");
-        switch (best) {
-            case 8: return v2 ? launch_dense2<8, false, false, true>(d, st) : launch_dense_f<8, false, true, false, 256, false, true>(d, st);
-            case 4: return v2 ? launch_dense2<4, false, false, true>(d, st) : launch_dense_f<4, false, true, false, 256, false, true>(d, st);
-            default: return v2 ? launch_dense2<2, false, false, true>(d, st) : launch_dense_f<2, false, true, false, 256, false, true>(d, st);
-        }
-    }
-    if (taps == 9) {
-        if (small_grid) return launch_dense_f<4, true, true, false, 128>(d, st);
-        if (use_model && rows_known > 0 && cout % 128 == 0 && tile_cost(2) < tile_cost(4))
-            return dense2_ok(2, 9, cin, cout) ? launch_dense2<2, true, false, false>(d, st) : launch_dense_f<2, true, true>(d, st);
-        if (cout % 128 == 0 && dense2_ok(4, 9, cin, cout)) return launch_dense2<4, true, false, false>(d, st);
-        if (cout % 128 != 0 && cout <= 64 && dense2_ok(2, 9, cin, cout)) return launch_dense2<2, true, false, false>(d, st);
-        return (cout % 128 == 0 || cout > 64) ? launch_dense<4, true>(d, st) : launch_dense<2, true>(d, st);
-    }
-    // ONE K chunk (a 32-wide input: LAD-RegNet's stage 1 behind its 32-channel stem): nothing to pipeline inside a workgroup -- load, multiply, store
-    // follow one another -- so the launch lives on workgroups overlapping EACH OTHER: 128-row tiles with a two-slot ring (49 KB: three per CU)
-    // instead of 256-row tiles with the 122 KB ring of the long-K form (one per CU).  LDN_DENSE_SHORTK=<widest cin> (0: off) for A/B.
-    static const int shortk = getenv("LDN_DENSE_SHORTK") ? atoi(getenv("LDN_DENSE_SHORTK")) : 32;      // widest input that takes this form (0: off; A/B)
-    if (cin <= shortk && !small_grid && !post_sub && !chan_mask && !ln_stats && relu != 3) {
-        if (cout <= 64) return cout % 64 == 0 ? launch_dense_f<2, false, true, false, 128>(d, st) : launch_dense_f<2, false, false, false, 128>(d, st);
-        if (cout % 128 == 0) return launch_dense_f<4, false, true, false, 128>(d, st);
-    }
-    static const int shortk5 = getenv("LDN_DENSE_SHORTK5") ? atoi(getenv("LDN_DENSE_SHORTK5")) : 144;  // the same for 160-column tiles (ragged widths above 128; RegNet 3.25 -> 3.22 ms); 0: off
-    if (cin <= shortk5 && !small_grid && !post_sub && !chan_mask && !ln_stats && relu != 3 && (cout % 160 == 0 || (cout % 32 != 0 && cout > 128)))
-        return cout % 160 == 0 ? launch_dense_f<5, false, true, false, 128>(d, st) : launch_dense_f<5, false, false, false, 128>(d, st);
-    if (use_model && rows_known > 0 && !small_grid) {
-        int best = 0;
-        double best_cost = 0.0;
-        for (int ns : {8, 6, 5, 4, 2}) {
-            if (cout % (ns * 32) != 0) continue;
-            const double cost = tile_cost(ns);
-            if (!best || cost < best_cost) { best = ns; best_cost = cost; }
-        }
-        const bool v2 = best && dense2_ok(best, 1, cin, cout);
-        switch (best) {
-            case 8: return v2 ? launch_dense2<8, false, false, false>(d, st) : launch_dense_f<8, false, true>(d, st);
-            case 6: return v2 ? launch_dense2<6, false, false, false>(d, st) : launch_dense_f<6, false, true>(d, st);
-            case 5: return v2 ? launch_dense2<5, false, false, false>(d, st) : (rag2 && cin <= 2048 ? launch_dense2<5, false, false, false, true, true>(d, st) : launch_dense_f<5, false, true>(d, st));
-            case 4: return v2 ? launch_dense2<4, false, false, false>(d, st) : launch_dense_f<4, false, true>(d, st);
-            case 2: return v2 ? launch_dense2<2, false, false, false>(d, st) : (rag2 && cin <= 2048 && cin > 64 ? launch_dense2<2, false, false, false, true, true>(d, st) : launch_dense_f<2, false, true>(d, st));
-            default: break;
-        }
-    }
-    if (cout % 256 == 0 && (long)mt * (cout / 256) >= 384) return dense2_ok(8, 1, cin, cout) ? launch_dense2<8, false, false, false>(d, st) : launch_dense<8, false>(d, st);
-    if (small_grid) return launch_dense_f<4, false, true, false, 128>(d, st);
-    if (cout % 128 == 0) return dense2_ok(4, 1, cin, cout) ? launch_dense2<4, false, false, false>(d, st) : launch_dense<4, false>(d, st);
-    if (cout <= 64) return dense2_ok(2, 1, cin, cout) ? launch_dense2<2, false, false, false>(d, st) : (rag2 && cin <= 2048 && cin > 64 ? launch_dense2<2, false, false, false, true, true>(d, st) : launch_dense<2, false>(d, st));
-    // 160-column tiles: layers whose width is a multiple of 160 (320: two whole tiles instead of 128 + 128 + 64), and ragged widths
-    // above 128 (144 in one tile; 784 = 4 x 160 + 144) -- LAD-RegNet
-    static const bool use5 = !getenv("LDN_DENSE_NO5");
-    if (use5 && (cout % 160 == 0 || (cout % 32 != 0 && cout > 128))) {
-        if (rag2 && cin <= 2048) return launch_dense2<5, false, false, false, true, true>(d, st);      // (the ragged form carries every epilogue term)
-        return launch_dense<5, false>(d, st);
-    }
-    if (cout % 32 != 0 && cout > 128 && cout <= 256) return launch_dense<8, false>(d, st);   // a ragged layer in ONE column tile (144, 168, 216 ...)
-    return launch_dense<4, false>(d, st);
+static int row_stats(const char* what, const float* x, int ld, int rows, int C, float eps, const int32_t* list, const int32_t* count, float* stats, void* stream) {
+    LDN_REQUIRE(rows >= 0 && C > 0 && C % 4 == 0 && C <= 2048 && ld >= C && ld % 4 == 0, "%s: C must be a multiple of 4, at most 2048 (got %d), ld >= C", what, C);
+    LDN_REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)stats % 8 == 0, "%s: pointers must be 16 / 8-byte aligned", what);
+    if (rows == 0) return LDN_OK;
+    hipLaunchKernelGGL(ldn::k_row_stats, dim3((unsigned)ceil_div(rows, 4)), dim3(256), 0, static_cast<hipStream_t>(stream), x, ld, rows, C, eps, stats, list, count);
+    LDN_CHECK_LAUNCH("k_row_stats");
+    return LDN_OK;
 }
 
 extern "C" int ldn_row_stats(const float* x, int ld, int rows, int C, float eps, float* stats, void* stream) {
     LDN_REQUIRE(x && stats, "ldn_row_stats: null pointer");
-    LDN_REQUIRE(rows >= 0 && C > 0 && C % 4 == 0 && C <= 2048 && ld >= C && ld % 4 == 0, "ldn_row_stats: C must be a multiple of 4, at most 2048 (got %d), ld >= C", C);
-    LDN_REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)stats % 8 == 0, "ldn_row_stats: pointers must be 16 / 8-byte aligned");
-    if (rows == 0) return LDN_OK;
-    hipLaunchKernelGGL(ldn::k_row_stats, dim3((unsigned)ceil_div(rows, 4)), dim3(256), 0, static_cast<hipStream_t>(stream), x, ld, rows, C, eps, stats,
-                       nullptr, nullptr);
-    LDN_CHECK_LAUNCH("k_row_stats");
-    return LDN_OK;
+    return row_stats("ldn_row_stats", x, ld, rows, C, eps, nullptr, nullptr, stats, stream);
 }
 
-extern "C" int ldn_row_stats_list(const float* x, int ld, int rows, int C, float eps, const int32_t* list, const int32_t* count, float* stats,
-                                  void* stream) {
+extern "C" int ldn_row_stats_list(const float* x, int ld, int rows, int C, float eps, const int32_t* list, const int32_t* count, float* stats, void* stream) {
     LDN_REQUIRE(x && stats && list && count, "ldn_row_stats_list: null pointer");
-    LDN_REQUIRE(rows >= 0 && C > 0 && C % 4 == 0 && C <= 2048 && ld >= C && ld % 4 == 0, "ldn_row_stats_list: C must be a multiple of 4, at most 2048 (got %d), ld >= C", C);
-    LDN_REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)stats % 8 == 0, "ldn_row_stats_list: pointers must be 16 / 8-byte aligned");
-    if (rows == 0) return LDN_OK;
-    hipLaunchKernelGGL(ldn::k_row_stats, dim3((unsigned)ceil_div(rows, 4)), dim3(256), 0, static_cast<hipStream_t>(stream), x, ld, rows, C, eps, stats,
-                       list, count);
-    LDN_CHECK_LAUNCH("k_row_stats");
-    return LDN_OK;
+    return row_stats("ldn_row_stats_list", x, ld, rows, C, eps, list, count, stats, stream);
 }

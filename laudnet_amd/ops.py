@@ -372,10 +372,10 @@ USE_DENSE_F32 = os.environ.get("LDN_DENSE_F32", "0") != "0"
 USE_FUSED_F32 = os.environ.get("LDN_FUSED_F32", "1") != "0"
 
 
-def dense_kernel_ok():
-    """Does the current arithmetic mode run the shared-weight row convolutions on k_dense (bf16x3: ldn_conv_rows_split; fp32:
-    ldn_conv_rows_f32)?"""
-    mode = get_math_mode()
+def dense_kernel_ok(mode=None):
+    """Does the arithmetic mode (default: the current one) run the shared-weight row convolutions on k_dense (bf16x3:
+    ldn_conv_rows_split; fp32: ldn_conv_rows_f32)?"""
+    mode = mode if mode is not None else get_math_mode()
     return USE_DENSE_KERNEL and (mode == "bf16x3" or (mode == "fp32" and USE_DENSE_F32))
 
 
@@ -475,8 +475,7 @@ def conv_rows(a2d, w, scale, shift, out2d, *, a_rows=None, taps=1, m_count=None,
     # k_conv_bf3 (DENSE_CHANNEL_3X3).  LDN_DENSE_TAPS=1 restores the old dispatch.
     # round 4: the same kernel in true-fp32 MFMA arithmetic (ldn_conv_rows_f32: plain fp32 weights, no split copy) -- the fp32 math mode
     # no longer falls back to round 1's producer / consumer kernel on the shared-weight row paths
-    dense_ok = (USE_DENSE_KERNEL and (mode == "bf16x3" or (mode == "fp32" and USE_DENSE_F32)) and taps in DENSE_TAPS
-                and cin % DENSE_K_MULT == 0 and cout % DENSE_N_MULT == 0 and a2d.stride(0) >= cin)
+    dense_ok = (dense_kernel_ok(mode) and taps in DENSE_TAPS and cin % DENSE_K_MULT == 0 and cout % DENSE_N_MULT == 0 and a2d.stride(0) >= cin)
     classes = 1 if shift.dim() == 1 else shift.shape[0]
     if (post_sub is not None or chan_mask is not None or classes != 1 or relu == 3 or ln_stats is not None) and not dense_ok:
         raise L.LdnError("conv_rows: post_sub / chan_mask / a shift table / the GELU and LayerNorm epilogues need the k_dense path (cin % 8 == 0, cout % 4 == 0)")

@@ -124,7 +124,9 @@ def test_token_skip_trunk_deit_s_shape():
     assert (got - want).abs().max().item() < 1e-3 * max(1.0, want.abs().max().item())
 
 
-@pytest.mark.parametrize("rows,cin,cout,gather", [(2000, 384, 1152, False), (1500, 384, 1536, True), (300, 64, 128, True)])
+@pytest.mark.parametrize("rows,cin,cout,gather", [(2000, 384, 1152, False), (1500, 384, 1536, True), (300, 64, 128, True),
+                                                  # k_dense2's FEAT epilogue on 160- / 128- / 192- / 256-column tiles (the cost model's choice at these rows)
+                                                  (300, 64, 160, False), (16385, 64, 256, False), (49153, 64, 192, False), (49153, 64, 256, False)])
 def test_layernorm_and_gelu_as_epilogue_terms(rows, cin, cout, gather):
     """LN(x) . w + b with the LayerNorm applied AFTER the GEMM (ldn_row_stats + ln_stats / ln_c1 of ldn_conv_rows_split), and the exact
     GELU of relu mode 3, against torch's layer_norm -> linear -> gelu in fp64; rows with a large mean (cancellation in the folded

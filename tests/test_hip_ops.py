@@ -514,7 +514,10 @@ def test_expand_mask_module_vs_reference_fixtures(ops):
         assert torch.equal(got.cpu(), case["y"].bool()), (case["stride"], case["padding"], tuple(m.shape))
 
 
-@pytest.mark.parametrize("B,H,C,cout,stride", [(2, 14, 32, 64, 1), (3, 14, 64, 64, 2)])
+@pytest.mark.parametrize("B,H,C,cout,stride", [(2, 14, 32, 64, 1), (3, 14, 64, 64, 2),
+                                               # ragged last column tile of 64 / of 128 columns, whole 128-column tiles on a K that k_dense2 cannot
+                                               # tile: k_dense<2 | 4, T9, !FULL> and k_dense<4, T9, FULL>, each in both arithmetics (392 rows: ragged M)
+                                               (2, 14, 24, 40, 1), (2, 14, 24, 100, 1), (2, 14, 48, 128, 1)])
 def test_dense_kernel_3x3_neighbour_table(ops, B, H, C, cout, stride, math_mode):
     """k_dense's 3x3 form (ldn_conv_rows_split / ldn_conv_rows_f32, taps == 9): same result as round 1's kernel on the spatial-mode slice
     mask -> index -> 3x3 through the neighbour table, in both arithmetic modes (round 4: the fp32 mode has its own k_dense form, opt-in)."""
@@ -605,7 +608,14 @@ def test_grouped16_conv3x3_whole_images_vs_rows_kernel(ops, B, Ho, stride, C, p)
 
 
 # ------------------------------------------------------------------ k_dense<8>: 256 x 256 tiles at full-size row counts
-@pytest.mark.parametrize("rows,cin,cout,count", [(50176, 256, 512, None), (100001, 64, 256, 99001), (100352, 40, 256, None)])
+@pytest.mark.parametrize("rows,cin,cout,count", [(50176, 256, 512, None), (100001, 64, 256, 99001), (100352, 40, 256, None),
+                                                 # one case per remaining plain 1x1 kernel of LDN_DENSE_KERNELS (csrc/ldn_dense_plan.h), ragged last M tile:
+                                                 (300, 72, 40, None),        # k_dense2's ragged form on 64 columns (ragged column tile)
+                                                 (300, 192, 160, None),      # k_dense2<5>: one whole 160-column tile
+                                                 (300, 24, 64, None), (300, 24, 128, None),      # one K chunk: k_dense's 128-row tiles, 64 / 128 columns
+                                                 (300, 2056, 144, None), (300, 2056, 160, None),    # cin > 2048: k_dense<5>, ragged / whole column tile
+                                                 (49153, 24, 192, None),     # k_dense<6>: 192-column tiles
+                                                 (50001, 200, 256, None)])   # k_dense<8> (cin % 64 != 0) chosen by the cost model
 def test_dense_256_tiles_fullsize_rows_vs_fp64(ops, rows, cin, cout, count):
     """Shared-weight 1x1 rows on k_dense's 256-column tiles at the row counts of the bench (>= 384 tiles): against fp64; ragged last M
     tile, device-side count, K not a multiple of 32, row gather + scatter + conditional ReLU + scale vector."""
@@ -638,7 +648,9 @@ def test_dense_256_tiles_fullsize_rows_vs_fp64(ops, rows, cin, cout, count):
         ops.set_math_mode(None)
 
 
-@pytest.mark.parametrize("rows,cin,cout,taps", [(1000, 64, 256, 1), (700, 256, 64, 1), (513, 40, 144, 1), (600, 32, 128, 9)])
+@pytest.mark.parametrize("rows,cin,cout,taps", [(1000, 64, 256, 1), (700, 256, 64, 1), (513, 40, 144, 1), (600, 32, 128, 9),
+                                                # ragged 64- / 128-column tile, one whole 160-column tile, 256-column tiles (>= 384 workgroups)
+                                                (300, 24, 40, 1), (300, 24, 100, 1), (300, 24, 160, 1), (12100, 24, 2048, 1)])
 def test_conv_rows_f32_kernel_vs_fp64(ops, rows, cin, cout, taps):
     """ldn_conv_rows_f32 (k_dense in true-fp32 MFMA arithmetic, opt-in: ops.USE_DENSE_F32): gathered rows, ragged widths, the 3x3
     neighbour-table form, residual + ReLU -- against fp64 at fp32 round-off."""

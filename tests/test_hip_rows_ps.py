@@ -45,7 +45,9 @@ def test_presplit_helpers_round_trip(ops):
     assert (back - x).abs().max().item() <= 2.0 ** -16 * x.abs().max().item()
 
 
-@pytest.mark.parametrize("rows,cin,cout,count", [(1000, 64, 64, 1000), (700, 256, 128, 613), (300, 1024, 256, 300), (513, 512, 512, 1)])
+@pytest.mark.parametrize("rows,cin,cout,count", [(1000, 64, 64, 1000), (700, 256, 128, 613), (300, 1024, 256, 300), (513, 512, 512, 1),
+                                                 # cin % 64 != 0: k_dense<2 | 4 | 8, OF>; 256-column tiles (>= 384 workgroups) on k_dense2<8, OF>
+                                                 (300, 32, 64, 257), (300, 32, 128, 257), (12100, 32, 2048, 12000), (12100, 64, 2048, 12000)])
 def test_conv1_writes_presplit_rows(ops, rows, cin, cout, count):
     """conv1's epilogue in the OF form: the pre-split rows it stores are exactly the bf16 hi / lo split of what the fp32 form stores."""
     x = seeded_randn((rows + 50, cin), 2).to(DEV)
@@ -98,7 +100,9 @@ def test_rows3_bit_identical_to_unsplit_kernel(ops, B, H, stride, C, cout, p, ou
     assert (val.double() - ref).abs().max().item() < 1e-4 * max(1.0, ref.abs().max().item())
 
 
-@pytest.mark.parametrize("rows,cin,cout,count", [(900, 64, 256, 900), (700, 256, 1024, 650), (257, 128, 512, 257), (400, 512, 2048, 33)])
+@pytest.mark.parametrize("rows,cin,cout,count", [(900, 64, 256, 900), (700, 256, 1024, 650), (257, 128, 512, 257), (400, 512, 2048, 33),
+                                                 # cin % 64 != 0: k_dense<2 | 4 | 8, PS>; k_dense2<8, PS> (>= 384 workgroups) and k_dense2<2, PS>
+                                                 (300, 32, 64, 257), (300, 32, 128, 257), (12100, 32, 2048, 12000), (12100, 64, 2048, 12000), (300, 64, 64, 257)])
 def test_conv3_reads_presplit_rows(ops, rows, cin, cout, count):
     """conv3 in the PS form (scatter-add into the residual stream + ReLU): bit-identical to the form that splits h2 in its K loop."""
     h2 = torch.relu(seeded_randn((rows, cin), 21)).to(DEV)
