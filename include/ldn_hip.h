@@ -635,12 +635,24 @@ int ldn_packed_mha_heads(const float* qkv, int ld_qkv, const int32_t* tok_rows, 
  * D_i = sum_j P_ij dP_ij, dS = P o (dP - D), dQ = scale dS K, dK = scale dS^T Q; P is recomputed from qkv (bf16x3 products, fp32 softmax).
  * Only rows of kept tokens are written, all 3 * 64 columns of every head of them; a head dropped by head_keep [B][heads] (nullable) gets
  * exact zeros in its 3 * 64 columns and its workgroup does nothing else; an image without listed tokens is not touched; tokens of an image
- * past max_tokens are neither read nor written.  max_tokens > 256 is an error (the tiled form has no backward).  One workgroup per
+ * past max_tokens are neither read nor written.  max_tokens > 256 is an error (ldn_packed_mha_bwd_long below tiles beyond).  One workgroup per
  * (image, head), dK / dV summed inside it in a fixed order: no atomics, two runs are bit-identical; the launch depends on B, heads and
  * max_tokens only. */
 int ldn_packed_mha_bwd(const float* qkv, int ld_qkv, const int32_t* tok_rows, const int32_t* img_prefix, int B, int heads, int head_dim,
                        int max_tokens, float scale, const float* head_keep, const float* d_out, int ldo, float* d_qkv, int ld_dqkv,
                        void* stream);
+/* ... for any max_tokens <= 65535 * 256 (the grid's second dimension), e.g. the 577 tokens of a 384 px DeiT input: the same contract, as TWO
+ * launches on `stream` with grid (B * heads, ceil(max_tokens / 256)).  k_packed_mha_bwd_q: one workgroup per tile of 256 queries, the image's K / V
+ * rows streamed through LDS 256 at a time, writes the dq columns and each query's softmax statistics {max, 1 / sum, D}; k_packed_mha_bwd_kv: one
+ * workgroup per tile of 256 keys, the Q / dO rows streamed the same way, dk / dv summed over the query tiles in ascending order inside the
+ * workgroup.  The statistics cross the launches in ws, fp32 [heads][3][ws_rows], column = packed row n (the row index of d_out): the caller
+ * provides it (the library allocates nothing) with ws_rows >= the rows it promises for d_out, i.e. img_prefix[b] + min(count_b, max_tokens) <=
+ * ws_rows for every image; a list that breaks the promise is cut at ws_rows, never followed outside.  ws needs no initialisation (an entry that
+ * was not written is not read) and holds nothing the caller needs afterwards.  An image with <= 256 kept tokens gets the floats of
+ * ldn_packed_mha_bwd, bit for bit; no atomics, two runs are bit-identical; the launches depend on B, heads and max_tokens only. */
+int ldn_packed_mha_bwd_long(const float* qkv, int ld_qkv, const int32_t* tok_rows, const int32_t* img_prefix, int B, int heads, int head_dim,
+                            int max_tokens, float scale, const float* head_keep, const float* d_out, int ldo, float* d_qkv, int ld_dqkv,
+                            float* ws, int ws_rows, void* stream);
 
 #ifdef __cplusplus
 }

@@ -16,9 +16,13 @@ list.  The modules are eval-only; no CPU fallback.
 TRAINING goes through block_train / train_forward below (forward + backward on the same packed lists, one autograd.Function per block): the
 forward runs the inference kernels and keeps each sub-block's input rows, the backward is ldn_packed_mha_bwd (attention), ldn_rows_ln_bwd (both
 LayerNorms), the transposed linears on ldn_conv_rows (gather in, scatter out) and the weight gradients on ldn_wgrad_rows.  A dropped token's
-gradient passes through untouched.  Not built (LdnError): more than 256 kept tokens per image, gradients of the keep masks, q / k / v of
-unattending tokens (qkv_kept_only = False), dropout / drop-path."""
+gradient passes through untouched.  Sequences of more than 256 tokens (384 px: 577) train behind USE_LONG_BWD (env LDN_MHA_BWD_LONG=1; default
+off): their attention backward is ldn_packed_mha_bwd_long, two launches over tiles of 256 queries / keys.  Not built (LdnError): more than 256
+kept tokens per image with the switch off, gradients of the keep masks, q / k / v of unattending tokens (qkv_kept_only = False), dropout /
+drop-path."""
 from __future__ import annotations
+
+import os
 
 import torch
 import torch.nn as nn
@@ -172,7 +176,10 @@ class TokenSkipViT(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------------------------ training
-BWD_MAX_TOKENS = 256      # kept tokens per image ldn_packed_mha_bwd takes
+BWD_MAX_TOKENS = 256      # kept tokens per image ldn_packed_mha_bwd (the one-launch kernel) takes
+# sequences beyond BWD_MAX_TOKENS on ldn_packed_mha_bwd_long (LDN_MHA_BWD_LONG=1).  Off by default: block_train refuses them as before; up to
+# BWD_MAX_TOKENS the one-launch kernel runs either way (the dispatch is by L, the floats do not change)
+USE_LONG_BWD = os.environ.get("LDN_MHA_BWD_LONG", "0") == "1"
 
 
 def _wgrad_T(dy, a2d, a_rows, count, cap, valid):
@@ -261,7 +268,8 @@ class _TokenSkipBlockFn(torch.autograd.Function):
         g_pb = torch.where(ka, gx, zero).sum(0)
         g_pw = _wgrad_T(att, gx, a_rows, a_count, rows, va).t()
         datt = _linear_T(gx, pw, D, a_rows=a_rows, count=a_count, cap=rows)                        # packed
-        dqkv = ops.packed_mha_bwd(qkv, a_rows, prefix, B, ctx.heads, Lt, datt, head_keep=ctx.hk)   # dense rows, zeros off the list
+        mha_bwd = ops.packed_mha_bwd if Lt <= BWD_MAX_TOKENS else ops.packed_mha_bwd_long      # block_train let Lt > 256 in with USE_LONG_BWD only
+        dqkv = mha_bwd(qkv, a_rows, prefix, B, ctx.heads, Lt, datt, head_keep=ctx.hk)              # dense rows, zeros off the list
         g_qb = dqkv.sum(0)
         dyln = _linear_T(dqkv, qw, D, a_rows=a_rows, count=a_count, cap=rows)                      # d L / d norm1(x0), packed
         g_n1w, g_n1b, xh = ops.rows_ln_bwd(x0, st1, n1w, dyln, gx, rows=a_rows, count=a_count, m_cap=rows, want_xhat=True)   # gx += : now d L / d x0
@@ -285,8 +293,9 @@ def block_train(block, x, keep, head_keep=None, attn_keep=None, mlp_keep=None):
     if x.dim() != 3 or x.shape[2] != block.dim or tuple(keep.shape) != tuple(x.shape[:2]):
         raise LdnError(f"block_train: x must be [B, L, {block.dim}] and keep [B, L], got {tuple(x.shape)} and {tuple(keep.shape)}")
     B, Lt, _ = x.shape
-    if Lt > BWD_MAX_TOKENS:
-        raise LdnError(f"block_train: the attention backward for more than {BWD_MAX_TOKENS} kept tokens per image is not built (L = {Lt})")
+    if Lt > BWD_MAX_TOKENS and not USE_LONG_BWD:
+        raise LdnError(f"block_train: the attention backward for more than {BWD_MAX_TOKENS} kept tokens per image is not built (L = {Lt}) unless "
+                       "adavit.USE_LONG_BWD is on (env LDN_MHA_BWD_LONG=1)")
     keep = keep.detach()
     lists = block.skip_lists(keep, attn_keep, mlp_keep)
     row_mask = lambda k: (k.reshape(B * Lt, 1) > 0.5)

@@ -1314,40 +1314,69 @@ def packed_mha(qkv2d, tok_rows, prefix, B, heads, max_tokens, scale=None, head_k
     return out
 
 
+def _packed_mha_bwd_args(name, qkv2d, tok_rows, prefix, B, heads, d_out, head_keep, out):
+    """The checks the two forms of the attention backward share -> (rows, three_dim, dim, head_dim, out)."""
+    if qkv2d.dim() != 2 or qkv2d.dtype != torch.float32 or qkv2d.stride(1) != 1:
+        raise L.LdnError(f"{name}: qkv must be fp32 [rows, 3 * heads * head_dim] with contiguous rows")
+    rows, three_dim = qkv2d.shape
+    dim = three_dim // 3
+    d = dim // max(int(heads), 1)
+    if heads <= 0 or three_dim != 3 * dim or dim != heads * d:
+        raise L.LdnError(f"{name}: qkv must be fp32 [rows, 3 * heads * head_dim]")
+    if d_out.dim() != 2 or d_out.shape[1] != dim or d_out.dtype != torch.float32 or d_out.stride(1) != 1:
+        raise L.LdnError(f"{name}: d_out must be fp32 [capacity, {dim}] with contiguous rows, got {d_out.dtype} {tuple(d_out.shape)}")
+    if prefix.numel() != B + 1:
+        raise L.LdnError(f"{name}: prefix must be [B + 1] = [{B + 1}], got {prefix.numel()} entries")
+    if d_out.shape[0] < tok_rows.numel():
+        raise L.LdnError(f"{name}: d_out has {d_out.shape[0]} rows, the token list {tok_rows.numel()} (the capacity of packed_mha's rows)")
+    if head_keep is not None and tuple(head_keep.shape) != (B, heads):
+        raise L.LdnError(f"{name}: head_keep must be [B, heads]")
+    if out is None:
+        out = torch.zeros(rows, three_dim, device=qkv2d.device, dtype=torch.float32)
+    elif tuple(out.shape) != (rows, three_dim):
+        raise L.LdnError(f"{name}: out must be [{rows}, {three_dim}], got {tuple(out.shape)}")
+    return rows, three_dim, dim, d, out
+
+
 def packed_mha_bwd(qkv2d, tok_rows, prefix, B, heads, max_tokens, d_out, scale=None, head_keep=None, out=None):
     """Backward of packed_mha for images with at most 256 kept tokens (see ldn_packed_mha_bwd).  qkv2d [B*L, 3*dim] and the lists as in the
     forward; d_out [capacity, dim]: the gradient of the forward's packed rows.  Returns d_qkv [B*L, 3*dim] in qkv2d's dense row layout: the
     gradient of kept token n is row tok_rows[n].  ONLY the rows of kept tokens are written (out: a buffer to write into; by default a zeroed
     one), a head dropped by head_keep [B, heads] gets exact zeros, an image without listed tokens is not touched.  max_tokens > 256 raises
-    LdnError: the tiled form has no backward.  Deterministic (no atomics)."""
+    LdnError: packed_mha_bwd_long is the tiled form.  Deterministic (no atomics)."""
     L.require_device(qkv2d, tok_rows, prefix, d_out, head_keep, out)
     lib = L.load()
-    if qkv2d.dim() != 2 or qkv2d.dtype != torch.float32 or qkv2d.stride(1) != 1:
-        raise L.LdnError("packed_mha_bwd: qkv must be fp32 [rows, 3 * heads * head_dim] with contiguous rows")
-    rows, three_dim = qkv2d.shape
-    dim = three_dim // 3
-    d = dim // max(int(heads), 1)
-    if heads <= 0 or three_dim != 3 * dim or dim != heads * d:
-        raise L.LdnError("packed_mha_bwd: qkv must be fp32 [rows, 3 * heads * head_dim]")
     if max_tokens > 256:
-        raise L.LdnError(f"packed_mha_bwd: more than 256 kept tokens per image are not built (max_tokens {max_tokens}): the tiled form of "
-                         "packed_mha has no backward")
-    if d_out.dim() != 2 or d_out.shape[1] != dim or d_out.dtype != torch.float32 or d_out.stride(1) != 1:
-        raise L.LdnError(f"packed_mha_bwd: d_out must be fp32 [capacity, {dim}] with contiguous rows, got {d_out.dtype} {tuple(d_out.shape)}")
-    if prefix.numel() != B + 1:
-        raise L.LdnError(f"packed_mha_bwd: prefix must be [B + 1] = [{B + 1}], got {prefix.numel()} entries")
-    if d_out.shape[0] < tok_rows.numel():
-        raise L.LdnError(f"packed_mha_bwd: d_out has {d_out.shape[0]} rows, the token list {tok_rows.numel()} (the capacity of packed_mha's rows)")
-    if head_keep is not None and tuple(head_keep.shape) != (B, heads):
-        raise L.LdnError("packed_mha_bwd: head_keep must be [B, heads]")
-    if out is None:
-        out = torch.zeros(rows, three_dim, device=qkv2d.device, dtype=torch.float32)
-    elif tuple(out.shape) != (rows, three_dim):
-        raise L.LdnError(f"packed_mha_bwd: out must be [{rows}, {three_dim}], got {tuple(out.shape)}")
+        raise L.LdnError(f"packed_mha_bwd: at most 256 kept tokens per image (max_tokens {max_tokens}): packed_mha_bwd_long is the tiled form")
+    rows, three_dim, dim, d, out = _packed_mha_bwd_args("packed_mha_bwd", qkv2d, tok_rows, prefix, B, heads, d_out, head_keep, out)
     L.check(lib.ldn_packed_mha_bwd(L.ptr(_f32rows(qkv2d, "qkv")), qkv2d.stride(0), L.ptr(_i32c(tok_rows, "tok_rows")), L.ptr(_i32c(prefix, "prefix")),
                                    B, heads, d, max_tokens, float(scale if scale is not None else d ** -0.5), L.ptr(_f32c(head_keep, "head_keep")),
                                    L.ptr(_f32rows(d_out, "d_out")), d_out.stride(0), L.ptr(_f32rows(out, "out")), out.stride(0),
                                    L.stream_ptr(out)), "ldn_packed_mha_bwd")
+    return out
+
+
+def packed_mha_bwd_long(qkv2d, tok_rows, prefix, B, heads, max_tokens, d_out, scale=None, head_keep=None, out=None, ws=None):
+    """Backward of packed_mha for any max_tokens >= 1 (see ldn_packed_mha_bwd_long): the contract and the checks of packed_mha_bwd, as two launches
+    (k_packed_mha_bwd_q: dq and the queries' softmax statistics per tile of 256 queries; k_packed_mha_bwd_kv: dk / dv per tile of 256 keys, summed
+    over the query tiles in ascending order).  An image with <= 256 kept tokens gets the floats of packed_mha_bwd, bit for bit.  ws: the fp32
+    workspace the statistics cross the launches in, at least 3 * heads * d_out.shape[0] elements (default: torch.empty; it needs no
+    initialisation and a smaller one raises LdnError).  Deterministic (no atomics)."""
+    L.require_device(qkv2d, tok_rows, prefix, d_out, head_keep, out, ws)
+    lib = L.load()
+    rows, three_dim, dim, d, out = _packed_mha_bwd_args("packed_mha_bwd_long", qkv2d, tok_rows, prefix, B, heads, d_out, head_keep, out)
+    if max_tokens < 1:
+        raise L.LdnError(f"packed_mha_bwd_long: max_tokens must be positive (got {max_tokens})")
+    cap = d_out.shape[0]
+    if ws is None:
+        ws = torch.empty(3 * heads * cap, device=qkv2d.device, dtype=torch.float32)
+    elif ws.dtype != torch.float32 or not ws.is_contiguous() or ws.numel() < 3 * heads * cap:
+        raise L.LdnError(f"packed_mha_bwd_long: ws must be a contiguous fp32 workspace of at least 3 * heads * {cap} = {3 * heads * cap} elements, "
+                         f"got {ws.dtype} with {ws.numel()}")
+    L.check(lib.ldn_packed_mha_bwd_long(L.ptr(_f32rows(qkv2d, "qkv")), qkv2d.stride(0), L.ptr(_i32c(tok_rows, "tok_rows")),
+                                        L.ptr(_i32c(prefix, "prefix")), B, heads, d, max_tokens, float(scale if scale is not None else d ** -0.5),
+                                        L.ptr(_f32c(head_keep, "head_keep")), L.ptr(_f32rows(d_out, "d_out")), d_out.stride(0),
+                                        L.ptr(_f32rows(out, "out")), out.stride(0), L.ptr(ws), cap, L.stream_ptr(out)), "ldn_packed_mha_bwd_long")
     return out
 
 

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""One forward + backward of a DeiT-S-shaped token-skipping trunk (12 x 384 / 6 heads, L 197) on the packed kernels
+"""One forward + backward of a DeiT-S-shaped token-skipping trunk (12 x 384 / 6 heads, L 197; --tokens 577 = the 384 px input) on the packed kernels
 (laudnet_amd.adavit.train_forward) beside oracle/adavit_ref.TokenSkipViTRef under PyTorch autograd in fp32 on the same GPU, at keep 0.5 and
 keep 1.0.  Same process, the two legs ALTERNATE step by step behind warm-up steps of each; the figure is the median of each leg's own
 device-event intervals.  One JSON line per keep ratio (profiles/train_step_adavit.jsonl).
-usage: tools/bench_train_adavit.py [--batch 64] [--steps 10] [--warmup 3] [--keeps 0.5,1.0] [--depth 12]"""
+Beyond 256 tokens the attention backward is ldn_packed_mha_bwd_long: the tool turns adavit.USE_LONG_BWD on for such a run.
+usage: tools/bench_train_adavit.py [--batch 64] [--steps 10] [--warmup 3] [--keeps 0.5,1.0] [--depth 12] [--tokens 197]"""
 import argparse
 import json
 import os
@@ -15,7 +16,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 import torch  # noqa: E402
 
 from fill import seeded_bernoulli, seeded_randn  # noqa: E402
-from laudnet_amd import ops, training  # noqa: E402
+from laudnet_amd import adavit, ops, training  # noqa: E402
 from laudnet_amd.adavit import TokenSkipViT, train_forward  # noqa: E402
 from oracle import adavit_ref as AR  # noqa: E402
 
@@ -25,9 +26,12 @@ ap.add_argument("--steps", type=int, default=10)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--keeps", default="0.5,1.0")
 ap.add_argument("--depth", type=int, default=12)
+ap.add_argument("--tokens", type=int, default=197, help="sequence length L (197: 224 px, 577: 384 px)")
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
-L, dim, heads = 197, 384, 6
+L, dim, heads = args.tokens, 384, 6
+if L > adavit.BWD_MAX_TOKENS:
+    adavit.USE_LONG_BWD = True
 ops.set_math_mode("bf16x3")
 ref = AR.TokenSkipViTRef(args.depth, dim, heads)
 gen = torch.Generator().manual_seed(1)
@@ -67,7 +71,7 @@ for keep_p in (float(k) for k in args.keeps.split(",")):
     med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
     print(json.dumps({"workload": f"token-skip trunk {args.depth} x {dim} / {heads} heads, L {L}", "batch": args.batch, "keep": keep_p,
                       "kept_tokens_mean": round(float(torch.stack(keeps).mean()), 4), "steps": args.steps, "warmup": args.warmup,
-                      "wgrad_kernel": training.USE_WGRAD_KERNEL, "what": "one forward + backward (d x and every parameter), median of device-event intervals, legs alternating",
+                      "wgrad_kernel": training.USE_WGRAD_KERNEL, "long_bwd": L > adavit.BWD_MAX_TOKENS, "what": "one forward + backward (d x and every parameter), median of device-event intervals, legs alternating",
                       "ms_per_step_median": {k: round(v, 3) for k, v in med.items()},
                       "ms_per_step_min_max": {k: [round(min(v), 3), round(max(v), 3)] for k, v in times.items()},
                       "speedup_vs_oracle": round(med["oracle_pytorch_fp32"] / med["hip_packed_kernels"], 3)}), flush=True)
