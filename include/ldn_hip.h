@@ -258,7 +258,8 @@ size_t ldn_wgrad_grouped_rows_workspace_bytes(int m_cap, int C, int gw);
 int ldn_wgrad_grouped_rows(const float* dy, int lddy, const float* a, int lda, int a_valid, const int32_t* nbr, const int32_t* m_count,
                            int m_cap, int C, int gw, float* dw, float* work, int math_mode, void* stream);
 
-/* ---- the ELEMENTWISE backward chain of training on packed rows (csrc/ldn_train_rows.hip).  Both are bandwidth-bound row kernels over
+/* ---- the ELEMENTWISE backward chain of training on packed rows (csrc/ldn_train_rows.hip): ldn_rows_chanmask, ldn_rows_act_bwd, ldn_rows_img_dot and
+ * ldn_rows_postmask_bwd.  All are bandwidth-bound row kernels over
  * [m_cap][ld >= C] fp32 matrices, C % 4 == 0, ld % 4 == 0, 16-byte aligned pointers, every access 16 bytes wide.
  *   count  = m_count ? clamp(*m_count, 0, m_cap) : m_cap, read on the device (no host read, no synchronisation)
  *   img(r) = the image b < B with row_prefix[b] <= r < row_prefix[b + 1] (row_prefix [B + 1] = the pre1 / pre3 output of
@@ -289,6 +290,34 @@ int ldn_rows_act_bwd(const float* dh, int lddh, const float* u, int ldu, const f
                      const float* chan_mask, const int32_t* row_prefix, int B, const float* zy, int ldzy, const int32_t* m_count,
                      int m_cap, int C, float* du, int lddu, float* g_shift, float* g_scale_num, float* g_mask, float* work,
                      void* stream);
+
+/* ldn_rows_img_dot: the per-image dot product of two packed-row matrices,
+ *   out[b][k] = sum_{r of image b, r < count} a[r][k] * b[r][k]        out [B][C], exactly 0 for an image without rows
+ * (the squeeze-excitation backward's d gate in front of the sigmoid).  a [m_cap][lda], b [m_cap][ldb]; rows r >= count are NOT READ.
+ * row_prefix [B + 1], B >= 1.  Deterministic like ldn_rows_act_bwd, whose split plan and per-image (split + b) slots it uses: partial sums
+ * go to `work` (ldn_rows_img_dot_workspace_bytes(m_cap, C, B); never NULL), a second small launch adds them in ascending order. */
+size_t ldn_rows_img_dot_workspace_bytes(int m_cap, int C, int B);
+int ldn_rows_img_dot(const float* a, int lda, const float* b, int ldb, const int32_t* row_prefix, int B, const int32_t* m_count, int m_cap,
+                     int C, float* out, float* work, void* stream);
+
+/* ldn_rows_postmask_bwd: the backward of  h = m[img] * relu(zy)  -- a channel mask applied AFTER conv + BN + ReLU (LAD-RegNet channel
+ * mode) -- on packed rows, given d L / d h (or, with the prologue, d L / d (gate . h)) and the stored UNMASKED r = relu(zy).
+ * Per element of a row r < count:
+ *   dh = gate ? dz * gate[img(r)][k] + dsq[img(r)][k] : dz      (the optional squeeze-excitation prologue, one fused multiply-add;
+ *                                                                gate and dsq are [B][C], both NULL or both given)
+ *   a  = r > 0 ? dh * m[img(r)][k] : 0                          (chan_mask m [B][C], NULL = all ones)
+ *   du = a * s[k]                                               du [m_cap][lddu] (may be dz itself), exactly 0 on rows >= count
+ *   g_shift[k]     = sum_r a
+ *   g_scale_num[k] = sum_r a * (r - t[k])                       (d L / d s = g_scale_num / s wherever s != 0, as ldn_rows_act_bwd states it)
+ *   g_mask[b][k]   = sum_{r of image b} dh * r                  [B][C], every channel, the masked ones included (the mask's straight-through
+ *                                                                term; there is no shift term in the post-activation form); NULL = not wanted
+ * Inputs: dz [m_cap][lddz], r [m_cap][ldr], scale s [C], shift t [C]; row_prefix [B + 1] is required with chan_mask, gate or g_mask.  Rows
+ * r >= count of dz / r are NOT READ.  Deterministic with the split plan, the workspace layout and the second launch of ldn_rows_act_bwd
+ * (ldn_rows_postmask_bwd_workspace_bytes(m_cap, C, B); B = 0 without g_mask; work is never NULL).  No floating-point atomics. */
+size_t ldn_rows_postmask_bwd_workspace_bytes(int m_cap, int C, int B);
+int ldn_rows_postmask_bwd(const float* dz, int lddz, const float* r, int ldr, const float* scale, const float* shift, const float* chan_mask,
+                          const int32_t* row_prefix, int B, const float* gate, const float* dsq, const int32_t* m_count, int m_cap, int C,
+                          float* du, int lddu, float* g_shift, float* g_scale_num, float* g_mask, float* work, void* stream);
 
 /* ldn_rows_ln_bwd: the LayerNorm backward on LISTED rows (a token-skip block's norm1 / norm2 in training).  For every list entry r < count
  * (count = clamp(*count, 0, m_cap), read on the device; list NULL: the rows 0 .. m_cap - 1 themselves), src = list[r]:

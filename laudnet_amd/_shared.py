@@ -65,6 +65,14 @@ def dense_index(B, Ho, Wo, stride, dev):
     return _INDEX_CACHE[key]
 
 
+def image_prefix(B, rows, dev):
+    """row_prefix [B + 1] int32 of B images that own `rows` consecutive packed rows each (the dense lists), cached per shape"""
+    key = ("prefix", B, rows, str(dev))
+    if key not in _INDEX_CACHE:
+        _INDEX_CACHE[key] = (torch.arange(B + 1, device=dev, dtype=torch.int32) * rows).contiguous()
+    return _INDEX_CACHE[key]
+
+
 def strided_rows(B, Hi, Wi, Ho, Wo, s, dev):
     """Source row of x (as [B * Hi * Wi, C]) of every output pixel of a stride-s 1x1 convolution (projection shortcuts), cached per shape."""
     key = ("rows", B, Hi, Wi, Ho, Wo, s, str(dev))

@@ -1,7 +1,7 @@
-// ldn_train_rows.hip -- the elementwise backward chain of training on packed rows (ldn_rows_chanmask, ldn_rows_act_bwd; include/ldn_hip.h), and the
-// LayerNorm backward on listed rows (ldn_rows_ln_bwd, further down with its own notes).
+// ldn_train_rows.hip -- the elementwise backward chain of training on packed rows (ldn_rows_chanmask, ldn_rows_act_bwd, ldn_rows_postmask_bwd,
+// ldn_rows_img_dot; include/ldn_hip.h), and the LayerNorm backward on listed rows (ldn_rows_ln_bwd, further down with its own notes).
 //
-// The first two are bandwidth-bound row kernels over [m_cap, C] fp32 matrices with a leading dimension: C % 4 == 0, every access 16 bytes wide, a wave
+// The first four are bandwidth-bound row kernels over [m_cap, C] fp32 matrices with a leading dimension: C % 4 == 0, every access 16 bytes wide, a wave
 // reads consecutive quads of a row.  The count is read on the device; rows r >= count are never read and are written as exact zeros.
 //
 // The image of a packed row comes from the per-image row prefix ([B + 1]: image b owns rows [prefix[b], prefix[b + 1])) inside the kernel --
@@ -25,6 +25,17 @@
 // every image b that owns rows of the split to the slot split + b: an image's rows may straddle splits, and because images and splits both
 // ascend along the rows, (split, b) -> split + b is one-to-one over the pairs that meet (splits + B slots instead of splits * B).
 // k_act_reduce adds the partials in ascending split order.  No floating-point atomics.
+//
+// ldn_rows_postmask_bwd is the same walk for a mask applied AFTER the ReLU (LAD-RegNet: h = m * relu(zy), the UNMASKED r = relu(zy) stored), with
+// an optional squeeze-excitation prologue on the incoming gradient; per element of a row r < count of image b:
+//     dh = gate ? fma(dz, gate[b, k], dsq[b, k]) : dz          (one rounding)
+//     a  = r > 0 ? dh * m[b, k] : 0
+//     du = a * s[k]
+//     g_shift[k]     += a
+//     g_scale_num[k] += a * (r - t[k])
+//     g_mask[b, k]   += dh * r              (every channel: non-zero exactly where the activation is on, masked channels included)
+// ldn_rows_img_dot is its per-image reduction alone: out[b, k] = sum over the rows of image b of a[r, k] * b[r, k].  Both use act_plan and the
+// (split + b) slots of ldn_rows_act_bwd.
 #include "ldn_common.h"
 
 namespace ldn {
@@ -162,6 +173,18 @@ __global__ __launch_bounds__(ACT_THREADS) void k_rows_act_bwd(const ActArgs p) {
     }
 }
 
+// the sum of image b's (split + b) slots in ascending split order (zero for an image without rows below the count)
+__device__ __forceinline__ f32x4 image_slots_sum(const float* slots, const int32_t* prefix, int B, int b, int count, int splits, int rps, int C, int k) {
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    const int lo = min(prefix[b], count), hi = b == B - 1 ? count : min(prefix[b + 1], count);     // (the walk of k_rows_act_bwd)
+    if (lo < hi) {
+        // image b meets the splits lo / rps .. (hi - 1) / rps -- unless an earlier image reaches past prefix[b] (never with a monotone prefix)
+        const int t_hi = min(splits - 1, (hi - 1) / rps);
+        for (int t = lo / rps; t <= t_hi; ++t) s += *reinterpret_cast<const f32x4*>(slots + (size_t)(t + b) * C + k);
+    }
+    return s;
+}
+
 // one thread per quad of g_shift (j == 0), g_scale_num (j == 1) and g_mask[b] (j == 2 + b): the partials in ascending split order
 __global__ __launch_bounds__(256) void k_act_reduce(const ActArgs p, int nvec) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -178,13 +201,175 @@ __global__ __launch_bounds__(256) void k_act_reduce(const ActArgs p, int nvec) {
         return;
     }
     const int b = j - 2;
-    const int lo = min(p.prefix[b], count), hi = b == p.B - 1 ? count : min(p.prefix[b + 1], count);     // (the walk of k_rows_act_bwd)
-    if (lo < hi) {
-        // image b meets the splits lo / rps .. (hi - 1) / rps -- unless an earlier image reaches past prefix[b] (never with a monotone prefix)
-        const int t_hi = min(p.splits - 1, (hi - 1) / p.rps);
-        for (int t = lo / p.rps; t <= t_hi; ++t) s += *reinterpret_cast<const f32x4*>(act_work_mask(p) + (size_t)(t + b) * p.C + k);
+    *reinterpret_cast<f32x4*>(p.g_mask + (size_t)b * p.C + k) = image_slots_sum(act_work_mask(p), p.prefix, p.B, b, count, p.splits, p.rps, p.C, k);
+}
+
+struct PmArgs {
+    const float* dz; const float* r; const float* scale; const float* shift; const float* chan_mask; const int32_t* prefix;
+    const float* gate; const float* dsq; const int32_t* m_count;
+    float* du; float* g_shift; float* g_scale; float* g_mask; float* work;
+    int lddz, ldr, lddu, B, m_cap, C, splits, rps;
+};
+
+// work layout of ldn_rows_postmask_bwd: that of ldn_rows_act_bwd
+__device__ __forceinline__ float* pm_work_shift(const PmArgs& p) { return p.work; }
+__device__ __forceinline__ float* pm_work_scale(const PmArgs& p) { return p.work + (size_t)p.splits * p.C; }
+__device__ __forceinline__ float* pm_work_mask(const PmArgs& p) { return p.work + (size_t)2 * p.splits * p.C; }
+
+// grid, threads and row walk of k_rows_act_bwd
+__global__ __launch_bounds__(ACT_THREADS) void k_rows_postmask_bwd(const PmArgs p) {
+    __shared__ f32x4 s_red[ACT_THREADS];
+    const int Q = p.C >> 2;
+    const int QT = Q < ACT_QT ? Q : ACT_QT;
+    const int RL = ACT_THREADS / QT;
+    const int tid = threadIdx.x, rl = tid / QT, ql = tid - rl * QT;
+    const int q = blockIdx.x * ACT_QT + ql;
+    const bool active = rl < RL && q < Q;
+    const int split = blockIdx.y;
+    const int count = rows_count(p.m_count, p.m_cap);
+    const int r_begin = split * p.rps;
+    const int r_cap_end = min(p.m_cap, r_begin + p.rps);
+    const int r_end = min(count, r_cap_end);
+    const int k = 4 * q;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+
+    // rows past the count: exact zeros, nothing read
+    if (active)
+        for (int r = max(r_end, r_begin) + rl; r < r_cap_end; r += RL) store16(p.du + (size_t)r * p.lddu + k, zero);
+    if (r_begin >= r_end) return;          // (uniform) no rows: k_postmask_reduce does not read this split's partials
+
+    auto lane_sum = [&](f32x4 v) {         // lane-order sum over the row lanes; the result is valid in row lane 0
+        s_red[tid] = v;
+        __syncthreads();
+        f32x4 s = zero;
+        if (rl == 0)
+            for (int j = 0; j < RL; ++j) s += s_red[j * QT + ql];
+        __syncthreads();
+        return s;
+    };
+
+    f32x4 sc = zero, sh = zero;
+    if (active) {
+        sc = *reinterpret_cast<const f32x4*>(p.scale + k);
+        sh = *reinterpret_cast<const f32x4*>(p.shift + k);
     }
-    *reinterpret_cast<f32x4*>(p.g_mask + (size_t)b * p.C + k) = s;
+    const bool per_image = p.B > 0;        // chan_mask, the SE prologue or g_mask
+    int b = per_image ? image_of_row(p.prefix, p.B, r_begin) : 0;
+    f32x4 g_sh = zero, g_sc = zero;
+    int r0 = r_begin;
+    while (r0 < r_end) {                   // (uniform) one segment per image that owns rows of this split
+        int seg_end = r_end;
+        if (per_image && b < p.B - 1) seg_end = min(r_end, max(p.prefix[b + 1], r0));
+        if (seg_end > r0) {
+            f32x4 m = {1.f, 1.f, 1.f, 1.f}, ga = zero, dq = zero, g_m = zero;
+            if (active && p.chan_mask) m = *reinterpret_cast<const f32x4*>(p.chan_mask + (size_t)b * p.C + k);
+            if (active && p.gate) {
+                ga = *reinterpret_cast<const f32x4*>(p.gate + (size_t)b * p.C + k);
+                dq = *reinterpret_cast<const f32x4*>(p.dsq + (size_t)b * p.C + k);
+            }
+            if (active)
+                for (int r = r0 + rl; r < seg_end; r += RL) {
+                    const f32x4 dz = *reinterpret_cast<const f32x4*>(p.dz + (size_t)r * p.lddz + k);
+                    const f32x4 rv = *reinterpret_cast<const f32x4*>(p.r + (size_t)r * p.ldr + k);
+                    f32x4 du;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const float dh = p.gate ? fmaf(dz[i], ga[i], dq[i]) : dz[i];
+                        const float a = rv[i] > 0.f ? dh * m[i] : 0.f;
+                        du[i] = a * sc[i];
+                        g_sh[i] += a;
+                        g_sc[i] += a * (rv[i] - sh[i]);
+                        g_m[i] += dh * rv[i];
+                    }
+                    store16(p.du + (size_t)r * p.lddu + k, du);
+                }
+            if (p.g_mask) {
+                const f32x4 s = lane_sum(g_m);
+                if (active && rl == 0) *reinterpret_cast<f32x4*>(pm_work_mask(p) + (size_t)(split + b) * p.C + k) = s;
+            }
+        }
+        r0 = seg_end;
+        ++b;
+    }
+    const f32x4 s1 = lane_sum(g_sh), s2 = lane_sum(g_sc);
+    if (active && rl == 0) {
+        *reinterpret_cast<f32x4*>(pm_work_shift(p) + (size_t)split * p.C + k) = s1;
+        *reinterpret_cast<f32x4*>(pm_work_scale(p) + (size_t)split * p.C + k) = s2;
+    }
+}
+
+// k_act_reduce for PmArgs
+__global__ __launch_bounds__(256) void k_postmask_reduce(const PmArgs p, int nvec) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int Q = p.C >> 2;
+    if (i >= nvec * Q) return;
+    const int j = i / Q, k = 4 * (i - j * Q);
+    const int count = rows_count(p.m_count, p.m_cap);
+    if (j < 2) {
+        f32x4 s = {0.f, 0.f, 0.f, 0.f};
+        const int live = min(p.splits, ceil_div(count, p.rps));
+        const float* w = j == 0 ? pm_work_shift(p) : pm_work_scale(p);
+        for (int t = 0; t < live; ++t) s += *reinterpret_cast<const f32x4*>(w + (size_t)t * p.C + k);
+        *reinterpret_cast<f32x4*>((j == 0 ? p.g_shift : p.g_scale) + k) = s;
+        return;
+    }
+    const int b = j - 2;
+    *reinterpret_cast<f32x4*>(p.g_mask + (size_t)b * p.C + k) = image_slots_sum(pm_work_mask(p), p.prefix, p.B, b, count, p.splits, p.rps, p.C, k);
+}
+
+struct DotArgs {
+    const float* a; const float* b; const int32_t* prefix; const int32_t* m_count; float* out; float* work;
+    int lda, ldb, B, m_cap, C, splits, rps;
+};
+
+// out[b, k] partials = sum over the rows of image b in this split of a * b: the walk of k_rows_act_bwd with its g_mask alone; work = [splits + B][C]
+__global__ __launch_bounds__(ACT_THREADS) void k_rows_img_dot(const DotArgs p) {
+    __shared__ f32x4 s_red[ACT_THREADS];
+    const int Q = p.C >> 2;
+    const int QT = Q < ACT_QT ? Q : ACT_QT;
+    const int RL = ACT_THREADS / QT;
+    const int tid = threadIdx.x, rl = tid / QT, ql = tid - rl * QT;
+    const int q = blockIdx.x * ACT_QT + ql;
+    const bool active = rl < RL && q < Q;
+    const int split = blockIdx.y;
+    const int count = rows_count(p.m_count, p.m_cap);
+    const int r_begin = split * p.rps;
+    const int r_end = min(count, min(p.m_cap, r_begin + p.rps));
+    const int k = 4 * q;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    if (r_begin >= r_end) return;          // (uniform) no rows: k_img_dot_reduce does not read this split's slots
+    int b = image_of_row(p.prefix, p.B, r_begin);
+    int r0 = r_begin;
+    while (r0 < r_end) {                   // (uniform) one segment per image that owns rows of this split
+        int seg_end = r_end;
+        if (b < p.B - 1) seg_end = min(r_end, max(p.prefix[b + 1], r0));
+        if (seg_end > r0) {
+            f32x4 acc = zero;
+            if (active)
+                for (int r = r0 + rl; r < seg_end; r += RL)
+                    acc += *reinterpret_cast<const f32x4*>(p.a + (size_t)r * p.lda + k) * *reinterpret_cast<const f32x4*>(p.b + (size_t)r * p.ldb + k);
+            s_red[tid] = acc;              // lane-order sum over the row lanes
+            __syncthreads();
+            if (active && rl == 0) {
+                f32x4 s = zero;
+                for (int j = 0; j < RL; ++j) s += s_red[j * QT + ql];
+                *reinterpret_cast<f32x4*>(p.work + (size_t)(split + b) * p.C + k) = s;
+            }
+            __syncthreads();
+        }
+        r0 = seg_end;
+        ++b;
+    }
+}
+
+// one thread per quad of out[b]
+__global__ __launch_bounds__(256) void k_img_dot_reduce(const DotArgs p) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int Q = p.C >> 2;
+    if (i >= p.B * Q) return;
+    const int b = i / Q, k = 4 * (i - b * Q);
+    *reinterpret_cast<f32x4*>(p.out + (size_t)b * p.C + k) =
+        image_slots_sum(p.work, p.prefix, p.B, b, rows_count(p.m_count, p.m_cap), p.splits, p.rps, p.C, k);
 }
 
 // the launch plan: a function of m_cap and C ONLY
@@ -370,6 +555,67 @@ extern "C" int ldn_rows_act_bwd(const float* dh, int lddh, const float* u, int l
     const int nvec = 2 + (zy ? B : 0);
     k_act_reduce<<<ceil_div(nvec * (C / 4), 256), 256, 0, st>>>(p, nvec);
     LDN_CHECK_LAUNCH("k_act_reduce");
+    return LDN_OK;
+}
+
+extern "C" size_t ldn_rows_postmask_bwd_workspace_bytes(int m_cap, int C, int B) { return ldn_rows_act_bwd_workspace_bytes(m_cap, C, B); }
+
+extern "C" int ldn_rows_postmask_bwd(const float* dz, int lddz, const float* r, int ldr, const float* scale, const float* shift,
+                                     const float* chan_mask, const int32_t* row_prefix, int B, const float* gate, const float* dsq,
+                                     const int32_t* m_count, int m_cap, int C, float* du, int lddu, float* g_shift, float* g_scale_num,
+                                     float* g_mask, float* work, void* stream) {
+    LDN_REQUIRE(dz && r && scale && shift && du && g_shift && g_scale_num && work, "ldn_rows_postmask_bwd: null pointer");
+    LDN_REQUIRE(m_cap >= 0 && C > 0 && C % 4 == 0, "ldn_rows_postmask_bwd: m_cap >= 0, C %% 4 == 0 (got %d, %d)", m_cap, C);
+    LDN_REQUIRE(lddz >= C && ldr >= C && lddu >= C && lddz % 4 == 0 && ldr % 4 == 0 && lddu % 4 == 0,
+                "ldn_rows_postmask_bwd: leading dimensions >= C and multiples of 4 (got %d, %d, %d)", lddz, ldr, lddu);
+    LDN_REQUIRE((gate != nullptr) == (dsq != nullptr), "ldn_rows_postmask_bwd: gate and dsq [B][C] are the SE prologue: give both or neither");
+    const bool per_image = chan_mask || gate || g_mask;
+    LDN_REQUIRE(!per_image || (row_prefix && B >= 1), "ldn_rows_postmask_bwd: chan_mask / gate / g_mask need row_prefix [B + 1] and B >= 1");
+    LDN_REQUIRE(aligned16(dz) && aligned16(r) && aligned16(scale) && aligned16(shift) && aligned16(chan_mask) && aligned16(gate) && aligned16(dsq) &&
+                aligned16(du) && aligned16(g_shift) && aligned16(g_scale_num) && aligned16(g_mask) && aligned16(work),
+                "ldn_rows_postmask_bwd: every float pointer must be 16-byte aligned");
+    PmArgs p;
+    p.dz = dz; p.r = r; p.scale = scale; p.shift = shift; p.chan_mask = chan_mask; p.prefix = row_prefix; p.gate = gate; p.dsq = dsq;
+    p.m_count = m_count; p.du = du; p.g_shift = g_shift; p.g_scale = g_scale_num; p.g_mask = g_mask; p.work = work;
+    p.lddz = lddz; p.ldr = ldr; p.lddu = lddu; p.B = per_image ? B : 0; p.m_cap = m_cap; p.C = C;
+    int tiles;
+    act_plan(m_cap, C, &tiles, &p.splits, &p.rps);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (m_cap > 0) {
+        k_rows_postmask_bwd<<<dim3((unsigned)tiles, (unsigned)p.splits), ACT_THREADS, 0, st>>>(p);
+        LDN_CHECK_LAUNCH("k_rows_postmask_bwd");
+    }
+    const int nvec = 2 + (g_mask ? B : 0);
+    k_postmask_reduce<<<ceil_div(nvec * (C / 4), 256), 256, 0, st>>>(p, nvec);
+    LDN_CHECK_LAUNCH("k_postmask_reduce");
+    return LDN_OK;
+}
+
+extern "C" size_t ldn_rows_img_dot_workspace_bytes(int m_cap, int C, int B) {
+    if (m_cap < 0 || C <= 0 || C % 4 || B < 1) return 0;
+    int tiles, splits, rps;
+    act_plan(m_cap, C, &tiles, &splits, &rps);
+    return ((size_t)splits + B) * C * sizeof(float);
+}
+
+extern "C" int ldn_rows_img_dot(const float* a, int lda, const float* b, int ldb, const int32_t* row_prefix, int B, const int32_t* m_count,
+                                int m_cap, int C, float* out, float* work, void* stream) {
+    LDN_REQUIRE(a && b && row_prefix && out && work, "ldn_rows_img_dot: null pointer");
+    LDN_REQUIRE(B >= 1 && m_cap >= 0 && C > 0 && C % 4 == 0, "ldn_rows_img_dot: B >= 1, m_cap >= 0, C %% 4 == 0 (got %d, %d, %d)", B, m_cap, C);
+    LDN_REQUIRE(lda >= C && ldb >= C && lda % 4 == 0 && ldb % 4 == 0, "ldn_rows_img_dot: leading dimensions >= C and multiples of 4 (got %d, %d)", lda, ldb);
+    LDN_REQUIRE(aligned16(a) && aligned16(b) && aligned16(out) && aligned16(work), "ldn_rows_img_dot: every float pointer must be 16-byte aligned");
+    DotArgs p;
+    p.a = a; p.b = b; p.prefix = row_prefix; p.m_count = m_count; p.out = out; p.work = work;
+    p.lda = lda; p.ldb = ldb; p.B = B; p.m_cap = m_cap; p.C = C;
+    int tiles;
+    act_plan(m_cap, C, &tiles, &p.splits, &p.rps);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (m_cap > 0) {
+        k_rows_img_dot<<<dim3((unsigned)tiles, (unsigned)p.splits), ACT_THREADS, 0, st>>>(p);
+        LDN_CHECK_LAUNCH("k_rows_img_dot");
+    }
+    k_img_dot_reduce<<<ceil_div(B * (C / 4), 256), 256, 0, st>>>(p);
+    LDN_CHECK_LAUNCH("k_img_dot_reduce");
     return LDN_OK;
 }
 

@@ -656,6 +656,68 @@ def rows_act_bwd(dh2d, u2d, scale, shift, *, post_sub=None, chan_mask=None, row_
     return out[:m_cap, :C] if tuple(out.shape) != (m_cap, C) else out, g_shift, g_scale, g_mask
 
 
+def rows_img_dot(a2d, b2d, row_prefix, m_count=None, m_cap=None):
+    """Per-image dot product of two packed-row matrices (see ldn_rows_img_dot): out[b, k] = sum over the rows r < count of image b of
+    a2d[r, k] * b2d[r, k] -> [B, C], exactly 0 for an image without rows.  a2d / b2d [rows, ld >= C] with C columns each; row_prefix [B + 1]
+    int32 (IndexSet.pre1 / pre3).  Rows past the device-side count are not read.  Deterministic: no atomics, the split plan of rows_act_bwd."""
+    L.require_device(a2d, b2d, row_prefix, m_count)
+    lib = L.load()
+    if a2d.dim() != 2 or b2d.dim() != 2 or a2d.shape[1] != b2d.shape[1] or a2d.shape[1] % 4:
+        raise L.LdnError(f"rows_img_dot: a2d / b2d must be [rows, C] with the same C % 4 == 0, got {tuple(a2d.shape)} and {tuple(b2d.shape)}")
+    if row_prefix is None or row_prefix.numel() < 2:
+        raise L.LdnError("rows_img_dot: row_prefix must be [B + 1], B >= 1")
+    B, C = row_prefix.numel() - 1, a2d.shape[1]
+    m_cap = _rows_cap(m_cap, "rows_img_dot", a2d, b2d)
+    out = torch.empty(B, C, device=a2d.device, dtype=torch.float32)
+    work = _work(lib.ldn_rows_img_dot_workspace_bytes(m_cap, C, B), a2d.device)
+    L.check(lib.ldn_rows_img_dot(L.ptr(_f32rows(a2d, "a")), a2d.stride(0), L.ptr(_f32rows(b2d, "b")), b2d.stride(0),
+                                 L.ptr(_i32c(row_prefix, "row_prefix")), B, L.ptr(_i32c(m_count, "m_count")), m_cap, C, L.ptr(out), L.ptr(work),
+                                 L.stream_ptr(out)), "ldn_rows_img_dot")
+    return out
+
+
+def rows_postmask_bwd(dz2d, r2d, scale, shift, *, chan_mask=None, row_prefix=None, gate=None, dsq=None, want_mask=False, m_count=None,
+                      m_cap=None, out=None):
+    """Backward of h = m * relu(zy) -- a channel mask applied AFTER the ReLU -- on packed rows (see ldn_rows_postmask_bwd), given dz2d and the
+    stored UNMASKED r2d = relu(zy): dh = dz * gate[img(r)] + dsq[img(r)] with the squeeze-excitation prologue (gate, dsq [B, C]: both or neither),
+    else dz; a = dh * m[img(r)] where r > 0; du = a * s.  -> (du [m_cap, C], g_shift [C] = sum a, g_scale_num [C] = sum a * (r - t) -- the caller
+    divides by s --, g_mask [B, C] = sum over the image's rows of dh * r with want_mask, else None).  chan_mask [B, C] (None = ones), the
+    prologue and want_mask need row_prefix [B + 1] (IndexSet.pre1 / pre3).  Rows past the device-side count are not read; du is exactly 0
+    there.  out: a [m_cap, >= C] matrix for du (dz2d itself is allowed).  Deterministic: no atomics, the split plan of rows_act_bwd."""
+    L.require_device(dz2d, r2d, scale, shift, chan_mask, row_prefix, gate, dsq, m_count, out)
+    lib = L.load()
+    C = scale.numel()
+    for name, t in (("dz", dz2d), ("r", r2d), ("out", out)):
+        if t is not None and (t.dim() != 2 or t.shape[1] < C):
+            raise L.LdnError(f"rows_postmask_bwd: {name} must be [rows, >= {C}], got {tuple(t.shape)}")
+    if C % 4 or shift.numel() != C:
+        raise L.LdnError("rows_postmask_bwd: scale / shift must be [C] with C % 4 == 0")
+    if (gate is None) != (dsq is None):
+        raise L.LdnError("rows_postmask_bwd: gate and dsq are the SE prologue: give both or neither")
+    B = 0
+    if chan_mask is not None or gate is not None or want_mask:
+        if row_prefix is None or row_prefix.numel() < 2:
+            raise L.LdnError("rows_postmask_bwd: chan_mask / gate / want_mask need row_prefix [B + 1]")
+        B = row_prefix.numel() - 1
+        for name, t in (("chan_mask", chan_mask), ("gate", gate), ("dsq", dsq)):
+            if t is not None and tuple(t.shape) != (B, C):
+                raise L.LdnError(f"rows_postmask_bwd: {name} must be [{B}, {C}], got {tuple(t.shape)}")
+    m_cap = _rows_cap(m_cap, "rows_postmask_bwd", dz2d, r2d, out)
+    dev = dz2d.device
+    if out is None:
+        out = torch.empty(m_cap, C, device=dev, dtype=torch.float32)
+    g_shift = torch.empty(C, device=dev, dtype=torch.float32)
+    g_scale = torch.empty(C, device=dev, dtype=torch.float32)
+    g_mask = torch.empty(B, C, device=dev, dtype=torch.float32) if want_mask else None
+    work = _work(lib.ldn_rows_postmask_bwd_workspace_bytes(m_cap, C, B if want_mask else 0), dev)
+    L.check(lib.ldn_rows_postmask_bwd(L.ptr(_f32rows(dz2d, "dz")), dz2d.stride(0), L.ptr(_f32rows(r2d, "r")), r2d.stride(0),
+                                      L.ptr(_f32c(scale, "scale")), L.ptr(_f32c(shift, "shift")), L.ptr(_f32c(chan_mask, "chan_mask")),
+                                      L.ptr(_i32c(row_prefix, "row_prefix")), B, L.ptr(_f32c(gate, "gate")), L.ptr(_f32c(dsq, "dsq")),
+                                      L.ptr(_i32c(m_count, "m_count")), m_cap, C, L.ptr(_f32rows(out, "out")), out.stride(0), L.ptr(g_shift),
+                                      L.ptr(g_scale), L.ptr(g_mask), L.ptr(work), L.stream_ptr(out)), "ldn_rows_postmask_bwd")
+    return out[:m_cap, :C] if tuple(out.shape) != (m_cap, C) else out, g_shift, g_scale, g_mask
+
+
 USE_ROWS_PS = os.environ.get("LDN_ROWS_PS", "1") != "0"     # the pre-split packed path (k_dense<PS / OF> + k_rows3); 0 = round 4's three launches
 
 

@@ -49,7 +49,15 @@ LAD-RegNet (`laud_regnet.ResBottleneckBlock`) trains in its LAYER-SKIP form -- d
 the squeeze / excite and their backward tensor ops on the [slots, Ho Wo, C] view of the rows); the same three entry points take it and a whole
 `LAD_RegNet` (tests/test_hip_training_regnet.py).
 
-Not built: mask groups > 1, dilated conv2, grouped conv2 outside that block, BatchNorm in batch-statistics mode, LAD-RegNet 'channel' / 'both' /
+LAD-RegNet dyn_mode 'channel' -- the one LAD-RegNet recipe the reference trains (train_scripts.sh:29-40) -- trains behind USE_REGNET_CHANNEL (env
+LDN_TRAIN_REGNET_CHANNEL=1; default OFF: with it off a channel block is refused as before).  The mask multiplies the outputs of a and b AFTER
+conv + BN + ReLU (laud_regnet.py:182-189), so none of the LAUD-ResNet channel algebra applies: `_RegNetChannelBranchFn` runs the row kernels over all
+pixels, DENSE in the channels -- the mask saves no FLOPs in training, for the same reason as above: the straight-through term sum_p d h . relu(zy) needs
+relu(zy) and the upstream gradient at the masked channels too -- and its backward's elementwise chain with all its reductions is `ops.rows_postmask_bwd`
+(SE prologue, mask, ReLU gate, scale; d shift, d scale, d mask: two launches per layer, deterministic) plus `ops.rows_img_dot` (the SE's d gate)
+(tests/test_hip_rows_postmask.py, tests/test_regnet_channel_ref.py, tests/test_hip_training_regnet_channel.py).
+
+Not built: mask groups > 1, dilated conv2, grouped conv2 outside the LAD-RegNet blocks, BatchNorm in batch-statistics mode, LAD-RegNet 'both' /
 patch-mask (mask_size > 1) training."""
 from __future__ import annotations
 
@@ -62,13 +70,17 @@ import torch.nn.functional as F
 
 from . import ops
 from ._lib import LdnError
-from ._shared import channel_constants, dense_channel_convs, dense_index
+from ._shared import channel_constants, dense_channel_convs, dense_index, image_prefix
 from .laud_regnet import LAD_RegNet, ResBottleneckBlock, _conv_b_rows
 
 # weight gradients on ldn_wgrad_rows / ldn_wgrad_grouped_rows; LDN_WGRAD=0 = the gather + PyTorch GEMM / bmm path.  On by default: the median step is shorter with the kernel for
 # all three full-width workloads at batch 32 and 128 (profiles/train_step_wgrad.jsonl), and for LAD-RegNetY-800MF layer skip with the grouped
 # kernel (profiles/train_step_regnet.jsonl)
 USE_WGRAD_KERNEL = os.environ.get("LDN_WGRAD", "1") != "0"
+
+# LAD-RegNet channel-mode training (_RegNetChannelBranchFn); env LDN_TRAIN_REGNET_CHANNEL=1 turns it on.  Off by default: with it off every
+# LAD-RegNet form but layer skip is refused, as before the path existed
+USE_REGNET_CHANNEL = os.environ.get("LDN_TRAIN_REGNET_CHANNEL", "0") == "1"
 
 
 # ------------------------------------------------------------------------------------------------------------------ index helpers
@@ -607,6 +619,94 @@ class _RegNetSkipBranchFn(torch.autograd.Function):
         return grad_x, gwa, gwb, gwc, gm, gsa, gta, gsb, gtb, gsc, gtc, gw1s, gb1s, gw2s, gb2s, None, None, None
 
 
+# ------------------------------------------------------------------------------------------------------------------ LAD-RegNet, channel masks
+class _RegNetChannelBranchFn(torch.autograd.Function):
+    """branch = sc * c(gate . h_b) + tc,  h_a = m . relu(sa * a(x) + ta),  h_b = m . relu(sb * b(h_a) + tb),  gate = sigmoid(fc2(relu(fc1(mean_pixels h_b))))
+    (laud_regnet.py:182-200, dyn_mode 'channel'): the {0,1} channel mask m [B, W] multiplies the outputs of a and b AFTER conv + BN + ReLU, so
+    none of the LAUD-ResNet channel algebra applies (no constants, no border classes).  The row kernels run over ALL pixels (ix = the cached
+    dense_index) and DENSE in the channels -- the mask saves no FLOPs in training: its straight-through term sum_p d h . relu(zy) needs relu(zy)
+    and the upstream gradient at the masked channels too.  a and c on conv_rows, the grouped 3x3 b on ldn_grouped_conv3x3_rows (adjoint and weight
+    gradient as in _RegNetSkipBranchFn), the masking ops.rows_chanmask; the backward's elementwise chain with all its reductions is one
+    ops.rows_postmask_bwd per layer (layer b's with the squeeze-excitation prologue), d gate ops.rows_img_dot; the excite MLP stays on [B, .]
+    tensors.  The UNMASKED relu outputs are kept only when the mask requires grad: a masked unit has a = 0 either way.  Differentiable in x,
+    the three weights, the six folded BatchNorm vectors, the four SE tensors and the channel mask."""
+
+    @staticmethod
+    def forward(ctx, x, wa, wb, wc, chm, sa, ta, sb, tb, sc, tc, w1, b1, w2, b2, stride, f, ix):
+        p = _prep(x, wa, wb, wc, (sa, ta, sb, tb, sc, tc), stride)
+        B, _, Hi, Wi, Ho, Wo, W, cout = p.shape
+        sa, ta, sb, tb, sc, tc = p.bn
+        dev, P = x.device, Ho * Wo
+        se = (w1.detach().float().reshape(-1, W).contiguous(), b1.detach().float().contiguous(),
+              w2.detach().float().reshape(W, -1).contiguous(), b2.detach().float().contiguous())
+        m2d = chm.detach().float().reshape(B, W).contiguous()
+        keep_r = ctx.needs_input_grad[4]
+        pre1, pre3 = image_prefix(B, Hi * Wi, dev), image_prefix(B, P, dev)
+        r_a = torch.empty(ix.cap1, W, device=dev)
+        ops.conv_rows(p.x2d, p.w1r, sa, ta, r_a, a_rows=ix.idx1, taps=1, m_cap=ix.cap1)
+        h_a = ops.rows_chanmask(r_a.clone() if keep_r else r_a, pre1, m2d, m_cap=ix.cap1)
+        r_b = torch.empty(ix.cap3, W, device=dev)
+        _conv_b_rows(_conv_b_params(p.w2r, sb, tb, f.group_width), f, h_a, ix.nbr, r_b, ix.cnt[0:1], ix.cap3)
+        h_b = ops.rows_chanmask(r_b.clone() if keep_r else r_b, pre3, m2d, m_cap=ix.cap3)
+        hbv = h_b.view(B, P, W)
+        sq = hbv.mean(1)
+        u, gate = _se_gate(sq, *se)
+        br = torch.empty(ix.cap3, cout, device=dev)
+        ops.conv_rows((hbv * gate.unsqueeze(1)).view(ix.cap3, W), p.w3s, None, tc, br, taps=1, m_cap=ix.cap3, relu=0)
+        # r_a / r_b: the unmasked ReLU outputs where the mask wants its gradient, else the masked copies themselves (h_b is r_b . m: not saved)
+        ctx.save_for_backward(p.x2d, r_a, h_a, r_b, sq, u, gate, br, p.w1r, p.w2r, p.w3r, *p.bn, *se, m2d)
+        ctx.ix, ctx.shape, ctx.stride, ctx.f, ctx.se_shapes, ctx.keep_r = ix, p.shape, stride, f, (w1.shape, w2.shape), keep_r
+        ctx.math_mode = ops.get_math_mode()
+        return ops.from_nhwc(br.view(B, Ho, Wo, cout))
+
+    @staticmethod
+    @_in_forward_mode
+    def backward(ctx, g):
+        x2d, r_a, h_a, r_b, sq, u, gate, br, war, wbr, wcr, sa, ta, sb, tb, sc, tc, w1, b1, w2, b2, m2d = ctx.saved_tensors
+        ix, shape, stride, f, need, dev, keep_r = ctx.ix, ctx.shape, ctx.stride, ctx.f, ctx.needs_input_grad, g.device, ctx.keep_r
+        B, _, Hi, Wi, Ho, Wo, W, cout = shape
+        P, gw = Ho * Wo, f.group_width
+        pre1, pre3 = image_prefix(B, Hi * Wi, dev), image_prefix(B, P, dev)
+        go = ops.as_nhwc(g.contiguous()).reshape(-1, cout)                       # [B Ho Wo, cout]
+        zW = torch.zeros(W, device=dev)
+        dz = _conv3_T(go, _fold_w3(wcr, sc), zW, None, ix.cap3, torch.empty)     # d L / d (gate . h_b)
+        # squeeze-excitation: d gate = sum_p dz . h_b in one kernel (h_b = r_b . m), the excite MLP by hand on [B, .] tensors
+        dgate = ops.rows_img_dot(dz, r_b, pre3, m_cap=ix.cap3)
+        if keep_r:
+            dgate = dgate * m2d
+        dv = dgate * gate * (1.0 - gate)                                         # through the sigmoid
+        du = (dv @ w2) * (u > 0)
+        dsq = du @ w1
+        gw1s = (du.t() @ sq).reshape(ctx.se_shapes[0]) if need[11] else None
+        gb1s = du.sum(0) if need[12] else None
+        gw2s = (dv.t() @ torch.relu(u)).reshape(ctx.se_shapes[1]) if need[13] else None
+        gb2s = dv.sum(0) if need[14] else None
+        gm_gate = gate * m2d if keep_r else gate
+        z = (r_b.view(B, P, W) * gm_gate.unsqueeze(1)).view(ix.cap3, W) if need[3] else None      # conv c's input
+        # layer b: d h_b = dz . gate + dsq / P, the mask, the ReLU, sb and every reduction in one kernel (in place on dz)
+        dub, gtb, gsbn, gmb = ops.rows_postmask_bwd(dz, r_b, sb, tb, chan_mask=m2d, row_prefix=pre3, gate=gate, dsq=(dsq / P).contiguous(),
+                                                    want_mask=keep_r, m_cap=ix.cap3, out=dz)
+        # b^T: the forward kernel over the transposed neighbour table with per-group transposed weights, scale 1, shift 0, no ReLU
+        nbrT = transposed_neighbour_table(ix, B, Hi, Wi, stride, Ho, Wo)
+        dha = torch.empty(ix.cap1, W, device=dev)
+        ops.grouped_conv3x3_rows(dub, nbrT, grouped_weight_T(wbr, gw), gw, torch.ones(W, device=dev), zW, dha, m_count=ix.cnt[1:2], m_cap=ix.cap1, relu=0)
+        dua, gta, gsan, gma = ops.rows_postmask_bwd(dha, r_a, sa, ta, chan_mask=m2d, row_prefix=pre1, want_mask=keep_r, m_cap=ix.cap1, out=dha)
+        grad_x = _grad_x(dua, war, ix, None, shape) if need[0] else None
+        gwa, _, gwc = _weight_grads(need[1], False, need[3], go, z, None, h_a, dua, x2d, ix, sc, counted=False)
+        gwb = None
+        if need[2]:       # conv b sees the MASKED h_a inside the map, zeros in the padding ring
+            if _wgrad_grouped_kernel(W, gw):
+                gwb = ops.wgrad_grouped_rows(dub, h_a, ix.nbr, gw, m_count=ix.cnt[0:1], m_cap=ix.cap3, a_valid=ix.cap1).permute(0, 2, 1).reshape(W, gw, 3, 3)
+            else:
+                gwb = _weight_grad_grouped_3x3(dub, h_a, ix.nbr, ix.cap1, gw)
+        gsa = gsan / _safe(sa) if need[5] else None
+        gsb = gsbn / _safe(sb) if need[7] else None
+        gsc, gtc = _bn3_grads(need[9], need[10], go, br, sc, tc)
+        gc = gma + gmb if keep_r else None
+        return (grad_x, gwa, gwb, gwc, gc, gsa, gta if need[6] else None, gsb, gtb if need[8] else None, gsc, gtc, gw1s, gb1s, gw2s, gb2s,
+                None, None, None)
+
+
 # ------------------------------------------------------------------------------------------------------------------ blocks
 def _fold_live(bn):
     """(scale, shift) of a BatchNorm with FROZEN statistics as differentiable functions of its affine parameters."""
@@ -650,14 +750,21 @@ def _expand_channel_mask(block, x, mask):
 
 
 def _check_regnet_block(block, x):
-    """what of LAD-RegNet trains: the layer-skip form run_dynamic executes itself (one keep / skip bit per image, one mask group, SE present)"""
+    """what of LAD-RegNet trains: the layer-skip form run_dynamic executes itself (one keep / skip bit per image, one mask group, SE present) and,
+    behind USE_REGNET_CHANNEL, dyn_mode 'channel'"""
     f = block.f
-    if f.dyn_mode != "spatial":
-        raise LdnError(f"training: LAD-RegNet dyn_mode {f.dyn_mode!r} is not built (layer skip only: dyn_mode 'spatial' with one mask bit per image)")
-    if f.mask_size != 1:
-        raise LdnError("training: LAD-RegNet patch masks (mask_size > 1) are not built (layer skip only)")
-    if f.masker_spatial.mask_channel_group != 1:
-        raise LdnError("training: LAD-RegNet spatial mask groups > 1 are not built")
+    channel = f.dyn_mode == "channel" and USE_REGNET_CHANNEL
+    if f.dyn_mode != "spatial" and not channel:
+        raise LdnError(f"training: LAD-RegNet dyn_mode {f.dyn_mode!r} is not built (layer skip: dyn_mode 'spatial' with one mask bit per image; "
+                       "dyn_mode 'channel' trains behind training.USE_REGNET_CHANNEL, env LDN_TRAIN_REGNET_CHANNEL=1, off by default)")
+    if channel:
+        if f.w_b % 8 != 0:
+            raise LdnError("training: LAD-RegNet channel mode needs a bottleneck width that is a multiple of 8 (as inference does)")
+    else:
+        if f.mask_size != 1:
+            raise LdnError("training: LAD-RegNet patch masks (mask_size > 1) are not built (layer skip only)")
+        if f.masker_spatial.mask_channel_group != 1:
+            raise LdnError("training: LAD-RegNet spatial mask groups > 1 are not built")
     if not f.has_se:
         raise LdnError("training: LAD-RegNet without squeeze-excitation (RegNet-X) is not built")
     if not x.is_cuda:
@@ -671,16 +778,26 @@ def _check_regnet_block(block, x):
 
 
 def _branch_regnet(block, x, mask):
-    """_branch for a laud_regnet.ResBottleneckBlock in its layer-skip form (mask [B, 1, 1, 1])"""
+    """_branch for a laud_regnet.ResBottleneckBlock: its layer-skip form (mask [B, 1, 1, 1]) or, behind USE_REGNET_CHANNEL, dyn_mode 'channel'
+    (mask [B, G], G = w_b // channel_dyn_granularity: the expansion to channels is plain autograd, outside the Fn)"""
     _check_regnet_block(block, x)
     f = block.f
-    if isinstance(mask, (tuple, list)) or mask.dim() != 4 or tuple(mask.shape[1:]) != (1, 1, 1) or mask.shape[0] != x.shape[0]:
-        raise LdnError("training: a LAD-RegNet layer-skip block takes one keep / skip bit per image (mask [B, 1, 1, 1])")
-    m3 = F.interpolate(mask, size=(f.output_size, f.output_size), mode="nearest")      # laud_regnet.py:173
-    ix = _pixel_lists(m3, block.stride)
     bn = _fold_live(f.a[1]) + _fold_live(f.b[1]) + _fold_live(f.c[1])
-    branch = _RegNetSkipBranchFn.apply(x, f.a[0].weight, f.b[0].weight, f.c[0].weight, m3, *bn, f.se.fc1.weight, f.se.fc1.bias,
-                                       f.se.fc2.weight, f.se.fc2.bias, block.stride, f, ix)
+    w = (f.a[0].weight, f.b[0].weight, f.c[0].weight)
+    se = (f.se.fc1.weight, f.se.fc1.bias, f.se.fc2.weight, f.se.fc2.bias)
+    if f.dyn_mode == "channel":
+        G = f.masker_channel.channel_dyn_group
+        if isinstance(mask, (tuple, list)) or mask.dim() != 2 or mask.shape[0] != x.shape[0] or mask.shape[1] != G:
+            raise LdnError(f"training: a LAD-RegNet channel block takes one bit per image and channel group (mask [B, {G}])")
+        chm = mask.unsqueeze(2).expand(-1, -1, f.w_b // G).reshape(mask.shape[0], f.w_b)      # group j owns channels [j * gran, (j + 1) * gran)
+        ix = dense_index(x.shape[0], f.output_size, f.output_size, block.stride, x.device)
+        branch = _RegNetChannelBranchFn.apply(x, *w, chm, *bn, *se, block.stride, f, ix)
+    else:
+        if isinstance(mask, (tuple, list)) or mask.dim() != 4 or tuple(mask.shape[1:]) != (1, 1, 1) or mask.shape[0] != x.shape[0]:
+            raise LdnError("training: a LAD-RegNet layer-skip block takes one keep / skip bit per image (mask [B, 1, 1, 1])")
+        m3 = F.interpolate(mask, size=(f.output_size, f.output_size), mode="nearest")      # laud_regnet.py:173
+        ix = _pixel_lists(m3, block.stride)
+        branch = _RegNetSkipBranchFn.apply(x, *w, m3, *bn, *se, block.stride, f, ix)
     identity = x if block.proj is None else block.proj(x)      # (conv 1x1 stride s + BatchNorm on frozen statistics: plain autograd)
     return F.relu(branch + identity), ix
 
@@ -717,7 +834,8 @@ def sparse_block_train(block, x, mask):
     dyn_mode 'spatial' / 'layer': mask [B, 1, S, S] {0,1};  dyn_mode 'channel': mask [B, G] {0,1};  dyn_mode 'both': mask = the pair
     (spatial [B, 1, S, S], channel [B, G]).  A mask may require grad (the hard Gumbel sample of the masker's logits): it receives the
     straight-through term.  A `laud_regnet.ResBottleneckBlock` in its layer-skip form (dyn_mode 'spatial', one mask bit per image, SE present):
-    mask [B, 1, 1, 1]; every other LAD-RegNet form raises LdnError.  Returns the block's output."""
+    mask [B, 1, 1, 1]; with USE_REGNET_CHANNEL on, one in dyn_mode 'channel': mask [B, G]; every other LAD-RegNet form raises LdnError.
+    Returns the block's output."""
     return _branch(block, x, mask)[0]
 
 
@@ -826,20 +944,28 @@ def block_train(block, state, temperature=1.0):
 
 
 def _regnet_block_train(block, state, temperature):
-    """ResBottleneckBlock.forward of the reference in TRAINING mode (laud_regnet.py:157-217,272-292), layer skip: the keep / skip bits are a hard
-    Gumbel sample of the block's masker (forced_spatial_mask is honoured); the bookkeeping of ResBottleneckBlock.forward, differentiable where
-    the reference's is (conv c's sparsity s3; the dilated masks' means come out of the list build, channel sparsity 1)."""
+    """ResBottleneckBlock.forward of the reference in TRAINING mode (laud_regnet.py:157-217,272-292).  Layer skip: the keep / skip bits are a hard
+    Gumbel sample of the block's masker (forced_spatial_mask is honoured); conv c's sparsity s3 is differentiable, the dilated masks' means come
+    out of the list build, channel sparsity 1.  Channel mode (USE_REGNET_CHANNEL): the channel mask likewise (forced_channel_mask is honoured);
+    the channel sparsity cs is differentiable, s1 = s2 = s3 = 1.  The bookkeeping is ResBottleneckBlock.forward's."""
     x, s3l, s2l, s1l, csl, percl, flops = state
     f = block.f
     _check_regnet_block(block, x)
-    m, s3, s_flops = _draw_spatial(f, x, temperature)
-    out, ix = _branch_regnet(block, x, m)
-    s2, s1 = ix.stats[1], ix.stats[2]
-    cs = torch.tensor(1.0, device=x.device)
-    f.last_spatial_mask = m.detach()
+    one = lambda: torch.tensor(1.0, device=x.device)
+    if f.dyn_mode == "channel":
+        cmask, cs, m_flops = _draw_channel(f, x, temperature)
+        out, _ = _branch_regnet(block, x, cmask)
+        s1, s2, s3 = one(), one(), one()
+        f.last_channel_mask = cmask.detach()
+    else:
+        m, s3, m_flops = _draw_spatial(f, x, temperature)
+        out, ix = _branch_regnet(block, x, m)
+        s2, s1 = ix.stats[1], ix.stats[2]
+        cs = one()
+        f.last_spatial_mask = m.detach()
     _, c1, c2, c3, proj, se = block.flops_terms(x.shape)
-    dense = s_flops + c1 + c2 + c3 + proj
-    sparse = s_flops + c1 * cs * s1
+    dense = m_flops + c1 + c2 + c3 + proj
+    sparse = m_flops + c1 * cs * s1
     sparse = sparse + c2 * cs ** 2 * s2
     sparse = sparse + c3 * cs * s3
     sparse = sparse + proj

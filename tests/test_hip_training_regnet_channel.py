@@ -1,0 +1,260 @@
+"""Training of LAD-RegNet CHANNEL-mode blocks under frozen BatchNorm statistics (laudnet_amd/training.py: _RegNetChannelBranchFn on
+ops.rows_postmask_bwd / ops.rows_img_dot, behind training.USE_REGNET_CHANNEL) against the ORACLE's autograd (oracle/regnet_ref.py: every BatchNorm
+in eval mode, the same hard channel mask as a leaf that requires grad).
+
+Blocks (tests/regnet_channel_ref.py: random weights, se_ratio 0.25, BatchNorm running statistics away from (0, 1)): the forward value and ALL
+gradients -- x, the mask's straight-through term, the a / b / c weights and their BatchNorm affine parameters, se.fc1 / se.fc2 weight and bias,
+proj and its BatchNorm -- at group widths 8 / 16 / 24, stride 1 and 2, granularity 1 / 2 / 8, random masks, all on, all off, and one image off;
+one case with the weight-gradient kernels off against the kernel path.  Whole model: regnet_tiny.pt::channel_g2 through train_forward against
+RegNetRef in training mode with identical Gumbel noise, fp32 arithmetic.
+
+Tolerances: those of tests/test_hip_training_regnet.py, restated: fp32 arithmetic -- every element within 1e-3 of max(1, scale), no allowance;
+bf16x3 -- that file's flip allowance."""
+import pytest
+import torch
+import torch.nn as nn
+
+import regnet_channel_ref as R
+from fill import fill_state_dict, seeded_randn
+from helpers import load_golden
+from test_hip_training import GumbelTape, _relative_param_grads, oracle_cpu_grads
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+REGNET = load_golden("regnet_tiny.pt")
+
+
+@pytest.fixture
+def channel_on(monkeypatch):
+    from laudnet_amd import training
+    monkeypatch.setattr(training, "USE_REGNET_CHANNEL", True)
+    return training
+
+
+def _err(got, want):
+    """max |got - want|, in units of max(1, max |want|): plain absolute error for O(1) tensors"""
+    return (got - want).abs().max().item() / max(1.0, want.abs().max().item())
+
+
+def _close(got, want, math_mode, what):
+    """tests/test_hip_training_regnet.py::_close: fp32 arithmetic -- every element within 1e-3 (of max(1, scale)); bf16x3 arithmetic -- a
+    pre-activation within the forward error of zero takes the other side of its ReLU: at most 8 % of the elements outside the tolerance,
+    relative Frobenius error below 5 %."""
+    print(f"{what}: err {_err(got, want):.2e} (scale {want.abs().max().item():.2e})")
+    if math_mode != "bf16x3":
+        assert _err(got, want) < 1e-3, f"{what}: {_err(got, want):.2e} (scale {want.abs().max().item():.2e})"
+        return
+    d = (got - want).abs()
+    tol = 1e-3 * max(1.0, want.abs().max().item())
+    frac = (d > tol).float().mean().item()
+    fro = (d.norm() / want.norm().clamp(min=1e-12)).item()
+    few = got.numel() < 2000
+    assert (few or frac <= 0.08) and fro < 0.05, f"{what}: {100 * frac:.2f} % of the elements outside 1e-3, relative Frobenius error {fro:.2e}"
+
+
+def _make(name):
+    from laudnet_amd.laud_regnet import ResBottleneckBlock
+    ref, sd = R.make_ref_block(name)
+    hip = ResBottleneckBlock(*R.block_args(name)[:3], nn.BatchNorm2d, nn.ReLU, *R.block_args(name)[3:], **R.dyn_kw(name)).eval()
+    hip.load_state_dict(sd)                                                             # the same state dict
+    x, m = R.case_inputs(name)
+    return hip.to(DEV), ref.to(DEV), x.to(DEV), m.to(DEV)
+
+
+def _run_ref(ref, x0, mask0):
+    xr, mr = x0.clone().requires_grad_(True), mask0.clone().requires_grad_(True)
+    ref.f.forced_channel_mask = mr
+    for p_ in ref.parameters():
+        p_.requires_grad_(True)
+        p_.grad = None
+    out = ref(R.start_state(xr), 1.0)[0]
+    gout = seeded_randn(tuple(out.shape), 77).to(DEV)           # upstream gradient
+    out.backward(gout)
+    return out.detach(), xr.grad, mr.grad, {k: v.grad for k, v in ref.named_parameters()}, gout
+
+
+def _run_hip(hip, x0, mask0, gout, mask_grad=True):
+    from laudnet_amd.training import sparse_block_train
+    xh, mh = x0.clone().requires_grad_(True), mask0.clone().requires_grad_(mask_grad)
+    for p_ in hip.parameters():
+        p_.requires_grad_(True)
+        p_.grad = None
+    out = sparse_block_train(hip, xh, mh)
+    out.backward(gout)
+    torch.cuda.synchronize()
+    return out.detach(), xh.grad, mh.grad, {k: v.grad for k, v in hip.named_parameters()}
+
+
+def _compare(got, want, math_mode, has_proj, mask_grad=True):
+    out_h, gx_h, gm_h, gp_h = got
+    out_r, gx_r, gm_r, gp_r = want
+    assert _err(out_h, out_r) < 1e-3, f"forward: {_err(out_h, out_r):.2e}"
+    _close(gx_h, gx_r, math_mode, "d x")
+    if mask_grad:
+        assert gm_h.shape == gm_r.shape
+        _close(gm_h, gm_r, math_mode, "straight-through term d mask")
+    checked = []
+    for pname, gh in gp_h.items():
+        if "masker" in pname:
+            continue                                             # (the mask is an input here: the masker is not part of the graph)
+        assert gh is not None and gp_r[pname] is not None, pname
+        _close(gh, gp_r[pname], math_mode, f"d {pname}")
+        checked.append(pname)
+    # three convs, three BatchNorms (weight + bias), the SE's two layers (weight + bias) [+ proj and its BatchNorm]
+    assert len(checked) == 13 + (3 if has_proj else 0), checked
+    for k in ("f.a.0.weight", "f.b.0.weight", "f.c.0.weight", "f.a.1.bias", "f.b.1.weight", "f.c.1.weight", "f.se.fc1.weight", "f.se.fc1.bias",
+              "f.se.fc2.weight", "f.se.fc2.bias"):
+        assert k in checked, k
+
+
+@pytest.mark.parametrize("name", list(R.CASES))
+def test_regnet_channel_block_gradients_vs_oracle_autograd(name, math_mode, channel_on):
+    from laudnet_amd import ops
+    ops.set_math_mode(math_mode)
+    try:
+        hip, ref, x0, mask0 = _make(name)
+        want = _run_ref(ref, x0, mask0)
+        got = _run_hip(hip, x0, mask0, want[4])
+        _compare(got, want[:4], math_mode, hip.proj is not None)
+        assert want[2].abs().max().item() > 0, "the straight-through term must not vanish"
+        if name.endswith("all_off"):
+            # every unit masked: no gradient reaches the branch -- c's BatchNorm shift excepted, which both of its affine parameters feed --
+            # while the mask's own gradient lives: the case a sparse shortcut gets wrong
+            for pname, gh in got[3].items():
+                if pname.startswith("f.") and "masker" not in pname and not pname.startswith("f.c.1."):
+                    assert gh.abs().max().item() == 0, f"{pname}: an all-zero mask must leave no gradient on the branch"
+            assert got[2].abs().max().item() > 0
+    finally:
+        ops.set_math_mode("fp32")
+
+
+def test_regnet_channel_block_without_mask_gradient(channel_on):
+    """the mask does not require grad: the Fn keeps the masked activations only -- the same gradients everywhere else"""
+    from laudnet_amd import ops
+    ops.set_math_mode("fp32")
+    hip, ref, x0, mask0 = _make("gw16_s2_proj_g2")
+    want = _run_ref(ref, x0, mask0)
+    got = _run_hip(hip, x0, mask0, want[4], mask_grad=False)
+    assert got[2] is None
+    _compare(got, want[:4], "fp32", True, mask_grad=False)
+
+
+def test_regnet_channel_block_wgrad_switch_off_agrees_with_the_kernel_path(monkeypatch, channel_on):
+    """training.USE_WGRAD_KERNEL = False (env LDN_WGRAD=0): the gather + bmm / GEMM weight gradients against the kernels' and the oracle's"""
+    from laudnet_amd import ops
+    training = channel_on
+    ops.set_math_mode("fp32")
+    hip, ref, x0, mask0 = _make("gw16_s2_proj_g2")
+    want = _run_ref(ref, x0, mask0)
+    assert training.USE_WGRAD_KERNEL and training._wgrad_grouped_kernel(64, 16)
+    on = _run_hip(hip, x0, mask0, want[4])
+    monkeypatch.setattr(training, "USE_WGRAD_KERNEL", False)
+    assert not training._wgrad_grouped_kernel(64, 16)
+    off = _run_hip(hip, x0, mask0, want[4])
+    _compare(off, want[:4], "fp32", True)
+    _close(off[0], on[0], "fp32", "forward: switch off vs kernel")
+    _close(off[1], on[1], "fp32", "d x: switch off vs kernel")
+    for pname, g_on in on[3].items():
+        if "masker" not in pname:
+            _close(off[3][pname], g_on, "fp32", f"d {pname}: switch off vs kernel")
+
+
+def _dyn(S, dyn_mode):
+    return dict(spatial_mask_channel_group=1, channel_dyn_granularity=1, output_size=S, mask_spatial_granularity=S, dyn_mode=dyn_mode)
+
+
+def test_regnet_channel_scope_is_enforced(monkeypatch):
+    from laudnet_amd import LdnError, training
+    from laudnet_amd.laud_regnet import ResBottleneckBlock
+    from laudnet_amd.training import sparse_block_train
+    x = torch.relu(seeded_randn((2, 32, 8, 8), 5)).to(DEV)
+    bit = torch.ones(2, 1, 1, 1, device=DEV)
+    ones = torch.ones(2, 32, device=DEV)
+    mk = lambda se=0.25, **dyn: ResBottleneckBlock(32, 32, 1, nn.BatchNorm2d, nn.ReLU, 8, 1.0, se, **dyn).eval().to(DEV)
+    assert training.USE_REGNET_CHANNEL is False, "the switch is off by default"
+    with pytest.raises(LdnError, match="not built.*LDN_TRAIN_REGNET_CHANNEL"):       # switch off: refused, and the message names the switch
+        sparse_block_train(mk(**_dyn(8, "channel")), x, ones)
+    monkeypatch.setattr(training, "USE_REGNET_CHANNEL", True)
+    assert tuple(sparse_block_train(mk(**_dyn(8, "channel")), x, ones).shape) == (2, 32, 8, 8)
+    with pytest.raises(LdnError, match="not built"):                 # a both block stays refused
+        sparse_block_train(mk(**_dyn(8, "both")), x, (bit, ones))
+    with pytest.raises(LdnError, match="not built"):                 # RegNet-X
+        sparse_block_train(mk(se=None, **_dyn(8, "channel")), x, ones)
+    with pytest.raises(LdnError):                                    # a mask of the wrong group count
+        sparse_block_train(mk(**_dyn(8, "channel")), x, torch.ones(2, 16, device=DEV))
+    with pytest.raises(LdnError):                                    # a layer-skip bit for a channel block
+        sparse_block_train(mk(**_dyn(8, "channel")), x, bit)
+    narrow = ResBottleneckBlock(32, 32, 1, nn.BatchNorm2d, nn.ReLU, 4, 0.375, 0.25, **_dyn(8, "channel")).eval().to(DEV)      # w_b = 12
+    with pytest.raises(LdnError, match="multiple of 8"):
+        sparse_block_train(narrow, x, torch.ones(2, 12, device=DEV))
+    blk = mk(**_dyn(8, "channel"))
+    blk.f.b[1].train()
+    with pytest.raises(LdnError, match="not built"):                 # BatchNorm in batch-statistics mode
+        sparse_block_train(blk, x, ones)
+
+
+def _freeze_bn_train(model):
+    model.train()
+    for m in model.modules():
+        if isinstance(m, torch.nn.modules.batchnorm._BatchNorm):
+            m.eval()
+    return model
+
+
+def test_regnet_channel_train_step_vs_oracle(channel_on):
+    """regnet_tiny.pt::channel_g2: one training forward + backward of the whole model under frozen BatchNorm statistics, the channel masks
+    sampled from its own MLP maskers with the oracle's Gumbel noise: the 7-tuple, and the gradient of EVERY one of the 102 parameters (stem,
+    convolutions, BatchNorm affine terms, SE, proj, maskers, classifier) of the loss of test_regnet_train_step_vs_oracle."""
+    import laudnet_amd
+    from laudnet_amd import ops
+    from laudnet_amd.training import prepare_for_training, train_forward
+    from oracle import regnet_ref as RR
+    ops.set_math_mode("fp32")     # (true-fp32 arithmetic: the Gumbel samples and every ReLU decision must coincide with the oracle's)
+    fx = REGNET["cases"]["channel_g2"]
+    ref = RR.RegNetRef(REGNET["tiny_params"] | {}, se_ratio=REGNET["tiny_params"]["se_ratio"], **fx["kw"])
+    hip = laudnet_amd.LAD_RegNet(laudnet_amd.BlockParams(**REGNET["tiny_params"]), **fx["kw"])
+    sd = fill_state_dict(ref.state_dict(), fx["seed"])
+    ref.load_state_dict(sd)
+    hip.load_state_dict(sd)
+    ref, hip = _freeze_bn_train(ref.to(DEV)), prepare_for_training(hip.to(DEV))
+    size = fx["kw"]["input_size"]
+    B = fx["batch"]
+    x = seeded_randn((B, 3, size, size), fx["x_seed"]).to(DEV)
+    g = seeded_randn((B, fx["kw"]["num_classes"]), 9).to(DEV)
+
+    def loss_of(out):
+        return (out[0] * g.to(out[0].device)).sum() / 10.0 + 10.0 * (out[5].mean() - 0.5) ** 2 + 1e-14 * out[6] ** 2
+
+    tape = GumbelTape()
+    torch.manual_seed(77)
+    with tape.record():
+        out_r = ref(x, 1.0)
+    loss_of(out_r).backward()
+    torch.manual_seed(77)
+    out_h = train_forward(hip, x, 1.0)
+    loss_of(out_h).backward()
+    torch.cuda.synchronize()
+    print(f"logits: err {_err(out_h[0].detach(), out_r[0].detach()):.2e}")
+    assert _err(out_h[0].detach(), out_r[0].detach()) < 1e-3, "logits"
+    for i in (1, 2, 3, 4):
+        assert len(out_h[i]) == len(out_r[i]) == 4
+        for a, b in zip(out_h[i], out_r[i]):
+            assert a.shape == b.shape and torch.allclose(a.detach().float(), b.detach().float(), atol=1e-6), i     # identical Gumbel samples
+    assert torch.allclose(out_h[5].detach(), out_r[5].detach(), atol=1e-5)
+    assert abs(float(out_h[6].detach()) - float(out_r[6].detach())) <= 1e-5 * float(out_r[6].detach())
+    cs = torch.cat([v.detach() for v in out_r[4]])
+    assert 0 < float(cs.min()) and float(cs.max()) < 1, "the sampled masks must keep some channels and drop some in every block"
+    for blk in hip.blocks():
+        assert blk.f.last_channel_mask is not None and blk.f.last_channel_mask.shape[0] == B
+    want = dict(ref.named_parameters())
+    n = 0
+    for name, p_ in hip.named_parameters():
+        w = want[name].grad
+        assert (w is None) == (p_.grad is None), f"{name}: gradient present on one side only"
+        assert w is not None and w.abs().max().item() > 0, f"{name}: every parameter gets a gradient in channel mode"
+        _close(p_.grad, w, "fp32", f"d {name}")
+        n += 1
+    assert n == len(want) == 102, (n, len(want))
+    # the scale-relative statement for the tensors on which the oracle's CPU and GPU steps agree (tests/test_hip_training.py)
+    cpu_grads = oracle_cpu_grads(ref, tape, lambda m, dev: loss_of(m(x.to(dev), 1.0)).backward())
+    _relative_param_grads(hip, ref, cpu_grads, "regnet_tiny.pt::channel_g2")

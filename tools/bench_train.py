@@ -5,11 +5,13 @@ it names the weight-gradient path (`wgrad_kernel`: laudnet_amd.training.USE_WGRA
 the row kernels (`peak_MiB_one_step`: torch.cuda.max_memory_allocated of a step of its own after the timed ones).
 `both` is the reference's constructor default (pixel x channel masks: spatial S=4-4-2-1 and channel-2222 together), same model, batch and loss
 convention as the other three.  `regnet` is the full-width LAD-RegNetY-800MF in its layer-skip form (bench.py's workload, keep 0.5) beside
-oracle/regnet_ref.py's dense emulation.  `--ab-wgrad` adds `wgrad_ab`: further steps of the row-kernel leg with the weight-gradient kernels
+oracle/regnet_ref.py's dense emulation; `regnet_channel` is the same model in dyn_mode 'channel' (the one LAD-RegNet recipe the reference trains:
+MLP maskers, two layers, reduction 16, granularity 1; training.USE_REGNET_CHANNEL is turned on for it) -- dense in the channels on the row kernels,
+so about the dense emulation's time is what to expect.  `--ab-wgrad` adds `wgrad_ab`: further steps of the row-kernel leg with the weight-gradient kernels
 (training.USE_WGRAD_KERNEL) off and on ALTERNATING step by step in this one process, the median of each setting's device-event intervals.
 `ms_per_step` is the mean of the timed steps (wall clock over the loop), `ms_per_step_median` the median of the
 steps' own device-event intervals.
-usage: [LDN_WGRAD=0] tools/bench_train.py [--batch 32] [--steps 5] [--warmup 2] [--workloads layer,spatial,channel,both,regnet] [--no-reference] [--ab-wgrad]"""
+usage: [LDN_WGRAD=0] tools/bench_train.py [--batch 32] [--steps 5] [--warmup 2] [--workloads layer,spatial,channel,both,regnet,regnet_channel] [--no-reference] [--ab-wgrad]"""
 import argparse
 import json
 import os
@@ -45,15 +47,41 @@ WORKLOADS["both"] = dict(name="LAUD-ResNet101 both (spatial S=4-4-2-1 x channel-
                          kw=dict(dyn_mode=["both"] * 4, mask_spatial_granularity=[4, 4, 2, 1], channel_dyn_granularity=[2, 2, 2, 2],
                                  channel_masker=["MLP"] * 4, channel_masker_layers=[2, 2, 2, 2], reduction_ratio=[16] * 4),
                          p_channel=0.62, p_spatial=0.5)
+WORKLOADS["regnet_channel"] = dict(name="LAUD-RegNetY-800MF channel target-0.5 @224", arch="lad_regnet_y_800mf",
+                                   kw=dict(dyn_mode=["channel"] * 4, channel_dyn_granularity=[1, 1, 1, 1], channel_masker=["MLP"] * 4,
+                                           channel_masker_layers=[2, 2, 2, 2], reduction_ratio=[16] * 4), p_channel=0.5, p_spatial=None)
+
+
+def calibrate_regnet_channel(model, x, p_channel):
+    """bench.calibrate_maskers for LAD-RegNet channel maskers (its channel branch reads an attribute LAUD-ResNet blocks alone carry): one sequential
+    pass that shifts each masker's keep-logit bias so that the requested fraction of channel groups is kept on this batch"""
+    with torch.no_grad():
+        state = (model.stem(x.contiguous(memory_format=torch.channels_last)), None, None, None, None, None, torch.tensor(0.0, device=x.device))
+        for blk in model.blocks():
+            mk = blk.f.masker_channel
+            G = mk.channel_dyn_group
+            _, _, _, logits = mk.lists(state[0], blk.f.w_b // G, want_logits=True)
+            diff = (logits[:, :G] - logits[:, G:]).flatten().float()
+            last = mk.conv[-1] if mk.layers == 2 else mk.conv
+            last.bias.data[:G] -= torch.quantile(diff.cpu(), 1.0 - p_channel).item()
+            mk._drop_cache()
+            state = blk(state, 1.0)
+
+
 for w in args.workloads.split(","):
     wl = WORKLOADS[w]
+    if w == "regnet_channel":
+        training.USE_REGNET_CHANNEL = True
     kw = dict(wl["kw"], num_classes=1000, input_size=224)
     arch = wl.get("arch", "uni_resnet101")
     hip = getattr(laudnet_amd, arch)(**kw)
     hip.load_state_dict(damp_residual_branches(fill_state_dict(hip.state_dict(), 1)))      # (the last BatchNorm of every residual branch x 0.3)
     hip = hip.to(dev).eval()
     x = seeded_randn((args.batch, 3, 224, 224), 1000).to(dev).contiguous(memory_format=torch.channels_last)
-    bench.calibrate_maskers(hip, x, wl["p_channel"], wl["p_spatial"])
+    if w == "regnet_channel":
+        calibrate_regnet_channel(hip, x, wl["p_channel"])
+    else:
+        bench.calibrate_maskers(hip, x, wl["p_channel"], wl["p_spatial"])
     sd = {k: v.detach().clone() for k, v in hip.state_dict().items()}
     ref = RR.regnet_y_ref(arch, **kw) if arch.startswith("lad_regnet") else TR.resnet101_ref(**kw)
     ref.load_state_dict(sd)
