@@ -618,8 +618,8 @@ def rows_chanmask(u2d, row_prefix, chan_mask, m_count=None, m_cap=None):
 
 def rows_act_bwd(dh2d, u2d, scale, shift, *, post_sub=None, chan_mask=None, row_prefix=None, zy2d=None, m_count=None, m_cap=None, out=None):
     """Backward of u = m * (relu(s * y + t) - c) on packed rows (see ldn_rows_act_bwd), given dh2d = d L / d h (h = u + c) and the stored u2d:
-    a = dh where u + c > 0, dz = a * m[img(r)], du = dz * s.  -> (du [m_cap, C], g_shift [C] = sum a, g_scale_num [C] = sum dz * (h - t) -- the
-    caller divides by s --, g_mask [B, C] = sum over the image's rows of a * (zy - t), or None without zy2d).
+    a = dh where u + c > 0, dz = a * m[img(r)], du = dz * s.  -> (du [m_cap, C], g_shift [C] = sum a, g_scale_num [C] = sum dz * (h - t)
+    (= s * d L / d s; training.py does not use it: it never divides by a scale, which may be 0, and passes scale = ones to get dz), g_mask [B, C] = sum over the image's rows of a * (zy - t), or None without zy2d).
     zy2d is the UNMASKED convolution output in its affine form zy = s * y + t (a relu=0 launch of conv_rows with (scale, shift)), so
     g_mask = sum a * s * y without a division.  chan_mask [B, C] (None = ones) and zy2d need row_prefix [B + 1] (IndexSet.pre1 / pre3).
     Rows past the device-side count are not read; du is exactly 0 there.  out: a [m_cap, >= C] matrix for du (dh2d itself is allowed).
@@ -680,8 +680,8 @@ def rows_postmask_bwd(dz2d, r2d, scale, shift, *, chan_mask=None, row_prefix=Non
                       m_cap=None, out=None):
     """Backward of h = m * relu(zy) -- a channel mask applied AFTER the ReLU -- on packed rows (see ldn_rows_postmask_bwd), given dz2d and the
     stored UNMASKED r2d = relu(zy): dh = dz * gate[img(r)] + dsq[img(r)] with the squeeze-excitation prologue (gate, dsq [B, C]: both or neither),
-    else dz; a = dh * m[img(r)] where r > 0; du = a * s.  -> (du [m_cap, C], g_shift [C] = sum a, g_scale_num [C] = sum a * (r - t) -- the caller
-    divides by s --, g_mask [B, C] = sum over the image's rows of dh * r with want_mask, else None).  chan_mask [B, C] (None = ones), the
+    else dz; a = dh * m[img(r)] where r > 0; du = a * s.  -> (du [m_cap, C], g_shift [C] = sum a, g_scale_num [C] = sum a * (r - t) (= s * d L / d s;
+    unused by training.py, as rows_act_bwd's), g_mask [B, C] = sum over the image's rows of dh * r with want_mask, else None).  chan_mask [B, C] (None = ones), the
     prologue and want_mask need row_prefix [B + 1] (IndexSet.pre1 / pre3).  Rows past the device-side count are not read; du is exactly 0
     there.  out: a [m_cap, >= C] matrix for du (dz2d itself is allowed).  Deterministic: no atomics, the split plan of rows_act_bwd."""
     L.require_device(dz2d, r2d, scale, shift, chan_mask, row_prefix, gate, dsq, m_count, out)

@@ -33,7 +33,8 @@ on the library's kernels:
   the final ReLU, the projection shortcut, the maskers' tiny heads, the static stem and the classifier are plain autograd ops.
 
 One `autograd.Function` per mask kind; what they share (operand layouts, transposed convolutions, weight / BatchNorm / pixel-mask gradients,
-every division by a scale: `_safe`) is written once above them.  The index lists are built once per block forward (`_branch`) and handed to the Fn.
+the split of dz^T A into a weight gradient and a BatchNorm scale gradient: `_split_scale` -- no gradient is obtained by dividing by a folded
+scale, which may be zero, tiny or negative) is written once above them.  The index lists are built once per block forward (`_branch`) and handed to the Fn.
 
 Entry points: `sparse_block_train(block, x, mask)` (one block, the mask an input), `block_train(block, state, temperature)` (the reference's
 block signature in training mode: samples its own masks), `train_forward(model, x, temperature)` (a whole LAUD-ResNet -> the reference's
@@ -41,7 +42,8 @@ block signature in training mode: samples its own masks), `train_forward(model, 
 frozen).  Checked against the oracle's autograd -- blocks on the reference-generated block fixtures, whole models on `det_tiny.pt` /
 `full_tiny.pt` with identical Gumbel noise (tests/test_hip_training.py, tests/test_hip_training_both.py, plain 1e-3; bf16x3 with a flip
 allowance) -- and, element by element to 1e-3 of each gradient's own maximum in both arithmetic modes, against a float64 restatement on inputs
-where no ReLU can flip (tests/test_hip_training_f64.py, tests/train_ref.py).
+where no ReLU can flip (tests/test_hip_training_f64.py, tests/train_ref.py), the same with zero, +-2^-24 and negative BatchNorm weights
+(tests/test_hip_training_bn_scales.py; zero_init_residual's bn3.weight == 0 on a whole detection backbone in tests/test_hip_training.py).
 
 LAD-RegNet (`laud_regnet.ResBottleneckBlock`) trains in its LAYER-SKIP form -- dyn_mode 'spatial' with one keep / skip bit per image, SE present, stride
 1 and 2, with and without `proj`: a kept image runs a -> grouped b -> SE -> c on packed rows in both directions (`_RegNetSkipBranchFn`: the grouped
@@ -234,57 +236,54 @@ def _grad_x(du1, w1r, ix, m_count, shape):
     return ops.from_nhwc(gx.view(B, Hi, Wi, Cin))
 
 
-def _weight_grads(want1, want2, want3, dy3, h2, du2, h1, du1, x2d, ix, s3, counted, consts=None):
-    """(d W1, d W2, d W3), None where not wanted, from d L / d (conv output) dy3 / du2 / du1 and the convs' inputs h2 / h1 / x2d: ldn_wgrad_rows, or
-    the gather + GEMM path for shapes outside its predicate and with the switch off.  counted: the lists are a pixel mask's -- the kernel gets the
-    device-side counts and reads no row past them; the GEMM path relies on dy3 / du2 / du1 being zero there (select, then clamp: the list entries
-    are uninitialised).  Not counted (the channel Fn's dense lists): every row is live.  consts = (c1, c2) where h1 / h2 are stored as u = h - c
-    (the both Fn): conv2 / conv3 see h at every channel, the constants of the masked ones included."""
+def _weight_grads(want1, want2, want3, dy3, h2, dz2, h1, dz1, x2d, ix, counted, consts=None):
+    """(G1, G2, G3), None where not wanted: G = dz^T A in the convolutions' own layouts [cout, cin, kh, kw], from d L / d (s y + t) -- dy3 / dz2 / dz1,
+    BEFORE the BatchNorm scale -- and the convs' inputs h2 / h1 / x2d: ldn_wgrad_rows, or the gather + GEMM path for shapes outside its predicate
+    and with the switch off.  `_split_scale` makes the weight and the scale gradient of G.  counted: the lists are a pixel mask's -- the kernel
+    gets the device-side counts and reads no row past them; the GEMM path relies on dy3 / dz2 / dz1 being zero there (select, then clamp: the
+    list entries are uninitialised).  Not counted (the channel Fn's dense lists): every row is live.  consts = (c1, c2) where h1 / h2 are stored
+    as u = h - c (the both Fn): conv2 / conv3 see h at every channel, the constants of the masked ones included."""
     W, Cin, cout = h1.shape[1], x2d.shape[1], dy3.shape[1]
     cnt3, cnt1 = (ix.cnt[0:1], ix.cnt[1:2]) if counted else (None, None)
     gw1 = gw2 = gw3 = None
     if want3:
         h2 = h2 if consts is None else h2 + consts[1]
         if _wgrad_kernel(W, cout, 1):
-            gw3 = (ops.wgrad_rows(dy3, h2, m_count=cnt3, m_cap=ix.cap3).view(cout, W) * s3.view(-1, 1)).reshape(cout, W, 1, 1)
+            gw3 = ops.wgrad_rows(dy3, h2, m_count=cnt3, m_cap=ix.cap3).reshape(cout, W, 1, 1)
         else:
-            gw3 = ((dy3.t() @ h2) * s3.view(-1, 1)).reshape(cout, W, 1, 1)
+            gw3 = (dy3.t() @ h2).reshape(cout, W, 1, 1)
     if want2:       # conv2 sees h1 inside the map, zeros in the padding ring
         h1 = h1 if consts is None else h1 + consts[0]
         if _wgrad_kernel(W, W, 9):
-            gw2 = ops.wgrad_rows(du2, h1, a_rows=ix.nbr, taps=9, m_count=cnt3, m_cap=ix.cap3, a_valid=ix.cap1).permute(0, 2, 1).reshape(W, W, 3, 3)
+            gw2 = ops.wgrad_rows(dz2, h1, a_rows=ix.nbr, taps=9, m_count=cnt3, m_cap=ix.cap3, a_valid=ix.cap1).permute(0, 2, 1).reshape(W, W, 3, 3)
         else:
-            gw2 = _weight_grad_3x3(du2, h1, ix.nbr, ix.cap1, ix.cnt[0] if counted else None)
+            gw2 = _weight_grad_3x3(dz2, h1, ix.nbr, ix.cap1, ix.cnt[0] if counted else None)
     if want1:
         if _wgrad_kernel(Cin, W, 1):
-            gw1 = ops.wgrad_rows(du1, x2d, a_rows=ix.idx1, taps=1, m_count=cnt1, m_cap=ix.cap1).reshape(W, Cin, 1, 1)
+            gw1 = ops.wgrad_rows(dz1, x2d, a_rows=ix.idx1, taps=1, m_count=cnt1, m_cap=ix.cap1).reshape(W, Cin, 1, 1)
         else:
-            rows1 = ix.idx1.long() if not counted else torch.where(torch.arange(ix.cap1, device=du1.device) < ix.cnt[1], ix.idx1.long(),
+            rows1 = ix.idx1.long() if not counted else torch.where(torch.arange(ix.cap1, device=dz1.device) < ix.cnt[1], ix.idx1.long(),
                                                                    torch.zeros_like(ix.idx1, dtype=torch.long))
-            gw1 = (du1.t() @ x2d[rows1.clamp(0, x2d.shape[0] - 1)]).reshape(W, Cin, 1, 1)
+            gw1 = (dz1.t() @ x2d[rows1.clamp(0, x2d.shape[0] - 1)]).reshape(W, Cin, 1, 1)
     return gw1, gw2, gw3
 
 
-def _safe(s):
-    """a folded BatchNorm scale as a divisor: 1 where it is 0"""
-    return torch.where(s == 0, torch.ones_like(s), s)
+def _split_scale(want_w, want_s, G, w, s):
+    """(d W, d s) of z = s conv(a; W) + t from G = dz^T A (the weight gradient BEFORE the scale; None: neither is wanted):  d W = s G by rows,
+    d s[c] = sum_p dz[p, c] conv(a)[p, c] = sum (G * W)[c] -- a contraction with the weights, never a division by s: exact at s == 0 (where
+    relu(z) - t carries nothing of conv(a)) and free of the cancellation in (h - t) / s at a tiny s.  w: the weights in any layout with the
+    output channel first and G's number of elements (the row kernels' tap-major one is brought to G's)."""
+    if G is None:
+        return None, None
+    if w.dim() == 3 and G.shape[2] == 3:      # [cout, 9, cin] -> [cout, cin, 3, 3]
+        w = w.view(w.shape[0], 3, 3, w.shape[2]).permute(0, 3, 1, 2)
+    return G * s.view(-1, 1, 1, 1) if want_w else None, (G * w.reshape(G.shape)).sum((1, 2, 3)) if want_s else None
 
 
-def _bn_grads(want_s, want_t, dz, dz_shift, h, s, t):
-    """(d s, d t) of a folded BatchNorm in front of a ReLU, z = s y + t: d t = sum d z, d s = sum d z * y with y = (z - t) / s wherever d z != 0
-    (there z = h, the stored ReLU output).  dz_shift = the d z that d t sums: under a channel mask every channel's, while d s sees the active ones."""
-    return (dz * (h - t)).sum(0) / _safe(s) if want_s else None, dz_shift.sum(0) if want_t else None
-
-
-def _bn3_grads(want_s, want_t, dy3, br, s3, t3, kept=None):
-    """(d s3, d t3): bn3 sits behind no ReLU, br - t3 = s3 * conv3(h2) on the rows that were computed.  dy3 = d L / d (s3 y3 + t3) on the rows of
-    br, or with kept = (ix, valid [cap3, 1] bool, a zero to select) on the packed rows of the kept pixels, whose br rows are gathered."""
-    if kept is None:
-        y3s = br - t3 if want_s else None
-    else:
-        ix, valid, zero = kept
-        y3s = torch.where(valid, ops.gather_rows(br, ix.idx3, count=ix.cnt[0:1], cap=ix.cap3) - t3, zero)
-    return (dy3 * y3s).sum(0) / _safe(s3) if want_s else None, dy3.sum(0) if want_t else None
+def _scaled_T(wr, s):
+    """the row kernels' weights [cout, taps, cin] with a BatchNorm scale folded into the OUTPUT channels: what a transposed convolution reads
+    when it is handed dz = d L / d (s y + t) rather than d L / d y"""
+    return wr * s.view(-1, 1, 1)
 
 
 def _pixel_lists(m3, stride):
@@ -349,15 +348,14 @@ class _PixelBranchFn(torch.autograd.Function):
         w3s = _fold_w3(w3r, s3)
         dh2 = _conv3_T(g3, w3s, zW, cnt3, ix.cap3, torch.zeros)
         dz2 = dh2 * (h2 > 0) * v3                         # through ReLU: d L / d (s2 y2 + t2)
-        du2 = dz2 * s2
-        dh1 = _conv2_T(du2, w2r, zW, ix, shape, stride, cnt1, torch.zeros)
+        dh1 = _conv2_T(dz2 * s2, w2r, zW, ix, shape, stride, cnt1, torch.zeros)
         dz1 = dh1 * (h1 > 0) * v1
-        du1 = dz1 * s1
-        grad_x = _grad_x(du1, w1r, ix, cnt1, shape) if need[0] else None
-        gw1, gw2, gw3 = _weight_grads(need[1], need[2], need[3], g3, h2, du2, h1, du1, x2d, ix, s3, counted=True)
-        gs1, gt1 = _bn_grads(need[5], need[6], dz1, dz1, h1, s1, t1)
-        gs2, gt2 = _bn_grads(need[7], need[8], dz2, dz2, h2, s2, t2)
-        gs3, gt3 = _bn3_grads(need[9], need[10], g3, br, s3, t3, kept=(ix, v3 > 0, zW[:1]))
+        grad_x = _grad_x(dz1 * s1, w1r, ix, cnt1, shape) if need[0] else None
+        G1, G2, G3 = _weight_grads(need[1] or need[5], need[2] or need[7], need[3] or need[9], g3, h2, dz2, h1, dz1, x2d, ix, counted=True)
+        gw1, gs1 = _split_scale(need[1], need[5], G1, w1r, s1)
+        gw2, gs2 = _split_scale(need[2], need[7], G2, w2r, s2)
+        gw3, gs3 = _split_scale(need[3], need[9], G3, w3r, s3)
+        gt1, gt2, gt3 = (d.sum(0) if n else None for d, n in ((dz1, need[6]), (dz2, need[8]), (g3, need[10])))
         chain = lambda cix, full: _pixel_chain(x2d, cix, w1r, w2r, w3s, s1, t1, s2, t2, t3, full)
         gm = _pixel_mask_grad(go, br, m3d, stride, chain) if need[4] else None
         return grad_x, gw1, gw2, gw3, gm, gs1, gt1, gs2, gt2, gs3, gt3, None, None
@@ -402,29 +400,30 @@ class _ChannelBranchFn(torch.autograd.Function):
         dh2 = _conv3_T(go, _fold_w3(w3r, s3), zW, None, ix.cap3, torch.empty)
         dz2_all = per_img(dh2) * on2                                  # d L / d z2 (z2 = s2 * (c . y2) + t2)
         dz2 = (dz2_all * cm3).reshape(-1, W)
-        du2 = dz2 * s2                                                # d L / d y2 on the active channels
-        dh1 = _conv2_T(du2, w2r, zW, ix, shape, stride, None, torch.empty)
+        dh1 = _conv2_T(dz2 * s2, w2r, zW, ix, shape, stride, None, torch.empty)      # (dz2 * s2 = d L / d y2 on the active channels)
         dz1_all = per_img(dh1) * on1
         dz1 = (dz1_all * cm3).reshape(-1, W)
-        du1 = dz1 * s1
-        grad_x = _grad_x(du1, w1r, ix, None, shape) if need[0] else None
-        gw1, gw2, gw3 = _weight_grads(need[1], need[2], need[3], go, h2f, du2, h1f, du1, x2d, ix, s3, counted=False)
-        # z = s (c . y) + t: d t sums d z over EVERY channel's pixels (a masked channel's z = t still feeds the ReLU); d s only sees active channels
-        gs1, gt1 = _bn_grads(need[5], need[6], dz1, dz1_all.reshape(-1, W), h1f, s1, t1)
-        gs2, gt2 = _bn_grads(need[7], need[8], dz2, dz2_all.reshape(-1, W), h2f, s2, t2)
-        gs3, gt3 = _bn3_grads(need[9], need[10], go, br, s3, t3)
+        grad_x = _grad_x(dz1 * s1, w1r, ix, None, shape) if need[0] else None
+        # z = s (c . y) + t: d W and d s only see the active channels (dz1 / dz2); d t sums d z over EVERY channel's pixels (a masked channel's
+        # z = t still feeds the ReLU)
+        G1, G2, G3 = _weight_grads(need[1] or need[5], need[2] or need[7], need[3] or need[9], go, h2f, dz2, h1f, dz1, x2d, ix, counted=False)
+        gw1, gs1 = _split_scale(need[1], need[5], G1, w1r, s1)
+        gw2, gs2 = _split_scale(need[2], need[7], G2, w2r, s2)
+        gw3, gs3 = _split_scale(need[3], need[9], G3, w3r, s3)
+        gt1 = dz1_all.reshape(-1, W).sum(0) if need[6] else None
+        gt2 = dz2_all.reshape(-1, W).sum(0) if need[8] else None
+        gt3 = go.sum(0) if need[10] else None
         gc = None
         if need[4]:
             # straight-through term: d L / d c[b, k] = sum_p d L / d (c . y)[b, k, p] * y[b, k, p] for both masked products, y = the UNMASKED conv
-            # output -- needed at the masked channels too: the library's dense execution without the mask (z = s y + t, no ReLU)
+            # output -- needed at the masked channels too: the library's dense execution without the mask (r = s y + t, no ReLU); d z * s * y
+            # = d z * (r - t), no division
             r1 = torch.empty(ix.cap1, W, device=dev)
             ops.conv_rows(x2d, w1r, s1, t1, r1, a_rows=ix.idx1, taps=1, m_cap=ix.cap1, relu=0)
-            y1 = (r1 - t1) / _safe(s1)
             r2 = torch.empty(ix.cap3, W, device=dev)
             # (conv2 of h1 = u1 + c1: the constants' share is the border-class table)
             _conv_const(u1, w2r, s2, tab, r2, a_rows=ix.nbr, taps=9, m_count=None, m_cap=ix.cap3, relu=0, pix_map=ix.idx3, geom=(Hi, Wi, Ho, Wo, stride))
-            y2 = (r2 - t2) / _safe(s2)
-            gc = (dz1_all * s1 * per_img(y1)).sum(1) + (dz2_all * s2 * per_img(y2)).sum(1)          # [B, W]
+            gc = (dz1_all * per_img(r1 - t1)).sum(1) + (dz2_all * per_img(r2 - t2)).sum(1)          # [B, W]
         return grad_x, gw1, gw2, gw3, gc, gs1, gt1, gs2, gt2, gs3, gt3, None, None
 
 
@@ -491,18 +490,23 @@ class _BothBranchFn(torch.autograd.Function):
             _conv_const(x2d, w1r, s1, t1, zy1, a_rows=ix.idx1, taps=1, m_count=cnt1, m_cap=ix.cap1, relu=0)
             zy2 = torch.empty(ix.cap3, W, device=dev)
             _conv_const(u1, w2r, s2, tab, zy2, a_rows=ix.nbr, taps=9, m_count=cnt3, m_cap=ix.cap3, relu=0, pix_map=ix.idx3, geom=geom)
-        # conv3^T on the kept rows, then layer 2's elementwise chain + reductions in one kernel; likewise conv2^T and layer 1's
+        # conv3^T on the kept rows, then layer 2's elementwise chain + reductions in one kernel; likewise conv2^T and layer 1's.  The kernel is given
+        # a scale of ones and so returns dz = d L / d (s y + t): the weight gradient call splits into d W and d s (_split_scale), and the
+        # transposed convolutions read the scale out of their weights.  (Its sum dz * (h - t) is not used: dividing that by s is wrong at s == 0.)
+        one = torch.ones(W, device=dev)
         dh2 = _conv3_T(g3, w3s, zW, cnt3, ix.cap3, torch.empty)
-        du2, gt2, gs2n, gm2 = ops.rows_act_bwd(dh2, u2, s2, t2, post_sub=c2, chan_mask=chm2d, row_prefix=ix.pre3, zy2d=zy2, m_count=cnt3,
-                                               m_cap=ix.cap3, out=dh2)
-        dh1 = _conv2_T(du2, w2r, zW, ix, shape, stride, cnt1, torch.empty)
-        du1, gt1, gs1n, gm1 = ops.rows_act_bwd(dh1, u1, s1, t1, post_sub=c1, chan_mask=chm2d, row_prefix=ix.pre1, zy2d=zy1, m_count=cnt1,
-                                               m_cap=ix.cap1, out=dh1)
-        grad_x = _grad_x(du1, w1r, ix, cnt1, shape) if need[0] else None
-        gw1, gw2, gw3 = _weight_grads(need[1], need[2], need[3], g3, u2, du2, u1, du1, x2d, ix, s3, counted=True, consts=(c1, c2))
-        gs1 = gs1n / _safe(s1) if need[6] else None
-        gs2 = gs2n / _safe(s2) if need[8] else None
-        gs3, gt3 = _bn3_grads(need[10], need[11], g3, br, s3, t3, kept=(ix, v3, zero))        # (t3c carries the constants' share)
+        dz2, gt2, _, gm2 = ops.rows_act_bwd(dh2, u2, one, t2, post_sub=c2, chan_mask=chm2d, row_prefix=ix.pre3, zy2d=zy2, m_count=cnt3,
+                                            m_cap=ix.cap3, out=dh2)
+        dh1 = _conv2_T(dz2, _scaled_T(w2r, s2), zW, ix, shape, stride, cnt1, torch.empty)
+        dz1, gt1, _, gm1 = ops.rows_act_bwd(dh1, u1, one, t1, post_sub=c1, chan_mask=chm2d, row_prefix=ix.pre1, zy2d=zy1, m_count=cnt1,
+                                            m_cap=ix.cap1, out=dh1)
+        grad_x = _grad_x(dz1, _scaled_T(w1r, s1), ix, cnt1, shape) if need[0] else None
+        G1, G2, G3 = _weight_grads(need[1] or need[6], need[2] or need[8], need[3] or need[10], g3, u2, dz2, u1, dz1, x2d, ix, counted=True,
+                                   consts=(c1, c2))
+        gw1, gs1 = _split_scale(need[1], need[6], G1, w1r, s1)
+        gw2, gs2 = _split_scale(need[2], need[8], G2, w2r, s2)
+        gw3, gs3 = _split_scale(need[3], need[10], G3, w3r, s3)        # (conv3 of h2 = u2 + c2: the constants' share is in G3)
+        gt3 = g3.sum(0) if need[11] else None
         chain = lambda cix, full: _both_chain(x2d, cix, geom, w1r, w2r, w3s, s1, t1, c1, s2, tab, c2, t3c, chm2d, full)     # WITH the channel mask
         gm = _pixel_mask_grad(go, br, m3d, stride, chain) if need[4] else None
         gc = gm1 + gm2 if need[5] else None
@@ -598,19 +602,19 @@ class _RegNetSkipBranchFn(torch.autograd.Function):
         dha = torch.zeros(ix.cap1, W, device=dev)
         ops.grouped_conv3x3_rows(dub, nbrT, grouped_weight_T(wbr, gw), gw, torch.ones(W, device=dev), zW, dha, m_count=cnt1, m_cap=ix.cap1, relu=0)
         dza = dha * (h_a > 0) * v1
-        dua = dza * sa
-        grad_x = _grad_x(dua, war, ix, cnt1, shape) if need[0] else None
-        z = (hbv * gate.unsqueeze(1)).view(ix.cap3, W) if need[3] else None       # conv c's input
-        gwa, _, gwc = _weight_grads(need[1], False, need[3], g3, z, None, h_a, dua, x2d, ix, sc, counted=True)
-        gwb = None
-        if need[2]:       # conv b sees h_a inside the map, zeros in the padding ring
+        grad_x = _grad_x(dza * sa, war, ix, cnt1, shape) if need[0] else None
+        z = (hbv * gate.unsqueeze(1)).view(ix.cap3, W) if need[3] or need[9] else None       # conv c's input
+        Ga, _, Gc = _weight_grads(need[1] or need[5], False, need[3] or need[9], g3, z, None, h_a, dza, x2d, ix, counted=True)
+        Gb = None
+        if need[2] or need[7]:       # conv b sees h_a inside the map, zeros in the padding ring
             if _wgrad_grouped_kernel(W, gw):
-                gwb = ops.wgrad_grouped_rows(dub, h_a, ix.nbr, gw, m_count=cnt3, m_cap=ix.cap3, a_valid=ix.cap1).permute(0, 2, 1).reshape(W, gw, 3, 3)
+                Gb = ops.wgrad_grouped_rows(dzb, h_a, ix.nbr, gw, m_count=cnt3, m_cap=ix.cap3, a_valid=ix.cap1).permute(0, 2, 1).reshape(W, gw, 3, 3)
             else:
-                gwb = _weight_grad_grouped_3x3(dub, h_a, ix.nbr, ix.cap1, gw, ix.cnt[0])
-        gsa, gta = _bn_grads(need[5], need[6], dza, dza, h_a, sa, ta)
-        gsb, gtb = _bn_grads(need[7], need[8], dzb, dzb, h_b, sb, tb)
-        gsc, gtc = _bn3_grads(need[9], need[10], g3, br, sc, tc, kept=(ix, v3 > 0, zW[:1]))
+                Gb = _weight_grad_grouped_3x3(dzb, h_a, ix.nbr, ix.cap1, gw, ix.cnt[0])
+        gwa, gsa = _split_scale(need[1], need[5], Ga, war, sa)
+        gwb, gsb = _split_scale(need[2], need[7], Gb, wbr, sb)
+        gwc, gsc = _split_scale(need[3], need[9], Gc, wcr, sc)
+        gta, gtb, gtc = (d.sum(0) if n else None for d, n in ((dza, need[6]), (dzb, need[8]), (g3, need[10])))
         # the straight-through term needs the branch of the DROPPED images: this Fn's own chain over the complement's lists (their SE squeezes
         # their own rows -- what the dense reference computes)
         se = (w1, b1, w2, b2)
@@ -682,26 +686,30 @@ class _RegNetChannelBranchFn(torch.autograd.Function):
         gw2s = (dv.t() @ torch.relu(u)).reshape(ctx.se_shapes[1]) if need[13] else None
         gb2s = dv.sum(0) if need[14] else None
         gm_gate = gate * m2d if keep_r else gate
-        z = (r_b.view(B, P, W) * gm_gate.unsqueeze(1)).view(ix.cap3, W) if need[3] else None      # conv c's input
-        # layer b: d h_b = dz . gate + dsq / P, the mask, the ReLU, sb and every reduction in one kernel (in place on dz)
-        dub, gtb, gsbn, gmb = ops.rows_postmask_bwd(dz, r_b, sb, tb, chan_mask=m2d, row_prefix=pre3, gate=gate, dsq=(dsq / P).contiguous(),
-                                                    want_mask=keep_r, m_cap=ix.cap3, out=dz)
-        # b^T: the forward kernel over the transposed neighbour table with per-group transposed weights, scale 1, shift 0, no ReLU
+        z = (r_b.view(B, P, W) * gm_gate.unsqueeze(1)).view(ix.cap3, W) if need[3] or need[9] else None      # conv c's input
+        # layer b: d h_b = dz . gate + dsq / P, the mask, the ReLU and every reduction in one kernel (in place on dz).  The kernel is given a scale
+        # of ones and so returns d L / d (sb y_b + tb): the weight gradient call splits into d W and d s (_split_scale), b^T reads sb out of its
+        # weights.  (Its sum a * (r - t) is not used: dividing that by s is wrong at s == 0.)
+        one = torch.ones(W, device=dev)
+        dzb, gtb, _, gmb = ops.rows_postmask_bwd(dz, r_b, one, tb, chan_mask=m2d, row_prefix=pre3, gate=gate, dsq=(dsq / P).contiguous(),
+                                                 want_mask=keep_r, m_cap=ix.cap3, out=dz)
+        # b^T: the forward kernel over the transposed neighbour table with per-group transposed weights (sb folded in), scale 1, shift 0, no ReLU
         nbrT = transposed_neighbour_table(ix, B, Hi, Wi, stride, Ho, Wo)
         dha = torch.empty(ix.cap1, W, device=dev)
-        ops.grouped_conv3x3_rows(dub, nbrT, grouped_weight_T(wbr, gw), gw, torch.ones(W, device=dev), zW, dha, m_count=ix.cnt[1:2], m_cap=ix.cap1, relu=0)
-        dua, gta, gsan, gma = ops.rows_postmask_bwd(dha, r_a, sa, ta, chan_mask=m2d, row_prefix=pre1, want_mask=keep_r, m_cap=ix.cap1, out=dha)
-        grad_x = _grad_x(dua, war, ix, None, shape) if need[0] else None
-        gwa, _, gwc = _weight_grads(need[1], False, need[3], go, z, None, h_a, dua, x2d, ix, sc, counted=False)
-        gwb = None
-        if need[2]:       # conv b sees the MASKED h_a inside the map, zeros in the padding ring
+        ops.grouped_conv3x3_rows(dzb, nbrT, grouped_weight_T(_scaled_T(wbr, sb), gw), gw, one, zW, dha, m_count=ix.cnt[1:2], m_cap=ix.cap1, relu=0)
+        dza, gta, _, gma = ops.rows_postmask_bwd(dha, r_a, one, ta, chan_mask=m2d, row_prefix=pre1, want_mask=keep_r, m_cap=ix.cap1, out=dha)
+        grad_x = _grad_x(dza, _scaled_T(war, sa), ix, None, shape) if need[0] else None
+        Ga, _, Gc = _weight_grads(need[1] or need[5], False, need[3] or need[9], go, z, None, h_a, dza, x2d, ix, counted=False)
+        Gb = None
+        if need[2] or need[7]:       # conv b sees the MASKED h_a inside the map, zeros in the padding ring
             if _wgrad_grouped_kernel(W, gw):
-                gwb = ops.wgrad_grouped_rows(dub, h_a, ix.nbr, gw, m_count=ix.cnt[0:1], m_cap=ix.cap3, a_valid=ix.cap1).permute(0, 2, 1).reshape(W, gw, 3, 3)
+                Gb = ops.wgrad_grouped_rows(dzb, h_a, ix.nbr, gw, m_count=ix.cnt[0:1], m_cap=ix.cap3, a_valid=ix.cap1).permute(0, 2, 1).reshape(W, gw, 3, 3)
             else:
-                gwb = _weight_grad_grouped_3x3(dub, h_a, ix.nbr, ix.cap1, gw)
-        gsa = gsan / _safe(sa) if need[5] else None
-        gsb = gsbn / _safe(sb) if need[7] else None
-        gsc, gtc = _bn3_grads(need[9], need[10], go, br, sc, tc)
+                Gb = _weight_grad_grouped_3x3(dzb, h_a, ix.nbr, ix.cap1, gw)
+        gwa, gsa = _split_scale(need[1], need[5], Ga, war, sa)
+        gwb, gsb = _split_scale(need[2], need[7], Gb, wbr, sb)
+        gwc, gsc = _split_scale(need[3], need[9], Gc, wcr, sc)
+        gtc = go.sum(0) if need[10] else None
         gc = gma + gmb if keep_r else None
         return (grad_x, gwa, gwb, gwc, gc, gsa, gta if need[6] else None, gsb, gtb if need[8] else None, gsc, gtc, gw1s, gb1s, gw2s, gb2s,
                 None, None, None)

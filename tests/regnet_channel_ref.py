@@ -50,11 +50,15 @@ def case_inputs(name, seed=31):
     return x, m
 
 
-def make_ref_block(name, seed=31):
-    """the oracle's block in eval mode (BatchNorm on its running statistics: frozen) with the seeded state dict -> (block, state dict)"""
+def make_ref_block(name, seed=31, variant=None):
+    """the oracle's block in eval mode (BatchNorm on its running statistics: frozen) with the seeded state dict -> (block, state dict).
+    variant: a BatchNorm scale edit of tests/train_ref.py ("mixed": zero, negated and +-2^-24 weights by channel index) on that state dict"""
     from oracle import regnet_ref as RR
     ref = RR.ResBlockRef(*block_args(name), **dyn_kw(name)).eval()
     sd = fill_state_dict(ref.state_dict(), seed)
+    if variant is not None:
+        from train_ref import edit_bn_weights
+        edit_bn_weights(sd, variant)
     ref.load_state_dict(sd)
     return ref, sd
 
@@ -124,19 +128,25 @@ def closed_form_f64(name, sd, x, group_mask, gout):
     grads["f.se.fc2.weight"] = (dv.t() @ torch.relu(u)).view_as(sd["f.se.fc2.weight"])
     grads["f.se.fc2.bias"] = dv.sum(0)
 
-    def postmask(dh, r, s, t):
-        """ldn_rows_postmask_bwd: -> (du, g_shift, g_scale, g_mask [B, W])"""
+    def postmask(dh, r):
+        """ldn_rows_postmask_bwd with a scale of ones: -> (a = d L / d (s y + t), g_shift, g_mask [B, W])"""
         a = torch.where(r > 0, dh * m, torch.zeros_like(dh))
-        return a * v(s), a.sum((0, 2, 3)), (a * (r - v(t))).sum((0, 2, 3)) / s, (dh * r).sum((2, 3))
+        return a, a.sum((0, 2, 3)), (dh * r).sum((2, 3))
 
-    dub, gtb, gsb, gmb = postmask(dz * gate.view(B, W, 1, 1) + dsq.view(B, W, 1, 1) / P, r_b, sb, tb)
-    grads["f.b.0.weight"] = conv2d_weight(h_a, Wb.shape, dub, stride=stride, padding=1, groups=groups)
+    def split_scale(G, Wt, s):
+        """training._split_scale: G = a^T A, the weight gradient BEFORE the scale -> (d W = s G, d s = sum G * W): no division by s, which may
+        be zero (there relu(s y + t) - t carries nothing of y), tiny or negative"""
+        return G * s.view(-1, 1, 1, 1), (G * Wt).sum((1, 2, 3))
+
+    s4 = lambda s: s.view(-1, 1, 1, 1)
+    dzb, gtb, gmb = postmask(dz * gate.view(B, W, 1, 1) + dsq.view(B, W, 1, 1) / P, r_b)
+    grads["f.b.0.weight"], gsb = split_scale(conv2d_weight(h_a, Wb.shape, dzb, stride=stride, padding=1, groups=groups), Wb, sb)
     grads["f.b.1.weight"], grads["f.b.1.bias"] = _bn_param_grads(gsb, gtb, ib, mb)
-    dha = conv2d_input(h_a.shape, Wb, dub, stride=stride, padding=1, groups=groups)
-    dua, gta, gsa, gma = postmask(dha, r_a, sa, ta)
-    grads["f.a.0.weight"] = conv2d_weight(x, Wa.shape, dua)
+    dha = conv2d_input(h_a.shape, Wb * s4(sb), dzb, stride=stride, padding=1, groups=groups)       # b^T reads s_b out of its weights
+    dza, gta, gma = postmask(dha, r_a)
+    grads["f.a.0.weight"], gsa = split_scale(conv2d_weight(x, Wa.shape, dza), Wa, sa)
     grads["f.a.1.weight"], grads["f.a.1.bias"] = _bn_param_grads(gsa, gta, ia, ma)
-    dx = conv2d_input(x.shape, Wa, dua)
+    dx = conv2d_input(x.shape, Wa * s4(sa), dza)
     if has_proj:
         dyp = g * v(sp)
         dx = dx + conv2d_input(x.shape, Wp, dyp, stride=stride)

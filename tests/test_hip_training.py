@@ -359,6 +359,76 @@ def test_detection_backbone_train_step_vs_oracle(case):
 
 
 @pytest.mark.gpu
+def test_detection_backbone_zero_init_residual_train_step_vs_oracle():
+    """det_tiny.pt::layer_r50 with every bn3.weight exactly 0 -- what LAD_MMDet_ResNet's zero_init_residual=True leaves in a freshly constructed
+    backbone -- through train_forward against the oracle's autograd with the same Gumbel tape, fp32 arithmetic.  Every branch is the constant
+    bn3.bias, so no mask decision can change a stage output (Gumbel ties are harmless); every bn3.weight gradient is within this file's fp32
+    bound and NON-ZERO in every block (a scale gradient recovered by dividing by the scale is 0 here, and the weights could never leave 0).
+    A block that skips all three images has d bn3.weight == 0 in the oracle as well, and with the seeded fill's masker weights several blocks skip
+    every image under any noise; so the spatial maskers get the keep bias of their constructor's kind (keep logit 3, drop logit 0) over weights
+    damped by 100: about 5 % of the images are skipped, a block skips all three with probability 1e-4 -- asserted below on the oracle's masks."""
+    from laudnet_amd import ops
+    from laudnet_amd.detection import LAD_MMDet_ResNet
+    from laudnet_amd.training import prepare_for_training, train_forward
+    from oracle import det_ref as DR
+    ops.set_math_mode("fp32")
+    fx = load_golden("det_tiny.pt")["layer_r50"]
+    ref = DR.LADDetResNetRef(**fx["kw"])
+    sd = fill_state_dict(ref.state_dict(), fx["seed"])
+    zeroed = [k for k in sd if k.endswith("bn3.weight")]
+    edit = {k: torch.zeros_like(sd[k]) for k in zeroed}
+    for k in sd:
+        if k.endswith("masker_spatial.conv.weight"):
+            edit[k] = sd[k] * 0.01
+        elif k.endswith("masker_spatial.conv.bias"):
+            edit[k] = torch.tensor([3.0] * (sd[k].numel() // 2) + [0.0] * (sd[k].numel() // 2))
+    sd.update(edit)
+    ref.load_state_dict(sd)
+    hip = LAD_MMDet_ResNet(**fx["kw"])
+    hsd = fill_state_dict(hip.state_dict(), fx["seed"])
+    assert zeroed and all(k in hsd and hsd[k].shape == v.shape for k, v in edit.items())
+    hsd.update(edit)
+    hip.load_state_dict(hsd)
+    ref, hip = _freeze_bn_train(ref.to(DEV)), prepare_for_training(hip.to(DEV))
+    x = seeded_randn(tuple(fx["shape"]), fx["x_seed"]).to(DEV)
+    gs = None
+
+    def loss_of(res):
+        nonlocal gs
+        outs, add, _ = res
+        if gs is None:
+            gs = [seeded_randn(tuple(o.shape), 500 + i).to(DEV) for i, o in enumerate(outs)]
+        return sum((o * g.to(o.device)).sum() for o, g in zip(outs, gs)) / 100.0 + 10.0 * (add["flops"] / add["dense_flops"] - 0.5) ** 2
+
+    tape = GumbelTape()
+    torch.manual_seed(1234)
+    with tape.record():
+        res_r = ref(x)
+    loss_of(res_r).backward()
+    torch.manual_seed(1234)
+    res_h = train_forward(hip, x)
+    loss_of(res_h).backward()
+    torch.cuda.synchronize()
+    for a, b in zip(res_h[0], res_r[0]):
+        assert _err(a.detach(), b.detach()) < 1e-3, "stage output"
+    kept = torch.cat([v.detach().flatten() for v in res_r[1]["spatial_sparsity_conv3"]])
+    assert kept.numel() == len(zeroed) and float(kept.min()) > 0, f"a block skipped every image (kept share per block {kept.tolist()})"
+    want, n = dict(ref.named_parameters()), 0
+    for name, p_ in hip.named_parameters():
+        if not name.endswith("bn3.weight"):
+            continue
+        w = want[name].grad
+        assert float(p_.detach().abs().max()) == 0 and w is not None and p_.grad is not None, name
+        print(f"zero_init_residual d {name}: err {_err(p_.grad, w):.2e} (scale {w.abs().max().item():.2e}, HIP max {p_.grad.abs().max().item():.2e})")
+        assert w.abs().max().item() > 0, f"d {name}: the oracle's gradient vanishes"
+        assert p_.grad.abs().max().item() > 0, f"d {name} is zero: bn3.weight can never leave 0"
+        assert bool(torch.isfinite(p_.grad).all()), name
+        _close(p_.grad, w, "fp32", f"d {name}")
+        n += 1
+    assert n == len(zeroed) == sum(len(getattr(hip, f"layer{s}")) for s in (1, 2, 3, 4)), (n, len(zeroed))
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("case", ["r101_channel2222", "r101_layer", "r101_spatial4421"])
 def test_classifier_train_step_vs_oracle(case):
     """The classifier's training forward (7-tuple) + backward under frozen BatchNorm statistics, the sparsity criterion on the tuple."""

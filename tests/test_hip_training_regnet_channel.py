@@ -52,9 +52,9 @@ def _close(got, want, math_mode, what):
     assert (few or frac <= 0.08) and fro < 0.05, f"{what}: {100 * frac:.2f} % of the elements outside 1e-3, relative Frobenius error {fro:.2e}"
 
 
-def _make(name):
+def _make(name, variant=None):
     from laudnet_amd.laud_regnet import ResBottleneckBlock
-    ref, sd = R.make_ref_block(name)
+    ref, sd = R.make_ref_block(name, variant=variant)
     hip = ResBottleneckBlock(*R.block_args(name)[:3], nn.BatchNorm2d, nn.ReLU, *R.block_args(name)[3:], **R.dyn_kw(name)).eval()
     hip.load_state_dict(sd)                                                             # the same state dict
     x, m = R.case_inputs(name)
@@ -137,6 +137,29 @@ def test_regnet_channel_block_without_mask_gradient(channel_on):
     got = _run_hip(hip, x0, mask0, want[4], mask_grad=False)
     assert got[2] is None
     _compare(got, want[:4], "fp32", True, mask_grad=False)
+
+
+def test_regnet_channel_block_with_zero_tiny_and_negative_bn_scales(channel_on):
+    """gw16_s2_proj_g2 with train_ref's `mixed` edit in its state dict (by channel index: BatchNorm weight 0 / negated / +2^-24 / -2^-24, every
+    BatchNorm of the block): fp32 arithmetic, this file's fp32 rule, no allowance.  Stated directly as well: on the ZERO-weight channels the
+    weight gradients of the three BatchNorms of the branch match the oracle's and are not all zero (a scale gradient recovered by dividing
+    sum a (r - t) by the scale is 0 there)."""
+    from laudnet_amd import ops
+    from train_ref import mixed_classes
+    ops.set_math_mode("fp32")
+    hip, ref, x0, mask0 = _make("gw16_s2_proj_g2", "mixed")
+    assert bool((hip.f.c[1].weight[mixed_classes(64)["zero"]] == 0).all())
+    want = _run_ref(ref, x0, mask0)
+    got = _run_hip(hip, x0, mask0, want[4])
+    _compare(got, want[:4], "fp32", True)
+    for pname, gh in got[3].items():
+        assert gh is None or bool(torch.isfinite(gh).all()), f"d {pname} holds NaN or Inf"
+    for k in ("f.a.1.weight", "f.b.1.weight", "f.c.1.weight"):
+        zero = mixed_classes(got[3][k].numel())["zero"].to(DEV)
+        gh, gr = got[3][k][zero], want[3][k][zero]
+        print(f"d {k} on the zero-weight channels: err {(gh - gr).abs().max().item():.2e}, max |want| {gr.abs().max().item():.2e}")
+        assert gr.abs().max().item() > 0 and gh.abs().max().item() > 0, f"d {k} vanishes on the zero-weight channels"
+        assert (gh - gr).abs().max().item() < 1e-3 * max(1.0, want[3][k].abs().max().item()), f"d {k} on the zero-weight channels"
 
 
 def test_regnet_channel_block_wgrad_switch_off_agrees_with_the_kernel_path(monkeypatch, channel_on):

@@ -13,9 +13,22 @@ def _err(got, want):
     return (got - want).abs().max().item() / max(1.0, want.abs().max().item())
 
 
+def test_closed_forms_vs_oracle_autograd_f64_mixed_bn_scales():
+    """zero, negated and +-2^-24 BatchNorm weights (train_ref's `mixed` edit) in the state dict of gw16_s2_proj_g2: the closed forms divide by no
+    scale, and the zero-weight channels of every BatchNorm of the branch carry a weight gradient"""
+    from train_ref import mixed_classes
+    got = _closed_forms_vs_oracle("gw16_s2_proj_g2", "mixed")
+    for k in ("f.a.1.weight", "f.b.1.weight", "f.c.1.weight", "proj.1.weight"):
+        assert got[3][k][mixed_classes(got[3][k].numel())["zero"]].abs().max().item() > 0, k
+
+
 @pytest.mark.parametrize("name", list(R.CASES))
 def test_closed_forms_vs_oracle_autograd_f64(name):
-    ref, sd = R.make_ref_block(name)
+    _closed_forms_vs_oracle(name)
+
+
+def _closed_forms_vs_oracle(name, variant=None):
+    ref, sd = R.make_ref_block(name, variant=variant)
     ref = ref.double()
     x, m = R.case_inputs(name)
     xr, mr = x.double().requires_grad_(True), m.double().requires_grad_(True)
@@ -43,3 +56,4 @@ def test_closed_forms_vs_oracle_autograd_f64(name):
             if not pname.startswith("f.c.1.") and not pname.startswith("proj"):
                 assert gr.abs().max().item() == 0, pname
         assert got[2].abs().max().item() > 0
+    return got

@@ -39,7 +39,9 @@ wide_s2_spatial and wide_s2_layer on no map at all, down to 2 x 2 / 1 x 1 output
 |z| >= 4 E(bf16x3) at every unit of every ReLU, no bias moving by more than 0.25.  Units that are exactly equal on both sides need no clearance: a
 dropped pixel over the identity shortcut (z = x, the final ReLU is plain torch everywhere) and a channel-masked unit (z = t[c]).
 
-`CASES` is the table of tests/test_hip_training_f64.py; `tie_free_case` / `reference` build each case once per process."""
+`CASES` is the table of tests/test_hip_training_f64.py; `tie_free_case` / `reference` build each case once per process.  `VARIANT_CASES`
+puts zero, tiny (2^-24) and negative BatchNorm weights into eleven of them (tests/test_hip_training_bn_scales.py): nothing above assumes a
+scale near 1 -- the bound carries |s|, and a channel whose scale is 0 is the constant t[c], cleared like any other unit."""
 from __future__ import annotations
 
 import copy
@@ -413,26 +415,72 @@ def case_params(fx):
     return params_from_state_dict(sd, **cfg)
 
 
+# ------------------------------------------------------------------------------------------------------------------ BatchNorm scale variants
+# Every seeded BatchNorm weight lies in [0.5, 1.5) (tests/golden/fill.py).  Real checkpoints hold zero, tiny and negative ones, and the
+# detection backbone is constructed with zero_init_residual: every bn3.weight exactly 0.  A variant edits the seeded BatchNorm WEIGHTS of a case
+# (so the folded scale of a zero weight is exactly 0) BEFORE make_tie_free runs, on the case's committed map and seed:
+#   mixed      every BatchNorm of the block, the projection's included, by channel index c:  c % 8 == 1 -> 0,  c % 8 == 3 -> negated,
+#              c % 8 == 5 -> +2^-24,  c % 8 == 7 -> -2^-24,  the rest as seeded
+#   zero_last  the branch's last BatchNorm weight (bn3.weight / f.c.1.weight) 0 throughout: what zero_init_residual leaves
+# find_map's rule (the largest map of the ladder) belongs to the base cases; the variants reuse their maps.
+VARIANTS = ("mixed", "zero_last")
+VARIANT_BASES = ["narrow_s1_spatial", "narrow_s1_layer", "narrow_s1_channel", "narrow_s1_both", "narrow_s2_spatial", "narrow_s2_channel",
+                 "narrow_s2_both", "mid_s1_both", "mid_s2_channel", "regnet_gw8_s1", "regnet_gw16_s2_proj"]
+VARIANT_CASES = [(n, v) for n in VARIANT_BASES for v in VARIANTS]
+TINY = 2.0 ** -24
+
+
+def last_bn(sd):
+    """the branch's last BatchNorm of a state dict: "bn3" (ResNet) / "f.c.1" (LAD-RegNet)"""
+    return "bn3" if "bn3.weight" in sd else "f.c.1"
+
+
+def mixed_classes(n):
+    """{class: bool [n]} of the `mixed` edit by channel index"""
+    c = torch.arange(n) % 8
+    return {"zero": c == 1, "negated": c == 3, "tiny": c == 5, "neg_tiny": c == 7}
+
+
+def edit_bn_weights(sd, variant):
+    """the variant's edit IN PLACE on a state dict (any float dtype): BatchNorm weights only (a `.weight` beside a `.running_var`)"""
+    if variant == "zero_last":
+        sd[last_bn(sd) + ".weight"].zero_()
+    elif variant == "mixed":
+        for k in [k for k in sd if k.endswith(".weight") and k[:-len("weight")] + "running_var" in sd and "masker" not in k]:
+            w, cls = sd[k], mixed_classes(sd[k].numel())
+            w[cls["zero"]] = 0.0
+            w[cls["negated"]] = -w[cls["negated"]]
+            w[cls["tiny"]] = TINY
+            w[cls["neg_tiny"]] = -TINY
+    else:
+        raise ValueError(f"unknown BatchNorm scale variant {variant!r}")
+    return sd
+
+
 @functools.lru_cache(maxsize=None)
-def tie_free_case(name):
-    """-> namespace(fx, params0 = as seeded, params = tie-free, x, masks, clearance, moved); built once per process, never modified"""
+def tie_free_case(name, variant=None):
+    """-> namespace(fx, params0 = as seeded [and edited by `variant`], params = tie-free, x, masks, clearance, moved); built once per process,
+    never modified"""
     fx = case_fixture(name)
     x, params0 = case_input(fx), case_params(fx)
+    if variant is not None:
+        edit_bn_weights(params0["sd"], variant)
     params, got, moved = make_tie_free(params0, x, fx["masks"])
-    return SimpleNamespace(name=name, fx=fx, params0=params0, params=params, x=x, masks=fx["masks"], clearance=got, moved=moved)
+    return SimpleNamespace(name=name, variant=variant, fx=fx, params0=params0, params=params, x=x, masks=fx["masks"], clearance=got, moved=moved)
 
 
-def case_gout(case):
+def case_gout(case, variant=None):
+    """the upstream gradient of a case: the same for every variant (seed 77 at the output's shape)"""
     stride, cout = case.fx["stride"], case.params["sd"]["bn3.weight" if case.fx["kind"] == "resnet" else "f.c.1.weight"].shape[0]
     B, _, H, W = case.fx["x_shape"]
     return seeded_randn((B, cout, (H - 1) // stride + 1, (W - 1) // stride + 1), 77)
 
 
 @functools.lru_cache(maxsize=None)
-def reference(name, dtype=torch.float64):
+def reference(name, dtype=torch.float64, variant=None):
     """-> (out, grads, gates) of the tie-free case in `dtype` (float64: THE reference, computed once and shared)"""
-    case = tie_free_case(name)
-    return gradients(case.params, case.x, case.masks, case_gout(case), dtype)
+    case = tie_free_case(name, variant)
+    return gradients(case.params, case.x, case.masks, case_gout(case, variant), dtype)
 
 
 def worst_ratio(got, want):

@@ -11,7 +11,12 @@ profiles/train_parity_f64.json (one line per case / model: the tensor names once
             parameters that have a non-zero oracle gradient; the tensors that are not eligible are named.
 The whole-model figures are what the tests themselves computed: this tool calls those test functions and reads test_hip_training.RELATIVE_RECORDS,
 which they fill as they run (deliberately coupled to the tests: the record is of exactly what they assert on).
-Needs one MI355X.  usage: tools/train_parity_f64.py [--out profiles/train_parity_f64.json] [--no-models]"""
+--bn-scales LABEL measures the BatchNorm scale variants instead (train_ref.VARIANT_CASES, tests/test_hip_training_bn_scales.py: zero, +-2^-24 and
+negated weights) and merges the figures under LABEL into profiles/train_parity_bn_scales.json: per case, variant and arithmetic mode every tensor's
+max |err| / max |want64| (max |got| itself where want64 is identically zero: only 0 passes), NaN / Inf reported as the string "nan".  The file
+holds two labels: "parent" = the tree before d scale stopped being a division by the scale (training.py of the commit before; the tests were
+run against it once to record what they catch) and "fixed".
+Needs one MI355X.  usage: tools/train_parity_f64.py [--out profiles/train_parity_f64.json] [--no-models] | --bn-scales LABEL [--out FILE]"""
 import argparse
 import json
 import os
@@ -59,11 +64,52 @@ def write_compact(path, blocks, worst, models):
         f.write("\n".join(lines) + "\n")
 
 
+def bn_scales(label, path):
+    """the 22 variant cases under both arithmetic modes -> `path`, merged under `label`: one line per case / variant / mode"""
+    import math
+    doc = {"bound": 0.001, "what": "max |err| / max |want64| per tensor; max |got| where want64 is identically zero", "labels": {}}
+    if os.path.exists(path):
+        with open(path) as f:
+            doc = json.load(f)
+    fig = lambda v: None if v is None else ("nan" if not math.isfinite(v) else _r(v))
+    rows, worst, failing = {}, [0.0, ""], 0
+    for name, variant in R.VARIANT_CASES:
+        for mode in ("fp32", "bf16x3"):
+            ops.set_math_mode(mode)
+            try:
+                res = T64.measure(name, variant)
+            finally:
+                ops.set_math_mode("fp32")
+            _, want, _ = R.reference(name, variant=variant)
+            bad = sorted(k for k, v in res.items() if v is None or not math.isfinite(v) or (v > 1e-3 if k == "forward" or want[k].abs().max().item() > 0 else v != 0))
+            rows[f"{name}/{variant}/{mode}"] = {"tensors": list(res), "ratio": [fig(v) for v in res.values()], "over_bound": bad}
+            failing += bool(bad)
+            for k, v in res.items():
+                if v is not None and (not math.isfinite(v) or v > worst[0]):
+                    worst = [v if math.isfinite(v) else float("inf"), f"{name}/{variant}/{mode}: {k}"]
+            print(name, variant, mode, "over the bound:", bad, flush=True)
+    doc["labels"][label] = {"worst": [fig(worst[0]) if math.isfinite(worst[0]) else "nan", worst[1]], "cases_over_bound": failing, "cases": rows}
+    dump = lambda v: json.dumps(v, separators=(",", ":"))
+    lines = ["{", f'"bound": {dump(doc["bound"])},', f'"what": {dump(doc["what"])},', '"labels": {']
+    blocks = []
+    for lab, rec in doc["labels"].items():
+        body = ",\n".join(f'"{k}": {dump(v)}' for k, v in rec["cases"].items())
+        blocks.append(f'"{lab}": {{"worst": {dump(rec["worst"])}, "cases_over_bound": {rec["cases_over_bound"]}, "cases": {{\n{body}\n}}}}')
+    lines += [",\n".join(blocks), "}", "}"]
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print(label, "worst", worst, "cases over the bound:", failing, "of", len(rows))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_parity_f64.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--no-models", action="store_true")
+    ap.add_argument("--bn-scales", metavar="LABEL", default=None)
     a = ap.parse_args()
+    if a.bn_scales is not None:
+        return bn_scales(a.bn_scales, a.out or os.path.join(ROOT, "profiles", "train_parity_bn_scales.json"))
+    a.out = a.out or os.path.join(ROOT, "profiles", "train_parity_f64.json")
     blocks, worst = {}, {"fp32": [0.0, ""], "bf16x3": [0.0, ""], "float32_cpu": [0.0, ""]}
     for name in R.CASES:
         case = R.tie_free_case(name)
