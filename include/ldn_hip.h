@@ -319,6 +319,47 @@ int ldn_rows_postmask_bwd(const float* dz, int lddz, const float* r, int ldr, co
                           const int32_t* row_prefix, int B, const float* gate, const float* dsq, const int32_t* m_count, int m_cap, int C,
                           float* du, int lddu, float* g_shift, float* g_scale_num, float* g_mask, float* work, void* stream);
 
+/* ---- BatchNorm on BATCH statistics over packed rows, forward and backward (csrc/ldn_train_bn.hip): ldn_rows_bn_stats, ldn_rows_bn_fwd and
+ * ldn_rows_bn_bwd -- training on the reference's own recipe, where bn1 / bn2 / bn3 normalise with the statistics of the batch.  Row kernels with
+ * the conventions above: [m_cap][ld >= C] fp32 matrices, C % 4 == 0, ld % 4 == 0, 16-byte aligned pointers (row_scale excepted), count and
+ * img(r) as above, rows r >= count NOT READ.  fp32 arithmetic whatever the math mode of the convolutions around them.
+ *   x[r][k] = chan_mask ? chan_mask[img(r)][k] * u[r][k] : u[r][k]      chan_mask c [B][C] (NULL = all ones; needs row_prefix [B + 1], B >= 1):
+ *             the reference's channel mask in front of bn1 / bn2 -- a channel dropped in one image contributes ZEROS to the batch statistics.
+ *             u itself is the UNMASKED convolution output.
+ *
+ * ldn_rows_bn_stats:  mean[k], var[k] = the mean and the BIASED variance of x over the rows below the count, invstd[k] = 1 / sqrt(var[k] + eps).
+ * Never E[x^2] - E[x]^2: a thread runs Welford's update over its rows, and (n, mean, M2) triples are merged pairwise with Chan's formula, the
+ * row lanes of a workgroup in ascending order, then -- second launch -- the workgroups in ascending order.  count == 0: mean = var = 0,
+ * invstd = 1 / sqrt(eps).  The split of the rows over workgroups is the plan of ldn_rows_act_bwd, a function of m_cap and C only (graph-capturable);
+ * partials go to `work` (ldn_rows_bn_stats_workspace_bytes(m_cap, C); never NULL).  No atomics: two runs are bit-identical. */
+size_t ldn_rows_bn_stats_workspace_bytes(int m_cap, int C);
+int ldn_rows_bn_stats(const float* u, int ldu, const float* chan_mask, const int32_t* row_prefix, int B, const int32_t* m_count, int m_cap,
+                      int C, float eps, float* mean, float* var, float* invstd, float* work, void* stream);
+
+/* ldn_rows_bn_fwd, one launch, one thread per (row, quad):
+ *   h[r][k] = row_scale[r] * act(gamma[k] * (x[r][k] - mean[k]) * invstd[k] + beta[k])      act = relu ? max(., 0) : identity
+ * row_scale [m_cap] (NULL = ones): a per-row factor, the {0,1} pixel mask on bn3's output.  h [m_cap][ldh]: exactly 0 on rows >= count. */
+int ldn_rows_bn_fwd(const float* u, int ldu, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                    const float* chan_mask, const int32_t* row_prefix, int B, const float* row_scale, int relu, const int32_t* m_count,
+                    int m_cap, int C, float* h, int ldh, void* stream);
+
+/* ldn_rows_bn_bwd: the backward of ldn_rows_bn_fwd THROUGH the batch statistics, given dh = d L / d h.  Per element of a row r < count:
+ *   xhat = (x - mean[k]) * invstd[k]
+ *   dz   = row_scale[r] * (h == NULL || h[r][k] > 0 ? dh[r][k] : 0)      the ReLU gate is READ from the stored forward output h [m_cap][ldh]
+ *                                                                         (h > 0 <=> gamma * xhat + beta > 0); h NULL: the forward had no ReLU
+ *   d_beta[k]  = sum_r dz          d_gamma[k] = sum_r dz * xhat          (launches 1 and 2; right at gamma == 0 too)
+ *   g    = gamma[k] * invstd[k] * (dz - d_beta[k] / n - xhat * d_gamma[k] / n)        n = count      (= d L / d x)
+ *   du[r][k] = chan_mask ? chan_mask[img(r)][k] * g : g                   (launch 3; = d L / d u; du may be dh itself; exactly 0 on rows >= count)
+ *   g_mask[b][k] = sum_{r of image b} g * u[r][k]      [B][C], NULL = not wanted: the channel mask's straight-through gradient, fused into
+ *                                                       launch 3 (per-image (split + b) slots as ldn_rows_act_bwd's) plus a fourth small launch
+ * Deterministic like ldn_rows_act_bwd, with its split plan; partials go to `work` (ldn_rows_bn_bwd_workspace_bytes(m_cap, C, B); B = 0 without
+ * g_mask; never NULL).  No floating-point atomics. */
+size_t ldn_rows_bn_bwd_workspace_bytes(int m_cap, int C, int B);
+int ldn_rows_bn_bwd(const float* dh, int lddh, const float* u, int ldu, const float* h, int ldh, const float* mean, const float* invstd,
+                    const float* gamma, const float* chan_mask, const int32_t* row_prefix, int B, const float* row_scale,
+                    const int32_t* m_count, int m_cap, int C, float* du, int lddu, float* d_gamma, float* d_beta, float* g_mask, float* work,
+                    void* stream);
+
 /* ldn_rows_ln_bwd: the LayerNorm backward on LISTED rows (a token-skip block's norm1 / norm2 in training).  For every list entry r < count
  * (count = clamp(*count, 0, m_cap), read on the device; list NULL: the rows 0 .. m_cap - 1 themselves), src = list[r]:
  *   x^ = (x[src] - mean) * rstd        {mean, rstd} = stats[src] (ldn_row_stats / ldn_row_stats_list; formed from the difference, so a row with

@@ -36,15 +36,9 @@
 //     g_mask[b, k]   += dh * r              (every channel: non-zero exactly where the activation is on, masked channels included)
 // ldn_rows_img_dot is its per-image reduction alone: out[b, k] = sum over the rows of image b of a[r, k] * b[r, k].  Both use act_plan and the
 // (split + b) slots of ldn_rows_act_bwd.
-#include "ldn_common.h"
+#include "ldn_rows_plan.h"      // thread-layout constants, rows_count, image_of_row, act_plan, aligned16
 
 namespace ldn {
-
-constexpr int ACT_THREADS = 256;
-constexpr int ACT_QT = 64;             // quads per column tile (256 channels)
-constexpr int ACT_MIN_SPLIT_ROWS = 64;
-constexpr int ACT_TARGET_WGS = 2048;
-constexpr int ACT_MAX_SPLITS = 256;
 
 struct ActArgs {
     const float* dh; const float* u; const float* post_sub; const float* scale; const float* shift; const float* chan_mask;
@@ -52,21 +46,6 @@ struct ActArgs {
     float* du; float* g_shift; float* g_scale; float* g_mask; float* work;
     int lddh, ldu, ldzy, lddu, B, m_cap, C, splits, rps;
 };
-
-__device__ __forceinline__ int rows_count(const int32_t* m_count, int m_cap) {
-    int c = m_count ? *m_count : m_cap;
-    return c < 0 ? 0 : (c > m_cap ? m_cap : c);
-}
-
-// the image b in [0, B) with prefix[b] <= r < prefix[b + 1] (images without rows are stepped over; rows past prefix[B] fall to B - 1)
-__device__ __forceinline__ int image_of_row(const int32_t* prefix, int B, int r) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (prefix[mid + 1] > r) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
 
 // work layout: [splits][C] g_shift partials | [splits][C] g_scale_num partials | [splits + B][C] g_mask partials
 __device__ __forceinline__ float* act_work_shift(const ActArgs& p) { return p.work; }
@@ -171,18 +150,6 @@ __global__ __launch_bounds__(ACT_THREADS) void k_rows_act_bwd(const ActArgs p) {
         *reinterpret_cast<f32x4*>(act_work_shift(p) + (size_t)split * p.C + k) = s1;
         *reinterpret_cast<f32x4*>(act_work_scale(p) + (size_t)split * p.C + k) = s2;
     }
-}
-
-// the sum of image b's (split + b) slots in ascending split order (zero for an image without rows below the count)
-__device__ __forceinline__ f32x4 image_slots_sum(const float* slots, const int32_t* prefix, int B, int b, int count, int splits, int rps, int C, int k) {
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    const int lo = min(prefix[b], count), hi = b == B - 1 ? count : min(prefix[b + 1], count);     // (the walk of k_rows_act_bwd)
-    if (lo < hi) {
-        // image b meets the splits lo / rps .. (hi - 1) / rps -- unless an earlier image reaches past prefix[b] (never with a monotone prefix)
-        const int t_hi = min(splits - 1, (hi - 1) / rps);
-        for (int t = lo / rps; t <= t_hi; ++t) s += *reinterpret_cast<const f32x4*>(slots + (size_t)(t + b) * C + k);
-    }
-    return s;
 }
 
 // one thread per quad of g_shift (j == 0), g_scale_num (j == 1) and g_mask[b] (j == 2 + b): the partials in ascending split order
@@ -371,20 +338,6 @@ __global__ __launch_bounds__(256) void k_img_dot_reduce(const DotArgs p) {
     *reinterpret_cast<f32x4*>(p.out + (size_t)b * p.C + k) =
         image_slots_sum(p.work, p.prefix, p.B, b, rows_count(p.m_count, p.m_cap), p.splits, p.rps, p.C, k);
 }
-
-// the launch plan: a function of m_cap and C ONLY
-static void act_plan(int m_cap, int C, int* tiles, int* splits, int* rps) {
-    *tiles = ceil_div(C / 4, ACT_QT);
-    int s = ceil_div(ACT_TARGET_WGS, *tiles);
-    const int most = m_cap / ACT_MIN_SPLIT_ROWS;
-    if (s > most) s = most;
-    if (s > ACT_MAX_SPLITS) s = ACT_MAX_SPLITS;
-    if (s < 1) s = 1;
-    *rps = ceil_div(m_cap > 0 ? m_cap : 1, s);
-    *splits = ceil_div(m_cap > 0 ? m_cap : 1, *rps);
-}
-
-static bool aligned16(const void* ptr) { return (uintptr_t)ptr % 16 == 0; }
 
 // ---- ldn_rows_ln_bwd: the LayerNorm backward on listed rows.  One WAVE per row (the row sums are wave reductions: lane l owns the quads l, l + 64, ...
 // of the row, at most LN_MAXQ of them); a workgroup of four waves owns the list entries [split * rps, + rps), wave w every fourth of them.  The lanes'

@@ -718,7 +718,105 @@ def rows_postmask_bwd(dz2d, r2d, scale, shift, *, chan_mask=None, row_prefix=Non
     return out[:m_cap, :C] if tuple(out.shape) != (m_cap, C) else out, g_shift, g_scale, g_mask
 
 
-USE_ROWS_PS = os.environ.get("LDN_ROWS_PS", "1") != "0"     # the pre-split packed path (k_dense<PS / OF> + k_rows3); 0 = round 4's three launches
+def _bn_mask_args(what, C, chan_mask, row_prefix):
+    """(B, chan_mask, row_prefix) of a batch-statistics BatchNorm call, checked: a channel mask [B, C] comes with row_prefix [B + 1]"""
+    if C % 4:
+        raise L.LdnError(f"{what}: C % 4 == 0 (got {C})")
+    if chan_mask is None and row_prefix is None:
+        return 0
+    if row_prefix is None or row_prefix.numel() < 2:
+        raise L.LdnError(f"{what}: chan_mask / want_mask need row_prefix [B + 1]")
+    B = row_prefix.numel() - 1
+    if chan_mask is not None and tuple(chan_mask.shape) != (B, C):
+        raise L.LdnError(f"{what}: chan_mask must be [{B}, {C}], got {tuple(chan_mask.shape)}")
+    return B
+
+
+def rows_bn_stats(u2d, eps=1e-5, *, chan_mask=None, row_prefix=None, m_count=None, m_cap=None):
+    """Batch statistics of a BatchNorm over packed rows (see ldn_rows_bn_stats): per channel the mean and the BIASED variance of
+    x = chan_mask[img(r)] * u2d[r] over the rows below the device-side count, and invstd = 1 / sqrt(var + eps) -> (mean, var, invstd), [C] each,
+    C = u2d.shape[1] (a column slice of a wider matrix is fine).  Welford per thread, Chan's pairwise merge in ascending order: never
+    E[x^2] - E[x]^2.  chan_mask [B, C] (None = ones) needs row_prefix [B + 1].  No rows: (0, 0, 1 / sqrt(eps)).  Deterministic, no atomics."""
+    L.require_device(u2d, chan_mask, row_prefix, m_count)
+    lib = L.load()
+    if u2d.dim() != 2:
+        raise L.LdnError(f"rows_bn_stats: u2d must be [rows, C], got {tuple(u2d.shape)}")
+    C = u2d.shape[1]
+    B = _bn_mask_args("rows_bn_stats", C, chan_mask, row_prefix if chan_mask is not None else None)
+    m_cap = _rows_cap(m_cap, "rows_bn_stats", u2d)
+    mean, var, invstd = (torch.empty(C, device=u2d.device, dtype=torch.float32) for _ in range(3))
+    work = _work(lib.ldn_rows_bn_stats_workspace_bytes(m_cap, C), u2d.device)
+    L.check(lib.ldn_rows_bn_stats(L.ptr(_f32rows(u2d, "u")), u2d.stride(0), L.ptr(_f32c(chan_mask, "chan_mask")),
+                                  L.ptr(_i32c(row_prefix, "row_prefix")), B, L.ptr(_i32c(m_count, "m_count")), m_cap, C, float(eps), L.ptr(mean),
+                                  L.ptr(var), L.ptr(invstd), L.ptr(work), L.stream_ptr(mean)), "ldn_rows_bn_stats")
+    return mean, var, invstd
+
+
+def rows_bn_fwd(u2d, mean, invstd, gamma, beta, *, chan_mask=None, row_prefix=None, row_scale=None, relu=True, m_count=None, m_cap=None, out=None):
+    """BatchNorm on given batch statistics over packed rows, one launch (see ldn_rows_bn_fwd):
+    h = row_scale[r] * relu?(gamma * (chan_mask[img(r)] * u2d[r] - mean) * invstd + beta) -> out [m_cap, C] (allocated unless given), exact
+    zeros on the rows past the device-side count.  mean / invstd from rows_bn_stats WITH THE SAME chan_mask; row_scale [m_cap] (None = ones): the
+    {0,1} pixel mask on bn3's output."""
+    L.require_device(u2d, mean, invstd, gamma, beta, chan_mask, row_prefix, row_scale, m_count, out)
+    C = gamma.numel()
+    for name, t in (("u", u2d), ("out", out)):
+        if t is not None and (t.dim() != 2 or t.shape[1] < C):
+            raise L.LdnError(f"rows_bn_fwd: {name} must be [rows, >= {C}], got {tuple(t.shape)}")
+    if any(v.numel() != C for v in (mean, invstd, beta)):
+        raise L.LdnError("rows_bn_fwd: mean / invstd / gamma / beta must be [C]")
+    B = _bn_mask_args("rows_bn_fwd", C, chan_mask, row_prefix if chan_mask is not None else None)
+    m_cap = _rows_cap(m_cap, "rows_bn_fwd", u2d, out)
+    if row_scale is not None and row_scale.numel() < m_cap:
+        raise L.LdnError(f"rows_bn_fwd: row_scale has {row_scale.numel()} entries for m_cap {m_cap}")
+    if out is None:
+        out = torch.empty(m_cap, C, device=u2d.device, dtype=torch.float32)
+    L.check(L.load().ldn_rows_bn_fwd(L.ptr(_f32rows(u2d, "u")), u2d.stride(0), L.ptr(_f32c(mean, "mean")), L.ptr(_f32c(invstd, "invstd")),
+                                     L.ptr(_f32c(gamma, "gamma")), L.ptr(_f32c(beta, "beta")), L.ptr(_f32c(chan_mask, "chan_mask")),
+                                     L.ptr(_i32c(row_prefix, "row_prefix")), B, L.ptr(_f32c(row_scale, "row_scale")), 1 if relu else 0,
+                                     L.ptr(_i32c(m_count, "m_count")), m_cap, C, L.ptr(_f32rows(out, "out")), out.stride(0),
+                                     L.stream_ptr(out)), "ldn_rows_bn_fwd")
+    return out[:m_cap, :C] if tuple(out.shape) != (m_cap, C) else out
+
+
+def rows_bn_bwd(dh2d, u2d, h2d, mean, invstd, gamma, *, chan_mask=None, row_prefix=None, row_scale=None, want_mask=False, m_count=None,
+                m_cap=None, out=None):
+    """Backward of rows_bn_fwd THROUGH the batch statistics (see ldn_rows_bn_bwd), given dh2d = d L / d h, the unmasked u2d and the stored
+    forward output h2d (the ReLU gate is read from it: h > 0; None = the forward had no ReLU):  dz = row_scale[r] * gate * dh,
+    d_beta = sum dz, d_gamma = sum dz * xhat, g = gamma * invstd * (dz - d_beta / n - xhat * d_gamma / n) with n the device-side count,
+    du = chan_mask[img(r)] * g.  -> (du [m_cap, C], d_gamma [C], d_beta [C], g_mask [B, C] = sum over the image's rows of g * u with want_mask
+    -- the channel mask's straight-through gradient, fused into the last pass -- else None).  chan_mask and want_mask need row_prefix [B + 1].
+    out: a [m_cap, >= C] matrix for du (dh2d itself is allowed); exact zeros on the rows past the count.  Three launches, four with want_mask;
+    deterministic, no atomics."""
+    L.require_device(dh2d, u2d, h2d, mean, invstd, gamma, chan_mask, row_prefix, row_scale, m_count, out)
+    lib = L.load()
+    C = gamma.numel()
+    for name, t in (("dh", dh2d), ("u", u2d), ("h", h2d), ("out", out)):
+        if t is not None and (t.dim() != 2 or t.shape[1] < C):
+            raise L.LdnError(f"rows_bn_bwd: {name} must be [rows, >= {C}], got {tuple(t.shape)}")
+    if mean.numel() != C or invstd.numel() != C:
+        raise L.LdnError("rows_bn_bwd: mean / invstd / gamma must be [C]")
+    B = _bn_mask_args("rows_bn_bwd", C, chan_mask, row_prefix if (chan_mask is not None or want_mask) else None)
+    if want_mask and B == 0:
+        raise L.LdnError("rows_bn_bwd: chan_mask / want_mask need row_prefix [B + 1]")
+    m_cap = _rows_cap(m_cap, "rows_bn_bwd", dh2d, u2d, h2d, out)
+    if row_scale is not None and row_scale.numel() < m_cap:
+        raise L.LdnError(f"rows_bn_bwd: row_scale has {row_scale.numel()} entries for m_cap {m_cap}")
+    dev = dh2d.device
+    if out is None:
+        out = torch.empty(m_cap, C, device=dev, dtype=torch.float32)
+    d_gamma = torch.empty(C, device=dev, dtype=torch.float32)
+    d_beta = torch.empty(C, device=dev, dtype=torch.float32)
+    g_mask = torch.empty(B, C, device=dev, dtype=torch.float32) if want_mask else None
+    work = _work(lib.ldn_rows_bn_bwd_workspace_bytes(m_cap, C, B if want_mask else 0), dev)
+    L.check(lib.ldn_rows_bn_bwd(L.ptr(_f32rows(dh2d, "dh")), dh2d.stride(0), L.ptr(_f32rows(u2d, "u")), u2d.stride(0), L.ptr(_f32rows(h2d, "h")),
+                                h2d.stride(0) if h2d is not None else 0, L.ptr(_f32c(mean, "mean")), L.ptr(_f32c(invstd, "invstd")),
+                                L.ptr(_f32c(gamma, "gamma")), L.ptr(_f32c(chan_mask, "chan_mask")), L.ptr(_i32c(row_prefix, "row_prefix")), B,
+                                L.ptr(_f32c(row_scale, "row_scale")), L.ptr(_i32c(m_count, "m_count")), m_cap, C, L.ptr(_f32rows(out, "out")),
+                                out.stride(0), L.ptr(d_gamma), L.ptr(d_beta), L.ptr(g_mask), L.ptr(work), L.stream_ptr(out)), "ldn_rows_bn_bwd")
+    return out[:m_cap, :C] if tuple(out.shape) != (m_cap, C) else out, d_gamma, d_beta, g_mask
+
+
+USE_ROWS_PS = os.environ.get("LDN_ROWS_PS", "1") != "0"    # the pre-split packed path (k_dense<PS / OF> + k_rows3); 0 = round 4's three launches
 
 
 ROWS_PS_MAX_WIDTH = 2048     # = ROWS3_MAX_CIN of csrc/ldn_rows3.hip

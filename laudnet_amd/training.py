@@ -1,7 +1,8 @@
-"""Training under FROZEN BatchNorm on the library's row kernels.
+"""Training under FROZEN BatchNorm on the library's row kernels -- and, behind USE_BATCH_STATS, on batch
+statistics.
 
 The reference's ImageNet recipe is dense by construction (BatchNorm in batch-statistics mode, `models/laud_resnet.py:115-133`): nothing
-to accelerate.  Its DETECTION fine-tuning freezes the BatchNorm STATISTICS (`norm_eval=True`, `mmdetection-2.21.0/mmdet/models/backbones/
+to accelerate (it trains, dense, behind USE_BATCH_STATS: further down).  Its DETECTION fine-tuning freezes the BatchNorm STATISTICS (`norm_eval=True`, `mmdetection-2.21.0/mmdet/models/backbones/
 lad_mmdet_resnet.py:753-758`) while the affine parameters keep training (`norm_cfg=dict(type='BN', requires_grad=True)`); the configs it
 ships are channel-2222 and layer (`configs/retinanet/scale_backbone_lr/retinanet_ladmmdet_r101_fpn_1x_coco_r101_channel_2222_0x6_lrmult0x2.py:8-17`,
 `..._layer_0x5_lrmult0x2.py:8-17`).  Under frozen statistics a block is
@@ -39,7 +40,7 @@ scale, which may be zero, tiny or negative) is written once above them.  The ind
 Entry points: `sparse_block_train(block, x, mask)` (one block, the mask an input), `block_train(block, state, temperature)` (the reference's
 block signature in training mode: samples its own masks), `train_forward(model, x, temperature)` (a whole LAUD-ResNet -> the reference's
 7-tuple; a `LAD_MMDet_ResNet` -> its (outs, additional, model_configs)), `prepare_for_training(model)` (train mode with BatchNorm statistics
-frozen).  Checked against the oracle's autograd -- blocks on the reference-generated block fixtures, whole models on `det_tiny.pt` /
+frozen; batch_stats=True: on batch statistics).  Checked against the oracle's autograd -- blocks on the reference-generated block fixtures, whole models on `det_tiny.pt` /
 `full_tiny.pt` with identical Gumbel noise (tests/test_hip_training.py, tests/test_hip_training_both.py, plain 1e-3; bf16x3 with a flip
 allowance) -- and, element by element to 1e-3 of each gradient's own maximum in both arithmetic modes, against a float64 restatement on inputs
 where no ReLU can flip (tests/test_hip_training_f64.py, tests/train_ref.py), the same with zero, +-2^-24 and negative BatchNorm weights
@@ -59,8 +60,23 @@ relu(zy) and the upstream gradient at the masked channels too -- and its backwar
 (SE prologue, mask, ReLU gate, scale; d shift, d scale, d mask: two launches per layer, deterministic) plus `ops.rows_img_dot` (the SE's d gate)
 (tests/test_hip_rows_postmask.py, tests/test_regnet_channel_ref.py, tests/test_hip_training_regnet_channel.py).
 
-Not built: mask groups > 1, dilated conv2, grouped conv2 outside the LAD-RegNet blocks, BatchNorm in batch-statistics mode, LAD-RegNet 'both' /
-patch-mask (mask_size > 1) training."""
+BatchNorm on BATCH statistics -- what all three commands of the reference's train_scripts.sh and train/main.py:527-604 train with: plain
+model.train() -- trains for LAUD-ResNet blocks behind USE_BATCH_STATS (env LDN_TRAIN_BATCH_STATS=1; default OFF: with it off a block whose
+BatchNorm is in training mode is refused as before).  `_BatchStatsBranchFn` serves all four dyn_modes (optional channel mask, optional pixel mask):
+    u1 = c . conv1(x)   h1 = relu(BN(u1))     u2 = c . conv2(h1)   h2 = relu(BN(u2))     u3 = conv3(h2)   branch = m3 * BN(u3)
+over ALL pixels at any stride.  bn1 / bn2 / bn3 see every pixel and every channel, dropped or not, so this mode is dense by construction: THE
+MASKS SAVE NO FLOPs IN IT (stated, not hidden).  The convolutions, their adjoints and weight gradients are the kernels above with scale 1 / shift 0
+/ no ReLU (nothing is folded: no _split_scale, bn.weight == 0 is no special case); BatchNorm's forward and its backward through the statistics are
+`ops.rows_bn_stats` / `ops.rows_bn_fwd` / `ops.rows_bn_bwd` (csrc/ldn_train_bn.hip: Welford + Chan's merge, never E[u^2] - E[u]^2; the channel
+mask in front of the statistics, the pixel mask as a row factor; d gamma, d beta, d u and the channel mask's straight-through sum in three / four
+launches per layer; deterministic).  The running statistics are updated once per forward, under no_grad, never in the backward (momentum, the
+unbiased variance, num_batches_tracked; momentum=None = the cumulative average).  The stem's, the projection's and the conv_linear masker's
+BatchNorms are plain modules.  `prepare_for_training(model, batch_stats=True)` leaves BatchNorm in training mode; block_train and
+train_forward(ResNet) are unchanged (tests/test_bn_batch_ref.py, tests/test_hip_rows_bn.py, tests/test_hip_training_batchstats.py).
+
+Not built: mask groups > 1, dilated conv2, grouped conv2 outside the LAD-RegNet blocks, BatchNorm on batch statistics for LAD-RegNet and the
+detection backbone, SyncBatchNorm / cross-rank statistics, a block with some BatchNorms frozen and some not, LAD-RegNet 'both' / patch-mask
+(mask_size > 1) training."""
 from __future__ import annotations
 
 import functools
@@ -83,6 +99,11 @@ USE_WGRAD_KERNEL = os.environ.get("LDN_WGRAD", "1") != "0"
 # LAD-RegNet channel-mode training (_RegNetChannelBranchFn); env LDN_TRAIN_REGNET_CHANNEL=1 turns it on.  Off by default: with it off every
 # LAD-RegNet form but layer skip is refused, as before the path existed
 USE_REGNET_CHANNEL = os.environ.get("LDN_TRAIN_REGNET_CHANNEL", "0") == "1"
+
+
+# BatchNorm on BATCH statistics in LAUD-ResNet blocks (_BatchStatsBranchFn on ops.rows_bn_*): the reference's own ImageNet recipe; env
+# LDN_TRAIN_BATCH_STATS=1 turns it on.  Off by default: with it off a block whose BatchNorm is in training mode is refused, as before the path existed
+USE_BATCH_STATS = os.environ.get("LDN_TRAIN_BATCH_STATS", "0") == "1"
 
 
 # ------------------------------------------------------------------------------------------------------------------ index helpers
@@ -715,6 +736,124 @@ class _RegNetChannelBranchFn(torch.autograd.Function):
                 None, None, None)
 
 
+# ------------------------------------------------------------------------------------------------------------------ batch statistics
+class _BatchStatsBranchFn(torch.autograd.Function):
+    """branch = m3 * bn3(conv3(relu(bn2(c . conv2(relu(bn1(c . conv1(x))))))))  with bn1 / bn2 / bn3 on the statistics of THE BATCH (laud_resnet.py:115-133
+    in plain model.train(): the reference's ImageNet recipe), for all four dyn_modes: the pixel mask m3 [B, 1, Ho, Wo] and the channel mask c [B, W]
+    are both optional.  Dense by construction -- every BatchNorm sees every pixel and every channel, dropped or not, so NEITHER mask saves FLOPs
+    here: the convolutions run over all pixels (ix = the cached dense_index, any stride) on ops.conv_rows with scale 1 / shift 0 / no ReLU and
+    store the UNMASKED outputs y; nothing is folded, so there is no _split_scale and bn.weight == 0 is no special case.  BatchNorm is
+    ops.rows_bn_stats (two launches) + ops.rows_bn_fwd (one) with the channel mask applied in front of both -- a channel dropped in one image
+    contributes zeros to the statistics -- and, in the backward, ops.rows_bn_bwd: d gamma, d beta, the gradient through the statistics, the
+    channel mask and its straight-through term sum_p d u . y in three (four) launches per layer.  The pixel mask is a per-row factor of layer 3's
+    forward and backward; its own gradient sum_k g . bn3(..) re-runs rows_bn_fwd without the factor.
+    Inputs: x, the three weights, m3 or None, c or None, (gamma, beta) x 3; eps3 = the three eps.  Returns (branch, mean1, var1, mean2, var2,
+    mean3, var3): the batch statistics (biased variances) are non-differentiable outputs -- _branch updates the running statistics from them,
+    once per forward and never in the backward."""
+
+    @staticmethod
+    def forward(ctx, x, w1, w2, w3, m3, chm, g1, b1, g2, b2, g3, b3, eps3, stride, ix):
+        one = torch.ones((), device=x.device)
+        p = _prep(x, w1, w2, w3, (g1, b1, g2, b2, g3, b3), stride)
+        B, _, _, _, Ho, Wo, W, cout = p.shape
+        g1, b1, g2, b2, g3, b3 = p.bn
+        dev = x.device
+        chm2d = None if chm is None else chm.detach().float().reshape(B, W).contiguous()
+        m3r = None if m3 is None else m3.detach().float().reshape(B * Ho * Wo).contiguous()
+        pre1, pre3 = (ix.pre1, ix.pre3) if chm2d is not None else (None, None)
+        zW, zc = torch.zeros(W, device=dev), torch.zeros(cout, device=dev)
+        y1 = torch.empty(ix.cap1, W, device=dev)
+        ops.conv_rows(p.x2d, p.w1r, None, zW, y1, a_rows=ix.idx1, taps=1, m_cap=ix.cap1, relu=0)
+        mean1, var1, inv1 = ops.rows_bn_stats(y1, eps3[0], chan_mask=chm2d, row_prefix=pre1, m_cap=ix.cap1)
+        h1 = ops.rows_bn_fwd(y1, mean1, inv1, g1, b1, chan_mask=chm2d, row_prefix=pre1, m_cap=ix.cap1)
+        y2 = torch.empty(ix.cap3, W, device=dev)
+        ops.conv_rows(h1, p.w2r, None, zW, y2, a_rows=ix.nbr, taps=9, m_cap=ix.cap3, relu=0)
+        mean2, var2, inv2 = ops.rows_bn_stats(y2, eps3[1], chan_mask=chm2d, row_prefix=pre3, m_cap=ix.cap3)
+        h2 = ops.rows_bn_fwd(y2, mean2, inv2, g2, b2, chan_mask=chm2d, row_prefix=pre3, m_cap=ix.cap3)
+        y3 = torch.empty(ix.cap3, cout, device=dev)
+        ops.conv_rows(h2, p.w3r.reshape(cout, 1, W), None, zc, y3, taps=1, m_cap=ix.cap3, relu=0)
+        mean3, var3, inv3 = ops.rows_bn_stats(y3, eps3[2], m_cap=ix.cap3)
+        br = ops.rows_bn_fwd(y3, mean3, inv3, g3, b3, row_scale=m3r, relu=False, m_cap=ix.cap3)
+        ctx.save_for_backward(p.x2d, y1, h1, y2, h2, y3, p.w1r, p.w2r, p.w3r, g1, g2, g3, b3, mean1, inv1, mean2, inv2, mean3, inv3,
+                              one if chm2d is None else chm2d, one if m3r is None else m3r)
+        ctx.ix, ctx.shape, ctx.stride, ctx.masks = ix, p.shape, stride, (m3r is not None, chm2d is not None)
+        ctx.math_mode = ops.get_math_mode()
+        stats = (mean1, var1, mean2, var2, mean3, var3)
+        ctx.mark_non_differentiable(*stats)
+        return (ops.from_nhwc(br.view(B, Ho, Wo, cout)),) + stats
+
+    @staticmethod
+    @_in_forward_mode
+    def backward(ctx, g, *_stats):
+        x2d, y1, h1, y2, h2, y3, w1r, w2r, w3r, g1, g2, g3, b3, mean1, inv1, mean2, inv2, mean3, inv3, chm2d, m3r = ctx.saved_tensors
+        ix, shape, stride, need, dev = ctx.ix, ctx.shape, ctx.stride, ctx.needs_input_grad, g.device
+        B, _, _, _, Ho, Wo, W, cout = shape
+        has_m3, has_c = ctx.masks
+        m3r, chm2d = m3r if has_m3 else None, chm2d if has_c else None
+        pre1, pre3 = (ix.pre1, ix.pre3) if has_c else (None, None)
+        want_c = has_c and need[5]
+        go = ops.as_nhwc(g.contiguous()).reshape(-1, cout)                       # [B Ho Wo, cout] = d L / d branch
+        zW = torch.zeros(W, device=dev)
+        gm = None
+        if has_m3 and need[4]:      # the pixel mask's straight-through term needs bn3's output at the dropped pixels: the forward's launch without the factor
+            z3 = ops.rows_bn_fwd(y3, mean3, inv3, g3, b3, relu=False, m_cap=ix.cap3)
+            gm = (go * z3).sum(1).view(B, 1, Ho, Wo)
+        # per layer: ONE rows_bn_bwd (pixel / channel mask, ReLU gate read from the stored h, d gamma, d beta, the statistics' terms, d mask) -> d L / d y,
+        # then the transposed convolution with the plain weights
+        dy3, gg3, gb3, _ = ops.rows_bn_bwd(go, y3, None, mean3, inv3, g3, row_scale=m3r, m_cap=ix.cap3)
+        dh2 = _conv3_T(dy3, w3r.reshape(cout, 1, W), zW, None, ix.cap3, torch.empty)
+        dy2, gg2, gb2, gc2 = ops.rows_bn_bwd(dh2, y2, h2, mean2, inv2, g2, chan_mask=chm2d, row_prefix=pre3, want_mask=want_c, m_cap=ix.cap3, out=dh2)
+        dh1 = _conv2_T(dy2, w2r, zW, ix, shape, stride, None, torch.empty)
+        dy1, gg1, gb1, gc1 = ops.rows_bn_bwd(dh1, y1, h1, mean1, inv1, g1, chan_mask=chm2d, row_prefix=pre1, want_mask=want_c, m_cap=ix.cap1, out=dh1)
+        grad_x = _grad_x(dy1, w1r, ix, None, shape) if need[0] else None
+        gw1, gw2, gw3 = _weight_grads(need[1], need[2], need[3], dy3, h2, dy2, h1, dy1, x2d, ix, counted=False)
+        gc = gc1 + gc2 if want_c else None
+        keep = lambda v, n: v if n else None
+        return (grad_x, gw1, gw2, gw3, gm, gc, keep(gg1, need[6]), keep(gb1, need[7]), keep(gg2, need[8]), keep(gb2, need[9]), keep(gg3, need[10]),
+                keep(gb3, need[11]), None, None, None)
+
+
+def _update_running_stats(bn, mean, var, n):
+    """BatchNorm's own bookkeeping in training mode from the batch statistics of one forward (biased var over n values per channel):
+    num_batches_tracked += 1, running = (1 - f) running + f batch with the UNBIASED variance var n / (n - 1), f = momentum or, with
+    momentum=None, the cumulative average 1 / num_batches_tracked.  No host read."""
+    with torch.no_grad():
+        bn.num_batches_tracked += 1
+        f = 1.0 / bn.num_batches_tracked.to(torch.float32) if bn.momentum is None else bn.momentum
+        bn.running_mean.mul_(1.0 - f).add_(mean * f)
+        bn.running_var.mul_(1.0 - f).add_(var * (f * (n / max(n - 1, 1))))
+
+
+def _batch_stats_branch(block, x, mask):
+    """_branch's middle for a LAUD-ResNet block whose BatchNorms are in training mode (USE_BATCH_STATS): -> (branch, ix), running statistics updated"""
+    bns = (block.bn1, block.bn2, block.bn3)
+    if any(not bn.track_running_stats or bn.running_mean is None for bn in bns):
+        raise LdnError("training: batch statistics need track_running_stats=True (running statistics to update)")
+    if any(bn.weight is None for bn in bns):
+        raise LdnError("training: batch statistics need affine BatchNorm")
+    m3 = chm = None
+    if block.dyn_mode in ("spatial", "layer"):
+        m3 = _spatial_m3(block, x, mask)
+    elif block.dyn_mode == "channel":
+        chm = _expand_channel_mask(block, x, mask)
+    elif block.dyn_mode == "both":
+        if not isinstance(mask, (tuple, list)) or len(mask) != 2:
+            raise LdnError("training: a dyn_mode 'both' block takes mask = (spatial [B, 1, S, S], channel [B, G]), not a single tensor")
+        m3, chm = _spatial_m3(block, x, mask[0]), _expand_channel_mask(block, x, mask[1])
+    else:
+        raise LdnError(f"training: unknown dyn_mode {block.dyn_mode!r}")
+    Ho, Wo = _out_size(block, x)
+    # the index lists the block REPORTS are the pixel mask's (block_train reads the dilated masks' means off them); the Fn runs on the dense ones
+    ix = _pixel_lists(m3, block.stride) if m3 is not None else None
+    dense = dense_index(x.shape[0], Ho, Wo, block.stride, x.device)
+    affine = tuple(v for bn in bns for v in (bn.weight, bn.bias))
+    branch, *stats = _BatchStatsBranchFn.apply(x, block.conv1.weight, block.conv2.weight, block.conv3.weight, m3, chm, *affine,
+                                               tuple(bn.eps for bn in bns), block.stride, dense)
+    for bn, mean, var, n in zip(bns, stats[0::2], stats[1::2], (dense.cap1, dense.cap3, dense.cap3)):      # rows = values per channel
+        _update_running_stats(bn, mean, var, n)
+    return branch, ix if ix is not None else dense
+
+
 # ------------------------------------------------------------------------------------------------------------------ blocks
 def _fold_live(bn):
     """(scale, shift) of a BatchNorm with FROZEN statistics as differentiable functions of its affine parameters."""
@@ -723,18 +862,27 @@ def _fold_live(bn):
 
 
 def _check_block(block, x):
+    """refuses what is not built; -> does the block run on batch statistics (every BatchNorm in training mode, behind USE_BATCH_STATS)?"""
     if block.conv2.groups != 1 or block.conv2.dilation[0] != 1:
         raise LdnError("training: grouped / dilated conv2 is not built")
     if not x.is_cuda:
         raise LdnError("laudnet_amd ops need tensors on a HIP device (cuda:N); there is no CPU path")
-    for bn in (block.bn1, block.bn2, block.bn3):
-        if bn.training:
-            raise LdnError("training: BatchNorm must run on its frozen statistics (norm_eval; call prepare_for_training(model)) -- the "
-                           "batch-statistics recipe is dense by construction and not built")
+    live = [bn.training for bn in (block.bn1, block.bn2, block.bn3)]
+    if any(live) and not USE_BATCH_STATS:
+        raise LdnError("training: BatchNorm must run on its frozen statistics (norm_eval; call prepare_for_training(model)) -- the "
+                       "batch-statistics recipe is dense by construction and trains only behind training.USE_BATCH_STATS (env "
+                       "LDN_TRAIN_BATCH_STATS=1, off by default)")
+    if not any(live):
+        return False
+    if block.downsample is not None:      # (the projection shortcut's BatchNorm is a plain module under autograd: it only has to be in the same mode)
+        live += [m.training for m in block.downsample.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)]
+    if not all(live):
+        raise LdnError("training: a block with some BatchNorms in training mode and some frozen is not built (all on batch statistics or all frozen)")
+    return True
 
 
 def _identity(block, x):
-    return x if block.downsample is None else block.downsample(x)      # (conv 1x1 stride s + BatchNorm on frozen statistics: plain autograd)
+    return x if block.downsample is None else block.downsample(x)      # (conv 1x1 stride s + BatchNorm in the block's mode: plain autograd)
 
 
 def _out_size(block, x):
@@ -815,7 +963,9 @@ def _branch(block, x, mask):
     block_train reads the dilated masks' means off the same object."""
     if isinstance(block, ResBottleneckBlock):
         return _branch_regnet(block, x, mask)
-    _check_block(block, x)
+    if _check_block(block, x):          # every BatchNorm on batch statistics
+        branch, ix = _batch_stats_branch(block, x, mask)
+        return F.relu(branch + _identity(block, x)), ix
     bn = _fold_live(block.bn1) + _fold_live(block.bn2) + _fold_live(block.bn3)
     w = (block.conv1.weight, block.conv2.weight, block.conv3.weight)
     if block.dyn_mode in ("spatial", "layer"):
@@ -987,10 +1137,13 @@ def _regnet_block_train(block, state, temperature):
 
 
 # ------------------------------------------------------------------------------------------------------------------ models
-def prepare_for_training(model):
+def prepare_for_training(model, batch_stats=False):
     """Train mode with the BatchNorm STATISTICS frozen (mmdet's norm_eval=True, lad_mmdet_resnet.py:753-758): every BatchNorm runs on its
-    running statistics, its affine parameters keep their requires_grad."""
+    running statistics, its affine parameters keep their requires_grad.  batch_stats=True: plain model.train() -- every BatchNorm on the
+    statistics of the batch, the reference's ImageNet recipe (LAUD-ResNet only, behind USE_BATCH_STATS)."""
     model.train()
+    if batch_stats:
+        return model
     for m in model.modules():
         if isinstance(m, torch.nn.modules.batchnorm._BatchNorm):
             m.eval()

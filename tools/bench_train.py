@@ -11,7 +11,10 @@ so about the dense emulation's time is what to expect.  `--ab-wgrad` adds `wgrad
 (training.USE_WGRAD_KERNEL) off and on ALTERNATING step by step in this one process, the median of each setting's device-event intervals.
 `ms_per_step` is the mean of the timed steps (wall clock over the loop), `ms_per_step_median` the median of the
 steps' own device-event intervals.
-usage: [LDN_WGRAD=0] tools/bench_train.py [--batch 32] [--steps 5] [--warmup 2] [--workloads layer,spatial,channel,both,regnet,regnet_channel] [--no-reference] [--ab-wgrad]"""
+`--batch-stats` is the reference's own ImageNet recipe: every BatchNorm on the statistics of the batch (plain model.train() on both legs;
+training.USE_BATCH_STATS is turned on), on the full-width LAUD-ResNet50 that train_scripts.sh trains -- LAUD-ResNet workloads only.  Dense by
+construction on both legs (the masks save no FLOPs), so about the dense emulation's time is what to expect.
+usage: [LDN_WGRAD=0] tools/bench_train.py [--batch 32] [--steps 5] [--warmup 2] [--workloads layer,spatial,channel,both,regnet,regnet_channel] [--no-reference] [--ab-wgrad] [--batch-stats]"""
 import argparse
 import json
 import os
@@ -39,6 +42,7 @@ ap.add_argument("--math", default="bf16x3")
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--no-reference", action="store_true", help="time the row kernels only (no dense emulation through PyTorch, no speedup)")
 ap.add_argument("--ab-wgrad", action="store_true", help="also time the row-kernel leg with the weight-gradient kernels off / on, alternating per step")
+ap.add_argument("--batch-stats", action="store_true", help="BatchNorm on batch statistics (plain model.train()) on a LAUD-ResNet50, both legs")
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
 ops.set_math_mode(args.math)
@@ -74,6 +78,10 @@ for w in args.workloads.split(","):
         training.USE_REGNET_CHANNEL = True
     kw = dict(wl["kw"], num_classes=1000, input_size=224)
     arch = wl.get("arch", "uni_resnet101")
+    if args.batch_stats:
+        assert not arch.startswith("lad_regnet"), "--batch-stats: LAUD-ResNet workloads only (LAD-RegNet on batch statistics is not built)"
+        training.USE_BATCH_STATS = True
+        arch, wl = "uni_resnet50", dict(wl, name=wl["name"].replace("ResNet101", "ResNet50"))
     hip = getattr(laudnet_amd, arch)(**kw)
     hip.load_state_dict(damp_residual_branches(fill_state_dict(hip.state_dict(), 1)))      # (the last BatchNorm of every residual branch x 0.3)
     hip = hip.to(dev).eval()
@@ -83,13 +91,13 @@ for w in args.workloads.split(","):
     else:
         bench.calibrate_maskers(hip, x, wl["p_channel"], wl["p_spatial"])
     sd = {k: v.detach().clone() for k, v in hip.state_dict().items()}
-    ref = RR.regnet_y_ref(arch, **kw) if arch.startswith("lad_regnet") else TR.resnet101_ref(**kw)
+    ref = RR.regnet_y_ref(arch, **kw) if arch.startswith("lad_regnet") else (TR.resnet50_ref if arch == "uni_resnet50" else TR.resnet101_ref)(**kw)
     ref.load_state_dict(sd)
     ref = ref.to(dev).train()
     for m in ref.modules():
-        if isinstance(m, torch.nn.BatchNorm2d):
+        if isinstance(m, torch.nn.BatchNorm2d) and not args.batch_stats:
             m.eval()
-    prepare_for_training(hip)
+    prepare_for_training(hip, batch_stats=args.batch_stats)
     g = seeded_randn((args.batch, 1000), 5).to(dev)
 
     def step(fwd, model):
@@ -147,6 +155,8 @@ for w in args.workloads.split(","):
     if not args.no_reference:
         res["speedup"] = res["dense_emulation_pytorch"]["ms_per_step"] / res["hip_row_kernels"]["ms_per_step"]
     print(json.dumps({"workload": wl["name"], "batch": args.batch, "steps": args.steps, "math": args.math, "wgrad_kernel": training.USE_WGRAD_KERNEL,
-                      "what": "one training step = forward + backward of every parameter, frozen BatchNorm statistics, Gumbel-hard masks", **res}), flush=True)
+                      "batch_stats": args.batch_stats,
+                      "what": "one training step = forward + backward of every parameter, " + ("BatchNorm on batch statistics" if args.batch_stats else
+                                                                                              "frozen BatchNorm statistics") + ", Gumbel-hard masks", **res}), flush=True)
     del hip, ref
     torch.cuda.empty_cache()
