@@ -1,17 +1,13 @@
 // ldn_train_bn.hip -- BatchNorm on BATCH statistics over packed rows, forward and backward (ldn_rows_bn_stats, ldn_rows_bn_fwd, ldn_rows_bn_bwd;
 // include/ldn_hip.h): what training needs of the reference's own recipe, where bn1 / bn2 / bn3 normalise with the statistics of the batch.
 //
-// Bandwidth-bound row kernels with the conventions of ldn_train_rows.hip (ldn_rows_plan.h): [m_cap, C] fp32 matrices with a leading dimension,
-// C % 4 == 0, every access 16 bytes wide; the count is read on the device, rows r >= count are never read and are written as exact zeros; the
-// rows are split over `splits` workgroups per 256-channel column tile by act_plan -- a function of (m_cap, C) only, so every launch is
-// graph-capturable; inside a workgroup a thread owns one channel quad and every RL-th row, the row lanes are combined in ascending lane order
-// through the LDS, the workgroups' partials in ascending split order by a second small launch.  No floating-point atomics: two runs are
-// bit-identical.  fp32 arithmetic whatever the math mode of the convolutions around them.
+// Bandwidth-bound fp32 row kernels, whatever the math mode of the convolutions around them; all but ldn_rows_bn_fwd (one thread per row and
+// quad) are the walk of ldn_rows_plan.h, with its zeros past the count, its partials, its reducer and its bit-identical sums.
 //
 // The optional channel mask c [B][C] multiplies u BEFORE the statistics and the normalisation (the reference's apply_channel_mask in front of
 // bn1 / bn2): x = c[img(r)][k] * u[r][k], a channel dropped in one image contributes zeros to the batch statistics.  u itself is the UNMASKED
 // convolution output -- the backward needs it for the mask's straight-through term.  The image of a row comes from the per-image row prefix,
-// by a walk over the images of a workgroup's rows (statistics, backward) or a binary search per thread (forward).
+// by the walk's image segments (statistics, backward) or a binary search per thread (forward).
 //
 // ldn_rows_bn_stats: mean and BIASED variance over the rows below the count, never as E[x^2] - E[x]^2.  A thread runs Welford's update over its
 // rows; (n, mean, M2) triples are merged pairwise with Chan's formula -- the row lanes in ascending lane order, then the splits in ascending
@@ -24,38 +20,12 @@
 // recomputed; h == NULL: no ReLU.  Launches 1 + 2: d_beta[k] = sum dz, d_gamma[k] = sum dz * xhat.  Launch 3:
 //     g  = gamma * invstd * (dz - d_beta / n - xhat * d_gamma / n)        n = the device-side count        (= d L / d x)
 //     du = c[img(r)][k] * g                                                                                (= d L / d u)
-// and, where the mask's straight-through gradient is wanted, g_mask[b][k] = sum over the rows of image b of g * u -- FUSED into launch 3 with the
-// (split + b) slots of ldn_rows_act_bwd and one more small launch that adds them: four launches, against six for the same through
+// and, where the mask's straight-through gradient is wanted, g_mask[b][k] = sum over the rows of image b of g * u -- FUSED into launch 3 through
+// the image slots and one more reducer launch that adds them: four launches, against six for the same through
 // ldn_rows_img_dot (two) and ldn_rows_chanmask (one) behind a three-launch backward.
 #include "ldn_rows_plan.h"
 
 namespace ldn {
-
-// thread = (row lane rl, quad ql) of a QT-quad column tile, QT = min(C / 4, 64), RL = 256 / QT row lanes; grid = (column tiles, splits)
-struct RowWalk {
-    int QT, RL, rl, ql, k, split, count, r_begin, r_cap_end, r_end;
-    bool active;
-};
-
-__device__ __forceinline__ RowWalk row_walk(int C, const int32_t* m_count, int m_cap, int rps) {
-    RowWalk w;
-    const int Q = C >> 2;
-    w.QT = Q < ACT_QT ? Q : ACT_QT;
-    w.RL = ACT_THREADS / w.QT;
-    w.rl = threadIdx.x / w.QT;
-    w.ql = threadIdx.x - w.rl * w.QT;
-    const int q = blockIdx.x * ACT_QT + w.ql;
-    w.active = w.rl < w.RL && q < Q;
-    w.k = 4 * q;
-    w.split = blockIdx.y;
-    w.count = rows_count(m_count, m_cap);
-    w.r_begin = w.split * rps;
-    w.r_cap_end = min(m_cap, w.r_begin + rps);
-    w.r_end = min(w.count, w.r_cap_end);
-    return w;
-}
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
 // Chan's merge of (nb, mb, m2b) into (na, ma, m2a); nb > 0
 __device__ __forceinline__ void chan_merge(int& na, f32x4& ma, f32x4& m2a, int nb, const f32x4 mb, const f32x4 m2b) {
@@ -74,51 +44,44 @@ struct BnStatArgs {
     int ldu, B, m_cap, C, splits, rps;
 };
 
-// work layout of ldn_rows_bn_stats: [splits][C] mean partials | [splits][C] M2 partials
+// column partials 0 / 1 of the work layout: the split's mean and M2
 __global__ __launch_bounds__(ACT_THREADS) void k_bn_stats_partial(const BnStatArgs p) {
     __shared__ f32x4 s_mean[ACT_THREADS], s_m2[ACT_THREADS];
     __shared__ int s_n[ACT_THREADS];
     const RowWalk w = row_walk(p.C, p.m_count, p.m_cap, p.rps);
-    if (w.r_begin >= w.r_end) return;      // (uniform) no rows: k_bn_stats_reduce does not read this split's partials
+    if (w.empty()) return;                 // k_bn_stats_reduce does not read this split's partials either
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     f32x4 mean = zero, m2 = zero;
     int n = 0;
-    int b = p.chan_mask ? image_of_row(p.prefix, p.B, w.r_begin) : 0;
-    int r0 = w.r_begin;
-    while (r0 < w.r_end) {                 // (uniform) one segment per image that owns rows of this split
-        int seg_end = w.r_end;
-        if (p.chan_mask && b < p.B - 1) seg_end = min(w.r_end, max(p.prefix[b + 1], r0));
-        if (seg_end > r0 && w.active) {
-            f32x4 m = {1.f, 1.f, 1.f, 1.f};
-            if (p.chan_mask) m = ld4(p.chan_mask + (size_t)b * p.C + w.k);
-            for (int r = r0 + w.rl; r < seg_end; r += w.RL) {
-                const f32x4 x = ld4(p.u + (size_t)r * p.ldu + w.k) * m;
-                ++n;
-                const f32x4 d = x - mean;
-                mean += d * (1.f / (float)n);
-                m2 += d * (x - mean);
-            }
+    for_each_image_segment(w, p.prefix, p.B, [&](int b, int r0, int seg_end) {
+        if (!w.active) return;
+        f32x4 m = {1.f, 1.f, 1.f, 1.f};
+        if (p.chan_mask) m = ld4(p.chan_mask + (size_t)b * p.C + w.k);
+        for (int r = r0 + w.rl; r < seg_end; r += w.RL) {
+            const f32x4 x = ld4(p.u + (size_t)r * p.ldu + w.k) * m;
+            ++n;
+            const f32x4 d = x - mean;
+            mean += d * (1.f / (float)n);
+            m2 += d * (x - mean);
         }
-        r0 = seg_end;
-        ++b;
-    }
+    });
     s_mean[threadIdx.x] = mean;
     s_m2[threadIdx.x] = m2;
     s_n[threadIdx.x] = n;
     __syncthreads();
-    if (w.active && w.rl == 0) {           // the row lanes in ascending lane order
+    if (w.active && w.rl == 0) {           // lane_sum's order, Chan's merge for its addition
         f32x4 ma = zero, m2a = zero;
         int na = 0;
         for (int j = 0; j < w.RL; ++j) {
-            const int i = j * w.QT + w.ql;
+            const int i = w.lane_slot(j);
             if (s_n[i] > 0) chan_merge(na, ma, m2a, s_n[i], s_mean[i], s_m2[i]);
         }
-        *reinterpret_cast<f32x4*>(p.work + (size_t)w.split * p.C + w.k) = ma;
-        *reinterpret_cast<f32x4*>(p.work + (size_t)(p.splits + w.split) * p.C + w.k) = m2a;
+        st4(work_col(p.work, p.splits, p.C, 0, w.split) + w.k, ma);
+        st4(work_col(p.work, p.splits, p.C, 1, w.split) + w.k, m2a);
     }
 }
 
-// one thread per quad: the splits that hold rows in ascending order; a split's n follows from the count
+// rows_reduce with Chan's merge for its addition: one thread per quad, the splits that hold rows in ascending order; a split's n follows from the count
 __global__ __launch_bounds__(256) void k_bn_stats_reduce(const BnStatArgs p) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= (p.C >> 2)) return;
@@ -129,15 +92,15 @@ __global__ __launch_bounds__(256) void k_bn_stats_reduce(const BnStatArgs p) {
     int na = 0;
     for (int t = 0; t < live; ++t) {
         const int nb = min(count - t * p.rps, p.rps);
-        chan_merge(na, ma, m2a, nb, ld4(p.work + (size_t)t * p.C + k), ld4(p.work + (size_t)(p.splits + t) * p.C + k));
+        chan_merge(na, ma, m2a, nb, ld4(work_col(p.work, p.splits, p.C, 0, t) + k), ld4(work_col(p.work, p.splits, p.C, 1, t) + k));
     }
     const f32x4 var = na > 0 ? m2a * (1.f / (float)na) : m2a;
     f32x4 inv;
 #pragma unroll
     for (int e = 0; e < 4; ++e) inv[e] = 1.f / sqrtf(var[e] + p.eps);
-    *reinterpret_cast<f32x4*>(p.mean + k) = ma;
-    *reinterpret_cast<f32x4*>(p.var + k) = var;
-    *reinterpret_cast<f32x4*>(p.invstd + k) = inv;
+    st4(p.mean + k, ma);
+    st4(p.var + k, var);
+    st4(p.invstd + k, inv);
 }
 
 struct BnFwdArgs {
@@ -175,9 +138,6 @@ struct BnBwdArgs {
     int lddh, ldu, ldh, lddu, B, m_cap, C, splits, rps;
 };
 
-// work layout of ldn_rows_bn_bwd: [splits][C] d_beta partials | [splits][C] d_gamma partials | [splits + B][C] g_mask slots
-__device__ __forceinline__ float* bn_work_mask(const BnBwdArgs& p) { return p.work + (size_t)2 * p.splits * p.C; }
-
 // (xhat, dz) of one quad of row r; m = the channel mask of the row's image (ones without one)
 __device__ __forceinline__ void bn_bwd_quad(const BnBwdArgs& p, int r, int k, const f32x4 m, const f32x4 mean, const f32x4 inv, f32x4& u, f32x4& xhat,
                                             f32x4& dz) {
@@ -192,70 +152,40 @@ __device__ __forceinline__ void bn_bwd_quad(const BnBwdArgs& p, int r, int k, co
     if (p.row_scale) dz *= p.row_scale[r];
 }
 
-// launch 1: the partial d_beta / d_gamma of the split
+// launch 1: the split's partial d_beta / d_gamma, column partials 0 / 1 of the work layout
 __global__ __launch_bounds__(ACT_THREADS) void k_bn_bwd_partial(const BnBwdArgs p) {
-    __shared__ f32x4 s_red[2][ACT_THREADS];
+    __shared__ f32x4 s_red[ACT_THREADS];
     const RowWalk w = row_walk(p.C, p.m_count, p.m_cap, p.rps);
-    if (w.r_begin >= w.r_end) return;      // (uniform) no rows: k_bn_bwd_reduce does not read this split's partials
+    if (w.empty()) return;
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     f32x4 mean = zero, inv = zero, g_b = zero, g_g = zero;
     if (w.active) {
         mean = ld4(p.mean + w.k);
         inv = ld4(p.invstd + w.k);
     }
-    int b = p.chan_mask ? image_of_row(p.prefix, p.B, w.r_begin) : 0;
-    int r0 = w.r_begin;
-    while (r0 < w.r_end) {                 // (uniform) one segment per image that owns rows of this split
-        int seg_end = w.r_end;
-        if (p.chan_mask && b < p.B - 1) seg_end = min(w.r_end, max(p.prefix[b + 1], r0));
-        if (seg_end > r0 && w.active) {
-            f32x4 m = {1.f, 1.f, 1.f, 1.f};
-            if (p.chan_mask) m = ld4(p.chan_mask + (size_t)b * p.C + w.k);
-            for (int r = r0 + w.rl; r < seg_end; r += w.RL) {
-                f32x4 u, xhat, dz;
-                bn_bwd_quad(p, r, w.k, m, mean, inv, u, xhat, dz);
-                g_b += dz;
-                g_g += dz * xhat;
-            }
+    // (g_mask alone does not cut this launch's rows into images: a thread's rows, and so the order of its sum, depend on the segments)
+    for_each_image_segment(w, p.prefix, p.chan_mask ? p.B : 0, [&](int b, int r0, int seg_end) {
+        if (!w.active) return;
+        f32x4 m = {1.f, 1.f, 1.f, 1.f};
+        if (p.chan_mask) m = ld4(p.chan_mask + (size_t)b * p.C + w.k);
+        for (int r = r0 + w.rl; r < seg_end; r += w.RL) {
+            f32x4 u, xhat, dz;
+            bn_bwd_quad(p, r, w.k, m, mean, inv, u, xhat, dz);
+            g_b += dz;
+            g_g += dz * xhat;
         }
-        r0 = seg_end;
-        ++b;
-    }
-    s_red[0][threadIdx.x] = g_b;
-    s_red[1][threadIdx.x] = g_g;
-    __syncthreads();
-    if (w.active && w.rl == 0) {           // the row lanes in ascending lane order
-        f32x4 sb = zero, sg = zero;
-        for (int j = 0; j < w.RL; ++j) {
-            sb += s_red[0][j * w.QT + w.ql];
-            sg += s_red[1][j * w.QT + w.ql];
-        }
-        *reinterpret_cast<f32x4*>(p.work + (size_t)w.split * p.C + w.k) = sb;
-        *reinterpret_cast<f32x4*>(p.work + (size_t)(p.splits + w.split) * p.C + w.k) = sg;
-    }
+    });
+    lane_sum_to(s_red, w, g_b, work_col(p.work, p.splits, p.C, 0, w.split));
+    lane_sum_to(s_red, w, g_g, work_col(p.work, p.splits, p.C, 1, w.split));
 }
 
-// launch 2: one thread per quad of d_beta (j == 0) and d_gamma (j == 1), the partials in ascending split order
-__global__ __launch_bounds__(256) void k_bn_bwd_reduce(const BnBwdArgs p) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const int Q = p.C >> 2;
-    if (i >= 2 * Q) return;
-    const int j = i / Q, k = 4 * (i - j * Q);
-    const int live = min(p.splits, ceil_div(rows_count(p.m_count, p.m_cap), p.rps));
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    for (int t = 0; t < live; ++t) s += ld4(p.work + (size_t)(j * p.splits + t) * p.C + k);
-    *reinterpret_cast<f32x4*>((j == 0 ? p.d_beta : p.d_gamma) + k) = s;
-}
-
-// launch 3: du, and the partial g_mask of every image that owns rows of the split
+// launch 3 (launch 2 has reduced d_beta / d_gamma): du, and the partial g_mask of every image that owns rows of the split, in the image slots
 __global__ __launch_bounds__(ACT_THREADS) void k_bn_bwd_final(const BnBwdArgs p) {
     __shared__ f32x4 s_red[ACT_THREADS];
     const RowWalk w = row_walk(p.C, p.m_count, p.m_cap, p.rps);
+    zero_past_count(w, p.du, p.lddu);
+    if (w.empty()) return;
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-    // rows past the count: exact zeros, nothing read
-    if (w.active)
-        for (int r = max(w.r_end, w.r_begin) + w.rl; r < w.r_cap_end; r += w.RL) store16(p.du + (size_t)r * p.lddu + w.k, zero);
-    if (w.r_begin >= w.r_end) return;      // (uniform) no rows: k_bn_mask_reduce does not read this split's slots
     f32x4 mean = zero, inv = zero, gi = zero, cb = zero, cg = zero;
     if (w.active) {
         const float inv_n = 1.f / (float)w.count;          // (count >= r_end > 0)
@@ -265,48 +195,20 @@ __global__ __launch_bounds__(ACT_THREADS) void k_bn_bwd_final(const BnBwdArgs p)
         cb = ld4(p.d_beta + w.k) * inv_n;
         cg = ld4(p.d_gamma + w.k) * inv_n;
     }
-    const bool per_image = p.chan_mask || p.g_mask;
-    int b = per_image ? image_of_row(p.prefix, p.B, w.r_begin) : 0;
-    int r0 = w.r_begin;
-    while (r0 < w.r_end) {                 // (uniform) one segment per image that owns rows of this split
-        int seg_end = w.r_end;
-        if (per_image && b < p.B - 1) seg_end = min(w.r_end, max(p.prefix[b + 1], r0));
-        if (seg_end > r0) {
-            f32x4 m = {1.f, 1.f, 1.f, 1.f}, g_m = zero;
-            if (w.active) {
-                if (p.chan_mask) m = ld4(p.chan_mask + (size_t)b * p.C + w.k);
-                for (int r = r0 + w.rl; r < seg_end; r += w.RL) {
-                    f32x4 u, xhat, dz;
-                    bn_bwd_quad(p, r, w.k, m, mean, inv, u, xhat, dz);
-                    const f32x4 g = gi * (dz - cb - xhat * cg);
-                    g_m += g * u;
-                    store16(p.du + (size_t)r * p.lddu + w.k, g * m);
-                }
-            }
-            if (p.g_mask) {                // the row lanes in ascending lane order
-                s_red[threadIdx.x] = g_m;
-                __syncthreads();
-                if (w.active && w.rl == 0) {
-                    f32x4 s = zero;
-                    for (int j = 0; j < w.RL; ++j) s += s_red[j * w.QT + w.ql];
-                    *reinterpret_cast<f32x4*>(bn_work_mask(p) + (size_t)(w.split + b) * p.C + w.k) = s;
-                }
-                __syncthreads();
+    for_each_image_segment(w, p.prefix, p.B, [&](int b, int r0, int seg_end) {
+        f32x4 m = {1.f, 1.f, 1.f, 1.f}, g_m = zero;
+        if (w.active) {
+            if (p.chan_mask) m = ld4(p.chan_mask + (size_t)b * p.C + w.k);
+            for (int r = r0 + w.rl; r < seg_end; r += w.RL) {
+                f32x4 u, xhat, dz;
+                bn_bwd_quad(p, r, w.k, m, mean, inv, u, xhat, dz);
+                const f32x4 g = gi * (dz - cb - xhat * cg);
+                g_m += g * u;
+                store16(p.du + (size_t)r * p.lddu + w.k, g * m);
             }
         }
-        r0 = seg_end;
-        ++b;
-    }
-}
-
-// launch 4 (with g_mask only): one thread per quad of g_mask[b]
-__global__ __launch_bounds__(256) void k_bn_mask_reduce(const BnBwdArgs p) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const int Q = p.C >> 2;
-    if (i >= p.B * Q) return;
-    const int b = i / Q, k = 4 * (i - b * Q);
-    *reinterpret_cast<f32x4*>(p.g_mask + (size_t)b * p.C + k) =
-        image_slots_sum(bn_work_mask(p), p.prefix, p.B, b, rows_count(p.m_count, p.m_cap), p.splits, p.rps, p.C, k);
+        if (p.g_mask) lane_sum_to(s_red, w, g_m, work_slot(p.work, p.splits, p.C, 2, w.split + b));
+    });
 }
 
 }  // namespace ldn
@@ -315,9 +217,7 @@ using namespace ldn;
 
 extern "C" size_t ldn_rows_bn_stats_workspace_bytes(int m_cap, int C) {
     if (m_cap < 0 || C <= 0 || C % 4) return 0;
-    int tiles, splits, rps;
-    act_plan(m_cap, C, &tiles, &splits, &rps);
-    return (size_t)2 * splits * C * sizeof(float);
+    return rows_work_bytes(m_cap, C, 2, 0);
 }
 
 extern "C" int ldn_rows_bn_stats(const float* u, int ldu, const float* chan_mask, const int32_t* row_prefix, int B, const int32_t* m_count,
@@ -332,11 +232,10 @@ extern "C" int ldn_rows_bn_stats(const float* u, int ldu, const float* chan_mask
     BnStatArgs p;
     p.u = u; p.chan_mask = chan_mask; p.prefix = row_prefix; p.m_count = m_count; p.mean = mean; p.var = var; p.invstd = invstd; p.work = work;
     p.eps = eps; p.ldu = ldu; p.B = chan_mask ? B : 0; p.m_cap = m_cap; p.C = C;
-    int tiles;
-    act_plan(m_cap, C, &tiles, &p.splits, &p.rps);
+    const dim3 grid = rows_grid(m_cap, C, &p.splits, &p.rps);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (m_cap > 0) {
-        k_bn_stats_partial<<<dim3((unsigned)tiles, (unsigned)p.splits), ACT_THREADS, 0, st>>>(p);
+        k_bn_stats_partial<<<grid, ACT_THREADS, 0, st>>>(p);
         LDN_CHECK_LAUNCH("k_bn_stats_partial");
     }
     k_bn_stats_reduce<<<ceil_div(C / 4, 256), 256, 0, st>>>(p);
@@ -365,12 +264,7 @@ extern "C" int ldn_rows_bn_fwd(const float* u, int ldu, const float* mean, const
     return LDN_OK;
 }
 
-extern "C" size_t ldn_rows_bn_bwd_workspace_bytes(int m_cap, int C, int B) {
-    if (m_cap < 0 || C <= 0 || C % 4 || B < 0) return 0;
-    int tiles, splits, rps;
-    act_plan(m_cap, C, &tiles, &splits, &rps);
-    return ((size_t)2 * splits + (B > 0 ? splits + B : 0)) * C * sizeof(float);
-}
+extern "C" size_t ldn_rows_bn_bwd_workspace_bytes(int m_cap, int C, int B) { return rows_bwd_work_bytes(m_cap, C, B); }
 
 extern "C" int ldn_rows_bn_bwd(const float* dh, int lddh, const float* u, int ldu, const float* h, int ldh, const float* mean,
                                const float* invstd, const float* gamma, const float* chan_mask, const int32_t* row_prefix, int B,
@@ -389,23 +283,18 @@ extern "C" int ldn_rows_bn_bwd(const float* dh, int lddh, const float* u, int ld
     p.dh = dh; p.u = u; p.h = h; p.mean = mean; p.invstd = invstd; p.gamma = gamma; p.chan_mask = chan_mask; p.prefix = row_prefix;
     p.row_scale = row_scale; p.m_count = m_count; p.du = du; p.d_gamma = d_gamma; p.d_beta = d_beta; p.g_mask = g_mask; p.work = work;
     p.lddh = lddh; p.ldu = ldu; p.ldh = ldh; p.lddu = lddu; p.B = (chan_mask || g_mask) ? B : 0; p.m_cap = m_cap; p.C = C;
-    int tiles;
-    act_plan(m_cap, C, &tiles, &p.splits, &p.rps);
+    const dim3 grid = rows_grid(m_cap, C, &p.splits, &p.rps);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)tiles, (unsigned)p.splits);
     if (m_cap > 0) {
         k_bn_bwd_partial<<<grid, ACT_THREADS, 0, st>>>(p);
         LDN_CHECK_LAUNCH("k_bn_bwd_partial");
     }
-    k_bn_bwd_reduce<<<ceil_div(2 * (C / 4), 256), 256, 0, st>>>(p);
-    LDN_CHECK_LAUNCH("k_bn_bwd_reduce");
+    const int rc = rows_reduce({work, nullptr, nullptr, m_count, {d_beta, d_gamma}, nullptr, 2, 0, 0, m_cap, C, p.splits, p.rps}, st);
+    if (rc != LDN_OK) return rc;
     if (m_cap > 0) {
         k_bn_bwd_final<<<grid, ACT_THREADS, 0, st>>>(p);
         LDN_CHECK_LAUNCH("k_bn_bwd_final");
     }
-    if (g_mask) {
-        k_bn_mask_reduce<<<ceil_div(B * (C / 4), 256), 256, 0, st>>>(p);
-        LDN_CHECK_LAUNCH("k_bn_mask_reduce");
-    }
+    if (g_mask) return rows_reduce({nullptr, work_slot(work, p.splits, C, 2, 0), row_prefix, m_count, {nullptr, nullptr}, g_mask, 0, B, B, m_cap, C, p.splits, p.rps}, st);
     return LDN_OK;
 }

@@ -599,6 +599,36 @@ def _rows_cap(m_cap, what, *mats):
     return m_cap
 
 
+def _rows_wide(what, C, **mats):
+    """The matrices of a row kernel over C channels, checked: C % 4 == 0 and every matrix given (None = absent) is [rows, >= C]."""
+    if C % 4:
+        raise L.LdnError(f"{what}: C % 4 == 0 (got {C})")
+    for name, t in mats.items():
+        if t is not None and (t.dim() != 2 or t.shape[1] < C):
+            raise L.LdnError(f"{what}: {name} must be [rows, >= {C}], got {tuple(t.shape)}")
+
+
+def _rows_images(what, C, row_prefix, per_image_out, **per_image):
+    """B of a row kernel call, checked: any per-image argument [B, C] given (None = absent), or an output per image, needs row_prefix [B + 1];
+    0 when nothing is per image (row_prefix is then not looked at)."""
+    if not per_image_out and all(t is None for t in per_image.values()):
+        return 0
+    if row_prefix is None or row_prefix.numel() < 2:
+        raise L.LdnError(f"{what}: {' / '.join(per_image)} and a per-image output need row_prefix [B + 1]")
+    B = row_prefix.numel() - 1
+    for name, t in per_image.items():
+        if t is not None and tuple(t.shape) != (B, C):
+            raise L.LdnError(f"{what}: {name} must be [{B}, {C}], got {tuple(t.shape)}")
+    return B
+
+
+def _rows_out(out, m_cap, C, device):
+    """(the matrix a row kernel writes, what the caller gets): out if given, else a new [m_cap, C]; and its [m_cap, C] view."""
+    if out is None:
+        out = torch.empty(m_cap, C, device=device, dtype=torch.float32)
+    return out, out if tuple(out.shape) == (m_cap, C) else out[:m_cap, :C]
+
+
 def rows_chanmask(u2d, row_prefix, chan_mask, m_count=None, m_cap=None):
     """In place on packed rows (see ldn_rows_chanmask): u2d[r, k] *= chan_mask[img(r), k] for r < count, exact zeros on rows [count, m_cap).
     u2d [rows, ld >= C] (C = chan_mask.shape[1]); row_prefix [B + 1] int32 = IndexSet.pre1 / pre3 (image b owns rows [prefix[b],
@@ -627,22 +657,13 @@ def rows_act_bwd(dh2d, u2d, scale, shift, *, post_sub=None, chan_mask=None, row_
     L.require_device(dh2d, u2d, scale, shift, post_sub, chan_mask, row_prefix, zy2d, m_count, out)
     lib = L.load()
     C = scale.numel()
-    for name, t in (("dh", dh2d), ("u", u2d), ("zy", zy2d), ("out", out)):
-        if t is not None and (t.dim() != 2 or t.shape[1] < C):
-            raise L.LdnError(f"rows_act_bwd: {name} must be [rows, >= {C}], got {tuple(t.shape)}")
-    if C % 4 or shift.numel() != C or (post_sub is not None and post_sub.numel() != C):
-        raise L.LdnError("rows_act_bwd: scale / shift / post_sub must be [C] with C % 4 == 0")
-    B = 0
-    if chan_mask is not None or zy2d is not None:
-        if row_prefix is None or row_prefix.numel() < 2:
-            raise L.LdnError("rows_act_bwd: chan_mask / zy2d need row_prefix [B + 1]")
-        B = row_prefix.numel() - 1
-        if chan_mask is not None and tuple(chan_mask.shape) != (B, C):
-            raise L.LdnError(f"rows_act_bwd: chan_mask must be [{B}, {C}], got {tuple(chan_mask.shape)}")
+    _rows_wide("rows_act_bwd", C, dh=dh2d, u=u2d, zy=zy2d, out=out)
+    if shift.numel() != C or (post_sub is not None and post_sub.numel() != C):
+        raise L.LdnError("rows_act_bwd: scale / shift / post_sub must be [C]")
+    B = _rows_images("rows_act_bwd", C, row_prefix, zy2d is not None, chan_mask=chan_mask)
     m_cap = _rows_cap(m_cap, "rows_act_bwd", dh2d, u2d, zy2d, out)
     dev = dh2d.device
-    if out is None:
-        out = torch.empty(m_cap, C, device=dev, dtype=torch.float32)
+    out, du = _rows_out(out, m_cap, C, dev)
     g_shift = torch.empty(C, device=dev, dtype=torch.float32)
     g_scale = torch.empty(C, device=dev, dtype=torch.float32)
     g_mask = torch.empty(B, C, device=dev, dtype=torch.float32) if zy2d is not None else None
@@ -653,7 +674,7 @@ def rows_act_bwd(dh2d, u2d, scale, shift, *, post_sub=None, chan_mask=None, row_
                                  L.ptr(_f32rows(zy2d, "zy")), zy2d.stride(0) if zy2d is not None else 0, L.ptr(_i32c(m_count, "m_count")),
                                  m_cap, C, L.ptr(_f32rows(out, "out")), out.stride(0), L.ptr(g_shift), L.ptr(g_scale), L.ptr(g_mask),
                                  L.ptr(work), L.stream_ptr(out)), "ldn_rows_act_bwd")
-    return out[:m_cap, :C] if tuple(out.shape) != (m_cap, C) else out, g_shift, g_scale, g_mask
+    return du, g_shift, g_scale, g_mask
 
 
 def rows_img_dot(a2d, b2d, row_prefix, m_count=None, m_cap=None):
@@ -687,25 +708,15 @@ def rows_postmask_bwd(dz2d, r2d, scale, shift, *, chan_mask=None, row_prefix=Non
     L.require_device(dz2d, r2d, scale, shift, chan_mask, row_prefix, gate, dsq, m_count, out)
     lib = L.load()
     C = scale.numel()
-    for name, t in (("dz", dz2d), ("r", r2d), ("out", out)):
-        if t is not None and (t.dim() != 2 or t.shape[1] < C):
-            raise L.LdnError(f"rows_postmask_bwd: {name} must be [rows, >= {C}], got {tuple(t.shape)}")
-    if C % 4 or shift.numel() != C:
-        raise L.LdnError("rows_postmask_bwd: scale / shift must be [C] with C % 4 == 0")
+    _rows_wide("rows_postmask_bwd", C, dz=dz2d, r=r2d, out=out)
+    if shift.numel() != C:
+        raise L.LdnError("rows_postmask_bwd: scale / shift must be [C]")
     if (gate is None) != (dsq is None):
         raise L.LdnError("rows_postmask_bwd: gate and dsq are the SE prologue: give both or neither")
-    B = 0
-    if chan_mask is not None or gate is not None or want_mask:
-        if row_prefix is None or row_prefix.numel() < 2:
-            raise L.LdnError("rows_postmask_bwd: chan_mask / gate / want_mask need row_prefix [B + 1]")
-        B = row_prefix.numel() - 1
-        for name, t in (("chan_mask", chan_mask), ("gate", gate), ("dsq", dsq)):
-            if t is not None and tuple(t.shape) != (B, C):
-                raise L.LdnError(f"rows_postmask_bwd: {name} must be [{B}, {C}], got {tuple(t.shape)}")
+    B = _rows_images("rows_postmask_bwd", C, row_prefix, want_mask, chan_mask=chan_mask, gate=gate, dsq=dsq)
     m_cap = _rows_cap(m_cap, "rows_postmask_bwd", dz2d, r2d, out)
     dev = dz2d.device
-    if out is None:
-        out = torch.empty(m_cap, C, device=dev, dtype=torch.float32)
+    out, du = _rows_out(out, m_cap, C, dev)
     g_shift = torch.empty(C, device=dev, dtype=torch.float32)
     g_scale = torch.empty(C, device=dev, dtype=torch.float32)
     g_mask = torch.empty(B, C, device=dev, dtype=torch.float32) if want_mask else None
@@ -715,21 +726,7 @@ def rows_postmask_bwd(dz2d, r2d, scale, shift, *, chan_mask=None, row_prefix=Non
                                       L.ptr(_i32c(row_prefix, "row_prefix")), B, L.ptr(_f32c(gate, "gate")), L.ptr(_f32c(dsq, "dsq")),
                                       L.ptr(_i32c(m_count, "m_count")), m_cap, C, L.ptr(_f32rows(out, "out")), out.stride(0), L.ptr(g_shift),
                                       L.ptr(g_scale), L.ptr(g_mask), L.ptr(work), L.stream_ptr(out)), "ldn_rows_postmask_bwd")
-    return out[:m_cap, :C] if tuple(out.shape) != (m_cap, C) else out, g_shift, g_scale, g_mask
-
-
-def _bn_mask_args(what, C, chan_mask, row_prefix):
-    """(B, chan_mask, row_prefix) of a batch-statistics BatchNorm call, checked: a channel mask [B, C] comes with row_prefix [B + 1]"""
-    if C % 4:
-        raise L.LdnError(f"{what}: C % 4 == 0 (got {C})")
-    if chan_mask is None and row_prefix is None:
-        return 0
-    if row_prefix is None or row_prefix.numel() < 2:
-        raise L.LdnError(f"{what}: chan_mask / want_mask need row_prefix [B + 1]")
-    B = row_prefix.numel() - 1
-    if chan_mask is not None and tuple(chan_mask.shape) != (B, C):
-        raise L.LdnError(f"{what}: chan_mask must be [{B}, {C}], got {tuple(chan_mask.shape)}")
-    return B
+    return du, g_shift, g_scale, g_mask
 
 
 def rows_bn_stats(u2d, eps=1e-5, *, chan_mask=None, row_prefix=None, m_count=None, m_cap=None):
@@ -739,10 +736,10 @@ def rows_bn_stats(u2d, eps=1e-5, *, chan_mask=None, row_prefix=None, m_count=Non
     E[x^2] - E[x]^2.  chan_mask [B, C] (None = ones) needs row_prefix [B + 1].  No rows: (0, 0, 1 / sqrt(eps)).  Deterministic, no atomics."""
     L.require_device(u2d, chan_mask, row_prefix, m_count)
     lib = L.load()
-    if u2d.dim() != 2:
-        raise L.LdnError(f"rows_bn_stats: u2d must be [rows, C], got {tuple(u2d.shape)}")
+    if u2d.dim() != 2 or u2d.shape[1] % 4:
+        raise L.LdnError(f"rows_bn_stats: u2d must be [rows, C] with C % 4 == 0, got {tuple(u2d.shape)}")
     C = u2d.shape[1]
-    B = _bn_mask_args("rows_bn_stats", C, chan_mask, row_prefix if chan_mask is not None else None)
+    B = _rows_images("rows_bn_stats", C, row_prefix, False, chan_mask=chan_mask)
     m_cap = _rows_cap(m_cap, "rows_bn_stats", u2d)
     mean, var, invstd = (torch.empty(C, device=u2d.device, dtype=torch.float32) for _ in range(3))
     work = _work(lib.ldn_rows_bn_stats_workspace_bytes(m_cap, C), u2d.device)
@@ -759,23 +756,20 @@ def rows_bn_fwd(u2d, mean, invstd, gamma, beta, *, chan_mask=None, row_prefix=No
     {0,1} pixel mask on bn3's output."""
     L.require_device(u2d, mean, invstd, gamma, beta, chan_mask, row_prefix, row_scale, m_count, out)
     C = gamma.numel()
-    for name, t in (("u", u2d), ("out", out)):
-        if t is not None and (t.dim() != 2 or t.shape[1] < C):
-            raise L.LdnError(f"rows_bn_fwd: {name} must be [rows, >= {C}], got {tuple(t.shape)}")
+    _rows_wide("rows_bn_fwd", C, u=u2d, out=out)
     if any(v.numel() != C for v in (mean, invstd, beta)):
         raise L.LdnError("rows_bn_fwd: mean / invstd / gamma / beta must be [C]")
-    B = _bn_mask_args("rows_bn_fwd", C, chan_mask, row_prefix if chan_mask is not None else None)
+    B = _rows_images("rows_bn_fwd", C, row_prefix, False, chan_mask=chan_mask)
     m_cap = _rows_cap(m_cap, "rows_bn_fwd", u2d, out)
     if row_scale is not None and row_scale.numel() < m_cap:
         raise L.LdnError(f"rows_bn_fwd: row_scale has {row_scale.numel()} entries for m_cap {m_cap}")
-    if out is None:
-        out = torch.empty(m_cap, C, device=u2d.device, dtype=torch.float32)
+    out, h = _rows_out(out, m_cap, C, u2d.device)
     L.check(L.load().ldn_rows_bn_fwd(L.ptr(_f32rows(u2d, "u")), u2d.stride(0), L.ptr(_f32c(mean, "mean")), L.ptr(_f32c(invstd, "invstd")),
                                      L.ptr(_f32c(gamma, "gamma")), L.ptr(_f32c(beta, "beta")), L.ptr(_f32c(chan_mask, "chan_mask")),
                                      L.ptr(_i32c(row_prefix, "row_prefix")), B, L.ptr(_f32c(row_scale, "row_scale")), 1 if relu else 0,
                                      L.ptr(_i32c(m_count, "m_count")), m_cap, C, L.ptr(_f32rows(out, "out")), out.stride(0),
                                      L.stream_ptr(out)), "ldn_rows_bn_fwd")
-    return out[:m_cap, :C] if tuple(out.shape) != (m_cap, C) else out
+    return h
 
 
 def rows_bn_bwd(dh2d, u2d, h2d, mean, invstd, gamma, *, chan_mask=None, row_prefix=None, row_scale=None, want_mask=False, m_count=None,
@@ -790,20 +784,15 @@ def rows_bn_bwd(dh2d, u2d, h2d, mean, invstd, gamma, *, chan_mask=None, row_pref
     L.require_device(dh2d, u2d, h2d, mean, invstd, gamma, chan_mask, row_prefix, row_scale, m_count, out)
     lib = L.load()
     C = gamma.numel()
-    for name, t in (("dh", dh2d), ("u", u2d), ("h", h2d), ("out", out)):
-        if t is not None and (t.dim() != 2 or t.shape[1] < C):
-            raise L.LdnError(f"rows_bn_bwd: {name} must be [rows, >= {C}], got {tuple(t.shape)}")
+    _rows_wide("rows_bn_bwd", C, dh=dh2d, u=u2d, h=h2d, out=out)
     if mean.numel() != C or invstd.numel() != C:
         raise L.LdnError("rows_bn_bwd: mean / invstd / gamma must be [C]")
-    B = _bn_mask_args("rows_bn_bwd", C, chan_mask, row_prefix if (chan_mask is not None or want_mask) else None)
-    if want_mask and B == 0:
-        raise L.LdnError("rows_bn_bwd: chan_mask / want_mask need row_prefix [B + 1]")
+    B = _rows_images("rows_bn_bwd", C, row_prefix, want_mask, chan_mask=chan_mask)
     m_cap = _rows_cap(m_cap, "rows_bn_bwd", dh2d, u2d, h2d, out)
     if row_scale is not None and row_scale.numel() < m_cap:
         raise L.LdnError(f"rows_bn_bwd: row_scale has {row_scale.numel()} entries for m_cap {m_cap}")
     dev = dh2d.device
-    if out is None:
-        out = torch.empty(m_cap, C, device=dev, dtype=torch.float32)
+    out, du = _rows_out(out, m_cap, C, dev)
     d_gamma = torch.empty(C, device=dev, dtype=torch.float32)
     d_beta = torch.empty(C, device=dev, dtype=torch.float32)
     g_mask = torch.empty(B, C, device=dev, dtype=torch.float32) if want_mask else None
@@ -813,7 +802,7 @@ def rows_bn_bwd(dh2d, u2d, h2d, mean, invstd, gamma, *, chan_mask=None, row_pref
                                 L.ptr(_f32c(gamma, "gamma")), L.ptr(_f32c(chan_mask, "chan_mask")), L.ptr(_i32c(row_prefix, "row_prefix")), B,
                                 L.ptr(_f32c(row_scale, "row_scale")), L.ptr(_i32c(m_count, "m_count")), m_cap, C, L.ptr(_f32rows(out, "out")),
                                 out.stride(0), L.ptr(d_gamma), L.ptr(d_beta), L.ptr(g_mask), L.ptr(work), L.stream_ptr(out)), "ldn_rows_bn_bwd")
-    return out[:m_cap, :C] if tuple(out.shape) != (m_cap, C) else out, d_gamma, d_beta, g_mask
+    return du, d_gamma, d_beta, g_mask
 
 
 USE_ROWS_PS = os.environ.get("LDN_ROWS_PS", "1") != "0"    # the pre-split packed path (k_dense<PS / OF> + k_rows3); 0 = round 4's three launches

@@ -90,7 +90,7 @@ def _assert_reduced(got, exact, abs_sum, n, what):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("count", [0, 1, 197, M_CAP])
-@pytest.mark.parametrize("C", [16, 40, 256])
+@pytest.mark.parametrize("C", [16, 40, 256, 264])
 def test_rows_act_bwd_vs_float64(C, count):
     from laudnet_amd import ops
     # chan_mask / zy / post_sub each absent and present
@@ -145,7 +145,7 @@ def test_rows_act_bwd_in_place_and_without_count():
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("count", [0, 1, 197, M_CAP])
-@pytest.mark.parametrize("C", [16, 40, 256])
+@pytest.mark.parametrize("C", [16, 40, 256, 264])
 def test_rows_chanmask_vs_float64(C, count):
     from laudnet_amd import ops
     d = _inputs(C, count, True, False, 3 * C + count)
