@@ -22,28 +22,11 @@
 
 namespace ldn {
 
-#ifndef LDN_LD_PRIO
-#define LDN_LD_PRIO 0        // tuning: s_setprio of the younger consumer waves (4-6); the loader gets 3
-#endif
-#ifndef LDN_LD_R2MAX
-#define LDN_LD_R2MAX 4       // tuning: deepest W2 ring
-#endif
 #ifndef LDN_LD3_ABLATE
 #define LDN_LD3_ABLATE 0      // tuning only (wrong results): conv3 of the chained kernel without 1 = its whole epilogue, 2 = the residual loads and output stores only, 4 = its MFMAs
 #endif
-#ifndef LDN_LD3_DEFER
-#define LDN_LD3_DEFER 0        // conv3's per-chunk epilogue deferred into the next chunk's K loop (0 = epilogue behind its own K loop)
-#endif
-#ifndef LDN_LD3_STORE_STEP
-#define LDN_LD3_STORE_STEP 1     // K step (n-subtile) of the next chunk behind which a deferred epilogue waits for its residual tile and stores
-#endif
-#ifndef LDN_LD2_STAGED
-#define LDN_LD2_STAGED 0     // conv2's weight tiles through the loader's registers as well: measured SLOWER -- 45 tiles of 20 KB per block are more than one wave can shuffle (4.3 k cycles per tile against the consumers' 2.8 k: conv2 149 k -> 195 k cycles per block); conv2 keeps LDS-DMA into the dense pair layout + per-wave shuffles
-#endif
-#ifndef LDN_LD3_STAGED
-#define LDN_LD3_STAGED 1     // conv3's weights through the loader's registers, shuffled once into fragment order (0 = LDS-DMA + per-wave shuffles: A/B measurements)
-#endif
 
+constexpr int LD_R2MAX = 4;                       // deepest W2 ring
 constexpr int LD_SYNC_OFF = T_KIDX_BYTES;         // the sync words live behind the channel list in every phase
 constexpr int LD_SYNC_BYTES = 256;
 constexpr int LD_LOADER = 7;                      // the wave without pixels
@@ -406,7 +389,6 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
     constexpr int MAXP = NS * 4;                      // pieces of a W2 / W3 chunk when the image keeps every channel (Kp / 8)
     constexpr int MAXH = 28;                          // pieces of an h1 slice (<= 224 pixels, 8 per piece)
     constexpr int NP = W;
-    constexpr int W3_ROW = LD_CW * 8;
     int* const s_kidx = reinterpret_cast<int*>(smem);
     LdSync* const sy = reinterpret_cast<LdSync*>(smem + LD_SYNC_OFF);
     unsigned char* const s_lo = smem + LD_SYNC_OFF + LD_SYNC_BYTES;
@@ -435,7 +417,7 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
     __syncthreads();
 
     const int avail2 = lds_total - (LD_SYNC_OFF + LD_SYNC_BYTES) - 2 * p.slice_bytes;
-    const int R2 = __builtin_amdgcn_readfirstlane(nsub > 0 ? min(LDN_LD_R2MAX, avail2 / slot2) : LDN_LD_R2MAX);          // >= 3 for a 224-pixel map of width 256
+    const int R2 = __builtin_amdgcn_readfirstlane(nsub > 0 ? min(LD_R2MAX, avail2 / slot2) : LD_R2MAX);          // >= 3 for a 224-pixel map of width 256
     const int avail3 = lds_total - (LD_SYNC_OFF + LD_SYNC_BYTES) - 18 * NP * 4 - 7 * 4096;
     const int R3 = __builtin_amdgcn_readfirstlane(nsub > 0 ? min(4, avail3 / slot3) : 4);
     const int nchunks = nsub * 9;
@@ -457,102 +439,6 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
     // ======================================================================================================== conv2 (3x3)
     f32x16 acc[NS];
     if (loader) {
-#if LDN_LD2_STAGED
-        // W2 tiles through the loader's registers (as conv3's chunks below: the shuffle into fragment order happens ONCE, not in seven waves).  A tile =
-        // 16 k-pair rows x Kp / 2 channel pairs of 16 B = 2 Kp pieces = nsub per lane, staged in HALVES of two groups each: item i (< nsub / 2
-        // rounded up) of a lane = e = lane + 64 i over (group-in-half gh = e / (Kp / 2), packed channel pair v = e % (Kp / 2)); half hf holds groups
-        // 2 hf + gh (K16 half hf of lane half gh: rows 8 hf + 4 gh + {0 .. 3}).  One register buffer per half: while a half is shuffled and written,
-        // the other half's sixteen-byte loads are in flight -- a whole tile of loads is always outstanding.  Slot layout
-        // [group][hi | lo plane][Kp channels][16 B]: a consumer fragment is one conflict-free ds_read_b128.
-        constexpr int NH = NS / 2;                    // items per lane and half (all channels kept)
-        const int nhi = (nsub + 1) / 2;               // ... for this image
-        unsigned colo[NH];                            // source offset of the item's channel pair
-        unsigned dsto[NH];                            // destination offset in the slot's half (a multiple of 32) | gh;  ~0u = no such item (odd nsub)
-        const int hp = max(Kp / 2, 1);
-#pragma unroll
-        for (int i = 0; i < NH; ++i) {
-            const int e = 64 * i + lane;
-            const int gh = e / hp, v = e - gh * hp;
-            const int ch = 2 * v < Kb ? s_kidx[2 * v] : 0;               // columns beyond the list fetch pair 0 (their accumulator columns meet zero tables)
-            colo[i] = (unsigned)((ch >> 1) * 16);
-            dsto[i] = gh < 2 ? ((unsigned)(gh * Kp * 32 + v * 32) | (unsigned)gh) : ~0u;
-        }
-        unsigned ro[2][NH][4];                        // this slice's source offsets per half: rows through the channel list (rows beyond it meet zero h1 columns)
-        auto slice_rows = [&](int s_) {
-#pragma unroll
-            for (int hf = 0; hf < 2; ++hf)
-#pragma unroll
-                for (int i = 0; i < NH; ++i) {
-                    const int gh = (int)(dsto[i] & 1u);
-#pragma unroll
-                    for (int qq = 0; qq < 4; ++qq) {
-                        const int kch = s_kidx[32 * s_ + 2 * (8 * hf + 4 * gh + qq)];
-                        ro[hf][i][qq] = (unsigned)((max(kch, 0) >> 1) * (W / 2) * 16) + colo[i];
-                    }
-                }
-        };
-        u32x4 LA[NH][4], LB[NH][4];                   // the two halves' pieces
-        auto load_half = [&](int t_, int hf, u32x4 (&L_)[NH][4]) {
-            const unsigned char* src = reinterpret_cast<const unsigned char*>(uniform_ptr(p.w2p + (long)t_ * ((W / 2) * (W / 2) * 16)));
-#pragma unroll
-            for (int i = 0; i < NH; ++i)
-                if (i < nhi)
-#pragma unroll
-                    for (int qq = 0; qq < 4; ++qq) L_[i][qq] = ld_global16(src, ro[hf][i][qq]);
-        };
-        auto store_half = [&](unsigned char* slotp, int hf, const u32x4 (&L_)[NH][4]) {
-            const int lo = Kp * 16;
-            unsigned char* hb = slotp + hf * (Kp * 64);
-#pragma unroll
-            for (int i = 0; i < NH; ++i)
-                if (i < nhi && dsto[i] != ~0u) {
-                    unsigned char* d = hb + (dsto[i] & ~31u);
-                    *reinterpret_cast<u32x4*>(d) = u32x4{L_[i][0][0], L_[i][1][0], L_[i][2][0], L_[i][3][0]};             // channel 2 v: hi quad
-                    *reinterpret_cast<u32x4*>(d + lo) = u32x4{L_[i][0][1], L_[i][1][1], L_[i][2][1], L_[i][3][1]};        //              lo quad
-                    *reinterpret_cast<u32x4*>(d + 16) = u32x4{L_[i][0][2], L_[i][1][2], L_[i][2][2], L_[i][3][2]};        // channel 2 v + 1
-                    *reinterpret_cast<u32x4*>(d + lo + 16) = u32x4{L_[i][0][3], L_[i][1][3], L_[i][2][3], L_[i][3][3]};
-                }
-        };
-        const unsigned lds_h1 = lds_off(s_h1);
-        const unsigned char* const h1b = p.h1 + pix0 * p.h1_row_bytes;
-        // h1 slice piece i: rows 8 i + (lane >> 3), physical 16-byte slot lane & 7 (XOR swizzle on the source side)
-        auto h1_piece = [&](int i, const void* sb, unsigned dst) {
-            const int r = 8 * i + (lane >> 3);
-            const unsigned o = (unsigned)(min(r, NR - 1) * (int)p.h1_row_bytes + (((lane & 7) ^ ((r >> 1) & 7)) << 4));
-            dma16_pieces<1>({o}, sb, (unsigned)__builtin_amdgcn_readfirstlane((int)(dst + (unsigned)i * 1024u)));
-        };
-        if (nchunks > 0) {
-            const void* sb0 = uniform_ptr(h1b);
-            for (int i = 0; i < nq; ++i) h1_piece(i, sb0, lds_h1);       // slice 0 -> slot 0
-            slice_rows(0);
-            load_half(0, 0, LA);
-            load_half(0, 1, LB);
-        }
-        int slot = 0;
-        int sn = 0, tn = 1;                           // slice / tap of chunk c + 1
-        for (int c = 0; c < nchunks; ++c) {
-            const int sc = c / 9, tc = c - 9 * sc;
-            const bool nxt = c + 1 < nchunks;
-            if (c >= R2) LD_TIMED(6, ld_wait_done(sy, ncomp, base2 + (unsigned)(c - R2 + 1), dead))
-            if (tc == 0) wait_vm<0>();              // slice sc has landed (its pieces went out with taps TMIN .. 8 of the slice before)
-            unsigned char* const slotp = s_w2 + slot * slot2;
-            slot = slot + 1 == R2 ? 0 : slot + 1;
-            store_half(slotp, 0, LA);                 // (waits for half 0's pieces only: half 1's and nothing younger may still fly)
-            if (nxt) {
-                if (tn == 0) slice_rows(sn);          // (both halves' rows of the next slice: ro[1] of THIS chunk has been consumed by its loads)
-                load_half(tn, 0, LA);
-            }
-            store_half(slotp, 1, LB);
-            ld_publish(sy, base2 + (unsigned)c + 1u);                  // (LDS executes this wave's writes in order: the word lands behind the quads)
-            if (nxt) load_half(tn, 1, LB);
-            if (tc >= TMIN && sc + 1 < nsub) {        // slice sc + 1: piece i goes out with tap TMIN + i % 6 (every reader has left slice sc - 1 by then: R2 <= 4)
-                const void* hsb = uniform_ptr(h1b + (long)(sc + 1) * 128);
-                const unsigned hdst = lds_h1 + (unsigned)((sc + 1) & 1) * (unsigned)p.slice_bytes;
-                for (int i = tc - TMIN; i < nq; i += 6) h1_piece(i, hsb, hdst);
-            }
-            if (++tn == 9) { tn = 0; ++sn; }
-        }
-#else
         unsigned ho[MAXH];                            // h1 slice piece i: rows 8 i + (lane >> 3), physical 16-byte slot lane & 7
 #pragma unroll
         for (int i = 0; i < MAXH; ++i) {
@@ -611,7 +497,6 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
                 if (c > 0) { wait_vm_rt<62, 63>(pieces); ld_publish(sy, base2 + (unsigned)c); }      // chunks < c (and every slice piece issued with them) have landed
             }
         }
-#endif
         wait_vm<0>();
         ld_publish(sy, base2 + (unsigned)nchunks);
         LT(tb)
@@ -620,7 +505,6 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
         // barriers, its offsets and the consumers' 128 accumulator registers would be live together and hipcc spills the offsets -- scratch reloads
         // inside the stream loop, whose s_waitcnt vmcnt(0) then drains the ring every chunk.
         __syncthreads();       // (1) every wave is out of conv2: the slice / W2 regions are free
-#if LDN_LD3_STAGED
         // conv3's weights through the loader's REGISTERS (it idles ~100 k cycles per block in this phase): a W3 piece (16 B) holds one k-pair of two
         // channels as {hi k0k1, lo k0k1} x 2, a consumer's A fragment the hi (or lo) halves of FOUR k-pairs of ONE channel -- staged by DMA, every one of
         // the seven consumer waves rebuilt it with eight ds_read_b64 + sixteen v_mov per n-subtile.  Here the loader shuffles ONCE: item i of a lane =
@@ -668,29 +552,6 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
                 if (cc + 1 < nchunk3) load_chunk(cc + 1);                 // ... and fly through the wait for the next free slot
             }
         }
-#else
-        const unsigned lds_w3 = lds_off(s_w3);
-        unsigned w3o[MAXP];    // W3 piece i = k-pair rows 4 i .. 4 i + 3 (256 B each: 32 channels x 8 B): lane = (row 4 i + lane / 16, channel pair lane % 16)
-#pragma unroll
-        for (int i = 0; i < MAXP; ++i) {
-            const int u = 4 * i + (lane >> 4);
-            const int kch = 2 * u < Kp ? s_kidx[2 * u] : -1;              // rows beyond the list meet zero h2 values
-            w3o[i] = (unsigned)(((long)(max(kch, 0) >> 1) * p.cout + 2 * (lane & 15)) * 8) + ld_bias(i);
-        }
-        if (nchunk3 > 0 && nsub > 0) ld_dma_run<MAXP>(w3o, P2, p.w3p, lds_w3);      // chunk 0 flies through the table build
-        __syncthreads();       // (2) the tables are in LDS
-        if (nsub > 0) {
-            int slot3i = 1 == R3 ? 0 : 1;
-            for (int cc = 1; cc < nchunk3; ++cc) {
-                if (cc >= R3) LD_TIMED(7, ld_wait_done(sy, ncomp, base3 + (unsigned)(cc - R3 + 1), dead))
-                ld_dma_run<MAXP>(w3o, P2, p.w3p + (long)cc * (LD_CW * 8), lds_w3 + (unsigned)slot3i * (unsigned)slot3);
-                slot3i = slot3i + 1 == R3 ? 0 : slot3i + 1;
-                wait_vm_rt<62, 63>(P2);
-                ld_publish(sy, base3 + (unsigned)cc);
-            }
-            wait_vm<0>();
-        }
-#endif
         ld_publish(sy, base3 + (unsigned)nchunk3);
         LT(tc)
         LD_SPAN(4, tb, tc)
@@ -719,15 +580,8 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
         unsigned arow[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) arow[i] = (unsigned)(4 * h + (i & 3) + 8 * (i >> 2)) * RL + (unsigned)l31 * 8u;
-        // staged form: slot = [group 2 half + h][hi | lo plane][Kp channels][16 B]; bq[2 half + plane]
-        unsigned bq[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) bq[i] = (unsigned)((2 * (i >> 1) + h) * Kp * 32 + (i & 1) * Kp * 16 + l31 * 16);
-#ifndef LDN_LD2_STYLE
-#define LDN_LD2_STYLE 1     // 1 = per n-subtile eight entry reads, then six MFMAs, scheduled by hipcc; 3 = a hand-pipelined sequence (entries of subtile j - 1 requested in front of the MFMAs of subtile j, the next chunk's first operands in front of the last ones): measured SLOWER (conv2 151 k vs 143 k cycles per block) -- the loop is not bound by LDS latency
-#endif
 #ifndef LDN_LD_ABLATE
-#define LDN_LD_ABLATE 0     // tuning only, style 1 (results are wrong): 1 = entries are not shuffled into hi / lo quads, 2 = entries are not read from LDS, 4 = no MFMA
+#define LDN_LD_ABLATE 0     // tuning only (results are wrong): 1 = entries are not shuffled into hi / lo quads, 2 = entries are not read from LDS, 4 = no MFMA
 #endif
 #if LDN_LD_ABLATE & 2
 #define LD_ABL_RD(PTR_, I_) (u32x2{(unsigned)(I_) + (unsigned)l31, (unsigned)(I_) * 3u + (unsigned)h})
@@ -746,7 +600,6 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
 #else
 #define LD_ABL_K16(ACC_, AH_, AL_, BH_, BL_) LDN_K16(false, ACC_, AH_, AL_, BH_, BL_)
 #endif
-#if LDN_LD2_STYLE == 1
         int slot = 0;
         for (int s = 0; s < nsub; ++s) {
             const unsigned char* hs = s_h1 + (s & 1) * p.slice_bytes;
@@ -765,22 +618,6 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
                         bh[half] = *reinterpret_cast<const bf16x8*>(hs + rbase + ((sl ^ rx) << 4));
                         bl[half] = *reinterpret_cast<const bf16x8*>(hs + rbase + (((sl + 1) ^ rx) << 4));
                     }
-#if LDN_LD2_STAGED
-#pragma unroll
-                    for (int j = 0; j < NS; ++j) {
-                        if (j < nsub) {      // fragment (j, K16 half, hi | lo) = one ds_read_b128: group 2 half + h, plane, channel 32 j + l31
-                            const bf16x8 ah0 = *reinterpret_cast<const bf16x8*>(ws + bq[0] + j * 512);
-                            const bf16x8 al0 = *reinterpret_cast<const bf16x8*>(ws + bq[1] + j * 512);
-                            const bf16x8 ah1 = *reinterpret_cast<const bf16x8*>(ws + bq[2] + j * 512);
-                            const bf16x8 al1 = *reinterpret_cast<const bf16x8*>(ws + bq[3] + j * 512);
-                            LDN_K16(false, acc[j], ah0, al0, bh[0], bl[0])
-                            LDN_K16(false, acc[j], ah1, al1, bh[1], bl[1])
-                            __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
-                        }
-                    }
-                }
-#else
 #pragma unroll
                     for (int j = 0; j < NS; ++j) {
                         if (j < nsub) {
@@ -806,123 +643,9 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
                         }
                     }
                 }
-#endif
                 ld_post_done(sy, wave, base2 + (unsigned)c + 1u);
             }
         }
-#else
-        // One chunk = tap t of K slice s: B fragment = the tap's h1 row (per-lane LDS address), A = the staged W2 rows.  The image's n-subtiles in
-        // DESCENDING order as ONE linear, software-pipelined sequence with an entry point per subtile count (a switch that falls through): the
-        // eight weight entries of subtile j - 1 are requested in front of the six MFMAs of subtile j (a full step of matrix time covers their LDS
-        // latency -- half a step did not: measured), and the NEXT chunk's B fragment and first entries in front of the last six MFMAs of this one
-        // when that chunk has already landed (a non-blocking look at the landed word; otherwise at the top of the next chunk).  Per accumulator the
-        // products keep tail_body's order (half 0, then half 1, chunk after chunk).
-        struct Ent { u32x2 e0[4], e1[4]; };
-        bf16x8 bh[2], bl[2];
-        Ent cur;
-        // (the tap row behind an optimisation barrier: left alone, hipcc hoists the nine taps' four fragment addresses out of the slice loop --
-        // 36 registers that it then spills and reloads inside the chunk)
-        auto rdB = [&](const unsigned char* hs_, int tr, bf16x8 (&dh)[2], bf16x8 (&dl)[2]) {
-            asm volatile("" : "+v"(tr));
-            const unsigned rbase = (unsigned)tr * 128u, rx = ((unsigned)tr >> 1) & 7u;
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                const unsigned sl = 2u * (2u * half + h);
-                dh[half] = *reinterpret_cast<const bf16x8*>(hs_ + rbase + ((sl ^ rx) << 4));
-                dl[half] = *reinterpret_cast<const bf16x8*>(hs_ + rbase + (((sl + 1) ^ rx) << 4));
-            }
-        };
-        auto rdBh = [&](const unsigned char* hs_, int tr, int half, bf16x8& dh, bf16x8& dl) {
-            asm volatile("" : "+v"(tr));
-            const unsigned rbase = (unsigned)tr * 128u, rx = ((unsigned)tr >> 1) & 7u;
-            const unsigned sl = 2u * (2u * half + h);
-            dh = *reinterpret_cast<const bf16x8*>(hs_ + rbase + ((sl ^ rx) << 4));
-            dl = *reinterpret_cast<const bf16x8*>(hs_ + rbase + (((sl + 1) ^ rx) << 4));
-        };
-        auto rdE = [&](const unsigned char* ws_, int j, Ent& d) {
-#pragma unroll
-            for (int qq = 0; qq < 4; ++qq) d.e0[qq] = *reinterpret_cast<const u32x2*>(ws_ + arow[qq] + j * 256);
-#pragma unroll
-            for (int qq = 0; qq < 4; ++qq) d.e1[qq] = *reinterpret_cast<const u32x2*>(ws_ + arow[4 + qq] + j * 256);
-        };
-#define LDN_LD2_ASM(E_, AH_, AL_)                                                                         \
-            const bf16x8 AH_ = __builtin_bit_cast(bf16x8, (u32x4{E_[0][0], E_[1][0], E_[2][0], E_[3][0]})); \
-            const bf16x8 AL_ = __builtin_bit_cast(bf16x8, (u32x4{E_[0][1], E_[1][1], E_[2][1], E_[3][1]}));
-#define LDN_LD2_STEP(J) {                                                                                 \
-            Ent nxt;                                                                                      \
-            rdE(ws, J - 1, nxt);                                                                          \
-            __builtin_amdgcn_sched_barrier(0);                                                            \
-            { LDN_LD2_ASM(cur.e0, ah0, al0) LDN_LD2_ASM(cur.e1, ah1, al1)                                 \
-              LDN_K16(false, acc[J], ah0, al0, bh[0], bl[0])                                              \
-              LDN_K16(false, acc[J], ah1, al1, bh[1], bl[1]) }                                            \
-            __builtin_amdgcn_sched_barrier(0);                                                            \
-            cur = nxt; }
-        int slot = 0;
-        const unsigned char* ws = s_w2;
-        bool pre = false;                  // this chunk's B fragment and first entries were requested during the previous chunk
-        for (int s = 0; s < nsub; ++s) {
-            const unsigned char* hs = s_h1 + (s & 1) * p.slice_bytes;
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int c = 9 * s + t;
-                if (!pre) {
-                    LD_TIMED(6, ld_wait_landed(sy, base2 + (unsigned)c + 1u, q.seen))
-                    rdB(hs, trow[t], bh, bl);
-                    rdE(ws, nsub - 1, cur);
-                }
-                slot = slot + 1 == R2 ? 0 : slot + 1;
-                const unsigned char* wsn = s_w2 + slot * slot2;                                    // the next chunk's slot,
-                const unsigned char* hsn = t == 8 ? s_h1 + ((s + 1) & 1) * p.slice_bytes : hs;     // slice
-                const int trn = trow[(t + 1) % 9];                                                 // and tap row
-                switch (nsub) {
-                    default:
-                        if constexpr (NS >= 8) LDN_LD2_STEP(7)
-                        [[fallthrough]];
-                    case 7:
-                        if constexpr (NS >= 8) LDN_LD2_STEP(6)
-                        [[fallthrough]];
-                    case 6:
-                        if constexpr (NS >= 8) LDN_LD2_STEP(5)
-                        [[fallthrough]];
-                    case 5:
-                        if constexpr (NS >= 8) LDN_LD2_STEP(4)
-                        [[fallthrough]];
-                    case 4:
-                        if constexpr (NS >= 4) LDN_LD2_STEP(3)
-                        [[fallthrough]];
-                    case 3:
-                        if constexpr (NS >= 4) LDN_LD2_STEP(2)
-                        [[fallthrough]];
-                    case 2:
-                        LDN_LD2_STEP(1)
-                        [[fallthrough]];
-                    case 1: {
-                        LDN_LD2_ASM(cur.e0, ah0, al0) LDN_LD2_ASM(cur.e1, ah1, al1)
-                        __builtin_amdgcn_sched_barrier(0);
-                        pre = false;
-                        if (c + 1 < nchunks) {      // (wave-uniform)
-                            const unsigned need = base2 + (unsigned)c + 2u;
-                            if (q.seen < need) q.seen = __builtin_amdgcn_readfirstlane(ld_lds_read(&sy->landed));      // one look, no spin
-                            pre = q.seen >= need;
-                        }
-                        if (pre) rdE(wsn, nsub - 1, cur);
-                        __builtin_amdgcn_sched_barrier(0);
-                        LDN_K16(false, acc[0], ah0, al0, bh[0], bl[0])
-                        __builtin_amdgcn_sched_barrier(0);
-                        if (pre) rdBh(hsn, trn, 0, bh[0], bl[0]);      // (in place: the MFMAs that read this half have been issued)
-                        __builtin_amdgcn_sched_barrier(0);
-                        LDN_K16(false, acc[0], ah1, al1, bh[1], bl[1])
-                        __builtin_amdgcn_sched_barrier(0);
-                        if (pre) rdBh(hsn, trn, 1, bh[1], bl[1]);
-                    }
-                }
-                ld_post_done(sy, wave, base2 + (unsigned)c + 1u);
-                ws = wsn;
-            }
-        }
-#undef LDN_LD2_ASM
-#undef LDN_LD2_STEP
-#endif
     }
     LT(tb)
     LD_SPAN(2, ta, tb)
@@ -1002,109 +725,8 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
     LT(tc)
     LD_SPAN(3, tb, tc)
     const int trw = lane >> 3, tcq = lane & 7;                 // epilogue layout: lane = (row trw + 8 it, 4 channels at 4 tcq)
-    const unsigned a3_lane = (unsigned)(2 * h * W3_ROW + l31 * 8);
-    const unsigned a3q = (unsigned)(h * 1024 + l31 * 16);      // staged form: the lane's channel in the hi plane of lane half h's group
+    const unsigned a3q = (unsigned)(h * 1024 + l31 * 16);      // the lane's channel in the hi plane of lane half h's group
     float* const scr = reinterpret_cast<float*>(s_scr + wave * 4096);   // this wave's 32 x 32 transpose scratch
-#if LDN_LD3_DEFER && LDN_LD3_STAGED
-    // DEFERRED epilogue (round 6, an experiment kept as a switch: measured NEUTRAL, 221-225 us per block either way -- timers around its pieces
-    // show ~1.0 k cycles per chunk of instruction issue (VALU + stores) against ~0.2 k of waiting for the residual tile: the epilogue is issue-bound,
-    // there is no latency to hide).  A chunk's K loop ends with the four
-    // ds_write_b128 of its accumulators into the wave's scratch and the request of its residual tile; everything that has to WAIT -- the transposed
-    // read-back, the residual's arrival, the stores -- is placed between the n-subtile steps of the NEXT chunk's K loop (program order = issue order:
-    // the steps are separate basic blocks), where the MFMAs of this wave and its SIMD partner cover it.  Same values, same order per element.
-    int slot = 0;
-    f32x4 res[4], xr[4], sh;
-    int c0p = 0;                                            // first channel of the chunk whose epilogue is pending
-    auto epi_read = [&]() {                                 // piece 1: the tile back from the scratch in the row layout (written one K loop ago)
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const int row = trw + 8 * it;
-            xr[it] = *reinterpret_cast<const f32x4*>(scr + row * 32 + ((tcq ^ (row & 7)) << 2));
-        }
-    };
-    auto epi_store = [&]() {                                // piece 2: + shift + residual, ReLU, store; piece 3: the GAP partials
-        wait_vm<0>();                                       // the residual tile (requested behind the previous K loop) and this wave's earlier stores
-        asm volatile("" : "+v"(res[0]), "+v"(res[1]), "+v"(res[2]), "+v"(res[3]), "+v"(sh));
-        f32x4 csum = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const int prow = wave * 32 + trw + 8 * it;
-            f32x4 x = xr[it] + sh + res[it];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) x[e] = fmaxf(x[e], 0.f);
-            if (prow < npix) {
-                __builtin_nontemporal_store(x, reinterpret_cast<f32x4*>(p.out + (size_t)(pix0 + prow) * p.ldo + c0p + tcq * 4));
-                csum += x;
-            }
-        }
-        xr[0] = csum;                                       // (handed to the third piece)
-    };
-    auto epi_gap = [&]() {
-        if (p.colsum) {
-            f32x4 csum = xr[0];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) csum[e] = sum_lane_bits_345(csum[e]);
-            if (trw == 0) *reinterpret_cast<f32x4*>(p.colsum + ((size_t)b * 8 + wave) * p.cout + c0p + tcq * 4) = csum;
-        }
-    };
-    for (int cc = 0; cc < nchunk3; ++cc) {
-        const int c0 = cc * LD_CW;
-        const bool pend = cc > 0;                           // (wave-uniform) chunk cc - 1's epilogue is pending
-        f32x16 acc3;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc3[r] = 0.f;
-        LD_TIMED(7, ld_wait_landed(sy, base3 + (unsigned)cc + 1u, q.seen))
-        const unsigned char* ws = s_w3 + slot * slot3;
-        slot = slot + 1 == R3 ? 0 : slot + 1;
-        // pieces of the pending epilogue: the read-back behind step 0, the stores behind step js (late: the residual tile then had most of
-        // a K loop to arrive), the GAP partials one step later
-        const int js = min(LDN_LD3_STORE_STEP, nsub - 1), jg = min(js + 1, nsub - 1);
-        bool todo = pend;
-#pragma unroll
-        for (int j = 0; j < NS; ++j) {
-            if (j < nsub) {
-                bf16x8 ah[2], al[2];      // group 4 j + 2 t + h of the slot: [hi plane 32 channels x 16 B | lo plane]
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    ah[t] = *reinterpret_cast<const bf16x8*>(ws + a3q + (4 * j + 2 * t) * 1024);
-                    al[t] = *reinterpret_cast<const bf16x8*>(ws + a3q + (4 * j + 2 * t) * 1024 + 512);
-                }
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    const bf16x8 hb = frag_hi(j, t), lb = frag_lo(j, t);
-                    LDN_K16(false, acc3, ah[t], al[t], hb, lb)
-                }
-                __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
-                if (pend) {
-                    if (j == 0) epi_read();
-                    if (j == js) epi_store();
-                    if (j == jg) { epi_gap(); todo = false; }
-                }
-            }
-        }
-        if (todo) { epi_read(); epi_store(); epi_gap(); }   // (an image without live conv2 channels: no K steps to hide behind)
-        ld_post_done(sy, wave, base3 + (unsigned)cc + 1u);
-        // this chunk's accumulators into the scratch (C layout -> rows of 32 channels per pixel, 16-byte slots XOR-swizzled with the pixel), its
-        // residual tile and shift requested: both are consumed inside the next K loop
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-            const f32x4 v = {acc3[4 * q4], acc3[4 * q4 + 1], acc3[4 * q4 + 2], acc3[4 * q4 + 3]};
-            *reinterpret_cast<f32x4*>(scr + l31 * 32 + (((2 * q4 + h) ^ (l31 & 7)) << 2)) = v;
-        }
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const int prow = wave * 32 + trw + 8 * it;
-            const float* src = (p.residual && prow < npix) ? p.residual + (size_t)(pix0 + prow) * p.ldr + c0 + tcq * 4 : g_tail_zero;
-            res[it] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src));
-        }
-        sh = ld_global_f4(p.sh3 + c0 + tcq * 4);            // (address space 1: a flat load here makes the compiler drain vmcnt in front of it)
-        c0p = c0;
-    }
-    if (nchunk3 > 0) { epi_read(); epi_store(); epi_gap(); }      // the last chunk's epilogue
-#else
     int slot = 0;
     for (int cc = 0; cc < nchunk3; ++cc) {
         const int c0 = cc * LD_CW;
@@ -1127,7 +749,6 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
         LD_TIMED(7, ld_wait_landed(sy, base3 + (unsigned)cc + 1u, q.seen))
         const unsigned char* ws = s_w3 + slot * slot3;
         slot = slot + 1 == R3 ? 0 : slot + 1;
-#if LDN_LD3_STAGED
 #pragma unroll
         for (int j = 0; j < NS; ++j) {
             if (j < nsub) {
@@ -1150,29 +771,6 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
                 __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
             }
         }
-#else
-#pragma unroll
-        for (int j = 0; j < NS; ++j) {
-            if (j < nsub) {
-                u32x2 e[2][4];
-#pragma unroll
-                for (int t = 0; t < 2; ++t)
-#pragma unroll
-                    for (int qq = 0; qq < 4; ++qq)
-                        e[t][qq] = *reinterpret_cast<const u32x2*>(ws + a3_lane + (16 * j + 8 * t + (qq & 1) + 4 * (qq >> 1)) * W3_ROW);
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    const u32x4 ahu = {e[t][0][0], e[t][1][0], e[t][2][0], e[t][3][0]};
-                    const u32x4 alu = {e[t][0][1], e[t][1][1], e[t][2][1], e[t][3][1]};
-                    const bf16x8 ah = __builtin_bit_cast(bf16x8, ahu), al = __builtin_bit_cast(bf16x8, alu);
-                    const bf16x8 hb = frag_hi(j, t), lb = frag_lo(j, t);
-                    LDN_K16(false, acc3, ah, al, hb, lb)
-                }
-                __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
-            }
-        }
-#endif
         ld_post_done(sy, wave, base3 + (unsigned)cc + 1u);
         // the residual (and this wave's earlier stores) before this chunk's stores, which then fly through the next chunk (tail_body: gfx9 counts
         // loads and stores in one vmcnt and completes them out of order with each other)
@@ -1212,7 +810,6 @@ __device__ __forceinline__ void tail_ld(const TailArgs& p, const int b, unsigned
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();
     }
-#endif
     LT(td)
     LD_SPAN(4, tc, td)
 }
@@ -1230,16 +827,6 @@ __global__ __launch_bounds__(512, 2) void k_chain_ld(const ChainArgs p) {
             for (int c = lane * 4; c < p.C; c += 256)
                 *reinterpret_cast<f32x4*>(p.colsum + ((size_t)b * 8 + wave) * p.C + c) = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-#if LDN_LD_PRIO
-    // Static priorities (MI355X_MICROARCH.md, two waves per SIMD): the second-dispatched half of the workgroup (waves 4-6) loses every VALU / issue
-    // arbitration against its older SIMD partner and finishes every phase last -- and a phase ends with its LAST wave.  The loader's few instructions
-    // sit on every hand-off's critical path.
-    {
-        const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        if (w == LD_LOADER) __builtin_amdgcn_s_setprio(3);
-        else if (w >= 4) __builtin_amdgcn_s_setprio(LDN_LD_PRIO);
-    }
-#endif
     LdSeq q;
 #ifdef LDN_TRACE
     for (int k = 0; k < 8; ++k) q.t[k] = 0;

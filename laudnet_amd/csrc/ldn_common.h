@@ -115,15 +115,11 @@ __device__ __forceinline__ float sum_lane_bits_345(float x) {
     return __uint_as_float(q[0]) + __uint_as_float(q[1]);
 }
 
-// 16-byte global store, optionally WRITE-THROUGH (sc0 sc1: the line leaves the XCD's L2 at once instead of staying dirty until the
-// end-of-kernel write-back).  LDN_WT_STORES is a tuning switch (the ~5.6 us behind every large row kernel).
+// 16-byte global store (a write-through form, sc0 sc1, was tried against the ~5.6 us behind every large row kernel and removed: DESIGN.md
+// 4w found that figure to be the bench's own event leg).
 template <typename V>
 __device__ __forceinline__ void store16(void* ptr, const V v) {
-#ifdef LDN_WT_STORES
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" :: "v"(ptr), "v"(v) : "memory");
-#else
     *reinterpret_cast<V*>(ptr) = v;
-#endif
 }
 
 constexpr int kWave = 64;   // CDNA wavefront

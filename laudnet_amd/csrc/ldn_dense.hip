@@ -403,11 +403,7 @@ __global__ __launch_bounds__(2 * R, 2) void k_dense(const DenseArgs p) {
             }
         }
     };
-#ifndef LDN_DENSE_NO_PRE
     constexpr bool PRE = FULL;
-#else
-    constexpr bool PRE = false;
-#endif
     // own rows of a chunk = the first four DMA instructions of that chunk: landed once at most (chunks in flight) x per_chunk - 4 are outstanding
     const int own_landed = per_chunk * (D - 1) - 4;
     if (PRE && active && nchunks > 0) {

@@ -1,0 +1,73 @@
+#!/usr/bin/env python3
+"""Do two source trees compile to the same gfx950 device code?  No GPU needed.
+
+    tools/same_isa.py OLD [NEW] [-D NAME[=VALUE] ...] [-j N]
+
+OLD and NEW are directories or git revisions (a revision is exported to a temporary directory); NEW defaults to the working tree.
+Every entry of build.SOURCES is compiled device-only with build.FLAGS (+ the -D flags) from both trees, the gfx950 code object is
+unbundled, and two things are compared per translation unit: the disassembly (`llvm-objdump -d`, without its file-name line) and
+the kernel metadata note (`llvm-readelf --notes`: VGPR / SGPR counts, LDS bytes, scratch, kernarg layout).  The raw objects are
+NOT the criterion: hipcc derives a per-compilation id from the source text.  One line per unit; exit status 1 on any difference.
+"""
+import argparse
+import os
+import subprocess
+import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "laudnet_amd"))      # build.py alone: importing the package would load torch and the library
+import build  # noqa: E402
+
+LLVM = os.environ.get("ROCM_LLVM", "/opt/rocm/llvm/bin")
+
+
+def tree_of(spec: str, tmp: str) -> str:
+    """A directory as it is; a git revision exported under tmp."""
+    if os.path.isdir(spec):
+        return os.path.abspath(spec)
+    out = os.path.join(tmp, "src_" + spec.replace("/", "_"))
+    os.makedirs(out)
+    tar = subprocess.run(["git", "-C", REPO, "archive", spec, "include", "laudnet_amd/csrc"], check=True, stdout=subprocess.PIPE).stdout
+    subprocess.run(["tar", "-x", "-C", out], input=tar, check=True)
+    return out
+
+
+def device_code(tree: str, src: str, defs: list, out: str) -> tuple:
+    """(disassembly, metadata note) of one translation unit's gfx950 code object."""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    sp = os.path.join(tree, "laudnet_amd", "csrc", src)
+    subprocess.run([hipcc] + build.FLAGS + defs + ["--cuda-device-only", "-c", "-o", out + ".o", sp], check=True)
+    subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--unbundle", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                    "--input=" + out + ".o", "--output=" + out + ".co"], check=True)
+    dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", out + ".co"], check=True, capture_output=True, text=True).stdout
+    note = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", out + ".co"], check=True, capture_output=True, text=True).stdout
+    return [ln for ln in dis.splitlines() if "file format" not in ln], note.splitlines()
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("old")
+    ap.add_argument("new", nargs="?")
+    ap.add_argument("-D", dest="defs", action="append", default=[], metavar="NAME[=VALUE]")
+    ap.add_argument("-j", type=int, default=8)
+    a = ap.parse_args()
+    defs = ["-D" + d for d in a.defs]
+    with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(max(1, min(a.j, 16))) as pool:
+        trees = [tree_of(a.old, tmp), tree_of(a.new, tmp) if a.new else REPO]
+        jobs = {(s, i): pool.submit(device_code, t, s, defs, os.path.join(tmp, f"{i}_{s}")) for s in build.SOURCES for i, t in enumerate(trees)}
+        print(f"# {a.old} vs {a.new or 'the working tree'}, flags: {' '.join(build.FLAGS + defs)}")
+        bad = 0
+        for s in build.SOURCES:
+            (d0, n0), (d1, n1) = jobs[s, 0].result(), jobs[s, 1].result()
+            same = d0 == d1 and n0 == n1
+            bad += not same
+            what = "identical" if same else "DIFFERENT:" + (" disassembly" if d0 != d1 else "") + (" metadata" if n0 != n1 else "")
+            print(f"{s:24s} {what:24s} {len(d1)} disassembly lines, {len(n1)} metadata lines", flush=True)
+        print(f"# {len(build.SOURCES) - bad} of {len(build.SOURCES)} translation units identical")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
