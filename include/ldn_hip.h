@@ -360,6 +360,37 @@ int ldn_rows_bn_bwd(const float* dh, int lddh, const float* u, int ldu, const fl
                     const int32_t* m_count, int m_cap, int C, float* du, int lddu, float* d_gamma, float* d_beta, float* g_mask, float* work,
                     void* stream);
 
+/* ---- the POST-ACTIVATION form of the same (LAD-RegNet channel mode on batch statistics): the channel mask multiplies AFTER BatchNorm + ReLU, so
+ * every channel of every image feeds the statistics, dropped or not -- mean / invstd come from ldn_rows_bn_stats with chan_mask = NULL.  The
+ * conventions are those above (fp32, [m_cap][ld >= C], C % 4 == 0, ld % 4 == 0, 16-byte aligned pointers, count and img(r) on the device, rows
+ * r >= count NOT READ and written as exact zeros).
+ *
+ * ldn_rows_bn_postmask_fwd, one launch, one thread per (row, quad):
+ *   h[r][k] = m[img(r)][k] * max(gamma[k] * (u[r][k] - mean[k]) * invstd[k] + beta[k], 0)
+ * chan_mask m [B][C] (NULL = all ones; needs row_prefix [B + 1], B >= 1).  h [m_cap][ldh] may be u itself. */
+int ldn_rows_bn_postmask_fwd(const float* u, int ldu, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                             const float* chan_mask, const int32_t* row_prefix, int B, const int32_t* m_count, int m_cap, int C, float* h,
+                             int ldh, void* stream);
+
+/* ldn_rows_bn_postmask_bwd: the backward of ldn_rows_bn_postmask_fwd THROUGH the batch statistics, given dz = d L / d h (or, with the prologue,
+ * d L / d (gate . h)), the unmasked convolution output u and the stored MASKED h.  Per element of a row r < count:
+ *   dh   = gate ? dz * gate[img(r)][k] + dsq[img(r)][k] : dz      (the optional squeeze-excitation prologue, one fused multiply-add; gate and
+ *                                                                  dsq are [B][C], both NULL or both given)
+ *   xhat = (u - mean[k]) * invstd[k]
+ *   a    = h > 0 ? dh * m[img(r)][k] : 0                          the ReLU gate is READ from the stored h (where m == 0, a == 0 either way)
+ *   r_   = max(gamma[k] * xhat + beta[k], 0)                      RECOMPUTED: a masked channel's ReLU output is not in h
+ *   d_beta[k]    = sum_r a          d_gamma[k] = sum_r a * xhat   (right at gamma == 0 too)
+ *   g_mask[b][k] = sum_{r of image b} dh * r_                     [B][C], every channel, the masked ones included; NULL = not wanted
+ *   du[r][k]     = gamma[k] * invstd[k] * (a - d_beta[k] / n - xhat * d_gamma[k] / n)      n = count; du [m_cap][lddu] may be dz itself
+ * g_mask needs none of the reduced sums, so it rides in the first launch: partial sums, ONE reducer launch for d_beta, d_gamma and g_mask, then
+ * du -- three launches.  row_prefix [B + 1] is required with chan_mask, gate or g_mask.  Deterministic like ldn_rows_act_bwd, with its split plan
+ * and work layout (ldn_rows_bn_postmask_bwd_workspace_bytes(m_cap, C, B); B = 0 without g_mask; work is never NULL).  No floating-point atomics. */
+size_t ldn_rows_bn_postmask_bwd_workspace_bytes(int m_cap, int C, int B);
+int ldn_rows_bn_postmask_bwd(const float* dz, int lddz, const float* u, int ldu, const float* h, int ldh, const float* mean, const float* invstd,
+                             const float* gamma, const float* beta, const float* chan_mask, const int32_t* row_prefix, int B, const float* gate,
+                             const float* dsq, const int32_t* m_count, int m_cap, int C, float* du, int lddu, float* d_gamma, float* d_beta,
+                             float* g_mask, float* work, void* stream);
+
 /* ldn_rows_ln_bwd: the LayerNorm backward on LISTED rows (a token-skip block's norm1 / norm2 in training).  For every list entry r < count
  * (count = clamp(*count, 0, m_cap), read on the device; list NULL: the rows 0 .. m_cap - 1 themselves), src = list[r]:
  *   x^ = (x[src] - mean) * rstd        {mean, rstd} = stats[src] (ldn_row_stats / ldn_row_stats_list; formed from the difference, so a row with

@@ -59,6 +59,9 @@ SIGNATURES = {
     "ldn_rows_bn_fwd": ([_P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _P, _I, _P], _I),
     "ldn_rows_bn_bwd_workspace_bytes": ([_I, _I, _I], C.c_size_t),
     "ldn_rows_bn_bwd": ([_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P], _I),
+    "ldn_rows_bn_postmask_fwd": ([_P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _P, _I, _P], _I),
+    "ldn_rows_bn_postmask_bwd_workspace_bytes": ([_I, _I, _I], C.c_size_t),
+    "ldn_rows_bn_postmask_bwd": ([_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P], _I),
     "ldn_rows_ln_bwd_workspace_bytes": ([_I, _I], C.c_size_t),
     "ldn_rows_ln_bwd": ([_P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _I, _P, _I, _P, _P, _P, _I, _P, _P], _I),
     "ldn_row_stats": ([_P, _I, _I, _I, C.c_float, _P, _P], _I),

@@ -1,5 +1,5 @@
-// ldn_train_bn.hip -- BatchNorm on BATCH statistics over packed rows, forward and backward (ldn_rows_bn_stats, ldn_rows_bn_fwd, ldn_rows_bn_bwd;
-// include/ldn_hip.h): what training needs of the reference's own recipe, where bn1 / bn2 / bn3 normalise with the statistics of the batch.
+// ldn_train_bn.hip -- BatchNorm on BATCH statistics over packed rows, forward and backward (ldn_rows_bn_stats, ldn_rows_bn_fwd, ldn_rows_bn_bwd,
+// ldn_rows_bn_postmask_fwd, ldn_rows_bn_postmask_bwd; include/ldn_hip.h): what training needs of the reference's own recipe, where bn1 / bn2 / bn3 normalise with the statistics of the batch.
 //
 // Bandwidth-bound fp32 row kernels, whatever the math mode of the convolutions around them; all but ldn_rows_bn_fwd (one thread per row and
 // quad) are the walk of ldn_rows_plan.h, with its zeros past the count, its partials, its reducer and its bit-identical sums.
@@ -23,6 +23,14 @@
 // and, where the mask's straight-through gradient is wanted, g_mask[b][k] = sum over the rows of image b of g * u -- FUSED into launch 3 through
 // the image slots and one more reducer launch that adds them: four launches, against six for the same through
 // ldn_rows_img_dot (two) and ldn_rows_chanmask (one) behind a three-launch backward.
+//
+// ldn_rows_bn_postmask_fwd / ldn_rows_bn_postmask_bwd (further down) are the same for a mask applied AFTER BatchNorm + ReLU (LAD-RegNet channel
+// mode: h = m * relu(gamma * xhat + beta), statistics without a mask), with ldn_rows_postmask_bwd's optional squeeze-excitation prologue:
+//     dh = gate ? fma(dz, gate[b, k], dsq[b, k]) : dz        a = h > 0 ? dh * m[b, k] : 0        (the gate read from the stored MASKED h)
+//     d_beta[k] = sum a        d_gamma[k] = sum a * xhat        g_mask[b, k] = sum over image b of dh * relu(gamma * xhat + beta)
+//     du = gamma * invstd * (a - d_beta / n - xhat * d_gamma / n)
+// g_mask needs the UNMASKED ReLU output, which h does not hold at a masked channel: it is recomputed.  It needs none of the reduced sums, so it
+// rides in launch 1 and ONE reducer launch adds d_beta, d_gamma and g_mask: three launches.
 #include "ldn_rows_plan.h"
 
 namespace ldn {
@@ -211,6 +219,120 @@ __global__ __launch_bounds__(ACT_THREADS) void k_bn_bwd_final(const BnBwdArgs p)
     });
 }
 
+// ---- the POST-ACTIVATION form (LAD-RegNet channel mode): the mask multiplies after BatchNorm + ReLU, so every channel of every image feeds the
+// statistics (ldn_rows_bn_stats without a mask) and the stored h = m * relu(..) holds no unmasked ReLU output: the backward recomputes it.
+struct BnPmFwdArgs {
+    const float* u; const float* mean; const float* invstd; const float* gamma; const float* beta; const float* chan_mask;
+    const int32_t* prefix; const int32_t* m_count;
+    float* h;
+    int ldu, ldh, B, m_cap, C;
+};
+
+// one thread per (row, quad); h may be u itself
+__global__ __launch_bounds__(256) void k_rows_bn_postmask_fwd(const BnPmFwdArgs p) {
+    const int Q = p.C >> 2;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t r64 = i / Q;
+    if (r64 >= (size_t)p.m_cap) return;
+    const int r = (int)r64, k = 4 * (int)(i - r64 * Q);
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (r < rows_count(p.m_count, p.m_cap)) {
+        v = ld4(p.gamma + k) * ((ld4(p.u + (size_t)r * p.ldu + k) - ld4(p.mean + k)) * ld4(p.invstd + k)) + ld4(p.beta + k);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+        if (p.chan_mask) v *= ld4(p.chan_mask + (size_t)image_of_row(p.prefix, p.B, r) * p.C + k);
+    }
+    store16(p.h + (size_t)r * p.ldh + k, v);
+}
+
+struct BnPmBwdArgs {
+    const float* dz; const float* u; const float* h; const float* mean; const float* invstd; const float* gamma; const float* beta;
+    const float* chan_mask; const int32_t* prefix; const float* gate; const float* dsq; const int32_t* m_count;
+    float* du; float* d_gamma; float* d_beta; float* g_mask; float* work;
+    int lddz, ldu, ldh, lddu, B, m_cap, C, splits, rps;
+};
+
+// what a thread keeps of its image for the length of a segment: the mask and the SE prologue of its quad (ones / unused without them)
+struct BnPmImage { f32x4 m, ga, dq; };
+
+__device__ __forceinline__ BnPmImage bn_pm_image(const BnPmBwdArgs& p, int b, int k) {
+    BnPmImage im;
+    im.m = f32x4{1.f, 1.f, 1.f, 1.f};
+    im.ga = im.dq = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (p.chan_mask) im.m = ld4(p.chan_mask + (size_t)b * p.C + k);
+    if (p.gate) {
+        im.ga = ld4(p.gate + (size_t)b * p.C + k);
+        im.dq = ld4(p.dsq + (size_t)b * p.C + k);
+    }
+    return im;
+}
+
+// (dh, xhat, a) of one quad of row r: the prologue as ldn_rows_postmask_bwd's (one rounding), the ReLU gate READ FROM THE STORED h
+__device__ __forceinline__ void bn_pm_quad(const BnPmBwdArgs& p, int r, int k, const BnPmImage& im, const f32x4 mean, const f32x4 inv, f32x4& dh,
+                                           f32x4& xhat, f32x4& a) {
+    xhat = (ld4(p.u + (size_t)r * p.ldu + k) - mean) * inv;
+    const f32x4 dz = ld4(p.dz + (size_t)r * p.lddz + k);
+    const f32x4 h = ld4(p.h + (size_t)r * p.ldh + k);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        dh[e] = p.gate ? fmaf(dz[e], im.ga[e], im.dq[e]) : dz[e];
+        a[e] = h[e] > 0.f ? dh[e] * im.m[e] : 0.f;
+    }
+}
+
+// launch 1: the split's partial d_beta / d_gamma (column partials 0 / 1) and -- it needs none of the reduced sums -- the partial g_mask of every
+// image that owns rows of the split (image slots); launch 2, ONE rows_reduce, adds all three
+__global__ __launch_bounds__(ACT_THREADS) void k_bn_pm_bwd_partial(const BnPmBwdArgs p) {
+    __shared__ f32x4 s_red[ACT_THREADS];
+    const RowWalk w = row_walk(p.C, p.m_count, p.m_cap, p.rps);
+    if (w.empty()) return;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    f32x4 mean = zero, inv = zero, gam = zero, bet = zero, g_b = zero, g_g = zero;
+    if (w.active) {
+        mean = ld4(p.mean + w.k);
+        inv = ld4(p.invstd + w.k);
+        gam = ld4(p.gamma + w.k);
+        bet = ld4(p.beta + w.k);
+    }
+    for_each_image_segment(w, p.prefix, p.B, [&](int b, int r0, int seg_end) {
+        f32x4 g_m = zero;
+        if (w.active) {
+            const BnPmImage im = bn_pm_image(p, b, w.k);
+            for (int r = r0 + w.rl; r < seg_end; r += w.RL) {
+                f32x4 dh, xhat, a;
+                bn_pm_quad(p, r, w.k, im, mean, inv, dh, xhat, a);
+                g_b += a;
+                g_g += a * xhat;
+                f32x4 rv = gam * xhat + bet;               // the UNMASKED ReLU output: a masked channel's is not in h
+#pragma unroll
+                for (int e = 0; e < 4; ++e) rv[e] = rv[e] > 0.f ? rv[e] : 0.f;
+                g_m += dh * rv;
+            }
+        }
+        if (p.g_mask) lane_sum_to(s_red, w, g_m, work_slot(p.work, p.splits, p.C, 2, w.split + b));
+    });
+    lane_sum_to(s_red, w, g_b, work_col(p.work, p.splits, p.C, 0, w.split));
+    lane_sum_to(s_red, w, g_g, work_col(p.work, p.splits, p.C, 1, w.split));
+}
+
+// launch 3: du
+__global__ __launch_bounds__(ACT_THREADS) void k_bn_pm_bwd_final(const BnPmBwdArgs p) {
+    const RowWalk w = row_walk(p.C, p.m_count, p.m_cap, p.rps);
+    zero_past_count(w, p.du, p.lddu);
+    if (w.empty() || !w.active) return;                    // (no barrier below)
+    const float inv_n = 1.f / (float)w.count;              // (count >= r_end > 0)
+    const f32x4 mean = ld4(p.mean + w.k), inv = ld4(p.invstd + w.k);
+    const f32x4 gi = ld4(p.gamma + w.k) * inv, cb = ld4(p.d_beta + w.k) * inv_n, cg = ld4(p.d_gamma + w.k) * inv_n;
+    for_each_image_segment(w, p.prefix, p.B, [&](int b, int r0, int seg_end) {
+        const BnPmImage im = bn_pm_image(p, b, w.k);
+        for (int r = r0 + w.rl; r < seg_end; r += w.RL) {
+            f32x4 dh, xhat, a;
+            bn_pm_quad(p, r, w.k, im, mean, inv, dh, xhat, a);
+            store16(p.du + (size_t)r * p.lddu + w.k, gi * (a - cb - xhat * cg));
+        }
+    });
+}
+
 }  // namespace ldn
 
 using namespace ldn;
@@ -296,5 +418,62 @@ extern "C" int ldn_rows_bn_bwd(const float* dh, int lddh, const float* u, int ld
         LDN_CHECK_LAUNCH("k_bn_bwd_final");
     }
     if (g_mask) return rows_reduce({nullptr, work_slot(work, p.splits, C, 2, 0), row_prefix, m_count, {nullptr, nullptr}, g_mask, 0, B, B, m_cap, C, p.splits, p.rps}, st);
+    return LDN_OK;
+}
+
+extern "C" int ldn_rows_bn_postmask_fwd(const float* u, int ldu, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                                        const float* chan_mask, const int32_t* row_prefix, int B, const int32_t* m_count, int m_cap, int C,
+                                        float* h, int ldh, void* stream) {
+    LDN_REQUIRE(u && mean && invstd && gamma && beta && h, "ldn_rows_bn_postmask_fwd: null pointer");
+    LDN_REQUIRE(m_cap >= 0 && C > 0 && C % 4 == 0, "ldn_rows_bn_postmask_fwd: m_cap >= 0, C %% 4 == 0 (got %d, %d)", m_cap, C);
+    LDN_REQUIRE(ldu >= C && ldh >= C && ldu % 4 == 0 && ldh % 4 == 0,
+                "ldn_rows_bn_postmask_fwd: leading dimensions >= C and multiples of 4 (got %d, %d)", ldu, ldh);
+    LDN_REQUIRE(!chan_mask || (row_prefix && B >= 1), "ldn_rows_bn_postmask_fwd: chan_mask needs row_prefix [B + 1] and B >= 1");
+    LDN_REQUIRE(aligned16(u) && aligned16(mean) && aligned16(invstd) && aligned16(gamma) && aligned16(beta) && aligned16(chan_mask) && aligned16(h),
+                "ldn_rows_bn_postmask_fwd: every float pointer must be 16-byte aligned");
+    if (m_cap == 0) return LDN_OK;
+    const size_t n = (size_t)m_cap * (C / 4);
+    LDN_REQUIRE((n + 255) / 256 <= 0x7fffffffull, "ldn_rows_bn_postmask_fwd: m_cap * C too large");
+    BnPmFwdArgs p;
+    p.u = u; p.mean = mean; p.invstd = invstd; p.gamma = gamma; p.beta = beta; p.chan_mask = chan_mask; p.prefix = row_prefix;
+    p.m_count = m_count; p.h = h; p.ldu = ldu; p.ldh = ldh; p.B = chan_mask ? B : 0; p.m_cap = m_cap; p.C = C;
+    k_rows_bn_postmask_fwd<<<(unsigned)((n + 255) / 256), 256, 0, static_cast<hipStream_t>(stream)>>>(p);
+    LDN_CHECK_LAUNCH("k_rows_bn_postmask_fwd");
+    return LDN_OK;
+}
+
+extern "C" size_t ldn_rows_bn_postmask_bwd_workspace_bytes(int m_cap, int C, int B) { return rows_bwd_work_bytes(m_cap, C, B); }
+
+extern "C" int ldn_rows_bn_postmask_bwd(const float* dz, int lddz, const float* u, int ldu, const float* h, int ldh, const float* mean,
+                                        const float* invstd, const float* gamma, const float* beta, const float* chan_mask,
+                                        const int32_t* row_prefix, int B, const float* gate, const float* dsq, const int32_t* m_count, int m_cap,
+                                        int C, float* du, int lddu, float* d_gamma, float* d_beta, float* g_mask, float* work, void* stream) {
+    LDN_REQUIRE(dz && u && h && mean && invstd && gamma && beta && du && d_gamma && d_beta && work, "ldn_rows_bn_postmask_bwd: null pointer");
+    LDN_REQUIRE(m_cap >= 0 && C > 0 && C % 4 == 0, "ldn_rows_bn_postmask_bwd: m_cap >= 0, C %% 4 == 0 (got %d, %d)", m_cap, C);
+    LDN_REQUIRE(lddz >= C && ldu >= C && ldh >= C && lddu >= C && lddz % 4 == 0 && ldu % 4 == 0 && ldh % 4 == 0 && lddu % 4 == 0,
+                "ldn_rows_bn_postmask_bwd: leading dimensions >= C and multiples of 4 (got %d, %d, %d, %d)", lddz, ldu, ldh, lddu);
+    LDN_REQUIRE((gate != nullptr) == (dsq != nullptr), "ldn_rows_bn_postmask_bwd: gate and dsq [B][C] are the SE prologue: give both or neither");
+    const bool per_image = chan_mask || gate || g_mask;
+    LDN_REQUIRE(!per_image || (row_prefix && B >= 1), "ldn_rows_bn_postmask_bwd: chan_mask / gate / g_mask need row_prefix [B + 1] and B >= 1");
+    LDN_REQUIRE(aligned16(dz) && aligned16(u) && aligned16(h) && aligned16(mean) && aligned16(invstd) && aligned16(gamma) && aligned16(beta) &&
+                aligned16(chan_mask) && aligned16(gate) && aligned16(dsq) && aligned16(du) && aligned16(d_gamma) && aligned16(d_beta) &&
+                aligned16(g_mask) && aligned16(work), "ldn_rows_bn_postmask_bwd: every float pointer must be 16-byte aligned");
+    BnPmBwdArgs p;
+    p.dz = dz; p.u = u; p.h = h; p.mean = mean; p.invstd = invstd; p.gamma = gamma; p.beta = beta; p.chan_mask = chan_mask;
+    p.prefix = row_prefix; p.gate = gate; p.dsq = dsq; p.m_count = m_count; p.du = du; p.d_gamma = d_gamma; p.d_beta = d_beta; p.g_mask = g_mask;
+    p.work = work; p.lddz = lddz; p.ldu = ldu; p.ldh = ldh; p.lddu = lddu; p.B = per_image ? B : 0; p.m_cap = m_cap; p.C = C;
+    const dim3 grid = rows_grid(m_cap, C, &p.splits, &p.rps);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (m_cap > 0) {
+        k_bn_pm_bwd_partial<<<grid, ACT_THREADS, 0, st>>>(p);
+        LDN_CHECK_LAUNCH("k_bn_pm_bwd_partial");
+    }
+    const int rc = rows_reduce({work, work_slot(work, p.splits, C, 2, 0), row_prefix, m_count, {d_beta, d_gamma}, g_mask, 2, g_mask ? B : 0, B, m_cap, C,
+                                p.splits, p.rps}, st);
+    if (rc != LDN_OK) return rc;
+    if (m_cap > 0) {
+        k_bn_pm_bwd_final<<<grid, ACT_THREADS, 0, st>>>(p);
+        LDN_CHECK_LAUNCH("k_bn_pm_bwd_final");
+    }
     return LDN_OK;
 }

@@ -805,6 +805,62 @@ def rows_bn_bwd(dh2d, u2d, h2d, mean, invstd, gamma, *, chan_mask=None, row_pref
     return du, d_gamma, d_beta, g_mask
 
 
+def rows_bn_postmask_fwd(u2d, mean, invstd, gamma, beta, *, chan_mask=None, row_prefix=None, m_count=None, m_cap=None, out=None):
+    """BatchNorm on given batch statistics, ReLU, THEN the channel mask, over packed rows in one launch (see ldn_rows_bn_postmask_fwd):
+    h = chan_mask[img(r)] * relu(gamma * (u2d[r] - mean) * invstd + beta) -> out [m_cap, C] (allocated unless given; u2d itself is allowed), exact
+    zeros on the rows past the device-side count.  mean / invstd from rows_bn_stats WITHOUT a mask: in this form every channel of every image
+    feeds the statistics.  chan_mask [B, C] (None = ones) needs row_prefix [B + 1]."""
+    L.require_device(u2d, mean, invstd, gamma, beta, chan_mask, row_prefix, m_count, out)
+    C = gamma.numel()
+    _rows_wide("rows_bn_postmask_fwd", C, u=u2d, out=out)
+    if any(v.numel() != C for v in (mean, invstd, beta)):
+        raise L.LdnError("rows_bn_postmask_fwd: mean / invstd / gamma / beta must be [C]")
+    B = _rows_images("rows_bn_postmask_fwd", C, row_prefix, False, chan_mask=chan_mask)
+    m_cap = _rows_cap(m_cap, "rows_bn_postmask_fwd", u2d, out)
+    out, h = _rows_out(out, m_cap, C, u2d.device)
+    L.check(L.load().ldn_rows_bn_postmask_fwd(L.ptr(_f32rows(u2d, "u")), u2d.stride(0), L.ptr(_f32c(mean, "mean")), L.ptr(_f32c(invstd, "invstd")),
+                                              L.ptr(_f32c(gamma, "gamma")), L.ptr(_f32c(beta, "beta")), L.ptr(_f32c(chan_mask, "chan_mask")),
+                                              L.ptr(_i32c(row_prefix, "row_prefix")), B, L.ptr(_i32c(m_count, "m_count")), m_cap, C,
+                                              L.ptr(_f32rows(out, "out")), out.stride(0), L.stream_ptr(out)), "ldn_rows_bn_postmask_fwd")
+    return h
+
+
+def rows_bn_postmask_bwd(dz2d, u2d, h2d, mean, invstd, gamma, beta, *, chan_mask=None, row_prefix=None, gate=None, dsq=None, want_mask=False,
+                         m_count=None, m_cap=None, out=None):
+    """Backward of rows_bn_postmask_fwd THROUGH the batch statistics (see ldn_rows_bn_postmask_bwd), given dz2d, the unmasked u2d and the stored
+    MASKED h2d: dh = dz * gate[img(r)] + dsq[img(r)] with the squeeze-excitation prologue (gate, dsq [B, C]: both or neither), else dz;
+    a = dh * m[img(r)] where h > 0 (the ReLU gate is read from h2d); d_beta = sum a, d_gamma = sum a * xhat,
+    du = gamma * invstd * (a - d_beta / n - xhat * d_gamma / n) with n the device-side count.  -> (du [m_cap, C], d_gamma [C], d_beta [C],
+    g_mask [B, C] = sum over the image's rows of dh * relu(gamma * xhat + beta) with want_mask -- every channel, the masked ones included, the
+    ReLU output recomputed -- else None).  chan_mask [B, C] (None = ones), the prologue and want_mask need row_prefix [B + 1].  out: a
+    [m_cap, >= C] matrix for du (dz2d itself is allowed); exact zeros on the rows past the count.  Three launches; deterministic, no atomics."""
+    L.require_device(dz2d, u2d, h2d, mean, invstd, gamma, beta, chan_mask, row_prefix, gate, dsq, m_count, out)
+    lib = L.load()
+    C = gamma.numel()
+    if h2d is None:
+        raise L.LdnError("rows_bn_postmask_bwd: h2d, the stored forward output, is required")
+    _rows_wide("rows_bn_postmask_bwd", C, dz=dz2d, u=u2d, h=h2d, out=out)
+    if any(v.numel() != C for v in (mean, invstd, beta)):
+        raise L.LdnError("rows_bn_postmask_bwd: mean / invstd / gamma / beta must be [C]")
+    if (gate is None) != (dsq is None):
+        raise L.LdnError("rows_bn_postmask_bwd: gate and dsq are the SE prologue: give both or neither")
+    B = _rows_images("rows_bn_postmask_bwd", C, row_prefix, want_mask, chan_mask=chan_mask, gate=gate, dsq=dsq)
+    m_cap = _rows_cap(m_cap, "rows_bn_postmask_bwd", dz2d, u2d, h2d, out)
+    dev = dz2d.device
+    out, du = _rows_out(out, m_cap, C, dev)
+    d_gamma = torch.empty(C, device=dev, dtype=torch.float32)
+    d_beta = torch.empty(C, device=dev, dtype=torch.float32)
+    g_mask = torch.empty(B, C, device=dev, dtype=torch.float32) if want_mask else None
+    work = _work(lib.ldn_rows_bn_postmask_bwd_workspace_bytes(m_cap, C, B if want_mask else 0), dev)
+    L.check(lib.ldn_rows_bn_postmask_bwd(L.ptr(_f32rows(dz2d, "dz")), dz2d.stride(0), L.ptr(_f32rows(u2d, "u")), u2d.stride(0),
+                                         L.ptr(_f32rows(h2d, "h")), h2d.stride(0), L.ptr(_f32c(mean, "mean")), L.ptr(_f32c(invstd, "invstd")),
+                                         L.ptr(_f32c(gamma, "gamma")), L.ptr(_f32c(beta, "beta")), L.ptr(_f32c(chan_mask, "chan_mask")),
+                                         L.ptr(_i32c(row_prefix, "row_prefix")), B, L.ptr(_f32c(gate, "gate")), L.ptr(_f32c(dsq, "dsq")),
+                                         L.ptr(_i32c(m_count, "m_count")), m_cap, C, L.ptr(_f32rows(out, "out")), out.stride(0), L.ptr(d_gamma),
+                                         L.ptr(d_beta), L.ptr(g_mask), L.ptr(work), L.stream_ptr(out)), "ldn_rows_bn_postmask_bwd")
+    return du, d_gamma, d_beta, g_mask
+
+
 USE_ROWS_PS = os.environ.get("LDN_ROWS_PS", "1") != "0"    # the pre-split packed path (k_dense<PS / OF> + k_rows3); 0 = round 4's three launches
 
 

@@ -74,9 +74,21 @@ unbiased variance, num_batches_tracked; momentum=None = the cumulative average).
 BatchNorms are plain modules.  `prepare_for_training(model, batch_stats=True)` leaves BatchNorm in training mode; block_train and
 train_forward(ResNet) are unchanged (tests/test_bn_batch_ref.py, tests/test_hip_rows_bn.py, tests/test_hip_training_batchstats.py).
 
-Not built: mask groups > 1, dilated conv2, grouped conv2 outside the LAD-RegNet blocks, BatchNorm on batch statistics for LAD-RegNet and the
-detection backbone, SyncBatchNorm / cross-rank statistics, a block with some BatchNorms frozen and some not, LAD-RegNet 'both' / patch-mask
-(mask_size > 1) training."""
+LAD-RegNet dyn_mode 'channel' on batch statistics -- train_scripts.sh's third command -- trains with BOTH switches on (USE_REGNET_CHANNEL and
+USE_BATCH_STATS): a channel block whose BatchNorms (a, b, c and proj's) are all in training mode runs `_RegNetBatchStatsBranchFn`:
+    y_a = a(x)   h_a = m . relu(BN(y_a))     y_b = b(h_a)   h_b = m . relu(BN(y_b))     y_c = c(gate . h_b)   branch = BN(y_c)
+The mask multiplies AFTER BatchNorm + ReLU, so the statistics see every channel of every image (`ops.rows_bn_stats` without a mask) and THE MASK
+SAVES NO FLOPs.  Layers a / b are `ops.rows_bn_postmask_fwd` forward and `ops.rows_bn_postmask_bwd` backward (csrc/ldn_train_bn.hip: SE prologue,
+mask, ReLU gate read from the stored masked h, d gamma, d beta, the statistics' terms and the mask's straight-through sum over the RECOMPUTED
+unmasked ReLU output, three launches, deterministic); a layer saves the unmasked y and the masked h, one matrix fewer than the frozen path that
+keeps relu(zy) for the mask.  Layer c is `ops.rows_bn_fwd` / `ops.rows_bn_bwd` without ReLU; nothing is folded.  The running statistics move once
+per forward (`_branch_regnet`); proj, the stem and the maskers stay plain modules.  block_train, train_forward(LAD_RegNet) and
+prepare_for_training(model, batch_stats=True) take it unchanged (tests/test_regnet_bn_ref.py, tests/test_hip_rows_bn_postmask.py,
+tests/test_hip_training_regnet_batchstats.py).
+
+Not built: mask groups > 1, dilated conv2, grouped conv2 outside the LAD-RegNet blocks, BatchNorm on batch statistics for LAD-RegNet layer skip
+and the detection backbone, SyncBatchNorm / cross-rank statistics, a block with some BatchNorms frozen and some not, LAD-RegNet 'both' /
+patch-mask (mask_size > 1) training."""
 from __future__ import annotations
 
 import functools
@@ -813,6 +825,113 @@ class _BatchStatsBranchFn(torch.autograd.Function):
                 keep(gb3, need[11]), None, None, None)
 
 
+def _conv_b_plain(wbr, gw, h_a, nbr, y_b, m_count, m_cap):
+    """the grouped 3x3 alone -- scale 1, shift 0, no ReLU -- with laud_regnet._conv_b_rows' choice of kernel: the matrix cores for group width 16
+    in bf16x3 mode, else the fp32 VALU kernel"""
+    W, dev = wbr.shape[0], h_a.device
+    one, zero = torch.ones(W, device=dev), torch.zeros(W, device=dev)
+    pb = _conv_b_params(wbr, one, zero, gw)
+    if "wb_frag" in pb:
+        ops.grouped16_conv3x3_rows(h_a, nbr, pb["wb_frag"], one, zero, y_b, m_count=m_count, m_cap=m_cap, relu=0)
+    else:
+        ops.grouped_conv3x3_rows(h_a, nbr, wbr, gw, one, zero, y_b, m_count=m_count, m_cap=m_cap, relu=0)
+
+
+class _RegNetBatchStatsBranchFn(torch.autograd.Function):
+    """branch = bn_c(c(gate . h_b)),  h_a = m . relu(bn_a(a(x))),  h_b = m . relu(bn_b(b(h_a))),  gate = sigmoid(fc2(relu(fc1(mean_pixels h_b))))
+    with bn_a / bn_b / bn_c on the statistics of THE BATCH (laud_regnet.py:182-200, dyn_mode 'channel', in plain model.train(): the third command
+    of the reference's train_scripts.sh).  The {0,1} channel mask m [B, W] multiplies AFTER BatchNorm + ReLU, so every channel of every image
+    feeds the statistics, dropped or not: dense by construction, THE MASK SAVES NO FLOPs.  a and c on ops.conv_rows, the grouped 3x3 b on the
+    grouped kernels, all three with scale 1 / shift 0 / no ReLU over all pixels (ix = the cached dense_index) -- nothing is folded, so there is no
+    _split_scale and bn.weight == 0 is no special case.  Layers a / b: ops.rows_bn_stats (no mask) + ops.rows_bn_postmask_fwd forward,
+    ops.rows_bn_postmask_bwd backward (layer b's with the squeeze-excitation prologue): the unmasked y and the masked h are all a layer saves.
+    Layer c: ops.rows_bn_fwd / ops.rows_bn_bwd without ReLU.  d gate = ops.rows_img_dot(dz, h_b): h_b is masked already.  Adjoints and weight
+    gradients as in _RegNetChannelBranchFn, with the plain weights.
+    Inputs: x, the three weights, the channel mask, (gamma, beta) x 3, the four SE tensors; eps3 = the three eps.  Returns (branch, mean_a, var_a,
+    mean_b, var_b, mean_c, var_c): the batch statistics (biased variances) are non-differentiable outputs -- _branch_regnet updates the running
+    statistics from them, once per forward and never in the backward."""
+
+    @staticmethod
+    def forward(ctx, x, wa, wb, wc, chm, ga, ba, gb, bb, gc, bc, w1, b1, w2, b2, eps3, stride, f, ix):
+        p = _prep(x, wa, wb, wc, (ga, ba, gb, bb, gc, bc), stride)
+        B, _, _, _, Ho, Wo, W, cout = p.shape
+        ga, ba, gb, bb, gc, bc = p.bn
+        dev, P = x.device, Ho * Wo
+        se = (w1.detach().float().reshape(-1, W).contiguous(), b1.detach().float().contiguous(),
+              w2.detach().float().reshape(W, -1).contiguous(), b2.detach().float().contiguous())
+        m2d = chm.detach().float().reshape(B, W).contiguous()
+        zW, zc = torch.zeros(W, device=dev), torch.zeros(cout, device=dev)
+        y_a = torch.empty(ix.cap1, W, device=dev)
+        ops.conv_rows(p.x2d, p.w1r, None, zW, y_a, a_rows=ix.idx1, taps=1, m_cap=ix.cap1, relu=0)
+        mean_a, var_a, inv_a = ops.rows_bn_stats(y_a, eps3[0], m_cap=ix.cap1)
+        h_a = ops.rows_bn_postmask_fwd(y_a, mean_a, inv_a, ga, ba, chan_mask=m2d, row_prefix=ix.pre1, m_cap=ix.cap1)
+        y_b = torch.empty(ix.cap3, W, device=dev)
+        _conv_b_plain(p.w2r, f.group_width, h_a, ix.nbr, y_b, ix.cnt[0:1], ix.cap3)
+        mean_b, var_b, inv_b = ops.rows_bn_stats(y_b, eps3[1], m_cap=ix.cap3)
+        h_b = ops.rows_bn_postmask_fwd(y_b, mean_b, inv_b, gb, bb, chan_mask=m2d, row_prefix=ix.pre3, m_cap=ix.cap3)
+        hbv = h_b.view(B, P, W)
+        sq = hbv.mean(1)
+        u, gate = _se_gate(sq, *se)
+        y_c = torch.empty(ix.cap3, cout, device=dev)
+        ops.conv_rows((hbv * gate.unsqueeze(1)).view(ix.cap3, W), p.w3r.reshape(cout, 1, W), None, zc, y_c, taps=1, m_cap=ix.cap3, relu=0)
+        mean_c, var_c, inv_c = ops.rows_bn_stats(y_c, eps3[2], m_cap=ix.cap3)
+        br = ops.rows_bn_fwd(y_c, mean_c, inv_c, gc, bc, relu=False, m_cap=ix.cap3)
+        ctx.save_for_backward(p.x2d, y_a, h_a, y_b, h_b, y_c, sq, u, gate, p.w1r, p.w2r, p.w3r, ga, ba, gb, bb, gc, mean_a, inv_a, mean_b, inv_b,
+                              mean_c, inv_c, *se, m2d)
+        ctx.ix, ctx.shape, ctx.stride, ctx.f, ctx.se_shapes = ix, p.shape, stride, f, (w1.shape, w2.shape)
+        ctx.math_mode = ops.get_math_mode()
+        stats = (mean_a, var_a, mean_b, var_b, mean_c, var_c)
+        ctx.mark_non_differentiable(*stats)
+        return (ops.from_nhwc(br.view(B, Ho, Wo, cout)),) + stats
+
+    @staticmethod
+    @_in_forward_mode
+    def backward(ctx, g, *_stats):
+        (x2d, y_a, h_a, y_b, h_b, y_c, sq, u, gate, war, wbr, wcr, ga, ba, gb, bb, gc, mean_a, inv_a, mean_b, inv_b, mean_c, inv_c,
+         w1, b1, w2, b2, m2d) = ctx.saved_tensors
+        ix, shape, stride, f, need, dev = ctx.ix, ctx.shape, ctx.stride, ctx.f, ctx.needs_input_grad, g.device
+        B, _, Hi, Wi, Ho, Wo, W, cout = shape
+        P, gw = Ho * Wo, f.group_width
+        want_m = need[4]
+        go = ops.as_nhwc(g.contiguous()).reshape(-1, cout)                       # [B Ho Wo, cout] = d L / d branch
+        zW = torch.zeros(W, device=dev)
+        # layer c: through the statistics, no ReLU, then c^T with the plain weights -> d L / d (gate . h_b)
+        dyc, ggc, gbc, _ = ops.rows_bn_bwd(go, y_c, None, mean_c, inv_c, gc, m_cap=ix.cap3)
+        dz = _conv3_T(dyc, wcr.reshape(cout, 1, W), zW, None, ix.cap3, torch.empty)
+        # squeeze-excitation: d gate = sum_p dz . h_b in one kernel (h_b is masked already), the excite MLP by hand on [B, .] tensors
+        dgate = ops.rows_img_dot(dz, h_b, ix.pre3, m_cap=ix.cap3)
+        dv = dgate * gate * (1.0 - gate)                                         # through the sigmoid
+        du = (dv @ w2) * (u > 0)
+        dsq = du @ w1
+        gw1s = (du.t() @ sq).reshape(ctx.se_shapes[0]) if need[11] else None
+        gb1s = du.sum(0) if need[12] else None
+        gw2s = (dv.t() @ torch.relu(u)).reshape(ctx.se_shapes[1]) if need[13] else None
+        gb2s = dv.sum(0) if need[14] else None
+        z = (h_b.view(B, P, W) * gate.unsqueeze(1)).view(ix.cap3, W) if need[3] else None       # conv c's input
+        # layer b: d h_b = dz . gate + dsq / P, the mask, the ReLU gate, d gamma, d beta, d mask and the statistics' terms in one op (in place on dz)
+        dyb, ggb, gbb, gmb = ops.rows_bn_postmask_bwd(dz, y_b, h_b, mean_b, inv_b, gb, bb, chan_mask=m2d, row_prefix=ix.pre3, gate=gate,
+                                                      dsq=(dsq / P).contiguous(), want_mask=want_m, m_cap=ix.cap3, out=dz)
+        # b^T: the forward kernel over the transposed neighbour table with the plain per-group transposed weights, scale 1, shift 0, no ReLU
+        nbrT = transposed_neighbour_table(ix, B, Hi, Wi, stride, Ho, Wo)
+        dha = torch.empty(ix.cap1, W, device=dev)
+        ops.grouped_conv3x3_rows(dyb, nbrT, grouped_weight_T(wbr, gw), gw, torch.ones(W, device=dev), zW, dha, m_count=ix.cnt[1:2], m_cap=ix.cap1,
+                                 relu=0)
+        dya, gga, gba, gma = ops.rows_bn_postmask_bwd(dha, y_a, h_a, mean_a, inv_a, ga, ba, chan_mask=m2d, row_prefix=ix.pre1, want_mask=want_m,
+                                                      m_cap=ix.cap1, out=dha)
+        grad_x = _grad_x(dya, war, ix, None, shape) if need[0] else None
+        gwa, _, gwc = _weight_grads(need[1], False, need[3], dyc, z, None, h_a, dya, x2d, ix, counted=False)
+        gwb = None
+        if need[2]:                  # conv b sees the MASKED h_a inside the map, zeros in the padding ring
+            if _wgrad_grouped_kernel(W, gw):
+                gwb = ops.wgrad_grouped_rows(dyb, h_a, ix.nbr, gw, m_count=ix.cnt[0:1], m_cap=ix.cap3, a_valid=ix.cap1).permute(0, 2, 1).reshape(W, gw, 3, 3)
+            else:
+                gwb = _weight_grad_grouped_3x3(dyb, h_a, ix.nbr, ix.cap1, gw)
+        gm = gma + gmb if want_m else None
+        keep = lambda v, n: v if n else None
+        return (grad_x, gwa, gwb, gwc, gm, keep(gga, need[5]), keep(gba, need[6]), keep(ggb, need[7]), keep(gbb, need[8]), keep(ggc, need[9]),
+                keep(gbc, need[10]), gw1s, gb1s, gw2s, gb2s, None, None, None, None)
+
+
 def _update_running_stats(bn, mean, var, n):
     """BatchNorm's own bookkeeping in training mode from the batch statistics of one forward (biased var over n values per channel):
     num_batches_tracked += 1, running = (1 - f) running + f batch with the UNBIASED variance var n / (n - 1), f = momentum or, with
@@ -907,7 +1026,9 @@ def _expand_channel_mask(block, x, mask):
 
 def _check_regnet_block(block, x):
     """what of LAD-RegNet trains: the layer-skip form run_dynamic executes itself (one keep / skip bit per image, one mask group, SE present) and,
-    behind USE_REGNET_CHANNEL, dyn_mode 'channel'"""
+    behind USE_REGNET_CHANNEL, dyn_mode 'channel'; -> does the block run on batch statistics (a channel block with every BatchNorm of the branch
+    and of proj in training mode, behind USE_BATCH_STATS as well)?  Some BatchNorms training and some frozen, track_running_stats=False, a
+    non-affine BatchNorm and the layer-skip form with a training BatchNorm are refused"""
     f = block.f
     channel = f.dyn_mode == "channel" and USE_REGNET_CHANNEL
     if f.dyn_mode != "spatial" and not channel:
@@ -927,18 +1048,32 @@ def _check_regnet_block(block, x):
         raise LdnError("laudnet_amd ops need tensors on a HIP device (cuda:N); there is no CPU path")
     if x.shape[2] != f.output_size * block.stride or x.shape[3] != f.output_size * block.stride:
         raise LdnError(f"training: input {x.shape[2]}x{x.shape[3]} does not match output_size {f.output_size} * stride {block.stride}")
-    for bn in (f.a[1], f.b[1], f.c[1]) + (() if block.proj is None else (block.proj[1],)):
-        if bn.training:
-            raise LdnError("training: BatchNorm must run on its frozen statistics (norm_eval; call prepare_for_training(model)) -- the "
-                           "batch-statistics recipe is dense by construction and not built")
+    bns = (f.a[1], f.b[1], f.c[1])
+    live = [bn.training for bn in bns + (() if block.proj is None else (block.proj[1],))]
+    if not any(live):
+        return False
+    if not USE_BATCH_STATS:
+        raise LdnError("training: BatchNorm must run on its frozen statistics (norm_eval; call prepare_for_training(model)) -- the "
+                       "batch-statistics recipe is dense by construction and not built unless training.USE_BATCH_STATS is on (env "
+                       "LDN_TRAIN_BATCH_STATS=1, off by default; LAD-RegNet: dyn_mode 'channel' only)")
+    if not channel:
+        raise LdnError("training: a LAD-RegNet layer-skip block with a BatchNorm in training mode is not built (batch statistics: dyn_mode "
+                       "'channel' only; freeze the statistics with prepare_for_training(model))")
+    if not all(live):
+        raise LdnError("training: a block with some BatchNorms in training mode and some frozen is not built (all on batch statistics or all frozen)")
+    if any(not bn.track_running_stats or bn.running_mean is None for bn in bns):
+        raise LdnError("training: batch statistics need track_running_stats=True (running statistics to update)")
+    if any(bn.weight is None for bn in bns):
+        raise LdnError("training: batch statistics need affine BatchNorm")
+    return True
 
 
 def _branch_regnet(block, x, mask):
     """_branch for a laud_regnet.ResBottleneckBlock: its layer-skip form (mask [B, 1, 1, 1]) or, behind USE_REGNET_CHANNEL, dyn_mode 'channel'
-    (mask [B, G], G = w_b // channel_dyn_granularity: the expansion to channels is plain autograd, outside the Fn)"""
-    _check_regnet_block(block, x)
+    (mask [B, G], G = w_b // channel_dyn_granularity: the expansion to channels is plain autograd, outside the Fn) -- a channel block on frozen
+    statistics, or, with every BatchNorm in training mode and USE_BATCH_STATS on, on batch statistics (the running statistics are updated here)"""
+    batch_stats = _check_regnet_block(block, x)
     f = block.f
-    bn = _fold_live(f.a[1]) + _fold_live(f.b[1]) + _fold_live(f.c[1])
     w = (f.a[0].weight, f.b[0].weight, f.c[0].weight)
     se = (f.se.fc1.weight, f.se.fc1.bias, f.se.fc2.weight, f.se.fc2.bias)
     if f.dyn_mode == "channel":
@@ -947,14 +1082,23 @@ def _branch_regnet(block, x, mask):
             raise LdnError(f"training: a LAD-RegNet channel block takes one bit per image and channel group (mask [B, {G}])")
         chm = mask.unsqueeze(2).expand(-1, -1, f.w_b // G).reshape(mask.shape[0], f.w_b)      # group j owns channels [j * gran, (j + 1) * gran)
         ix = dense_index(x.shape[0], f.output_size, f.output_size, block.stride, x.device)
-        branch = _RegNetChannelBranchFn.apply(x, *w, chm, *bn, *se, block.stride, f, ix)
+        if batch_stats:
+            bns = (f.a[1], f.b[1], f.c[1])
+            affine = tuple(v for bn in bns for v in (bn.weight, bn.bias))
+            branch, *stats = _RegNetBatchStatsBranchFn.apply(x, *w, chm, *affine, *se, tuple(bn.eps for bn in bns), block.stride, f, ix)
+            for bn, mean, var, n in zip(bns, stats[0::2], stats[1::2], (ix.cap1, ix.cap3, ix.cap3)):      # rows = values per channel
+                _update_running_stats(bn, mean, var, n)
+        else:
+            bn = _fold_live(f.a[1]) + _fold_live(f.b[1]) + _fold_live(f.c[1])
+            branch = _RegNetChannelBranchFn.apply(x, *w, chm, *bn, *se, block.stride, f, ix)
     else:
+        bn = _fold_live(f.a[1]) + _fold_live(f.b[1]) + _fold_live(f.c[1])
         if isinstance(mask, (tuple, list)) or mask.dim() != 4 or tuple(mask.shape[1:]) != (1, 1, 1) or mask.shape[0] != x.shape[0]:
             raise LdnError("training: a LAD-RegNet layer-skip block takes one keep / skip bit per image (mask [B, 1, 1, 1])")
         m3 = F.interpolate(mask, size=(f.output_size, f.output_size), mode="nearest")      # laud_regnet.py:173
         ix = _pixel_lists(m3, block.stride)
         branch = _RegNetSkipBranchFn.apply(x, *w, m3, *bn, *se, block.stride, f, ix)
-    identity = x if block.proj is None else block.proj(x)      # (conv 1x1 stride s + BatchNorm on frozen statistics: plain autograd)
+    identity = x if block.proj is None else block.proj(x)      # (conv 1x1 stride s + BatchNorm in the block's mode: plain autograd)
     return F.relu(branch + identity), ix
 
 
@@ -992,8 +1136,9 @@ def sparse_block_train(block, x, mask):
     dyn_mode 'spatial' / 'layer': mask [B, 1, S, S] {0,1};  dyn_mode 'channel': mask [B, G] {0,1};  dyn_mode 'both': mask = the pair
     (spatial [B, 1, S, S], channel [B, G]).  A mask may require grad (the hard Gumbel sample of the masker's logits): it receives the
     straight-through term.  A `laud_regnet.ResBottleneckBlock` in its layer-skip form (dyn_mode 'spatial', one mask bit per image, SE present):
-    mask [B, 1, 1, 1]; with USE_REGNET_CHANNEL on, one in dyn_mode 'channel': mask [B, G]; every other LAD-RegNet form raises LdnError.
-    Returns the block's output."""
+    mask [B, 1, 1, 1]; with USE_REGNET_CHANNEL on, one in dyn_mode 'channel': mask [B, G] -- on frozen statistics or, with USE_BATCH_STATS on
+    too and every BatchNorm of the block in training mode, on the statistics of the batch (the running statistics move once per call); every
+    other LAD-RegNet form raises LdnError.  Returns the block's output."""
     return _branch(block, x, mask)[0]
 
 
@@ -1105,7 +1250,8 @@ def _regnet_block_train(block, state, temperature):
     """ResBottleneckBlock.forward of the reference in TRAINING mode (laud_regnet.py:157-217,272-292).  Layer skip: the keep / skip bits are a hard
     Gumbel sample of the block's masker (forced_spatial_mask is honoured); conv c's sparsity s3 is differentiable, the dilated masks' means come
     out of the list build, channel sparsity 1.  Channel mode (USE_REGNET_CHANNEL): the channel mask likewise (forced_channel_mask is honoured);
-    the channel sparsity cs is differentiable, s1 = s2 = s3 = 1.  The bookkeeping is ResBottleneckBlock.forward's."""
+    the channel sparsity cs is differentiable, s1 = s2 = s3 = 1 -- on frozen statistics or, behind USE_BATCH_STATS, on the batch's.  The
+    bookkeeping is ResBottleneckBlock.forward's."""
     x, s3l, s2l, s1l, csl, percl, flops = state
     f = block.f
     _check_regnet_block(block, x)
@@ -1140,7 +1286,8 @@ def _regnet_block_train(block, state, temperature):
 def prepare_for_training(model, batch_stats=False):
     """Train mode with the BatchNorm STATISTICS frozen (mmdet's norm_eval=True, lad_mmdet_resnet.py:753-758): every BatchNorm runs on its
     running statistics, its affine parameters keep their requires_grad.  batch_stats=True: plain model.train() -- every BatchNorm on the
-    statistics of the batch, the reference's ImageNet recipe (LAUD-ResNet only, behind USE_BATCH_STATS)."""
+    statistics of the batch, the reference's ImageNet recipe (behind USE_BATCH_STATS: LAUD-ResNet, and LAD-RegNet in dyn_mode 'channel' with
+    USE_REGNET_CHANNEL on as well)."""
     model.train()
     if batch_stats:
         return model

@@ -12,7 +12,8 @@ so about the dense emulation's time is what to expect.  `--ab-wgrad` adds `wgrad
 `ms_per_step` is the mean of the timed steps (wall clock over the loop), `ms_per_step_median` the median of the
 steps' own device-event intervals.
 `--batch-stats` is the reference's own ImageNet recipe: every BatchNorm on the statistics of the batch (plain model.train() on both legs;
-training.USE_BATCH_STATS is turned on), on the full-width LAUD-ResNet50 that train_scripts.sh trains -- LAUD-ResNet workloads only.  Dense by
+training.USE_BATCH_STATS is turned on), on the full-width LAUD-ResNet50 that train_scripts.sh trains for the LAUD-ResNet workloads, and on
+LAD-RegNetY-800MF for `regnet_channel` (train_scripts.sh's third command); LAD-RegNet layer skip is not built in this mode.  Dense by
 construction on both legs (the masks save no FLOPs), so about the dense emulation's time is what to expect.
 usage: [LDN_WGRAD=0] tools/bench_train.py [--batch 32] [--steps 5] [--warmup 2] [--workloads layer,spatial,channel,both,regnet,regnet_channel] [--no-reference] [--ab-wgrad] [--batch-stats]"""
 import argparse
@@ -42,7 +43,7 @@ ap.add_argument("--math", default="bf16x3")
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--no-reference", action="store_true", help="time the row kernels only (no dense emulation through PyTorch, no speedup)")
 ap.add_argument("--ab-wgrad", action="store_true", help="also time the row-kernel leg with the weight-gradient kernels off / on, alternating per step")
-ap.add_argument("--batch-stats", action="store_true", help="BatchNorm on batch statistics (plain model.train()) on a LAUD-ResNet50, both legs")
+ap.add_argument("--batch-stats", action="store_true", help="BatchNorm on batch statistics (plain model.train()) on a LAUD-ResNet50 / LAD-RegNetY-800MF channel, both legs")
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
 ops.set_math_mode(args.math)
@@ -79,9 +80,11 @@ for w in args.workloads.split(","):
     kw = dict(wl["kw"], num_classes=1000, input_size=224)
     arch = wl.get("arch", "uni_resnet101")
     if args.batch_stats:
-        assert not arch.startswith("lad_regnet"), "--batch-stats: LAUD-ResNet workloads only (LAD-RegNet on batch statistics is not built)"
+        assert w == "regnet_channel" or not arch.startswith("lad_regnet"), \
+            "--batch-stats: LAUD-ResNet workloads and regnet_channel only (LAD-RegNet layer skip on batch statistics is not built)"
         training.USE_BATCH_STATS = True
-        arch, wl = "uni_resnet50", dict(wl, name=wl["name"].replace("ResNet101", "ResNet50"))
+        if w != "regnet_channel":
+            arch, wl = "uni_resnet50", dict(wl, name=wl["name"].replace("ResNet101", "ResNet50"))
     hip = getattr(laudnet_amd, arch)(**kw)
     hip.load_state_dict(damp_residual_branches(fill_state_dict(hip.state_dict(), 1)))      # (the last BatchNorm of every residual branch x 0.3)
     hip = hip.to(dev).eval()
