@@ -666,6 +666,18 @@ size_t ldn_grouped16_weight_bytes(int C);
 int ldn_grouped16_conv3x3_rows(const float* a, int lda, const int32_t* nbr, const int32_t* m_count, int m_cap,
                                const void* w_frag, int C, const float* scale, const float* shift, int relu, float* out,
                                int ldo, void* stream);
+/* b on the matrix cores for group widths 8 and 24 (RegNetY-400MF; RegNetY-1.6GF / 3.2GF), bf16x3 arithmetic: same contract again.
+ *    ldn_grouped_mfma_ok(C, gw) = 1 iff gw is 8 or 24, C > 0 and C % gw == 0 (any group count, odd ones included).
+ *    w_frag = ldn_grouped_mfma_weight_bytes(C, gw) bytes (0 outside _ok), [C/gw][steps][64 lanes][8 hi | 8 lo] bf16, a lane's eight values
+ *    being w[gw g + i][tap t][ch .. ch + 7]:
+ *      gw 24 (v_mfma_f32_32x32x16_bf16, 14 steps): i = lane & 31, chunk q = 2 s + (lane >> 5), t = q / 3, ch = 8 (q % 3); zero for i >= 24, q = 27
+ *      gw 8  (v_mfma_f32_16x16x32_bf16,  3 steps): i = lane & 15, chunk q = 4 s + (lane >> 4), t = q,     ch = 0;         zero for i >= 8,  q >= 9
+ *    Rows at or past the count and columns >= C are neither read nor written; deterministic (no atomics). */
+int ldn_grouped_mfma_ok(int C, int group_width);
+size_t ldn_grouped_mfma_weight_bytes(int C, int group_width);
+int ldn_grouped_mfma_conv3x3_rows(const float* a, int lda, const int32_t* nbr, const int32_t* m_count, int m_cap,
+                                  const void* w_frag, int C, int group_width, const float* scale, const float* shift, int relu,
+                                  float* out, int ldo, void* stream);
 
 /* The same convolution when the packed rows are WHOLE IMAGES (layer skip, one decision per image): kept image k owns the input rows
  * [k Hi Wi, (k+1) Hi Wi) of a and the output rows [k Ho Wo, (k+1) Ho Wo) of out; *m_count = kept images x Ho Wo (device side),

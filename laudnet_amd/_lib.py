@@ -75,6 +75,9 @@ SIGNATURES = {
     "ldn_grouped_conv3x3_rows": ([_P, _I, _P, _P, _I, _P, _I, _I, _P, _P, _I, _P, _I, _P], _I),
     "ldn_grouped16_weight_bytes": ([_I], C.c_size_t),
     "ldn_grouped16_conv3x3_rows": ([_P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P], _I),
+    "ldn_grouped_mfma_ok": ([_I, _I], _I),
+    "ldn_grouped_mfma_weight_bytes": ([_I, _I], C.c_size_t),
+    "ldn_grouped_mfma_conv3x3_rows": ([_P, _I, _P, _P, _I, _P, _I, _I, _P, _P, _I, _P, _I, _P], _I),
     "ldn_grouped16_images_fit": ([_I, _I, _I], _I),
     "ldn_grouped16_conv3x3_images": ([_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _I, _P], _I),
     "ldn_plan_work_zeroed": ([_I], _I),

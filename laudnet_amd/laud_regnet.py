@@ -131,6 +131,8 @@ class BottleneckTransform(_PrepCache):
             p["wb"] = self.b[0].weight.detach().permute(0, 2, 3, 1).reshape(w_b, 9, gw).float().contiguous()
             if gw == 16 and w_b % 16 == 0:      # matrix-core form of conv b (bf16x3 mode): weights pre-split in MFMA fragment order
                 p["wb_frag"] = ops.pack_grouped16_weights(p["wb"])
+            elif USE_GROUPED_MFMA_WIDTHS and ops.grouped_mfma_ok(w_b, gw):      # ... and, behind its switch, the one for widths 8 and 24
+                p["wb_frag_gw"] = ops.pack_grouped_mfma_weights(p["wb"], gw)
             p["sb"], p["tb"] = _fold_bn(self.b[1])
             p["wc"] = self.c[0].weight.detach().reshape(-1, 1, w_b).float().contiguous()
             p["wc_k"] = self.c[0].weight.detach().reshape(-1, w_b).float().t().reshape(1, w_b, -1).contiguous()   # k-major (channel mode)
@@ -154,12 +156,23 @@ def _conv_b_rows(p, f, h_a, nbr, h_b, m_count, m_cap, images=None):
             ops.grouped16_conv3x3_images(h_a, p["wb_frag"], p["sb"], p["tb"], h_b, m_count=m_count, images=images, relu=1)
         else:
             ops.grouped16_conv3x3_rows(h_a, nbr, p["wb_frag"], p["sb"], p["tb"], h_b, m_count=m_count, m_cap=m_cap, relu=1)
+    elif grouped_mfma_widths_on(h_b.shape[1], f.group_width):
+        # widths 8 and 24 (LDN_GROUPED_MFMA_WIDTHS=1): the neighbour-table form serves whole images too -- no LDS-staged image form yet
+        if "wb_frag_gw" not in p:           # (prepared before the switch was turned on)
+            p["wb_frag_gw"] = ops.pack_grouped_mfma_weights(p["wb"], f.group_width)
+        ops.grouped_mfma_conv3x3_rows(h_a, nbr, p["wb_frag_gw"], f.group_width, p["sb"], p["tb"], h_b, m_count=m_count, m_cap=m_cap, relu=1)
     else:
         ops.grouped_conv3x3_rows(h_a, nbr, p["wb"], f.group_width, p["sb"], p["tb"], h_b, m_count=m_count, m_cap=m_cap, relu=1)
 
 
 USE_GROUPED_MFMA = os.environ.get("LDN_GROUPED_MFMA", "1") != "0"    # tuning switch (A/B)
 USE_GROUPED_IMAGES = os.environ.get("LDN_GROUPED_IMAGES", "1") != "0"   # ... the whole-image form of it
+USE_GROUPED_MFMA_WIDTHS = os.environ.get("LDN_GROUPED_MFMA_WIDTHS", "0") == "1"   # ... group widths 8 and 24 on the matrix cores (OFF by default)
+
+
+def grouped_mfma_widths_on(C, gw):
+    """whether conv b of C channels in groups of gw runs on ldn_grouped_mfma_conv3x3_rows: its switch, USE_GROUPED_MFMA, bf16x3 mode and the shape"""
+    return bool(USE_GROUPED_MFMA_WIDTHS and USE_GROUPED_MFMA and ops.get_math_mode() == "bf16x3" and ops.grouped_mfma_ok(C, gw))
 USE_SE_FUSED = os.environ.get("LDN_SE_FUSED", "1") != "0"               # ... the SE block folded into conv b's epilogue and conv c's input rows
 
 

@@ -1070,6 +1070,50 @@ def grouped16_conv3x3_rows(a2d, nbr, w_frag, scale, shift, out2d, *, m_count=Non
     return out2d
 
 
+def grouped_mfma_ok(C, group_width):
+    """Whether ldn_grouped_mfma_conv3x3_rows takes the shape: group width 8 or 24, C a positive multiple of it (width 16 has its own kernel)."""
+    return bool(L.load().ldn_grouped_mfma_ok(int(C), int(group_width)))
+
+
+def pack_grouped_mfma_weights(w, group_width):
+    """w [C, 9, gw] fp32 (out channel, tap, in channel of the group), gw 8 | 24 -> MFMA fragment order [C/gw][steps][64][hi 8 | lo 8] bf16
+    (ldn_grouped_mfma_conv3x3_rows).  K is cut into chunks q of 8 consecutive channels of one tap; a lane's eight values are one chunk of
+    one out channel i:  gw 24: 14 steps, lane = i + 32 h (i < 32), q = 2 s + h = 3 tap + channel octet;  gw 8: 3 steps, lane = i + 16 kg
+    (i < 16), q = 4 s + kg = tap.  Out channels >= gw and chunks >= 27 / 9 are zeros."""
+    gw = int(group_width)
+    C = w.shape[0]
+    if gw not in (8, 24) or C == 0 or C % gw or tuple(w.shape[1:]) != (9, gw):
+        raise L.LdnError(f"pack_grouped_mfma_weights: expected [C % gw == 0, 9, gw] with gw 8 or 24 (got {tuple(w.shape)}, group width {gw})")
+    G = C // gw
+    rows, steps, per = (32, 14, 2) if gw == 24 else (16, 3, 4)          # tile rows (out channels), K steps, chunks per step
+    k = torch.zeros(G, rows, steps * per, 8, device=w.device, dtype=torch.float32)
+    k[:, :gw, :9 * gw // 8] = w.detach().float().reshape(G, gw, 9 * gw // 8, 8)      # [g][i][q = tap * (gw / 8) + octet][e]
+    k = k.reshape(G, rows, steps, per, 8).permute(0, 2, 3, 1, 4).reshape(G, steps, 64, 8)      # lane = i + rows * (chunk in step)
+    hi, lo = _hi_lo(k)
+    return torch.stack((hi, lo), dim=-2).contiguous()
+
+
+def grouped_mfma_conv3x3_rows(a2d, nbr, w_frag, group_width, scale, shift, out2d, *, m_count=None, m_cap=None, relu=1):
+    """Grouped 3x3 conv (group width 8 or 24) + BN (+ReLU) over packed rows on the matrix cores (see ldn_grouped_mfma_conv3x3_rows).
+    a2d / out2d may be column slices of wider matrices (row strides multiples of 4): the columns past C are neither read nor written."""
+    L.require_device(a2d, nbr, w_frag, out2d)
+    lib = L.load()
+    gw = int(group_width)
+    if gw not in (8, 24):
+        raise L.LdnError(f"grouped_mfma_conv3x3_rows: group width {gw} is not built (8 and 24; width 16 is grouped16_conv3x3_rows)")
+    C = w_frag.shape[0] * gw
+    if (w_frag.dtype != torch.bfloat16 or not w_frag.is_contiguous() or C == 0
+            or w_frag.numel() * 2 != lib.ldn_grouped_mfma_weight_bytes(C, gw)):
+        raise L.LdnError("grouped_mfma_conv3x3_rows: w_frag must be the contiguous bf16 tensor of pack_grouped_mfma_weights for this group width")
+    m_cap = out2d.shape[0] if m_cap is None else m_cap
+    L.check(lib.ldn_grouped_mfma_conv3x3_rows(L.ptr(_f32rows(a2d, "a")), a2d.stride(0), L.ptr(_i32c(nbr, "nbr")),
+                                              L.ptr(_i32c(m_count, "m_count")), m_cap, L.ptr(w_frag), C, gw,
+                                              L.ptr(_f32c(scale, "scale")), L.ptr(_f32c(shift, "shift")), relu,
+                                              L.ptr(_f32rows(out2d, "out")), out2d.stride(0), L.stream_ptr()),
+            "ldn_grouped_mfma_conv3x3_rows")
+    return out2d
+
+
 def grouped16_images_fit(Hi, Wi, C):
     """Groups per workgroup of ldn_grouped16_conv3x3_images for an Hi x Wi input map (0: it does not fit the LDS)."""
     return int(L.load().ldn_grouped16_images_fit(int(Hi), int(Wi), int(C)))

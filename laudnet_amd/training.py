@@ -101,7 +101,7 @@ import torch.nn.functional as F
 from . import ops
 from ._lib import LdnError
 from ._shared import channel_constants, dense_channel_convs, dense_index, image_prefix
-from .laud_regnet import LAD_RegNet, ResBottleneckBlock, _conv_b_rows
+from .laud_regnet import LAD_RegNet, ResBottleneckBlock, _conv_b_rows, grouped_mfma_widths_on
 
 # weight gradients on ldn_wgrad_rows / ldn_wgrad_grouped_rows; LDN_WGRAD=0 = the gather + PyTorch GEMM / bmm path.  On by default: the median step is shorter with the kernel for
 # all three full-width workloads at batch 32 and 128 (profiles/train_step_wgrad.jsonl), and for LAD-RegNetY-800MF layer skip with the grouped
@@ -558,7 +558,20 @@ def _conv_b_params(wbr, sb, tb, gw):
     pb = {"wb": wbr, "sb": sb, "tb": tb}
     if gw == 16 and wbr.shape[0] % 16 == 0 and ops.get_math_mode() == "bf16x3":
         pb["wb_frag"] = ops.pack_grouped16_weights(wbr)
+    elif grouped_mfma_widths_on(wbr.shape[0], gw):
+        pb["wb_frag_gw"] = ops.pack_grouped_mfma_weights(wbr, gw)
     return pb
+
+
+def _conv_b_adjoint(dy, nbrT, wbr, gw, dha, m_count, m_cap):
+    """b^T: the forward kernel over the transposed neighbour table with per-group transposed weights, scale 1, shift 0, no ReLU, into the zeroed dha.
+    The fp32 VALU kernel, or the matrix-core one for group widths 8 and 24 where laud_regnet.grouped_mfma_widths_on says so."""
+    W, dev = wbr.shape[0], dy.device
+    one, zero, wT = torch.ones(W, device=dev), torch.zeros(W, device=dev), grouped_weight_T(wbr, gw)
+    if grouped_mfma_widths_on(W, gw):
+        ops.grouped_mfma_conv3x3_rows(dy, nbrT, ops.pack_grouped_mfma_weights(wT, gw), gw, one, zero, dha, m_count=m_count, m_cap=m_cap, relu=0)
+    else:
+        ops.grouped_conv3x3_rows(dy, nbrT, wT, gw, one, zero, dha, m_count=m_count, m_cap=m_cap, relu=0)
 
 
 def _regnet_chain(x2d, ix, P, f, war, wbr, wcs, sa, ta, sb, tb, tc, se, br):
@@ -633,7 +646,7 @@ class _RegNetSkipBranchFn(torch.autograd.Function):
         # b^T: the forward kernel over the transposed neighbour table with per-group transposed weights, scale 1, shift 0, no ReLU
         nbrT = transposed_neighbour_table(ix, B, Hi, Wi, stride, Ho, Wo)
         dha = torch.zeros(ix.cap1, W, device=dev)
-        ops.grouped_conv3x3_rows(dub, nbrT, grouped_weight_T(wbr, gw), gw, torch.ones(W, device=dev), zW, dha, m_count=cnt1, m_cap=ix.cap1, relu=0)
+        _conv_b_adjoint(dub, nbrT, wbr, gw, dha, cnt1, ix.cap1)
         dza = dha * (h_a > 0) * v1
         grad_x = _grad_x(dza * sa, war, ix, cnt1, shape) if need[0] else None
         z = (hbv * gate.unsqueeze(1)).view(ix.cap3, W) if need[3] or need[9] else None       # conv c's input
@@ -729,7 +742,7 @@ class _RegNetChannelBranchFn(torch.autograd.Function):
         # b^T: the forward kernel over the transposed neighbour table with per-group transposed weights (sb folded in), scale 1, shift 0, no ReLU
         nbrT = transposed_neighbour_table(ix, B, Hi, Wi, stride, Ho, Wo)
         dha = torch.empty(ix.cap1, W, device=dev)
-        ops.grouped_conv3x3_rows(dzb, nbrT, grouped_weight_T(_scaled_T(wbr, sb), gw), gw, one, zW, dha, m_count=ix.cnt[1:2], m_cap=ix.cap1, relu=0)
+        _conv_b_adjoint(dzb, nbrT, _scaled_T(wbr, sb), gw, dha, ix.cnt[1:2], ix.cap1)
         dza, gta, _, gma = ops.rows_postmask_bwd(dha, r_a, one, ta, chan_mask=m2d, row_prefix=pre1, want_mask=keep_r, m_cap=ix.cap1, out=dha)
         grad_x = _grad_x(dza, _scaled_T(war, sa), ix, None, shape) if need[0] else None
         Ga, _, Gc = _weight_grads(need[1] or need[5], False, need[3] or need[9], go, z, None, h_a, dza, x2d, ix, counted=False)
@@ -833,6 +846,8 @@ def _conv_b_plain(wbr, gw, h_a, nbr, y_b, m_count, m_cap):
     pb = _conv_b_params(wbr, one, zero, gw)
     if "wb_frag" in pb:
         ops.grouped16_conv3x3_rows(h_a, nbr, pb["wb_frag"], one, zero, y_b, m_count=m_count, m_cap=m_cap, relu=0)
+    elif "wb_frag_gw" in pb:
+        ops.grouped_mfma_conv3x3_rows(h_a, nbr, pb["wb_frag_gw"], gw, one, zero, y_b, m_count=m_count, m_cap=m_cap, relu=0)
     else:
         ops.grouped_conv3x3_rows(h_a, nbr, wbr, gw, one, zero, y_b, m_count=m_count, m_cap=m_cap, relu=0)
 
@@ -914,8 +929,7 @@ class _RegNetBatchStatsBranchFn(torch.autograd.Function):
         # b^T: the forward kernel over the transposed neighbour table with the plain per-group transposed weights, scale 1, shift 0, no ReLU
         nbrT = transposed_neighbour_table(ix, B, Hi, Wi, stride, Ho, Wo)
         dha = torch.empty(ix.cap1, W, device=dev)
-        ops.grouped_conv3x3_rows(dyb, nbrT, grouped_weight_T(wbr, gw), gw, torch.ones(W, device=dev), zW, dha, m_count=ix.cnt[1:2], m_cap=ix.cap1,
-                                 relu=0)
+        _conv_b_adjoint(dyb, nbrT, wbr, gw, dha, ix.cnt[1:2], ix.cap1)
         dya, gga, gba, gma = ops.rows_bn_postmask_bwd(dha, y_a, h_a, mean_a, inv_a, ga, ba, chan_mask=m2d, row_prefix=ix.pre1, want_mask=want_m,
                                                       m_cap=ix.cap1, out=dha)
         grad_x = _grad_x(dya, war, ix, None, shape) if need[0] else None
