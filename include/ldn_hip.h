@@ -694,6 +694,19 @@ int ldn_grouped16_conv3x3_images(const float* a, int lda, const int32_t* m_count
 int ldn_grouped_conv3x3_image(const float* a, int lda, int B, int Hi, int Wi, int stride, int Ho, int Wo, const float* w,
                               int C, int group_width, const int32_t* ch_idx, const int32_t* ch_cnt, const float* scale,
                               const float* shift, int relu, float* out, int ldo, void* stream);
+/* b in channel mode on the matrix cores (group widths 8, 16 and 24; bf16x3 arithmetic): the contract of ldn_grouped_conv3x3_image with the
+ *    weights pre-split into MFMA fragment order -- w_frag is exactly the ldn_grouped16_weight_bytes(C) bytes of width 16 or the
+ *    ldn_grouped_mfma_weight_bytes(C, gw) bytes of widths 8 and 24 (no per-image gather: masked channels are exact zeros, so the dense
+ *    product of a group with zeros in its inactive input slots is exact; a group without an active channel is skipped).
+ *    Input columns >= ch_cnt[b] are never read, columns ch_cnt[b] <= j < C are written as zeros, columns >= C are never written;
+ *    lda and ldo multiples of 4 and >= C, 16-byte aligned pointers; deterministic (no atomics).
+ *    ldn_grouped_chan_mfma_ok = 1 iff gw is 8, 16 or 24, C > 0, C % gw == 0, stride is 1 or 2 and a band of the Hi x Wi map fits the
+ *    LDS (host arithmetic only); ldn_grouped_chan_mfma_bands = row bands per image (1: whole images), 0 outside _ok. */
+int ldn_grouped_chan_mfma_ok(int C, int group_width, int Hi, int Wi, int stride);
+int ldn_grouped_chan_mfma_bands(int C, int group_width, int Hi, int Wi, int Ho, int stride);
+int ldn_grouped_chan_mfma_conv3x3_image(const float* a, int lda, int B, int Hi, int Wi, int stride, int Ho, int Wo, const void* w_frag,
+                                        int C, int group_width, const int32_t* ch_idx, const int32_t* ch_cnt, const float* scale,
+                                        const float* shift, int relu, float* out, int ldo, void* stream);
 /* se: torchvision SqueezeExcitation (laud_regnet.py:119-123,194) applied IN PLACE to the packed rows of every kept
  *    image: gate[b,:] = sigmoid(W2 relu(W1 mean_rows(a_b) + b1) + b2), a[r,:] *= gate[image(r),:].
  *    w1 [S][C], w2 [C][S].  ch_idx / ch_cnt (optional, [B][C] / [B]): the columns of image b are its active channels

@@ -131,7 +131,7 @@ class BottleneckTransform(_PrepCache):
             p["wb"] = self.b[0].weight.detach().permute(0, 2, 3, 1).reshape(w_b, 9, gw).float().contiguous()
             if gw == 16 and w_b % 16 == 0:      # matrix-core form of conv b (bf16x3 mode): weights pre-split in MFMA fragment order
                 p["wb_frag"] = ops.pack_grouped16_weights(p["wb"])
-            elif USE_GROUPED_MFMA_WIDTHS and ops.grouped_mfma_ok(w_b, gw):      # ... and, behind its switch, the one for widths 8 and 24
+            elif (USE_GROUPED_MFMA_WIDTHS or USE_GROUPED_MFMA_CHANNEL) and ops.grouped_mfma_ok(w_b, gw):      # ... and, behind their switches, the one for widths 8 and 24
                 p["wb_frag_gw"] = ops.pack_grouped_mfma_weights(p["wb"], gw)
             p["sb"], p["tb"] = _fold_bn(self.b[1])
             p["wc"] = self.c[0].weight.detach().reshape(-1, 1, w_b).float().contiguous()
@@ -173,6 +173,30 @@ USE_GROUPED_MFMA_WIDTHS = os.environ.get("LDN_GROUPED_MFMA_WIDTHS", "0") == "1" 
 def grouped_mfma_widths_on(C, gw):
     """whether conv b of C channels in groups of gw runs on ldn_grouped_mfma_conv3x3_rows: its switch, USE_GROUPED_MFMA, bf16x3 mode and the shape"""
     return bool(USE_GROUPED_MFMA_WIDTHS and USE_GROUPED_MFMA and ops.get_math_mode() == "bf16x3" and ops.grouped_mfma_ok(C, gw))
+
+
+USE_GROUPED_MFMA_CHANNEL = os.environ.get("LDN_GROUPED_MFMA_CHANNEL", "0") == "1"   # ... conv b of channel / both mode on the matrix cores (OFF by default)
+
+
+def grouped_chan_mfma_on(C, gw, Hi, Wi, stride):
+    """whether conv b of a channel / both block runs on ldn_grouped_chan_mfma_conv3x3_image: its switch, USE_GROUPED_MFMA, bf16x3 mode and the shape"""
+    return bool(USE_GROUPED_MFMA_CHANNEL and USE_GROUPED_MFMA and ops.get_math_mode() == "bf16x3"
+                and ops.grouped_chan_mfma_ok(C, gw, Hi, Wi, stride))
+
+
+def _conv_b_image(p, f, h_a, idx, cnt, h_b, stride):
+    """conv b (grouped 3x3 + BN + ReLU) on the per-image active channels of a dense image (channel mode, and 'both'): on the matrix cores
+    for group widths 8 / 16 / 24 in bf16x3 mode with LDN_GROUPED_MFMA_CHANNEL=1, else the fp32 VALU kernel."""
+    gw = f.group_width
+    if grouped_chan_mfma_on(h_b.shape[3], gw, h_a.shape[1], h_a.shape[2], stride):
+        key = "wb_frag" if gw == 16 else "wb_frag_gw"
+        if key not in p:                    # (prepared before the switch was turned on)
+            p[key] = ops.pack_grouped16_weights(p["wb"]) if gw == 16 else ops.pack_grouped_mfma_weights(p["wb"], gw)
+        ops.grouped_chan_mfma_conv3x3_image(h_a, p[key], gw, idx, cnt, p["sb"], p["tb"], h_b, stride=stride, relu=1)
+    else:
+        ops.grouped_conv3x3_image(h_a, p["wb"], gw, idx, cnt, p["sb"], p["tb"], h_b, stride=stride, relu=1)
+
+
 USE_SE_FUSED = os.environ.get("LDN_SE_FUSED", "1") != "0"               # ... the SE block folded into conv b's epilogue and conv c's input rows
 
 
@@ -336,7 +360,7 @@ class ResBottleneckBlock(_PrepCache):
             h_a = torch.empty(B, Hi, Wi, w_b, device=dev, dtype=torch.float32)
             ops.conv_image(xn, p["wa"], p["sa"], p["ta"], h_a, n_idx=idx, n_cnt=cnt, relu=1)
             h_b = torch.empty(B, Ho, Wo, w_b, device=dev, dtype=torch.float32)
-            ops.grouped_conv3x3_image(h_a, p["wb"], f.group_width, idx, cnt, p["sb"], p["tb"], h_b, stride=s, relu=1)
+            _conv_b_image(p, f, h_a, idx, cnt, h_b, s)
             h_b2d = h_b.view(B * Ho * Wo, w_b)
             ops.se_packed(h_b2d, self._img_prefix(B, Ho * Wo, dev), p["se_w1"], p["se_b1"], p["se_w2"], p["se_b2"], Ho * Wo,
                           ch_idx=idx, ch_cnt=cnt)
@@ -398,7 +422,7 @@ class ResBottleneckBlock(_PrepCache):
         h_a = torch.empty(B, Hi, Wi, w_b, device=dev, dtype=torch.float32)
         ops.conv_image(xn, p["wa"], p["sa"], p["ta"], h_a, n_idx=idx, n_cnt=cnt, relu=1)
         h_b = torch.empty(B, Ho, Wo, w_b, device=dev, dtype=torch.float32)
-        ops.grouped_conv3x3_image(h_a, p["wb"], f.group_width, idx, cnt, p["sb"], p["tb"], h_b, stride=s, relu=1)
+        _conv_b_image(p, f, h_a, idx, cnt, h_b, s)
         ops.se_packed(h_b.view(B * Ho * Wo, w_b), self._img_prefix(B, Ho * Wo, dev), p["se_w1"], p["se_b1"], p["se_w2"],
                       p["se_b2"], Ho * Wo, ch_idx=idx, ch_cnt=cnt)
         cout = p["wc"].shape[0]

@@ -1219,6 +1219,38 @@ def grouped_conv3x3_image(a_nhwc, w, group_width, ch_idx, ch_cnt, scale, shift, 
     return out_nhwc
 
 
+def grouped_chan_mfma_ok(C, group_width, Hi, Wi, stride):
+    """Whether ldn_grouped_chan_mfma_conv3x3_image takes the shape: group width 8, 16 or 24, C a positive multiple of it, stride 1 or 2 and a
+    band of the Hi x Wi input map fits the LDS (host arithmetic only)."""
+    return bool(L.load().ldn_grouped_chan_mfma_ok(int(C), int(group_width), int(Hi), int(Wi), int(stride)))
+
+
+def grouped_chan_mfma_conv3x3_image(a_nhwc, w_frag, group_width, ch_idx, ch_cnt, scale, shift, out_nhwc, *, stride=1, relu=1):
+    """Grouped 3x3 conv (group width 8, 16 or 24) + BN (+ReLU) on left-packed per-image channel subsets on the matrix cores: the contract
+    of grouped_conv3x3_image (see ldn_grouped_chan_mfma_conv3x3_image) with w_frag = pack_grouped16_weights(w) for width 16,
+    pack_grouped_mfma_weights(w, gw) for widths 8 and 24."""
+    L.require_device(a_nhwc, w_frag, out_nhwc, ch_idx)
+    lib = L.load()
+    gw = int(group_width)
+    if gw not in (8, 16, 24):
+        raise L.LdnError(f"grouped_chan_mfma_conv3x3_image: group width {gw} is not built (8, 16 and 24)")
+    C = w_frag.shape[0] * gw
+    want = lib.ldn_grouped16_weight_bytes(C) if gw == 16 else lib.ldn_grouped_mfma_weight_bytes(C, gw)
+    if w_frag.dtype != torch.bfloat16 or not w_frag.is_contiguous() or C == 0 or w_frag.numel() * 2 != want:
+        raise L.LdnError("grouped_chan_mfma_conv3x3_image: w_frag must be the contiguous bf16 tensor of pack_grouped16_weights (width 16) / "
+                         "pack_grouped_mfma_weights (widths 8 and 24) for this group width")
+    if a_nhwc.dim() != 4 or out_nhwc.dim() != 4:
+        raise L.LdnError("grouped_chan_mfma_conv3x3_image: a and out must be [B, H, W, columns]")
+    B, Hi, Wi, lda = a_nhwc.shape
+    _, Ho, Wo, ldo = out_nhwc.shape
+    L.check(lib.ldn_grouped_chan_mfma_conv3x3_image(L.ptr(_f32c(a_nhwc, "a")), lda, B, Hi, Wi, stride, Ho, Wo, L.ptr(w_frag), C, gw,
+                                                    L.ptr(_i32c(ch_idx, "ch_idx")), L.ptr(_i32c(ch_cnt, "ch_cnt")),
+                                                    L.ptr(_f32c(scale, "scale")), L.ptr(_f32c(shift, "shift")), relu,
+                                                    L.ptr(_f32c(out_nhwc, "out")), ldo, L.stream_ptr(out_nhwc)),
+            "ldn_grouped_chan_mfma_conv3x3_image")
+    return out_nhwc
+
+
 def se_packed(a2d, row_prefix, w1, b1, w2, b2, max_rows_per_image, ch_idx=None, ch_cnt=None):
     """In-place squeeze-excitation over the packed rows of every kept image (see ldn_se_packed)."""
     L.require_device(a2d, row_prefix)
