@@ -707,6 +707,25 @@ int ldn_grouped_chan_mfma_bands(int C, int group_width, int Hi, int Wi, int Ho, 
 int ldn_grouped_chan_mfma_conv3x3_image(const float* a, int lda, int B, int Hi, int Wi, int stride, int Ho, int Wo, const void* w_frag,
                                         int C, int group_width, const int32_t* ch_idx, const int32_t* ch_cnt, const float* scale,
                                         const float* shift, int relu, float* out, int ldo, void* stream);
+/* b in channel mode on the matrix cores at group widths 56 and 112 (RegNetY-8GF / 16GF; bf16x3 arithmetic; csrc/ldn_grouped_wide.hip): the
+ *    contract and the argument list of ldn_grouped_chan_mfma_conv3x3_image, word for word.  A group's fragments (128 KB / 504 KB) do not fit
+ *    the LDS: they stream through registers while the LDS holds the expanded, pre-split input of up to 8 images or of one rectangle of one
+ *    image.  w_frag is exactly ldn_grouped_wide_weight_bytes(C, gw) bytes of bf16 in the order
+ *      [group g][K step s][row tile m][lane l][8 hi | 8 lo],   K steps: 32 (gw 56) / 63 (gw 112), row tiles of 32 out channels: 2 / 4,
+ *    lane l = i + 32 h holds out channel 32 m + i of the group (zeros for >= gw) and K octet q = 2 s + h = tap * (gw / 8) + o, i.e. the in
+ *    channels 8 o .. 8 o + 7 of the group at tap q / (gw / 8) (zeros for q = 63 at gw 56); 0 bytes for any other width or C % gw != 0.
+ *    ldn_grouped_wide_ok = 1 iff gw is 56 or 112, C > 0, C % gw == 0, stride is 1 or 2 and the plan finds a rectangle of the Hi x Wi map that
+ *    fits the LDS (host arithmetic only); ldn_grouped_wide_bands = bands of output rows per image (1: whole rows of the image in one
+ *    workgroup), 0 outside _ok or when Ho is not this geometry's; ldn_grouped_wide_strips = column strips the rows of a band are cut into
+ *    (1: whole rows); ldn_grouped_wide_images = images that share a workgroup; both 0 outside _ok. */
+int ldn_grouped_wide_ok(int C, int group_width, int Hi, int Wi, int stride);
+int ldn_grouped_wide_bands(int C, int group_width, int Hi, int Wi, int Ho, int stride);
+int ldn_grouped_wide_strips(int C, int group_width, int Hi, int Wi, int stride);
+int ldn_grouped_wide_images(int C, int group_width, int Hi, int Wi, int stride);
+size_t ldn_grouped_wide_weight_bytes(int C, int group_width);
+int ldn_grouped_wide_conv3x3_image(const float* a, int lda, int B, int Hi, int Wi, int stride, int Ho, int Wo, const void* w_frag,
+                                   int C, int group_width, const int32_t* ch_idx, const int32_t* ch_cnt, const float* scale,
+                                   const float* shift, int relu, float* out, int ldo, void* stream);
 /* se: torchvision SqueezeExcitation (laud_regnet.py:119-123,194) applied IN PLACE to the packed rows of every kept
  *    image: gate[b,:] = sigmoid(W2 relu(W1 mean_rows(a_b) + b1) + b2), a[r,:] *= gate[image(r),:].
  *    w1 [S][C], w2 [C][S].  ch_idx / ch_cnt (optional, [B][C] / [B]): the columns of image b are its active channels

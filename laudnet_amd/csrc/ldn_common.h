@@ -66,6 +66,7 @@ int tu_violations_rows3(unsigned* count, unsigned* code, int reset);
 int tu_violations_wgrad(unsigned* count, unsigned* code, int reset);
 int tu_violations_wgrad_grouped(unsigned* count, unsigned* code, int reset);
 int tu_violations_grouped_chan(unsigned* count, unsigned* code, int reset);
+int tu_violations_grouped_wide(unsigned* count, unsigned* code, int reset);
 int tu_chain_stalls(unsigned* count, int reset);      // csrc/ldn_tail.hip
 // The process's fault word: pinned host memory that a kernel sets when one of its bounded waits runs into its bound (ldn_fault_flag; csrc/ldn_index.hip).
 // fault_word_dev(): its device-side address (nullptr if the allocation failed).

@@ -133,6 +133,8 @@ class BottleneckTransform(_PrepCache):
                 p["wb_frag"] = ops.pack_grouped16_weights(p["wb"])
             elif (USE_GROUPED_MFMA_WIDTHS or USE_GROUPED_MFMA_CHANNEL) and ops.grouped_mfma_ok(w_b, gw):      # ... and, behind their switches, the one for widths 8 and 24
                 p["wb_frag_gw"] = ops.pack_grouped_mfma_weights(p["wb"], gw)
+            if USE_GROUPED_MFMA_WIDE and gw in (56, 112) and w_b % gw == 0:       # ... and the streamed fragments of widths 56 and 112
+                p["wb_frag_wide"] = ops.pack_grouped_wide_weights(p["wb"], gw)
             p["sb"], p["tb"] = _fold_bn(self.b[1])
             p["wc"] = self.c[0].weight.detach().reshape(-1, 1, w_b).float().contiguous()
             p["wc_k"] = self.c[0].weight.detach().reshape(-1, w_b).float().t().reshape(1, w_b, -1).contiguous()   # k-major (channel mode)
@@ -184,15 +186,29 @@ def grouped_chan_mfma_on(C, gw, Hi, Wi, stride):
                 and ops.grouped_chan_mfma_ok(C, gw, Hi, Wi, stride))
 
 
+USE_GROUPED_MFMA_WIDE = os.environ.get("LDN_GROUPED_MFMA_WIDE", "0") == "1"   # ... and at group widths 56 and 112 (OFF by default)
+
+
+def grouped_wide_on(C, gw, Hi, Wi, stride):
+    """whether conv b of a channel / both block runs on ldn_grouped_wide_conv3x3_image: its switch, USE_GROUPED_MFMA, bf16x3 mode and the shape"""
+    return bool(USE_GROUPED_MFMA_WIDE and USE_GROUPED_MFMA and ops.get_math_mode() == "bf16x3"
+                and ops.grouped_wide_ok(C, gw, Hi, Wi, stride))
+
+
 def _conv_b_image(p, f, h_a, idx, cnt, h_b, stride):
     """conv b (grouped 3x3 + BN + ReLU) on the per-image active channels of a dense image (channel mode, and 'both'): on the matrix cores
-    for group widths 8 / 16 / 24 in bf16x3 mode with LDN_GROUPED_MFMA_CHANNEL=1, else the fp32 VALU kernel."""
+    for group widths 8 / 16 / 24 in bf16x3 mode with LDN_GROUPED_MFMA_CHANNEL=1 and for widths 56 / 112 with LDN_GROUPED_MFMA_WIDE=1, else
+    the fp32 VALU kernel."""
     gw = f.group_width
     if grouped_chan_mfma_on(h_b.shape[3], gw, h_a.shape[1], h_a.shape[2], stride):
         key = "wb_frag" if gw == 16 else "wb_frag_gw"
         if key not in p:                    # (prepared before the switch was turned on)
             p[key] = ops.pack_grouped16_weights(p["wb"]) if gw == 16 else ops.pack_grouped_mfma_weights(p["wb"], gw)
         ops.grouped_chan_mfma_conv3x3_image(h_a, p[key], gw, idx, cnt, p["sb"], p["tb"], h_b, stride=stride, relu=1)
+    elif grouped_wide_on(h_b.shape[3], gw, h_a.shape[1], h_a.shape[2], stride):
+        if "wb_frag_wide" not in p:         # (prepared before the switch was turned on)
+            p["wb_frag_wide"] = ops.pack_grouped_wide_weights(p["wb"], gw)
+        ops.grouped_wide_conv3x3_image(h_a, p["wb_frag_wide"], gw, idx, cnt, p["sb"], p["tb"], h_b, stride=stride, relu=1)
     else:
         ops.grouped_conv3x3_image(h_a, p["wb"], gw, idx, cnt, p["sb"], p["tb"], h_b, stride=stride, relu=1)
 

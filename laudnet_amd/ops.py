@@ -1251,6 +1251,61 @@ def grouped_chan_mfma_conv3x3_image(a_nhwc, w_frag, group_width, ch_idx, ch_cnt,
     return out_nhwc
 
 
+_WIDE = {56: (32, 2), 112: (63, 4)}          # group width -> (K steps, row tiles of 32 out channels) of k_grouped_wide
+
+
+def grouped_wide_ok(C, group_width, Hi, Wi, stride):
+    """Whether ldn_grouped_wide_conv3x3_image takes the shape: group width 56 or 112, C a positive multiple of it, stride 1 or 2 and a
+    rectangle of the Hi x Wi input map fits the LDS (host arithmetic only)."""
+    return bool(L.load().ldn_grouped_wide_ok(int(C), int(group_width), int(Hi), int(Wi), int(stride)))
+
+
+def pack_grouped_wide_weights(w, group_width):
+    """w [C, 9, gw] fp32 (out channel, tap, in channel of the group), gw 56 or 112 -> the pre-split fragments of
+    ldn_grouped_wide_conv3x3_image, bf16 [G = C / gw][S][M][64][2][8] with S = 32 K steps and M = 2 row tiles (gw 56), S = 63 and M = 4
+    (gw 112); ldn_grouped_wide_weight_bytes(C, gw) bytes.  The index formula: with Q = gw / 8 octets per tap,
+
+        frag[g, s, m, l, p, e] = split_p( w[g * gw + 32 * m + (l & 31),  q // Q,  8 * (q % Q) + e] ),    q = 2 * s + (l >> 5),
+
+    p = 0 the hi part bf16(w), p = 1 the lo part bf16(w - hi); the element is ZERO where the out channel of the group 32 * m + (l & 31) is
+    >= gw (pad rows 56-63 / 112-127) or the octet q is >= 9 * Q (q = 63 at gw 56).  K is cut into octets q of 8 consecutive in channels
+    of one tap; a lane's 16 values [8 hi | 8 lo] are contiguous, a (step, row tile) is one 2 KB line, a group's fragments are 128 KB / 504 KB."""
+    gw = int(group_width)
+    if gw not in _WIDE or w.dim() != 3 or w.shape[0] == 0 or w.shape[0] % gw or tuple(w.shape[1:]) != (9, gw):
+        raise L.LdnError(f"pack_grouped_wide_weights: expected [C % gw == 0, 9, gw] with gw 56 or 112 (got {tuple(w.shape)}, group width {gw})")
+    steps, mt = _WIDE[gw]
+    G = w.shape[0] // gw
+    k = torch.zeros(G, 32 * mt, 2 * steps, 8, device=w.device, dtype=torch.float32)
+    k[:, :gw, :9 * gw // 8] = w.detach().float().reshape(G, gw, 9 * gw // 8, 8)          # [g][out channel][q = tap * Q + octet][e]
+    k = k.reshape(G, mt, 32, steps, 2, 8).permute(0, 3, 1, 4, 2, 5).reshape(G, steps, mt, 64, 8)     # lane = i + 32 h
+    hi, lo = _hi_lo(k)
+    return torch.stack((hi, lo), dim=-2).contiguous()
+
+
+def grouped_wide_conv3x3_image(a_nhwc, w_frag, group_width, ch_idx, ch_cnt, scale, shift, out_nhwc, *, stride=1, relu=1):
+    """Grouped 3x3 conv (group width 56 or 112) + BN (+ReLU) on left-packed per-image channel subsets on the matrix cores: the contract of
+    grouped_conv3x3_image (see ldn_grouped_wide_conv3x3_image) with w_frag = pack_grouped_wide_weights(w, gw)."""
+    L.require_device(a_nhwc, w_frag, out_nhwc, ch_idx)
+    lib = L.load()
+    gw = int(group_width)
+    if gw not in _WIDE:
+        raise L.LdnError(f"grouped_wide_conv3x3_image: group width {gw} is not built (56 and 112)")
+    C = w_frag.shape[0] * gw
+    if (w_frag.dtype != torch.bfloat16 or not w_frag.is_contiguous() or C == 0
+            or w_frag.numel() * 2 != lib.ldn_grouped_wide_weight_bytes(C, gw)):
+        raise L.LdnError("grouped_wide_conv3x3_image: w_frag must be the contiguous bf16 tensor of pack_grouped_wide_weights for this group width")
+    if a_nhwc.dim() != 4 or out_nhwc.dim() != 4:
+        raise L.LdnError("grouped_wide_conv3x3_image: a and out must be [B, H, W, columns]")
+    B, Hi, Wi, lda = a_nhwc.shape
+    _, Ho, Wo, ldo = out_nhwc.shape
+    L.check(lib.ldn_grouped_wide_conv3x3_image(L.ptr(_f32c(a_nhwc, "a")), lda, B, Hi, Wi, stride, Ho, Wo, L.ptr(w_frag), C, gw,
+                                               L.ptr(_i32c(ch_idx, "ch_idx")), L.ptr(_i32c(ch_cnt, "ch_cnt")),
+                                               L.ptr(_f32c(scale, "scale")), L.ptr(_f32c(shift, "shift")), relu,
+                                               L.ptr(_f32c(out_nhwc, "out")), ldo, L.stream_ptr(out_nhwc)),
+            "ldn_grouped_wide_conv3x3_image")
+    return out_nhwc
+
+
 def se_packed(a2d, row_prefix, w1, b1, w2, b2, max_rows_per_image, ch_idx=None, ch_cnt=None):
     """In-place squeeze-excitation over the packed rows of every kept image (see ldn_se_packed)."""
     L.require_device(a2d, row_prefix)
