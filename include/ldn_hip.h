@@ -726,6 +726,27 @@ size_t ldn_grouped_wide_weight_bytes(int C, int group_width);
 int ldn_grouped_wide_conv3x3_image(const float* a, int lda, int B, int Hi, int Wi, int stride, int Ho, int Wo, const void* w_frag,
                                    int C, int group_width, const int32_t* ch_idx, const int32_t* ch_cnt, const float* scale,
                                    const float* shift, int relu, float* out, int ldo, void* stream);
+/* b over PACKED ROWS on the matrix cores at group widths 56 and 112 (layer skip, the dense 'spatial' path, every training forward and adjoint;
+ *    bf16x3 arithmetic; csrc/ldn_grouped_wide_rows.hip): the contract and the argument list of ldn_grouped_mfma_conv3x3_rows,
+ *      out[r, gw g + n] = act(scale[c] * sum_{t<9} sum_{i<gw} a[nbr[r*9+t], gw g + i] * w[gw g + n, t, i] + shift[c]),   r < M,
+ *      M = m_count ? min(m_count[0], m_cap) : m_cap,
+ *    with w_frag EXACTLY the ldn_grouped_wide_weight_bytes(C, gw) bytes of ldn_grouped_wide_conv3x3_image above (one packed copy serves the
+ *    image form and the row form; the adjoint packs the per-group transposed weights the same way).  The fragments stream through registers;
+ *    one wave holds every row tile of its one or two pixel tiles of 32 rows, so an input octet is gathered and split once.
+ *    A table entry of -1 is a zero row.  Rows >= M are neither read through the table nor written.  Columns of a at or past C (row stride
+ *    lda >= C, lda % 4 == 0) are never read, columns of out at or past C (ldo >= C, ldo % 4 == 0) never written; the padded out channels of a
+ *    group (56-63, 112-127) are dropped.  16-byte aligned pointers.  m_cap <= 0 launches nothing.  The grid is a function of m_cap and the
+ *    shapes only, never of the device-side count (graph-capturable).  No atomics: two runs are bit-identical.
+ *    Refused with LDN_EINVAL before any launch: a null pointer (m_count may be null), a shape outside _ok, a row stride that is not a
+ *    multiple of 4 or is below C, a misaligned pointer, m_cap > INT32_MAX - 256.
+ *    ldn_grouped_wide_rows_ok(C, gw) = 1 iff gw is 56 or 112, C > 0 and C % gw == 0 (host arithmetic only).
+ *    ldn_grouped_wide_rows_tiles(C, gw, m_cap) = pixel tiles of 32 rows a wave keeps in that launch: 2, or 1 where
+ *    (C / gw) * ceil(ceil(m_cap / 32) / 2) < 3072 (fewer than 3 waves per SIMD of 256 CUs at the cap); 0 outside _ok or for m_cap <= 0 (host arithmetic only). */
+int ldn_grouped_wide_rows_ok(int C, int group_width);
+int ldn_grouped_wide_rows_tiles(int C, int group_width, int m_cap);
+int ldn_grouped_wide_conv3x3_rows(const float* a, int lda, const int32_t* nbr, const int32_t* m_count, int m_cap,
+                                  const void* w_frag, int C, int group_width, const float* scale, const float* shift, int relu,
+                                  float* out, int ldo, void* stream);
 /* se: torchvision SqueezeExcitation (laud_regnet.py:119-123,194) applied IN PLACE to the packed rows of every kept
  *    image: gate[b,:] = sigmoid(W2 relu(W1 mean_rows(a_b) + b1) + b2), a[r,:] *= gate[image(r),:].
  *    w1 [S][C], w2 [C][S].  ch_idx / ch_cnt (optional, [B][C] / [B]): the columns of image b are its active channels

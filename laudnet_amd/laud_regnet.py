@@ -133,7 +133,7 @@ class BottleneckTransform(_PrepCache):
                 p["wb_frag"] = ops.pack_grouped16_weights(p["wb"])
             elif (USE_GROUPED_MFMA_WIDTHS or USE_GROUPED_MFMA_CHANNEL) and ops.grouped_mfma_ok(w_b, gw):      # ... and, behind their switches, the one for widths 8 and 24
                 p["wb_frag_gw"] = ops.pack_grouped_mfma_weights(p["wb"], gw)
-            if USE_GROUPED_MFMA_WIDE and gw in (56, 112) and w_b % gw == 0:       # ... and the streamed fragments of widths 56 and 112
+            if (USE_GROUPED_MFMA_WIDE or USE_GROUPED_MFMA_WIDE_ROWS) and gw in (56, 112) and w_b % gw == 0:       # ... and the streamed fragments of widths 56 and 112 (one copy for the image and the row form)
                 p["wb_frag_wide"] = ops.pack_grouped_wide_weights(p["wb"], gw)
             p["sb"], p["tb"] = _fold_bn(self.b[1])
             p["wc"] = self.c[0].weight.detach().reshape(-1, 1, w_b).float().contiguous()
@@ -163,6 +163,11 @@ def _conv_b_rows(p, f, h_a, nbr, h_b, m_count, m_cap, images=None):
         if "wb_frag_gw" not in p:           # (prepared before the switch was turned on)
             p["wb_frag_gw"] = ops.pack_grouped_mfma_weights(p["wb"], f.group_width)
         ops.grouped_mfma_conv3x3_rows(h_a, nbr, p["wb_frag_gw"], f.group_width, p["sb"], p["tb"], h_b, m_count=m_count, m_cap=m_cap, relu=1)
+    elif grouped_wide_rows_on(h_b.shape[1], f.group_width):
+        # widths 56 and 112 (LDN_GROUPED_MFMA_WIDE_ROWS=1): the fragments of the channel-mode image kernel, streamed over the packed rows
+        if "wb_frag_wide" not in p:         # (prepared before the switch was turned on)
+            p["wb_frag_wide"] = ops.pack_grouped_wide_weights(p["wb"], f.group_width)
+        ops.grouped_wide_conv3x3_rows(h_a, nbr, p["wb_frag_wide"], f.group_width, p["sb"], p["tb"], h_b, m_count=m_count, m_cap=m_cap, relu=1)
     else:
         ops.grouped_conv3x3_rows(h_a, nbr, p["wb"], f.group_width, p["sb"], p["tb"], h_b, m_count=m_count, m_cap=m_cap, relu=1)
 
@@ -193,6 +198,14 @@ def grouped_wide_on(C, gw, Hi, Wi, stride):
     """whether conv b of a channel / both block runs on ldn_grouped_wide_conv3x3_image: its switch, USE_GROUPED_MFMA, bf16x3 mode and the shape"""
     return bool(USE_GROUPED_MFMA_WIDE and USE_GROUPED_MFMA and ops.get_math_mode() == "bf16x3"
                 and ops.grouped_wide_ok(C, gw, Hi, Wi, stride))
+
+
+USE_GROUPED_MFMA_WIDE_ROWS = os.environ.get("LDN_GROUPED_MFMA_WIDE_ROWS", "0") == "1"   # ... and their packed-row form: layer skip, 'spatial', training (OFF by default)
+
+
+def grouped_wide_rows_on(C, gw):
+    """whether conv b of C channels in groups of gw over packed rows runs on ldn_grouped_wide_conv3x3_rows: its switch, USE_GROUPED_MFMA, bf16x3 mode and the shape"""
+    return bool(USE_GROUPED_MFMA_WIDE_ROWS and USE_GROUPED_MFMA and ops.get_math_mode() == "bf16x3" and ops.grouped_wide_rows_ok(C, gw))
 
 
 def _conv_b_image(p, f, h_a, idx, cnt, h_b, stride):

@@ -1306,6 +1306,33 @@ def grouped_wide_conv3x3_image(a_nhwc, w_frag, group_width, ch_idx, ch_cnt, scal
     return out_nhwc
 
 
+def grouped_wide_rows_ok(C, group_width):
+    """Whether ldn_grouped_wide_conv3x3_rows takes the shape: group width 56 or 112, C a positive multiple of it (host arithmetic only)."""
+    return bool(L.load().ldn_grouped_wide_rows_ok(int(C), int(group_width)))
+
+
+def grouped_wide_conv3x3_rows(a2d, nbr, w_frag, group_width, scale, shift, out2d, *, m_count=None, m_cap=None, relu=1):
+    """Grouped 3x3 conv (group width 56 or 112) + BN (+ReLU) over packed rows on the matrix cores: the contract of grouped_mfma_conv3x3_rows
+    (see ldn_grouped_wide_conv3x3_rows) with w_frag = pack_grouped_wide_weights(w, gw), the fragments of grouped_wide_conv3x3_image.
+    a2d / out2d may be column slices of wider matrices (row strides multiples of 4): the columns past C are neither read nor written."""
+    L.require_device(a2d, nbr, w_frag, out2d)
+    lib = L.load()
+    gw = int(group_width)
+    if gw not in _WIDE:
+        raise L.LdnError(f"grouped_wide_conv3x3_rows: group width {gw} is not built (56 and 112)")
+    C = w_frag.shape[0] * gw
+    if (w_frag.dtype != torch.bfloat16 or not w_frag.is_contiguous() or C == 0
+            or w_frag.numel() * 2 != lib.ldn_grouped_wide_weight_bytes(C, gw)):
+        raise L.LdnError("grouped_wide_conv3x3_rows: w_frag must be the contiguous bf16 tensor of pack_grouped_wide_weights for this group width")
+    m_cap = out2d.shape[0] if m_cap is None else m_cap
+    L.check(lib.ldn_grouped_wide_conv3x3_rows(L.ptr(_f32rows(a2d, "a")), a2d.stride(0), L.ptr(_i32c(nbr, "nbr")),
+                                              L.ptr(_i32c(m_count, "m_count")), m_cap, L.ptr(w_frag), C, gw,
+                                              L.ptr(_f32c(scale, "scale")), L.ptr(_f32c(shift, "shift")), relu,
+                                              L.ptr(_f32rows(out2d, "out")), out2d.stride(0), L.stream_ptr()),
+            "ldn_grouped_wide_conv3x3_rows")
+    return out2d
+
+
 def se_packed(a2d, row_prefix, w1, b1, w2, b2, max_rows_per_image, ch_idx=None, ch_cnt=None):
     """In-place squeeze-excitation over the packed rows of every kept image (see ldn_se_packed)."""
     L.require_device(a2d, row_prefix)
