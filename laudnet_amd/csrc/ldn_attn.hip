@@ -31,11 +31,17 @@ struct MhaArgs {
     const float* head_keep;             // optional [B][heads] {0,1}: head skipping (simulate_adavit.py:81-88) -- a dropped head's output is 0
 };
 
-__global__ __launch_bounds__(512, 2) void k_packed_mha(const MhaArgs p) {
+struct MhaLongArgs {                    // what both kernels take: an image's tokens past max_tokens are neither attended to nor written
+    MhaArgs a;                          // a.vs = round_up(max_tokens, 32) + 4 (k_packed_mha: the LDS is sized from max_tokens), A_MAXTOK + 4 (k_packed_mha_long)
+    int max_tokens;                     // Lb = min(count, max_tokens): the rows of tok_rows / out the caller promises
+};
+
+__global__ __launch_bounds__(512, 2) void k_packed_mha(const MhaLongArgs pl) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const MhaArgs& p = pl.a;
     const int b = blockIdx.x / p.heads, hd = blockIdx.x - b * p.heads;
     const int n0 = p.prefix[b];
-    const int Lb = min(p.prefix[b + 1] - n0, A_MAXTOK);
+    const int Lb = min(min(p.prefix[b + 1] - n0, pl.max_tokens), A_MAXTOK);   // gather, query ownership, early return and head-skip zeroing alike
     if (Lb <= 0) return;
     if (p.head_keep && p.head_keep[(size_t)b * p.heads + hd] < 0.5f) {   // head skipped for this image: its 64 output columns are zero
         for (int i = threadIdx.x; i < Lb * 16; i += 512)
@@ -178,11 +184,6 @@ __global__ __launch_bounds__(512, 2) void k_packed_mha(const MhaArgs p) {
 // BARRIERS: the trip count of the tile loop comes from Lb alone, so every wave of a workgroup runs every gather and every barrier --
 // also a wave whose 32 queries lie past the image's count (it skips the arithmetic only).  A workgroup whose whole query tile lies
 // past Lb (Lb == 0 included) returns before its first barrier; so does the workgroup of a dropped head, after zeroing its tile's rows.
-struct MhaLongArgs {
-    MhaArgs a;                          // a.vs = A_MAXTOK + 4
-    int max_tokens;                     // Lb = min(count, max_tokens): the rows of tok_rows / out the caller promises
-};
-
 __global__ __launch_bounds__(512, 2) void k_packed_mha_long(const MhaLongArgs pl) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const MhaArgs& p = pl.a;
@@ -367,7 +368,8 @@ static int packed_mha_impl(const float* qkv, int ld_qkv, const int32_t* tok_rows
     const size_t lds = ((size_t)Lp * A_KS + (size_t)A_D * a.vs) * 4;
     LDN_REQUIRE(lds <= 160 * 1024, "ldn_packed_mha: %zu B of LDS exceed 160 KiB", lds);
     LDN_REQUIRE(allow_dynamic_lds(reinterpret_cast<const void*>(&k_packed_mha), lds), "k_packed_mha: cannot reserve %zu B of LDS", lds);
-    hipLaunchKernelGGL(k_packed_mha, dim3((unsigned)B * heads), dim3(512), lds, static_cast<hipStream_t>(stream), a);
+    const MhaLongArgs as{a, max_tokens};                                  // Lb = min(count, max_tokens) <= Lp: inside the LDS reserved above
+    hipLaunchKernelGGL(k_packed_mha, dim3((unsigned)B * heads), dim3(512), lds, static_cast<hipStream_t>(stream), as);
     LDN_CHECK_LAUNCH("k_packed_mha");
     return LDN_OK;
 }

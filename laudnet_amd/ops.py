@@ -1658,11 +1658,15 @@ def packed_mha(qkv2d, tok_rows, prefix, B, heads, max_tokens, scale=None, head_k
     tokens.  Tokens of an image past max_tokens are neither attended to nor written."""
     L.require_device(qkv2d, tok_rows, prefix)
     lib = L.load()
+    if qkv2d.dim() != 2 or qkv2d.dtype != torch.float32 or qkv2d.stride(1) != 1:
+        raise L.LdnError("packed_mha: qkv must be fp32 [rows, 3 * heads * head_dim] with contiguous rows")
     rows, three_dim = qkv2d.shape
     dim = three_dim // 3
-    d = dim // heads
-    if three_dim != 3 * dim or dim != heads * d or qkv2d.dtype != torch.float32 or qkv2d.stride(1) != 1:
+    d = dim // max(int(heads), 1)
+    if heads <= 0 or three_dim != 3 * dim or dim != heads * d:
         raise L.LdnError("packed_mha: qkv must be fp32 [rows, 3 * heads * head_dim]")
+    if prefix.numel() != B + 1:
+        raise L.LdnError(f"packed_mha: prefix must be [B + 1] = [{B + 1}], got {prefix.numel()} entries")
     out = torch.empty(rows, dim, device=qkv2d.device, dtype=torch.float32)
     if head_keep is not None:
         if tuple(head_keep.shape) != (B, heads):
