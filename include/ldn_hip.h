@@ -258,6 +258,29 @@ size_t ldn_wgrad_grouped_rows_workspace_bytes(int m_cap, int C, int gw);
 int ldn_wgrad_grouped_rows(const float* dy, int lddy, const float* a, int lda, int a_valid, const int32_t* nbr, const int32_t* m_count,
                            int m_cap, int C, int gw, float* dw, float* work, int math_mode, void* stream);
 
+/* ---- the same WEIGHT GRADIENT at group widths 56 and 112, on the matrix cores (csrc/ldn_wgrad_grouped_wide.hip): per group a gw x 9 gw GEMM
+ * (56 x 504 / 112 x 1008) reduced over the packed rows
+ *   dW[c, t, j] = sum_{r < count} dY[r, c] * A[nbr[r * 9 + t], (c / gw) * gw + j]          for c < C, t < 9, j < gw
+ *   an entry of nbr < 0 or >= a_valid is a ZERO row (a missing 3x3 neighbour)
+ *   count = m_count ? clamp(*m_count, 0, m_cap) : m_cap, read on the device (no host read, no synchronisation)
+ * dY [m_cap][lddy >= C] fp32, A [a_valid][lda >= C] fp32, nbr [m_cap][9] (the neighbour table of ldn_mask_to_index).  Rows r >= count are
+ * NOT READ -- neither dY nor nbr: they may hold anything, NaN included.
+ * dW [C][9][gw] fp32 = the weight layout of ldn_grouped_conv3x3_rows, fully overwritten (count == 0: zeros).
+ * The argument list and the contract are those of ldn_wgrad_grouped_rows; the ARITHMETIC is that of ldn_wgrad_rows: LDN_MATH_BF16X3 splits
+ * BOTH operands in the kernel and adds lo*hi + hi*lo + hi*hi on v_mfma_f32_32x32x16_bf16, in that order; LDN_MATH_FP32 runs on
+ * v_mfma_f32_32x32x2_f32; LDN_MATH_DEFAULT follows the thread's mode.
+ * Deterministic: the rows are split over workgroups -- how many ways is a function of m_cap and the shapes only, never of *m_count, so the
+ * launch can be captured into a graph -- the partial tiles go to `work` (ldn_wgrad_grouped_wide_rows_workspace_bytes = splits * C * 9 * gw * 4
+ * bytes, 0 when the rows are not split; `work` may be NULL then) and the live splits are added in ascending order by a second small launch.
+ * No floating-point atomics: two runs are bit-identical.
+ * Shapes (ldn_wgrad_grouped_wide_rows_ok): gw 56 | 112, C > 0, C % gw == 0, C <= 4096 (widths 8 | 16 | 24 belong to ldn_wgrad_grouped_rows and
+ * are false here); lddy, lda % 4 == 0, 16-byte aligned pointers.  Anything else is LDN_EINVAL with a message, before any launch -- there is
+ * no fallback inside the library.  LDN_DEBUG build: nbr entries below -1 are counted (code 621). */
+int ldn_wgrad_grouped_wide_rows_ok(int C, int gw);
+size_t ldn_wgrad_grouped_wide_rows_workspace_bytes(int m_cap, int C, int gw);
+int ldn_wgrad_grouped_wide_rows(const float* dy, int lddy, const float* a, int lda, int a_valid, const int32_t* nbr, const int32_t* m_count,
+                                int m_cap, int C, int gw, float* dw, float* work, int math_mode, void* stream);
+
 /* ---- the ELEMENTWISE backward chain of training on packed rows (csrc/ldn_train_rows.hip): ldn_rows_chanmask, ldn_rows_act_bwd, ldn_rows_img_dot and
  * ldn_rows_postmask_bwd.  All are bandwidth-bound row kernels over
  * [m_cap][ld >= C] fp32 matrices, C % 4 == 0, ld % 4 == 0, 16-byte aligned pointers, every access 16 bytes wide.

@@ -47,6 +47,9 @@ SIGNATURES = {
     "ldn_wgrad_grouped_rows_ok": ([_I, _I], _I),
     "ldn_wgrad_grouped_rows_workspace_bytes": ([_I, _I, _I], C.c_size_t),
     "ldn_wgrad_grouped_rows": ([_P, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P], _I),
+    "ldn_wgrad_grouped_wide_rows_ok": ([_I, _I], _I),
+    "ldn_wgrad_grouped_wide_rows_workspace_bytes": ([_I, _I, _I], C.c_size_t),
+    "ldn_wgrad_grouped_wide_rows": ([_P, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P], _I),
     "ldn_rows_chanmask": ([_P, _I, _P, _I, _P, _P, _I, _I, _P], _I),
     "ldn_rows_act_bwd_workspace_bytes": ([_I, _I, _I], C.c_size_t),
     "ldn_rows_act_bwd": ([_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P], _I),

@@ -65,6 +65,7 @@ int tu_violations_small(unsigned* count, unsigned* code, int reset);
 int tu_violations_rows3(unsigned* count, unsigned* code, int reset);
 int tu_violations_wgrad(unsigned* count, unsigned* code, int reset);
 int tu_violations_wgrad_grouped(unsigned* count, unsigned* code, int reset);
+int tu_violations_wgrad_grouped_wide(unsigned* count, unsigned* code, int reset);
 int tu_violations_grouped_chan(unsigned* count, unsigned* code, int reset);
 int tu_violations_grouped_wide(unsigned* count, unsigned* code, int reset);
 int tu_chain_stalls(unsigned* count, int reset);      // csrc/ldn_tail.hip

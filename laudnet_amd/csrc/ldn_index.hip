@@ -1191,6 +1191,7 @@ extern "C" int ldn_debug_violations(int* count, int* first_code, int reset) {
     if (!rc) rc = tu_violations_rows3(&c, &code, reset);
     if (!rc) rc = tu_violations_wgrad(&c, &code, reset);
     if (!rc) rc = tu_violations_wgrad_grouped(&c, &code, reset);
+    if (!rc) rc = tu_violations_wgrad_grouped_wide(&c, &code, reset);
     if (!rc) rc = tu_violations_grouped_chan(&c, &code, reset);
     if (!rc) rc = tu_violations_grouped_wide(&c, &code, reset);
     if (rc) { set_error("ldn_debug_violations: cannot read the counters"); return rc; }

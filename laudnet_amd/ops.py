@@ -590,6 +590,46 @@ def wgrad_grouped_rows(dy2d, a2d, nbr, group_width, *, m_count=None, m_cap=None,
     return out
 
 
+def wgrad_grouped_wide_rows_ok(C, gw):
+    """Does ldn_wgrad_grouped_wide_rows take this shape (group width 56 | 112, C % gw == 0, C <= 4096)?"""
+    return bool(L.load().ldn_wgrad_grouped_wide_rows_ok(int(C), int(gw)))
+
+
+def wgrad_grouped_wide_rows(dy2d, a2d, nbr, group_width, *, m_count=None, m_cap=None, a_valid=None, out=None, math=None):
+    """Weight gradient of the grouped 3x3 over packed rows at group widths 56 / 112, on the matrix cores (see ldn_wgrad_grouped_wide_rows):
+    dW[c, t, j] = sum_{r < count} dy2d[r, c] * a2d[nbr[r * 9 + t], (c // gw) * gw + j] (an index < 0 or >= a_valid is a zero row).  The
+    signature and the checks of wgrad_grouped_rows: dy2d [m_cap, lddy >= C], a2d [rows, lda >= C], both with C columns; rows past the
+    device-side count are not read.  Returns out [C, 9, gw] (= the weight layout of grouped_conv3x3_rows), fully overwritten.  Deterministic
+    (no atomics); the arithmetic of wgrad_rows (bf16x3: three MFMA products, fp32: the fp32 MFMA); a shape outside
+    wgrad_grouped_wide_rows_ok raises LdnError."""
+    L.require_device(dy2d, a2d, nbr, m_count, out)
+    lib = L.load()
+    C, gw = dy2d.shape[1], int(group_width)
+    if a2d.shape[1] != C:
+        raise L.LdnError(f"wgrad_grouped_wide_rows: dy2d has {C} columns, a2d {a2d.shape[1]}")
+    if nbr is None:
+        raise L.LdnError("wgrad_grouped_wide_rows: the neighbour table is required")
+    if m_cap is None:
+        m_cap = nbr.numel() // 9
+    if m_cap > dy2d.shape[0] or nbr.numel() < m_cap * 9:
+        raise L.LdnError(f"wgrad_grouped_wide_rows: m_cap {m_cap} exceeds dy2d ({dy2d.shape[0]} rows) or nbr")
+    if a_valid is None:
+        a_valid = a2d.shape[0]
+    if a_valid > a2d.shape[0]:
+        raise L.LdnError(f"wgrad_grouped_wide_rows: a_valid {a_valid} exceeds a2d ({a2d.shape[0]} rows)")
+    if gw <= 0 or C % gw:
+        raise L.LdnError(f"wgrad_grouped_wide_rows: {C} channels are no multiple of the group width {gw}")
+    if out is None:
+        out = torch.empty(C, 9, gw, device=dy2d.device, dtype=torch.float32)
+    elif tuple(out.shape) != (C, 9, gw):
+        raise L.LdnError(f"wgrad_grouped_wide_rows: out must be [{C}, 9, {gw}], got {tuple(out.shape)}")
+    work = _work(lib.ldn_wgrad_grouped_wide_rows_workspace_bytes(m_cap, C, gw), dy2d.device)
+    L.check(lib.ldn_wgrad_grouped_wide_rows(L.ptr(_f32rows(dy2d, "dy")), dy2d.stride(0), L.ptr(_f32rows(a2d, "a")), a2d.stride(0), a_valid,
+                                            L.ptr(_i32c(nbr, "nbr")), L.ptr(_i32c(m_count, "m_count")), m_cap, C, gw, L.ptr(_f32c(out, "out")),
+                                            L.ptr(work), _mm(math), L.stream_ptr(out)), "ldn_wgrad_grouped_wide_rows")
+    return out
+
+
 def _rows_cap(m_cap, what, *mats):
     """m_cap of a row kernel over several [rows, ld] matrices: the smallest row count unless given; no matrix may be shorter."""
     rows = min(t.shape[0] for t in mats if t is not None)

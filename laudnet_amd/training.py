@@ -48,7 +48,10 @@ where no ReLU can flip (tests/test_hip_training_f64.py, tests/train_ref.py), the
 
 LAD-RegNet (`laud_regnet.ResBottleneckBlock`) trains in its LAYER-SKIP form -- dyn_mode 'spatial' with one keep / skip bit per image, SE present, stride
 1 and 2, with and without `proj`: a kept image runs a -> grouped b -> SE -> c on packed rows in both directions (`_RegNetSkipBranchFn`: the grouped
-3x3's adjoint is its forward kernel over the transposed neighbour table with per-group transposed weights, its weight gradient `ops.wgrad_grouped_rows`,
+3x3's adjoint is its forward kernel over the transposed neighbour table with per-group transposed weights, its weight gradient `ops.wgrad_grouped_rows`
+at group widths 8 / 16 / 24 -- at widths 56 / 112 `ops.wgrad_grouped_wide_rows` behind USE_WGRAD_GROUPED_WIDE (env LDN_WGRAD_GROUPED_WIDE=1; default OFF:
+the gather + bmm path, as before that kernel existed; LDN_WGRAD=0 forces that path everywhere; one chooser, `_weight_grad_conv_b`, for all three
+LAD-RegNet branch Fns; tests/test_hip_training_wgrad_grouped_wide.py) --
 the squeeze / excite and their backward tensor ops on the [slots, Ho Wo, C] view of the rows); the same three entry points take it and a whole
 `LAD_RegNet` (tests/test_hip_training_regnet.py).
 
@@ -107,6 +110,11 @@ from .laud_regnet import LAD_RegNet, ResBottleneckBlock, _conv_b_rows, grouped_m
 # all three full-width workloads at batch 32 and 128 (profiles/train_step_wgrad.jsonl), and for LAD-RegNetY-800MF layer skip with the grouped
 # kernel (profiles/train_step_regnet.jsonl)
 USE_WGRAD_KERNEL = os.environ.get("LDN_WGRAD", "1") != "0"
+
+# conv b's weight gradient at group widths 56 / 112 (lad_regnet_y_8gf / 16gf) on ldn_wgrad_grouped_wide_rows (the matrix cores); env
+# LDN_WGRAD_GROUPED_WIDE=1 turns it on, under USE_WGRAD_KERNEL.  Off by default: with it off every dispatch is what it was before the kernel
+# existed (the gather + bmm path at these widths).  Independent of laud_regnet.USE_GROUPED_MFMA_WIDE_ROWS (the forward's and the adjoint's switch)
+USE_WGRAD_GROUPED_WIDE = os.environ.get("LDN_WGRAD_GROUPED_WIDE", "0") == "1"
 
 # LAD-RegNet channel-mode training (_RegNetChannelBranchFn); env LDN_TRAIN_REGNET_CHANNEL=1 turns it on.  Off by default: with it off every
 # LAD-RegNet form but layer skip is refused, as before the path existed
@@ -186,6 +194,27 @@ def _weight_grad_grouped_3x3(du2, h1, nbr, cap1, gw, count3=None):
 def _wgrad_grouped_kernel(C, gw):
     """Does the grouped weight gradient run on ldn_wgrad_grouped_rows (the same module switch, that kernel's shape predicate)?"""
     return USE_WGRAD_KERNEL and ops.wgrad_grouped_rows_ok(C, gw)
+
+
+def _wgrad_grouped_wide_kernel(C, gw):
+    """Does the grouped weight gradient run on ldn_wgrad_grouped_wide_rows (both switches -- LDN_WGRAD=0 still forces the PyTorch path
+    everywhere -- and that kernel's shape predicate: group widths 56 / 112)?"""
+    return USE_WGRAD_KERNEL and USE_WGRAD_GROUPED_WIDE and ops.wgrad_grouped_wide_rows_ok(C, gw)
+
+
+def _weight_grad_conv_b(dy, h_a, ix, gw, m_count, count3=None):
+    """d W_b [C, gw, 3, 3] of LAD-RegNet's conv b from d y_b [cap3, C] and conv b's input h_a [cap1, C]: the one place that chooses between
+    ldn_wgrad_grouped_rows (widths 8 / 16 / 24), ldn_wgrad_grouped_wide_rows (widths 56 / 112, behind USE_WGRAD_GROUPED_WIDE) and the
+    gather + bmm path.  m_count = the device-side row count for the kernels; count3 = the same for the fallback (None: rows past the
+    count carry d y_b == 0 and valid table entries)."""
+    C = dy.shape[1]
+    if _wgrad_grouped_kernel(C, gw):
+        op = ops.wgrad_grouped_rows
+    elif _wgrad_grouped_wide_kernel(C, gw):
+        op = ops.wgrad_grouped_wide_rows
+    else:
+        return _weight_grad_grouped_3x3(dy, h_a, ix.nbr, ix.cap1, gw, count3)
+    return op(dy, h_a, ix.nbr, gw, m_count=m_count, m_cap=ix.cap3, a_valid=ix.cap1).permute(0, 2, 1).reshape(C, gw, 3, 3)
 
 
 def grouped_weight_T(wbr, gw):
@@ -658,10 +687,7 @@ class _RegNetSkipBranchFn(torch.autograd.Function):
         Ga, _, Gc = _weight_grads(need[1] or need[5], False, need[3] or need[9], g3, z, None, h_a, dza, x2d, ix, counted=True)
         Gb = None
         if need[2] or need[7]:       # conv b sees h_a inside the map, zeros in the padding ring
-            if _wgrad_grouped_kernel(W, gw):
-                Gb = ops.wgrad_grouped_rows(dzb, h_a, ix.nbr, gw, m_count=cnt3, m_cap=ix.cap3, a_valid=ix.cap1).permute(0, 2, 1).reshape(W, gw, 3, 3)
-            else:
-                Gb = _weight_grad_grouped_3x3(dzb, h_a, ix.nbr, ix.cap1, gw, ix.cnt[0])
+            Gb = _weight_grad_conv_b(dzb, h_a, ix, gw, cnt3, ix.cnt[0])
         gwa, gsa = _split_scale(need[1], need[5], Ga, war, sa)
         gwb, gsb = _split_scale(need[2], need[7], Gb, wbr, sb)
         gwc, gsc = _split_scale(need[3], need[9], Gc, wcr, sc)
@@ -753,10 +779,7 @@ class _RegNetChannelBranchFn(torch.autograd.Function):
         Ga, _, Gc = _weight_grads(need[1] or need[5], False, need[3] or need[9], go, z, None, h_a, dza, x2d, ix, counted=False)
         Gb = None
         if need[2] or need[7]:       # conv b sees the MASKED h_a inside the map, zeros in the padding ring
-            if _wgrad_grouped_kernel(W, gw):
-                Gb = ops.wgrad_grouped_rows(dzb, h_a, ix.nbr, gw, m_count=ix.cnt[0:1], m_cap=ix.cap3, a_valid=ix.cap1).permute(0, 2, 1).reshape(W, gw, 3, 3)
-            else:
-                Gb = _weight_grad_grouped_3x3(dzb, h_a, ix.nbr, ix.cap1, gw)
+            Gb = _weight_grad_conv_b(dzb, h_a, ix, gw, ix.cnt[0:1])
         gwa, gsa = _split_scale(need[1], need[5], Ga, war, sa)
         gwb, gsb = _split_scale(need[2], need[7], Gb, wbr, sb)
         gwc, gsc = _split_scale(need[3], need[9], Gc, wcr, sc)
@@ -943,10 +966,7 @@ class _RegNetBatchStatsBranchFn(torch.autograd.Function):
         gwa, _, gwc = _weight_grads(need[1], False, need[3], dyc, z, None, h_a, dya, x2d, ix, counted=False)
         gwb = None
         if need[2]:                  # conv b sees the MASKED h_a inside the map, zeros in the padding ring
-            if _wgrad_grouped_kernel(W, gw):
-                gwb = ops.wgrad_grouped_rows(dyb, h_a, ix.nbr, gw, m_count=ix.cnt[0:1], m_cap=ix.cap3, a_valid=ix.cap1).permute(0, 2, 1).reshape(W, gw, 3, 3)
-            else:
-                gwb = _weight_grad_grouped_3x3(dyb, h_a, ix.nbr, ix.cap1, gw)
+            gwb = _weight_grad_conv_b(dyb, h_a, ix, gw, ix.cnt[0:1])
         gm = gma + gmb if want_m else None
         keep = lambda v, n: v if n else None
         return (grad_x, gwa, gwb, gwc, gm, keep(gga, need[5]), keep(gba, need[6]), keep(ggb, need[7]), keep(gbb, need[8]), keep(ggc, need[9]),
