@@ -1740,8 +1740,9 @@ static int dispatch_mode(const ImgArgs& p, int kgran, hipStream_t st) {
     LDN_REQUIRE(!p.k_idx || p.cin % 8 == 0, "conv: an input-channel list needs cin to be a multiple of 8 (got %d)", p.cin);
     LDN_REQUIRE(taps * p.cin * p.cout < (1L << 31), "conv: weight tensor of %ld elements exceeds the 32-bit offsets of the weight staging",
                 taps * p.cin * p.cout);
-    // wide 1x1 convolutions without an output-channel list: the persistent streaming kernel (bf16x3 arithmetic only)
-    if (p.math == 1 && stream_rows() >= ST_BM && taps == 1 && !p.n_idx && p.shift_classes == 1 &&
+    // wide 1x1 convolutions without an output-channel list: the persistent streaming kernel (bf16x3 arithmetic only;
+    // its epilogue stores fp32 rows, so a pre-split output stays with k_conv_bf3)
+    if (p.math == 1 && stream_rows() >= ST_BM && taps == 1 && !p.n_idx && p.shift_classes == 1 && !p.out_split &&
         p.cout % ST_BN == 0 && p.cout >= 2 * ST_BN && !(p.residual && p.scale) && p.cin <= 1024 &&
         (p.packed ? p.m_cap : p.Ho * p.Wo) >= 96)   // (7x7 images would leave most of every 128-row M block empty)
         return p.k_idx ? launch_stream<B_KN4>(p, st) : launch_stream<B_NK>(p, st);

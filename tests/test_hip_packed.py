@@ -6,7 +6,7 @@ A1  The three launches of Bottleneck._run_both -- conv1 on the dilated pixel lis
     float64 (helpers.bottleneck_stages_f64).  The model-level checks see these kernels only through a global average pool.
 A2  The options of the entry point that _run_both never combines, as literal-contract tests of include/ldn_hip.h:285-308,447-462.
 
-`expected_variant` restates the dispatch of csrc/ldn_conv_image.hip:1662-1769 in Python; the non-GPU test
+`expected_variant` (tests/conv_dispatch_ref.py) restates the dispatch of csrc/ldn_conv_image.hip in Python; the non-GPU test
 test_case_table_reaches_every_variant proves from it that the case table runs every tile shape, weight-staging mode and kernel a
 packed launch with channel lists can reach, in both arithmetic modes.
 
@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from conv_dispatch_ref import expected_variant, expected_wave_rows
 from fill import seeded_bernoulli, seeded_randn
 from helpers import apply_math_mode  # noqa: F401  (autouse fixture: a test that takes math_mode runs in that mode)
 from helpers import assert_close, bn_shift_f64, bottleneck_stages_f64, upsample_mask
@@ -34,58 +35,6 @@ def ops():
     from laudnet_amd import ops as _ops, load_library
     load_library()  # raises if libldn_hip.so is missing -- no fallback
     return _ops
-
-
-# ------------------------------------------------------------------ the dispatch rule, restated
-def expected_variant(packed, rows_per_image, cin, cout, taps, has_k, has_n, kgran, shift_classes, residual, scale, math):
-    """(kernel, MS, NS, BMODE) a conv launch runs, transcribed from csrc/ldn_conv_image.hip.  rows_per_image: m_cap of a packed launch,
-    Ho * Wo of an image launch (:1727); taps: 1 or 9 (:1783); has_k / has_n: input / output channel list; math: "fp32" | "bf16x3"."""
-    bf3 = math == "bf16x3"
-    hw = rows_per_image
-    # dispatch_mode, :1788-1791: the streaming kernel (ST_BM = ST_BN = 128, :1264; LDN_STREAM_ROWS at its default 512, :1751)
-    if (bf3 and taps == 1 and not has_n and shift_classes == 1 and cout % 128 == 0 and cout >= 2 * 128
-            and not (residual and scale) and cin <= 1024 and hw >= 96):
-        return ("k_conv1x1_stream", None, None, "B_KN4" if has_k else "B_NK")
-    # :1792-1796: how the weights are staged
-    if not has_k:
-        bmode = "B_NK"
-    else:
-        g = kgran if has_n else 4
-        bmode = "B_KN4" if g % 4 == 0 else ("B_KN2" if g % 2 == 0 else "B_KN1")
-    # launch_shape, :1726-1743
-    nsubs = -(-cout // 32)
-    if nsubs <= 4:
-        per = nsubs
-    elif hw <= 128:
-        per = min(nsubs, 10)
-    elif hw <= 256 and has_n:
-        per = min(nsubs, 6)
-    else:
-        per = 4
-    if per <= 2:
-        ms, ns = 6, 2
-    elif per <= 4:
-        ms, ns = 4, 4
-    elif per <= 6:
-        ms, ns = 8, 6
-    else:
-        ms, ns = 4, 10
-    # launch_k, :1692-1704 (bf16x3) / :1707-1720 (fp32)
-    if bf3:
-        if (ms, ns) == (4, 10) and -(-hw // 32) <= 2:      # :1696-1698, the 2 x 10 special case
-            ms = 2
-        return ("k_conv_bf3", ms, ns, bmode)
-    return ("k_conv_image", ms, ns, bmode)
-
-
-def expected_wave_rows(variant, residual):
-    """WM of k_conv_bf3 (:1699-1704): the 4 x 4 tile runs a 4 x 1 wave grid without a residual and 2 x 2 with one."""
-    kernel, ms, ns, _ = variant
-    if kernel != "k_conv_bf3":
-        return None
-    if (ms, ns) == (4, 4) and not residual:
-        return 4
-    return 4 if ms >= 8 else 2
 
 
 # (B, H, Wd, cin, width, channel granularity, stride, spatial mask groups)
@@ -132,7 +81,7 @@ def case_launches(case):
 
 def reachable_variants():
     """Every (kernel, MS, NS, BMODE, math) the three launches of a `both` block can run, by ENUMERATION of expected_variant over the blocks the
-    library admits: widths that are multiples of 8 (an input list needs cin % 8, :1784) from 8 to 2048, maps from one pixel to 112 x 112 on
+    library admits: widths that are multiples of 8 (an input list needs cin % 8, :1740) from 8 to 2048, maps from one pixel to 112 x 112 on
     both sides of every row threshold of the dispatch (64 | 96 | 128 | 256 rows), channel granularity 1 / 2 / 4, one / two / four spatial mask
     groups, stride 1 and 2, both arithmetic modes.  Nothing is excluded."""
     widths = sorted(set(range(8, 513, 8)) | {768, 1024, 2048})
@@ -152,7 +101,7 @@ def reachable_variants():
 
 
 # What reachable_variants() must come to, written out so that a reader sees it: every tile shape x every staging mode (conv1: B_NK, conv2:
-# B_KN<granularity>, conv3: B_KN4, :1793) in both modes, and the streaming kernel with an input list.  fp32 has no 2 x 10 tile and no
+# B_KN<granularity>, conv3: B_KN4, :1749-1753) in both modes, and the streaming kernel with an input list.  fp32 has no 2 x 10 tile and no
 # streaming kernel.  16 + 21 instantiations.
 REACHABLE = {
     ("k_conv_image", 6, 2, "B_NK", "fp32"), ("k_conv_image", 4, 4, "B_NK", "fp32"), ("k_conv_image", 8, 6, "B_NK", "fp32"),
@@ -605,7 +554,7 @@ def test_border_class_shift_table(ops, B, Hi, Wi, stride, math_mode):
 
 @gpu
 def test_argument_checks_refuse_before_any_launch(ops):
-    """The checks of ldn_conv_packed (csrc/ldn_conv_image.hip:1833-1851): an error code, and the output is not touched."""
+    """The checks of ldn_conv_packed (csrc/ldn_conv_image.hip:1818-1836): an error code, and the output is not touched."""
     from laudnet_amd import LdnError
     rows, cin, cout, B = 64, 32, 32, 2
     a = torch.zeros(rows, cin, device=DEV)

@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from conv_image_ref import decode_split as _decode_split
 from fill import seeded_bernoulli, seeded_randn
 from oracle import torch_ref as TR
 
@@ -18,13 +19,6 @@ def ops():
     from laudnet_amd import ops as _ops, load_library
     load_library()
     return _ops
-
-
-def _decode_split(h1s):
-    """[B,H,W,ld] fp32-typed storage of [octet][8 hi | 8 lo] bf16 -> fp32 values hi + lo, [B,H,W,ld]."""
-    B, H, W, ld = h1s.shape
-    raw = h1s.contiguous().view(torch.bfloat16).reshape(B, H, W, ld // 8, 2, 8).float()
-    return (raw[..., 0, :] + raw[..., 1, :]).reshape(B, H, W, ld)
 
 
 @pytest.mark.parametrize("B,H,cin,W,gran,st", [(4, 14, 1024, 256, 2, 1), (3, 28, 512, 128, 2, 1), (2, 56, 256, 64, 2, 1),
