@@ -2,6 +2,8 @@
 against the reference's stem in PyTorch fp32 (laud_resnet.py:316-326: conv1 -> bn1 -> relu -> maxpool, eval mode).
 Tolerance 1e-4 + 1e-5 relative on O(1) activations (north star: 1e-3); geometry cases cover odd sizes, non-square inputs,
 maps smaller than one tile and tiles cut by the image border."""
+import copy
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -82,9 +84,21 @@ def test_stem_in_model_matches_library_stem():
         if k.endswith("bn3.weight"):
             sd[k] = sd[k] * 0.3
     m.load_state_dict(sd)
-    m = m.to(dev)
     assert m.conv1.out_channels == 32
-    x = seeded_randn((3, 3, 64, 64), 12).to(dev)
+    x = seeded_randn((3, 3, 64, 64), 12)
+    # float64 oracle of the first block's channel decisions: how many of them sit within the tie threshold (test_channel_masker's)
+    # for this seeded input?  Only those may come out differently from two stems that agree to 1e-4.
+    mk = m.layer1[0].masker_channel
+    G = mk.channel_dyn_group
+    with torch.no_grad():
+        bn = m.bn1
+        y = F.batch_norm(F.conv2d(x.double(), m.conv1.weight.double(), None, 2, 3), bn.running_mean.double(), bn.running_var.double(),
+                         bn.weight.double(), bn.bias.double(), False, 0.0, bn.eps)
+        y = F.max_pool2d(F.relu(y), 3, 2, 1)
+        lg = copy.deepcopy(mk.conv).double()(y.mean(dim=(2, 3)))                   # [B, 2 G]
+    near_ties = int(((lg[:, :G] - lg[:, G:]).abs() <= 1e-4 * max(lg.abs().max().item(), 1.0)).sum())
+    m = m.to(dev)
+    x = x.to(dev)
     ops.set_math_mode("bf16x3")
     try:
         with torch.no_grad():
@@ -95,7 +109,15 @@ def test_stem_in_model_matches_library_stem():
             b = m(x, 1.0)
     finally:
         ops.set_math_mode("fp32")
-    assert torch.equal(a[1][0], b[1][0]) or True      # sparsities may differ only if a masker decision sits on a tie
+    # the first block's sparsities (a[1..4] = s3, s2, s1, channel sparsity per stage) may differ only if one of its masker's
+    # decisions sits on a tie: a flipped decision moves the channel sparsity by 1 / (B * G)
+    for k in (1, 2, 3):
+        assert torch.equal(a[k][0][:1], b[k][0][:1]), k
+    if near_ties == 0:
+        assert torch.equal(a[4][0][:1], b[4][0][:1]), (a[4][0], b[4][0])
+    else:
+        flips = (a[4][0][0] - b[4][0][0]).abs().item() * x.shape[0] * G
+        assert flips <= near_ties + 1e-3, (flips, near_ties)
     assert (a[0] - b[0]).abs().max().item() < 1e-4
 
 
