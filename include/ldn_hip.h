@@ -710,6 +710,25 @@ int ldn_grouped16_images_fit(int Hi, int Wi, int C);
 int ldn_grouped16_conv3x3_images(const float* a, int lda, const int32_t* m_count, int images_cap, int Hi, int Wi, int Ho, int Wo,
                                  int stride, const void* w_frag, int C, const float* scale, const float* shift, int relu, float* out,
                                  int ldo, void* stream);
+/* ... and at group widths 8 and 24 (csrc/ldn_grouped_gw.hip: k_grouped_gw_img): the contract of ldn_grouped16_conv3x3_images word for word, with
+ *    w_frag EXACTLY the ldn_grouped_mfma_weight_bytes(C, gw) bytes of ldn_grouped_mfma_conv3x3_rows (one packed copy serves both forms) and
+ *    results bit-identical to that entry point's over the same images' neighbour table.  3x3 / pad 1 / stride 1 or 2, any Hi x Wi with
+ *    Ho = (Hi - 1) / stride + 1, Wo = (Wi - 1) / stride + 1; rows at or past *m_count and columns >= C are neither read nor written; the grid
+ *    depends on the shapes and images_cap only; deterministic (no atomics).  lda / ldo multiples of 4 and >= C, 16-byte aligned pointers.
+ *    ldn_grouped_mfma_images_fit(Hi, Wi, C, gw) = groups per workgroup (> 0) iff the Hi x Wi input map fits the LDS at both strides, the
+ *    channel-sum scratch of the _gap form included; 0 also for a width or C that ldn_grouped_mfma_ok refuses.
+ *    ldn_grouped_mfma_images_bands(Hi, Wi, Ho, stride, C, gw) = bands of output rows per image (1: a workgroup holds a whole image; 0: refused).
+ *    ldn_grouped_mfma_conv3x3_images_gap also leaves gap_partial [images_cap][bands][C]: the channel sums of the launch's final output (after BN and
+ *    ReLU) over each band's pixels, in a fixed order (a tree over every 16 pixels, the partial sums added in ascending order); the input of
+ *    ldn_se_gate_slots with splits = bands.  Everything else is LDN_EINVAL before any launch. */
+int ldn_grouped_mfma_images_fit(int Hi, int Wi, int C, int group_width);
+int ldn_grouped_mfma_images_bands(int Hi, int Wi, int Ho, int stride, int C, int group_width);
+int ldn_grouped_mfma_conv3x3_images(const float* a, int lda, const int32_t* m_count, int images_cap, int Hi, int Wi, int Ho, int Wo,
+                                    int stride, const void* w_frag, int C, int group_width, const float* scale, const float* shift,
+                                    int relu, float* out, int ldo, void* stream);
+int ldn_grouped_mfma_conv3x3_images_gap(const float* a, int lda, const int32_t* m_count, int images_cap, int Hi, int Wi, int Ho, int Wo,
+                                        int stride, const void* w_frag, int C, int group_width, const float* scale, const float* shift,
+                                        int relu, float* out, int ldo, float* gap_partial, void* stream);
 /* b in CHANNEL mode (laud_regnet.py:160-189: the mask is applied AFTER conv+BN+ReLU, so masked channels are exact zeros and the
  *    subset execution is exact): dense image whose columns are left-packed per image (column j of image b = channel
  *    ch_idx[b,j], ascending, j < ch_cnt[b]); output column j sums over the ACTIVE input channels of its group only.

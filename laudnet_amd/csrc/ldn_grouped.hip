@@ -121,22 +121,6 @@ struct GiArgs {
                                             // (the squeeze of the SE block that follows conv b, laud_regnet.py:194: no second pass over h_b)
 };
 
-// sum over the 16 lanes of a DPP row (inline asm: hipcc 7.2 merges neighbouring update_dpp calls, see dpp_swap_pair); fixed order
-__device__ __forceinline__ float row16_sum(float v) {
-    float t;
-    asm volatile("s_nop 1\n\t"
-                 "v_add_f32_dpp %0, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-                 "s_nop 1\n\t"
-                 "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-                 "s_nop 1\n\t"
-                 "v_add_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
-                 "s_nop 1\n\t"
-                 "v_add_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"
-                 "s_nop 1"
-                 : "=&v"(t) : "v"(v));
-    return t;
-}
-
 __global__ __launch_bounds__(512, 2) void k_grouped16_img(const GiArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;

@@ -127,4 +127,21 @@ template <typename V> __device__ __forceinline__ void split8(const V a, const V 
     }
 }
 
+// ---- cross-lane
+// sum over the 16 lanes of a DPP row (inline asm: hipcc 7.2 merges neighbouring update_dpp calls, see dpp_swap_pair); fixed order
+__device__ __forceinline__ float row16_sum(float v) {
+    float t;
+    asm volatile("s_nop 1\n\t"
+                 "v_add_f32_dpp %0, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 1\n\t"
+                 "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 1\n\t"
+                 "v_add_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 1\n\t"
+                 "v_add_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 1"
+                 : "=&v"(t) : "v"(v));
+    return t;
+}
+
 }  // namespace ldn

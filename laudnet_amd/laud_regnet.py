@@ -149,9 +149,10 @@ class BottleneckTransform(_PrepCache):
 
 
 def _conv_b_rows(p, f, h_a, nbr, h_b, m_count, m_cap, images=None):
-    """conv b (grouped 3x3 + BN + ReLU) over packed rows: on the matrix cores for group width 16 in bf16x3 mode, else the fp32 VALU
-    kernel.  images = (B, Hi, Wi, Ho, Wo, stride) when the rows are whole images in order (layer skip, dense index): maps that fit
-    the LDS are staged there once per (image, group chunk) instead of being read once per tap through the neighbour table."""
+    """conv b (grouped 3x3 + BN + ReLU) over packed rows: on the matrix cores for group width 16 in bf16x3 mode (and behind their switches
+    for widths 8 / 24 and 56 / 112), else the fp32 VALU kernel.  images = (B, Hi, Wi, Ho, Wo, stride) when the rows are whole images in
+    order (layer skip, dense index): maps that fit the LDS are staged there once per (image, group chunk) instead of being read once per
+    tap through the neighbour table (width 16; widths 8 / 24 with LDN_GROUPED_MFMA_WIDTHS_IMAGES=1)."""
     if "wb_frag" in p and ops.get_math_mode() == "bf16x3" and USE_GROUPED_MFMA:
         if (images is not None and m_count is not None and USE_GROUPED_IMAGES
                 and ops.grouped16_images_fit(images[1], images[2], h_b.shape[1]) > 0):
@@ -159,10 +160,14 @@ def _conv_b_rows(p, f, h_a, nbr, h_b, m_count, m_cap, images=None):
         else:
             ops.grouped16_conv3x3_rows(h_a, nbr, p["wb_frag"], p["sb"], p["tb"], h_b, m_count=m_count, m_cap=m_cap, relu=1)
     elif grouped_mfma_widths_on(h_b.shape[1], f.group_width):
-        # widths 8 and 24 (LDN_GROUPED_MFMA_WIDTHS=1): the neighbour-table form serves whole images too -- no LDS-staged image form yet
+        # widths 8 and 24 (LDN_GROUPED_MFMA_WIDTHS=1): the neighbour-table form, or with LDN_GROUPED_MFMA_WIDTHS_IMAGES=1 the LDS-staged image form
+        # on whole images in order (the same fragments, the same bits)
         if "wb_frag_gw" not in p:           # (prepared before the switch was turned on)
             p["wb_frag_gw"] = ops.pack_grouped_mfma_weights(p["wb"], f.group_width)
-        ops.grouped_mfma_conv3x3_rows(h_a, nbr, p["wb_frag_gw"], f.group_width, p["sb"], p["tb"], h_b, m_count=m_count, m_cap=m_cap, relu=1)
+        if images is not None and m_count is not None and grouped_mfma_images_on(h_b.shape[1], f.group_width, images[1], images[2], images[5]):
+            ops.grouped_mfma_conv3x3_images(h_a, p["wb_frag_gw"], f.group_width, p["sb"], p["tb"], h_b, m_count=m_count, images=images, relu=1)
+        else:
+            ops.grouped_mfma_conv3x3_rows(h_a, nbr, p["wb_frag_gw"], f.group_width, p["sb"], p["tb"], h_b, m_count=m_count, m_cap=m_cap, relu=1)
     elif grouped_wide_rows_on(h_b.shape[1], f.group_width):
         # widths 56 and 112 (LDN_GROUPED_MFMA_WIDE_ROWS=1): the fragments of the channel-mode image kernel, streamed over the packed rows
         if "wb_frag_wide" not in p:         # (prepared before the switch was turned on)
@@ -180,6 +185,16 @@ USE_GROUPED_MFMA_WIDTHS = os.environ.get("LDN_GROUPED_MFMA_WIDTHS", "0") == "1" 
 def grouped_mfma_widths_on(C, gw):
     """whether conv b of C channels in groups of gw runs on ldn_grouped_mfma_conv3x3_rows: its switch, USE_GROUPED_MFMA, bf16x3 mode and the shape"""
     return bool(USE_GROUPED_MFMA_WIDTHS and USE_GROUPED_MFMA and ops.get_math_mode() == "bf16x3" and ops.grouped_mfma_ok(C, gw))
+
+
+USE_GROUPED_MFMA_WIDTHS_IMAGES = os.environ.get("LDN_GROUPED_MFMA_WIDTHS_IMAGES", "0") == "1"   # ... and their whole-image / SE-fused form (OFF by default)
+
+
+def grouped_mfma_images_on(C, gw, Hi, Wi, stride):
+    """whether conv b of C channels in groups of gw over whole images in order runs on ldn_grouped_mfma_conv3x3_images: its switch, everything
+    grouped_mfma_widths_on asks for, and a map that fits the LDS"""
+    return bool(USE_GROUPED_MFMA_WIDTHS_IMAGES and stride in (1, 2) and grouped_mfma_widths_on(C, gw)
+                and ops.grouped_mfma_images_fit(Hi, Wi, C, gw) > 0)
 
 
 USE_GROUPED_MFMA_CHANNEL = os.environ.get("LDN_GROUPED_MFMA_CHANNEL", "0") == "1"   # ... conv b of channel / both mode on the matrix cores (OFF by default)
@@ -319,6 +334,14 @@ class ResBottleneckBlock(_PrepCache):
                 and ops.conv_rows_gated_fits(w_b, Ho * Wo) and ops.grouped16_images_fit(Hi, Wi, w_b) > 0):
             gap = ops.grouped16_conv3x3_images_gap(h_a, p["wb_frag"], p["sb"], p["tb"], h_b, m_count=ix.cnt[0:1],
                                                    images=(B, Hi, Wi, Ho, Wo, self.stride), relu=1)
+            gate = ops.se_gate_slots(gap, ix.cnt[0:1], Ho * Wo, p["se_w1"], p["se_b1"], p["se_w2"], p["se_b2"])
+        elif (USE_SE_FUSED and ops.conv_rows_gated_fits(w_b, Ho * Wo)
+                and grouped_mfma_images_on(w_b, f.group_width, Hi, Wi, self.stride)):
+            # ... the same fold at group widths 8 and 24 (LDN_GROUPED_MFMA_WIDTHS=1 and LDN_GROUPED_MFMA_WIDTHS_IMAGES=1)
+            if "wb_frag_gw" not in p:           # (prepared before the switch was turned on)
+                p["wb_frag_gw"] = ops.pack_grouped_mfma_weights(p["wb"], f.group_width)
+            gap = ops.grouped_mfma_conv3x3_images_gap(h_a, p["wb_frag_gw"], f.group_width, p["sb"], p["tb"], h_b, m_count=ix.cnt[0:1],
+                                                      images=(B, Hi, Wi, Ho, Wo, self.stride), relu=1)
             gate = ops.se_gate_slots(gap, ix.cnt[0:1], Ho * Wo, p["se_w1"], p["se_b1"], p["se_w2"], p["se_b2"])
         else:
             _conv_b_rows(p, f, h_a, ix.nbr, h_b, ix.cnt[0:1], ix.cap3, images=(B, Hi, Wi, Ho, Wo, self.stride))

@@ -1204,6 +1204,65 @@ def grouped16_conv3x3_images_gap(a2d, w_frag, scale, shift, out2d, *, m_count, i
     return gap
 
 
+def grouped_mfma_images_fit(Hi, Wi, C, group_width):
+    """Groups per workgroup of ldn_grouped_mfma_conv3x3_images for an Hi x Wi input map at group width 8 or 24 (0: it does not fit the LDS, or
+    a width / channel count that grouped_mfma_ok refuses).  Both strides and the channel-sum scratch of the _gap form are included."""
+    return int(L.load().ldn_grouped_mfma_images_fit(int(Hi), int(Wi), int(C), int(group_width)))
+
+
+def grouped_mfma_images_bands(Hi, Wi, Ho, stride, C, group_width):
+    """Bands of output rows per image of ldn_grouped_mfma_conv3x3_images (1: a workgroup holds a whole image; 0: refused)."""
+    return int(L.load().ldn_grouped_mfma_images_bands(int(Hi), int(Wi), int(Ho), int(stride), int(C), int(group_width)))
+
+
+def _grouped_mfma_images_args(name, a2d, w_frag, gw, out2d, images):
+    """the checks the two image forms share -> (lib, C, B, Hi, Wi, Ho, Wo, stride)"""
+    lib = L.load()
+    if gw not in (8, 24):
+        raise L.LdnError(f"{name}: group width {gw} is not built (8 and 24; width 16 is grouped16_conv3x3_images)")
+    C = w_frag.shape[0] * gw
+    if (w_frag.dtype != torch.bfloat16 or not w_frag.is_contiguous() or C == 0
+            or w_frag.numel() * 2 != lib.ldn_grouped_mfma_weight_bytes(C, gw)):
+        raise L.LdnError(f"{name}: w_frag must be the contiguous bf16 tensor of pack_grouped_mfma_weights for this group width")
+    B, Hi, Wi, Ho, Wo, stride = (int(v) for v in images)
+    if a2d.shape[0] < B * Hi * Wi or out2d.shape[0] < B * Ho * Wo or a2d.shape[1] != C or out2d.shape[1] != C:
+        raise L.LdnError(f"{name}: a / out must hold B whole images of C channels")
+    return lib, C, B, Hi, Wi, Ho, Wo, stride
+
+
+def grouped_mfma_conv3x3_images(a2d, w_frag, group_width, scale, shift, out2d, *, m_count, images, relu=1):
+    """Grouped 3x3 conv (group width 8 or 24) + BN (+ReLU) over packed rows that are WHOLE IMAGES in order (see
+    ldn_grouped_mfma_conv3x3_images): bit-identical to grouped_mfma_conv3x3_rows over the same images' neighbour table, with the same
+    w_frag.  images = (B, Hi, Wi, Ho, Wo, stride); m_count = device-side number of output rows.  a2d / out2d may be column slices of wider
+    matrices (row strides multiples of 4)."""
+    L.require_device(a2d, w_frag, out2d, m_count)
+    gw = int(group_width)
+    lib, C, B, Hi, Wi, Ho, Wo, stride = _grouped_mfma_images_args("grouped_mfma_conv3x3_images", a2d, w_frag, gw, out2d, images)
+    L.check(lib.ldn_grouped_mfma_conv3x3_images(L.ptr(_f32rows(a2d, "a")), a2d.stride(0), L.ptr(_i32c(m_count, "m_count")), B, Hi, Wi, Ho,
+                                                Wo, stride, L.ptr(w_frag), C, gw, L.ptr(_f32c(scale, "scale")),
+                                                L.ptr(_f32c(shift, "shift")), relu, L.ptr(_f32rows(out2d, "out")), out2d.stride(0),
+                                                L.stream_ptr()), "ldn_grouped_mfma_conv3x3_images")
+    return out2d
+
+
+def grouped_mfma_conv3x3_images_gap(a2d, w_frag, group_width, scale, shift, out2d, *, m_count, images, relu=1):
+    """grouped_mfma_conv3x3_images that also returns the channel sums of its output per kept image and band: gap [B, bands, C]
+    (ldn_grouped_mfma_conv3x3_images_gap) -- the squeeze of the SE block that follows conv b, without a second pass over h_b."""
+    L.require_device(a2d, w_frag, out2d, m_count)
+    gw = int(group_width)
+    lib, C, B, Hi, Wi, Ho, Wo, stride = _grouped_mfma_images_args("grouped_mfma_conv3x3_images_gap", a2d, w_frag, gw, out2d, images)
+    bands = grouped_mfma_images_bands(Hi, Wi, Ho, stride, C, gw)
+    if bands <= 0:
+        raise L.LdnError("grouped_mfma_conv3x3_images_gap: not a 3x3 / pad 1 / stride 1 or 2 geometry, or the map does not fit the LDS "
+                         "(grouped_mfma_images_fit)")
+    gap = torch.empty(B, bands, C, device=a2d.device, dtype=torch.float32)
+    L.check(lib.ldn_grouped_mfma_conv3x3_images_gap(L.ptr(_f32rows(a2d, "a")), a2d.stride(0), L.ptr(_i32c(m_count, "m_count")), B, Hi, Wi,
+                                                    Ho, Wo, stride, L.ptr(w_frag), C, gw, L.ptr(_f32c(scale, "scale")),
+                                                    L.ptr(_f32c(shift, "shift")), relu, L.ptr(_f32rows(out2d, "out")), out2d.stride(0),
+                                                    L.ptr(gap), L.stream_ptr()), "ldn_grouped_mfma_conv3x3_images_gap")
+    return gap
+
+
 def se_gate_slots(gap, m_count, rows_per_image, w1, b1, w2, b2):
     """SE gate of every kept image from the channel sums of grouped16_conv3x3_images_gap (ldn_se_gate_slots) -> gate [B, C]."""
     L.require_device(gap, m_count, w1)
