@@ -10,17 +10,17 @@
 //             an odd group count (13, 55) needs no tail rule and no column at or past C is ever addressed.
 // One 1024-thread workgroup = a chunk of groups (their pre-split weight fragments sit in LDS for the workgroup's lifetime: 28 KB per
 // width-24 group, 6 KB per width-8 group, <= 140 / 144 KB) x a strided set of row tiles, one tile per wave at a time.  A lane's loads run
-// GwCfg::PF steps ahead of the MFMAs that consume them, across the group boundary.
+// GgCfg::PF steps ahead of the MFMAs that consume them, across the group boundary.
 #include "ldn_common.h"
 
 namespace ldn {
 
-template <int GW> struct GwCfg;
-template <> struct GwCfg<8> {
+template <int GW> struct GgCfg;
+template <> struct GgCfg<8> {
     static constexpr int STEPS = 3, TILE = 16, MAXG = 24, PF = 3;
     typedef f32x4 acc_t;
 };
-template <> struct GwCfg<24> {
+template <> struct GgCfg<24> {
     static constexpr int STEPS = 14, TILE = 32, MAXG = 5, PF = 2;
     typedef f32x16 acc_t;
 };
@@ -40,7 +40,7 @@ __device__ __attribute__((aligned(16))) float g_gg_zero[8] = {0.f, 0.f, 0.f, 0.f
 
 template <int GW>
 __global__ __launch_bounds__(GG_THREADS, 1) void k_grouped_gw(const GgArgs p) {
-    typedef GwCfg<GW> cfg;
+    typedef GgCfg<GW> cfg;
     constexpr int STEPS = cfg::STEPS, TILE = cfg::TILE, PF = cfg::PF, FRAG = STEPS * 64 * 32;
     static_assert(STEPS % PF == 0, "the prefetch ring must close at the group boundary");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(GG_THREADS, 1) void k_grouped_gw(const GgArgs p) {
 
 template <int GW>
 static int launch_grouped_gw(GgArgs g, hipStream_t stream) {
-    typedef GwCfg<GW> cfg;
+    typedef GgCfg<GW> cfg;
     constexpr int FRAG = cfg::STEPS * 64 * 32;
     const int G = g.C / GW;
     const int tiles = ceil_div(g.m_cap, cfg::TILE);
@@ -177,7 +177,7 @@ constexpr int GWI_THREADS = 512;
 
 template <int GW>
 __global__ __launch_bounds__(GWI_THREADS, 2) void k_grouped_gw_img(const GwiArgs p) {
-    typedef GwCfg<GW> cfg;
+    typedef GgCfg<GW> cfg;
     constexpr int STEPS = cfg::STEPS, TILE = cfg::TILE, FRAG = STEPS * 64 * 32, NW = GWI_THREADS / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -303,8 +303,8 @@ __global__ __launch_bounds__(GWI_THREADS, 2) void k_grouped_gw_img(const GwiArgs
 
 // LDS bytes of one k_grouped_gw_img workgroup: ng groups' fragments, in_rows input rows (+ the zero pixel) and, with gap, the 16-pixel partial sums
 static size_t gwi_bytes(int gw, int ng, int in_rows, int out_rows, int Wi, int Wo, bool gap) {
-    const size_t frag = (size_t)(gw == 24 ? GwCfg<24>::STEPS : GwCfg<8>::STEPS) * 64 * 32;
-    const int tile = gw == 24 ? GwCfg<24>::TILE : GwCfg<8>::TILE;
+    const size_t frag = (size_t)(gw == 24 ? GgCfg<24>::STEPS : GgCfg<8>::STEPS) * 64 * 32;
+    const int tile = gw == 24 ? GgCfg<24>::TILE : GgCfg<8>::TILE;
     const size_t ntile = ((size_t)out_rows * Wo + tile - 1) / tile;
     return (size_t)ng * frag + ((size_t)in_rows * Wi + 1) * (size_t)(gw * ng + 4) * 4 + (gap ? (size_t)ng * ntile * (tile / 16) * gw * 4 : 0);
 }
@@ -318,7 +318,7 @@ static bool gwi_plan(int gw, int Hi, int Wi, int Ho, int stride, int G, int* ng_
     constexpr size_t ONE = 150 * 1024, TWO = 80 * 1024;
     if (Hi <= 0 || Wi <= 0 || Ho <= 0 || G <= 0 || Wi > (1 << 16)) return false;      // (three rows of a 2^16-wide map are far past the LDS)
     const int Wo = (Wi - 1) / stride + 1;
-    const int maxg = gw == 24 ? GwCfg<24>::MAXG : GwCfg<8>::MAXG, tile = gw == 24 ? GwCfg<24>::TILE : GwCfg<8>::TILE;
+    const int maxg = gw == 24 ? GgCfg<24>::MAXG : GgCfg<8>::MAXG, tile = gw == 24 ? GgCfg<24>::TILE : GgCfg<8>::TILE;
     if ((size_t)Hi * Wi < (1u << 20) && gwi_bytes(gw, 1, Hi, Ho, Wi, Wo, gap) <= ONE) {
         int ng = 1;
         while (ng < G && ng < maxg && gwi_bytes(gw, ng + 1, Hi, Ho, Wi, Wo, gap) <= TWO) ++ng;
@@ -345,7 +345,7 @@ static bool gwi_geometry(int Hi, int Wi, int Ho, int Wo, int stride) {
 
 template <int GW>
 static int launch_grouped_gw_img(GwiArgs g, hipStream_t stream) {
-    constexpr int FRAG = GwCfg<GW>::STEPS * 64 * 32;
+    constexpr int FRAG = GgCfg<GW>::STEPS * 64 * 32;
     const int G = g.C / GW;
     g.nbands = ceil_div(g.Ho, g.R);
     g.in_ld = GW * g.gchunk + 4;
@@ -371,7 +371,7 @@ extern "C" int ldn_grouped_mfma_ok(int C, int group_width) {
 
 extern "C" size_t ldn_grouped_mfma_weight_bytes(int C, int group_width) {
     if (!ldn_grouped_mfma_ok(C, group_width)) return 0;
-    return (size_t)(C / group_width) * (group_width == 24 ? GwCfg<24>::STEPS : GwCfg<8>::STEPS) * 64 * 32;
+    return (size_t)(C / group_width) * (group_width == 24 ? GgCfg<24>::STEPS : GgCfg<8>::STEPS) * 64 * 32;
 }
 
 extern "C" int ldn_grouped_mfma_conv3x3_rows(const float* a, int lda, const int32_t* nbr, const int32_t* m_count, int m_cap,

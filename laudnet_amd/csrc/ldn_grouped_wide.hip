@@ -22,12 +22,12 @@
 #include <algorithm>
 
 #include "ldn_common.h"
+#include "ldn_grouped_wide_frag.h"
 
 namespace ldn {
 
-template <int GW> struct GwCfg;
-template <> struct GwCfg<56> { static constexpr int MT = 2, NSTEP = 32, PIXB = 224; };      // 224 B a pixel: 8 consecutive pixels cover the 64 banks
-template <> struct GwCfg<112> { static constexpr int MT = 4, NSTEP = 63, PIXB = 480; };     // 448 + 32: the same bank walk (448 B would repeat after 4)
+// bytes of a staged pixel.  Width 56: 224, 8 consecutive pixels cover the 64 banks; width 112: 448 + 32, the same bank walk (448 B would repeat after 4)
+constexpr int gwd_pixb(int gw) { return gw == 56 ? 224 : 480; }
 constexpr int GWD_THREADS = 512;
 constexpr int GWD_PT = 4;                    // pixel tiles (of 32) a wave keeps accumulators for
 constexpr int GWD_MAXIMG = 8;                // images per workgroup
@@ -47,17 +47,13 @@ struct GwArgs {
     int tab_bytes;                          // the tables in front of the staged input
 };
 
-__host__ __device__ inline int gwd_mt(int gw) { return gw == 56 ? 2 : 4; }
-__host__ __device__ inline int gwd_nstep(int gw) { return gw == 56 ? 32 : 63; }
-__host__ __device__ inline int gwd_pixb(int gw) { return gw == 56 ? 224 : 480; }
-__host__ __device__ inline size_t gwd_group_bytes(int gw) { return (size_t)gwd_nstep(gw) * gwd_mt(gw) * 64 * 32; }
 __host__ __device__ inline int gwd_tab_bytes(int gw, int nimg) { return round_up((nimg * gw + 2 * GWD_MAXIMG + 4) * 4, 32); }   // map, active list, counts, n
 
 // The K loop of one wave over NPT resident pixel tiles: this lane's fragments of step s + 1 are in flight under the MFMAs of step s.
 template <int GW, int NPT>
 __device__ __forceinline__ void gw_kloop(const unsigned char* wbase, const unsigned char* s_in, const int (&pbase)[GWD_PT], int sw, int h,
                                          f32x16 (&acc)[GWD_PT]) {
-    constexpr int MT = GwCfg<GW>::MT, NSTEP = GwCfg<GW>::NSTEP, PIXB = GwCfg<GW>::PIXB, OCT = GW / 8;
+    constexpr int MT = GwCfg<GW>::MT, NSTEP = GwCfg<GW>::NSTEP, PIXB = gwd_pixb(GW), OCT = GW / 8;
     bf16x8 ah = *reinterpret_cast<const bf16x8*>(wbase), al = *reinterpret_cast<const bf16x8*>(wbase + 16);
 #pragma unroll 1
     for (int s = 0; s < NSTEP; ++s) {
@@ -91,7 +87,7 @@ __device__ __forceinline__ void gw_kloop(const unsigned char* wbase, const unsig
 template <int GW>
 __global__ __launch_bounds__(GWD_THREADS, 4) void k_grouped_wide(const GwArgs p) {
     typedef GwCfg<GW> cfg;
-    constexpr int MT = cfg::MT, NSTEP = cfg::NSTEP, PIXB = cfg::PIXB, OCT = GW / 8, NSET = 8 / MT, PT = GWD_PT, CAP = NSET * PT;
+    constexpr int MT = cfg::MT, NSTEP = cfg::NSTEP, PIXB = gwd_pixb(GW), OCT = GW / 8, NSET = 8 / MT, PT = GWD_PT, CAP = NSET * PT;
     extern __shared__ __attribute__((aligned(32))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -266,7 +262,7 @@ struct GwPlan { int nimg, R, Wc, nrb, ncb; size_t lds; };
 static size_t gwd_bytes(int gw, int nimg, long sp) { return (size_t)gwd_tab_bytes(gw, nimg) + (size_t)nimg * (size_t)sp * gwd_pixb(gw); }
 
 static double gwd_cost(int gw, int nimg, int R, int Wc, long sp, size_t lds) {
-    const int nset = 8 / gwd_mt(gw), cap = nset * GWD_PT;
+    const int nset = 8 / gw_frag_mt(gw), cap = nset * GWD_PT;
     const long outpx = (long)R * Wc;
     const long tiles = (long)nimg * ((outpx + 31) / 32);
     const long full = tiles / cap, last = tiles - full * cap;
@@ -322,40 +318,35 @@ LDN_DEFINE_TU_VIOLATIONS(tu_violations_grouped_wide)
 
 using namespace ldn;
 
-static bool gwd_shape_ok(int C, int gw, int Hi, int Wi, int stride) {
-    return (gw == 56 || gw == 112) && C > 0 && C % gw == 0 && (stride == 1 || stride == 2) && Hi > 0 && Wi > 0;
+// the shape check and the plan behind the four queries: false outside ldn_grouped_wide_ok
+static bool gwd_query(int C, int gw, int Hi, int Wi, int stride, GwPlan* pl) {
+    return gw_frag_width(gw) && C > 0 && C % gw == 0 && (stride == 1 || stride == 2) && Hi > 0 && Wi > 0 &&
+           gwd_plan(gw, Hi, Wi, (Hi - 1) / stride + 1, (Wi - 1) / stride + 1, stride, pl);
 }
 
 extern "C" int ldn_grouped_wide_ok(int C, int group_width, int Hi, int Wi, int stride) {
     GwPlan pl;
-    return (gwd_shape_ok(C, group_width, Hi, Wi, stride) &&
-            gwd_plan(group_width, Hi, Wi, (Hi - 1) / stride + 1, (Wi - 1) / stride + 1, stride, &pl)) ? 1 : 0;
+    return gwd_query(C, group_width, Hi, Wi, stride, &pl) ? 1 : 0;
 }
 
 extern "C" int ldn_grouped_wide_bands(int C, int group_width, int Hi, int Wi, int Ho, int stride) {
     GwPlan pl;
-    if (!gwd_shape_ok(C, group_width, Hi, Wi, stride) || Ho != (Hi - 1) / stride + 1) return 0;
-    if (!gwd_plan(group_width, Hi, Wi, Ho, (Wi - 1) / stride + 1, stride, &pl)) return 0;
-    return pl.nrb;
+    return stride > 0 && Ho == (Hi - 1) / stride + 1 && gwd_query(C, group_width, Hi, Wi, stride, &pl) ? pl.nrb : 0;
 }
 
 extern "C" int ldn_grouped_wide_images(int C, int group_width, int Hi, int Wi, int stride) {
     GwPlan pl;
-    if (!gwd_shape_ok(C, group_width, Hi, Wi, stride)) return 0;
-    if (!gwd_plan(group_width, Hi, Wi, (Hi - 1) / stride + 1, (Wi - 1) / stride + 1, stride, &pl)) return 0;
-    return pl.nimg;
+    return gwd_query(C, group_width, Hi, Wi, stride, &pl) ? pl.nimg : 0;
 }
 
 extern "C" int ldn_grouped_wide_strips(int C, int group_width, int Hi, int Wi, int stride) {
     GwPlan pl;
-    if (!gwd_shape_ok(C, group_width, Hi, Wi, stride)) return 0;
-    if (!gwd_plan(group_width, Hi, Wi, (Hi - 1) / stride + 1, (Wi - 1) / stride + 1, stride, &pl)) return 0;
-    return pl.ncb;
+    return gwd_query(C, group_width, Hi, Wi, stride, &pl) ? pl.ncb : 0;
 }
 
 extern "C" size_t ldn_grouped_wide_weight_bytes(int C, int group_width) {
-    if ((group_width != 56 && group_width != 112) || C <= 0 || C % group_width) return 0;
-    return (size_t)(C / group_width) * gwd_group_bytes(group_width);
+    if (!gw_frag_width(group_width) || C <= 0 || C % group_width) return 0;
+    return (size_t)(C / group_width) * gw_frag_bytes(group_width);
 }
 
 extern "C" int ldn_grouped_wide_conv3x3_image(const float* a, int lda, int B, int Hi, int Wi, int stride, int Ho, int Wo,

@@ -20,12 +20,10 @@
 #include <string.h>
 
 #include "ldn_common.h"
+#include "ldn_grouped_wide_frag.h"
 
 namespace ldn {
 
-template <int GW> struct GwrCfg;
-template <> struct GwrCfg<56> { static constexpr int MT = 2, NSTEP = 32; };
-template <> struct GwrCfg<112> { static constexpr int MT = 4, NSTEP = 63; };
 constexpr int GWR_THREADS = 256;             // 4 waves: one per SIMD
 constexpr int GWR_WAVES = GWR_THREADS / 64;
 
@@ -44,7 +42,7 @@ __device__ __attribute__((aligned(16))) float g_gwr_zero[8] = {0.f, 0.f, 0.f, 0.
 template <int GW, int RT, int CAP, int NPT>
 __device__ __forceinline__ void gwr_kloop(const unsigned char* wbase, const float* abase, int lda, const int (&row)[CAP][9], int h,
                                           f32x16 (&acc)[RT][CAP]) {
-    constexpr int MT = GwrCfg<GW>::MT, NSTEP = GwrCfg<GW>::NSTEP, OCT = GW / 8;
+    constexpr int MT = GwCfg<GW>::MT, NSTEP = GwCfg<GW>::NSTEP, OCT = GW / 8;
     auto request = [&](int s, f32x4 (&x0)[NPT], f32x4 (&x1)[NPT]) {
         const int q = 2 * s + h;
         const int t = q / OCT, oct = q - t * OCT;                                    // t = 9: octet 63 of width 56, zero weights
@@ -96,7 +94,7 @@ __device__ __forceinline__ void gwr_kloop(const unsigned char* wbase, const floa
 
 template <int GW, int RT, int NPT>
 __global__ __launch_bounds__(GWR_THREADS) void k_grouped_wide_rows(const GwrArgs p) {
-    typedef GwrCfg<GW> cfg;
+    typedef GwCfg<GW> cfg;
     constexpr int MT = cfg::MT, NSTEP = cfg::NSTEP, NRS = MT / RT;
     static_assert(MT % RT == 0, "wave roles");
     const int lane = threadIdx.x & 63;
@@ -165,7 +163,7 @@ __global__ __launch_bounds__(GWR_THREADS) void k_grouped_wide_rows(const GwrArgs
 
 template <int GW, int RT, int NPT>
 static int launch_grouped_wide_rows(const GwrArgs& g, hipStream_t stream) {
-    constexpr int NRS = GwrCfg<GW>::MT / RT;
+    constexpr int NRS = GwCfg<GW>::MT / RT;
     const int bx = (int)(((long)g.m_cap + 32 * GWR_WAVES * NPT - 1) / (32 * GWR_WAVES * NPT));
     const long by = (long)(g.C / GW) * NRS;
     LDN_REQUIRE(by <= 65535, "k_grouped_wide_rows<%d>: too many groups (%d channels)", GW, g.C);
@@ -190,7 +188,7 @@ static int gwr_tiles_per_wave(int C, int gw, int m_cap) {
 // per row tile).
 template <int GW>
 static int dispatch_grouped_wide_rows(const GwrArgs& g, hipStream_t stream) {
-    constexpr int MT = GwrCfg<GW>::MT;
+    constexpr int MT = GwCfg<GW>::MT;
     const char* form = getenv("LDN_GROUPED_WIDE_ROWS_FORM");
     if (form && !strcmp(form, "a")) return launch_grouped_wide_rows<GW, 1, 4>(g, stream);
     if (form && !strcmp(form, "b4")) return launch_grouped_wide_rows<GW, MT, 4>(g, stream);
@@ -203,7 +201,7 @@ static int dispatch_grouped_wide_rows(const GwrArgs& g, hipStream_t stream) {
 using namespace ldn;
 
 extern "C" int ldn_grouped_wide_rows_ok(int C, int group_width) {
-    return (group_width == 56 || group_width == 112) && C > 0 && C % group_width == 0 ? 1 : 0;
+    return gw_frag_width(group_width) && C > 0 && C % group_width == 0 ? 1 : 0;
 }
 
 extern "C" int ldn_grouped_wide_rows_tiles(int C, int group_width, int m_cap) {

@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import math
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import torch
 import torch.nn as nn
@@ -129,12 +129,11 @@ class BottleneckTransform(_PrepCache):
             p["wa"] = self.a[0].weight.detach().reshape(w_b, 1, -1).float().contiguous()
             p["sa"], p["ta"] = _fold_bn(self.a[1])
             p["wb"] = self.b[0].weight.detach().permute(0, 2, 3, 1).reshape(w_b, 9, gw).float().contiguous()
-            if gw == 16 and w_b % 16 == 0:      # matrix-core form of conv b (bf16x3 mode): weights pre-split in MFMA fragment order
-                p["wb_frag"] = ops.pack_grouped16_weights(p["wb"])
-            elif (USE_GROUPED_MFMA_WIDTHS or USE_GROUPED_MFMA_CHANNEL) and ops.grouped_mfma_ok(w_b, gw):      # ... and, behind their switches, the one for widths 8 and 24
-                p["wb_frag_gw"] = ops.pack_grouped_mfma_weights(p["wb"], gw)
-            if (USE_GROUPED_MFMA_WIDE or USE_GROUPED_MFMA_WIDE_ROWS) and gw in (56, 112) and w_b % gw == 0:       # ... and the streamed fragments of widths 56 and 112 (one copy for the image and the row form)
-                p["wb_frag_wide"] = ops.pack_grouped_wide_weights(p["wb"], gw)
+            # the matrix-core forms of conv b read weights pre-split in MFMA fragment order: packed here where the width's family has its 'rows' or
+            # 'image' switch on (width 16: always; one copy of wb_frag_wide serves both forms); _conv_b_frag packs the rest on first use
+            family = _WIDTH_FAMILY.get(gw)
+            if family is not None and w_b % gw == 0 and (_on(CONV_B[family].forms["rows"].switch) or _on(CONV_B[family].forms["image"].switch)):
+                _conv_b_frag(p, family, gw)
             p["sb"], p["tb"] = _fold_bn(self.b[1])
             p["wc"] = self.c[0].weight.detach().reshape(-1, 1, w_b).float().contiguous()
             p["wc_k"] = self.c[0].weight.detach().reshape(-1, w_b).float().t().reshape(1, w_b, -1).contiguous()   # k-major (channel mode)
@@ -148,100 +147,163 @@ class BottleneckTransform(_PrepCache):
         return self._prep
 
 
-def _conv_b_rows(p, f, h_a, nbr, h_b, m_count, m_cap, images=None):
-    """conv b (grouped 3x3 + BN + ReLU) over packed rows: on the matrix cores for group width 16 in bf16x3 mode (and behind their switches
-    for widths 8 / 24 and 56 / 112), else the fp32 VALU kernel.  images = (B, Hi, Wi, Ho, Wo, stride) when the rows are whole images in
-    order (layer skip, dense index): maps that fit the LDS are staged there once per (image, group chunk) instead of being read once per
-    tap through the neighbour table (width 16; widths 8 / 24 with LDN_GROUPED_MFMA_WIDTHS_IMAGES=1)."""
-    if "wb_frag" in p and ops.get_math_mode() == "bf16x3" and USE_GROUPED_MFMA:
-        if (images is not None and m_count is not None and USE_GROUPED_IMAGES
-                and ops.grouped16_images_fit(images[1], images[2], h_b.shape[1]) > 0):
-            ops.grouped16_conv3x3_images(h_a, p["wb_frag"], p["sb"], p["tb"], h_b, m_count=m_count, images=images, relu=1)
-        else:
-            ops.grouped16_conv3x3_rows(h_a, nbr, p["wb_frag"], p["sb"], p["tb"], h_b, m_count=m_count, m_cap=m_cap, relu=1)
-    elif grouped_mfma_widths_on(h_b.shape[1], f.group_width):
-        # widths 8 and 24 (LDN_GROUPED_MFMA_WIDTHS=1): the neighbour-table form, or with LDN_GROUPED_MFMA_WIDTHS_IMAGES=1 the LDS-staged image form
-        # on whole images in order (the same fragments, the same bits)
-        if "wb_frag_gw" not in p:           # (prepared before the switch was turned on)
-            p["wb_frag_gw"] = ops.pack_grouped_mfma_weights(p["wb"], f.group_width)
-        if images is not None and m_count is not None and grouped_mfma_images_on(h_b.shape[1], f.group_width, images[1], images[2], images[5]):
-            ops.grouped_mfma_conv3x3_images(h_a, p["wb_frag_gw"], f.group_width, p["sb"], p["tb"], h_b, m_count=m_count, images=images, relu=1)
-        else:
-            ops.grouped_mfma_conv3x3_rows(h_a, nbr, p["wb_frag_gw"], f.group_width, p["sb"], p["tb"], h_b, m_count=m_count, m_cap=m_cap, relu=1)
-    elif grouped_wide_rows_on(h_b.shape[1], f.group_width):
-        # widths 56 and 112 (LDN_GROUPED_MFMA_WIDE_ROWS=1): the fragments of the channel-mode image kernel, streamed over the packed rows
-        if "wb_frag_wide" not in p:         # (prepared before the switch was turned on)
-            p["wb_frag_wide"] = ops.pack_grouped_wide_weights(p["wb"], f.group_width)
-        ops.grouped_wide_conv3x3_rows(h_a, nbr, p["wb_frag_wide"], f.group_width, p["sb"], p["tb"], h_b, m_count=m_count, m_cap=m_cap, relu=1)
-    else:
-        ops.grouped_conv3x3_rows(h_a, nbr, p["wb"], f.group_width, p["sb"], p["tb"], h_b, m_count=m_count, m_cap=m_cap, relu=1)
-
-
-USE_GROUPED_MFMA = os.environ.get("LDN_GROUPED_MFMA", "1") != "0"    # tuning switch (A/B)
-USE_GROUPED_IMAGES = os.environ.get("LDN_GROUPED_IMAGES", "1") != "0"   # ... the whole-image form of it
+# ------------------------------------------------------------------------------------------------ conv b: one table, one chooser
+# Tuning switches (A/B); each is read at call time, so a test or a tool may set it on the module.
+USE_GROUPED_MFMA = os.environ.get("LDN_GROUPED_MFMA", "1") != "0"    # the matrix-core forms of conv b at all (bf16x3 mode)
+USE_GROUPED_IMAGES = os.environ.get("LDN_GROUPED_IMAGES", "1") != "0"   # ... the whole-image form of width 16
 USE_GROUPED_MFMA_WIDTHS = os.environ.get("LDN_GROUPED_MFMA_WIDTHS", "0") == "1"   # ... group widths 8 and 24 on the matrix cores (OFF by default)
+USE_GROUPED_MFMA_WIDTHS_IMAGES = os.environ.get("LDN_GROUPED_MFMA_WIDTHS_IMAGES", "0") == "1"   # ... and their whole-image / SE-fused form (OFF by default)
+USE_GROUPED_MFMA_CHANNEL = os.environ.get("LDN_GROUPED_MFMA_CHANNEL", "0") == "1"   # ... conv b of channel / both mode on the matrix cores (OFF by default)
+USE_GROUPED_MFMA_WIDE = os.environ.get("LDN_GROUPED_MFMA_WIDE", "0") == "1"   # ... and at group widths 56 and 112 (OFF by default)
+USE_GROUPED_MFMA_WIDE_ROWS = os.environ.get("LDN_GROUPED_MFMA_WIDE_ROWS", "0") == "1"   # ... and their packed-row form: layer skip, 'spatial', training (OFF by default)
+USE_SE_FUSED = os.environ.get("LDN_SE_FUSED", "1") != "0"               # ... the SE block folded into conv b's epilogue and conv c's input rows
+
+# The families of conv b (grouped 3x3 + BN + ReLU).  Everything but the widths is a NAME, of ops or of a switch above, resolved at call time.
+# A form: 'rows' = packed rows through the neighbour table, 'images' = packed rows that are whole images in order (the map staged in the LDS),
+# 'images_gap' = that with the SE squeeze in its epilogue, 'image' = the per-image active channel lists of a dense image (channel mode, 'both');
+# it runs behind its switch (None: none) where its host-arithmetic fit query (None: none) says yes.
+ConvBForm = namedtuple("ConvBForm", "op switch fit")
+ConvBFamily = namedtuple("ConvBFamily", "key packer widths forms")      # key: the weights' key in the prepared dict
+CONV_B = {
+    "valu": ConvBFamily("wb", None, (), {"rows": ConvBForm("grouped_conv3x3_rows", None, None), "image": ConvBForm("grouped_conv3x3_image", None, None)}),
+    "g16": ConvBFamily("wb_frag", "pack_grouped16_weights", (16,), {
+        "rows": ConvBForm("grouped16_conv3x3_rows", None, None),
+        "images": ConvBForm("grouped16_conv3x3_images", "USE_GROUPED_IMAGES", "grouped16_images_fit"),
+        "images_gap": ConvBForm("grouped16_conv3x3_images_gap", "USE_SE_FUSED", "conv_rows_gated_fits"),
+        "image": ConvBForm("grouped_chan_mfma_conv3x3_image", "USE_GROUPED_MFMA_CHANNEL", "grouped_chan_mfma_ok")}),
+    "gw": ConvBFamily("wb_frag_gw", "pack_grouped_mfma_weights", (8, 24), {
+        "rows": ConvBForm("grouped_mfma_conv3x3_rows", "USE_GROUPED_MFMA_WIDTHS", None),
+        "images": ConvBForm("grouped_mfma_conv3x3_images", "USE_GROUPED_MFMA_WIDTHS_IMAGES", "grouped_mfma_images_fit"),
+        "images_gap": ConvBForm("grouped_mfma_conv3x3_images_gap", "USE_SE_FUSED", "conv_rows_gated_fits"),
+        "image": ConvBForm("grouped_chan_mfma_conv3x3_image", "USE_GROUPED_MFMA_CHANNEL", "grouped_chan_mfma_ok")}),
+    "wide": ConvBFamily("wb_frag_wide", "pack_grouped_wide_weights", (56, 112), {
+        "rows": ConvBForm("grouped_wide_conv3x3_rows", "USE_GROUPED_MFMA_WIDE_ROWS", None),
+        "image": ConvBForm("grouped_wide_conv3x3_image", "USE_GROUPED_MFMA_WIDE", "grouped_wide_ok")}),
+}
+_WIDTH_FAMILY = {gw: name for name, fam in CONV_B.items() for gw in fam.widths}
 
 
+_SWITCHES = globals()        # a switch is looked up by its name at call time
+
+
+def _on(switch):
+    return switch is None or _SWITCHES[switch]
+
+
+def _mfma_mode():
+    """what every matrix-core family of conv b needs"""
+    return USE_GROUPED_MFMA and ops.get_math_mode() == "bf16x3"
+
+
+def conv_b_choice(layout, C, gw, *, images=None, have_count=True, se_fused=False, families=None):
+    """-> (family, form) of CONV_B that conv b of C channels in groups of gw runs on.  layout 'rows': packed rows; images = (B, Hi, Wi, Ho, Wo,
+    stride) when they are whole images in order, have_count = a device-side row count comes with them, se_fused = the caller can take the SE
+    squeeze from conv b's epilogue.  layout 'image': the channel lists of the dense images.  families: the matrix-core families the caller may
+    use (None: all).  The family is the one built for the width (C a positive multiple of it), with USE_GROUPED_MFMA and bf16x3 mode, behind the
+    switch and fit query of its 'rows' / 'image' form; whole images go to 'images' behind that form's (widths 8 / 24: at stride 1 or 2) and to
+    'images_gap' behind that one's; everything else is the fp32 VALU kernel.  Cheap questions first: this runs once per block and forward."""
+    name = _WIDTH_FAMILY.get(gw)
+    if name is None or C <= 0 or C % gw or (families is not None and name not in families):
+        return "valu", "image" if layout == "image" else "rows"
+    forms = CONV_B[name].forms
+    if layout == "image":
+        f = forms["image"]
+        ok = _on(f.switch) and _mfma_mode() and getattr(ops, f.fit)(C, gw, images[1], images[2], images[5])
+        return (name if ok else "valu"), "image"
+    switch = forms["rows"].switch
+    if (switch is not None and not _SWITCHES[switch]) or not _mfma_mode():
+        return "valu", "rows"
+    f = forms.get("images")
+    if f is None or images is None or not have_count or not _on(f.switch):
+        return name, "rows"
+    _, Hi, Wi, Ho, Wo, stride = images
+    if (name != "g16" and stride not in (1, 2)) or getattr(ops, f.fit)(Hi, Wi, C, *_gw_arg(name, gw)) <= 0:
+        return name, "rows"
+    f = forms["images_gap"]
+    return name, "images_gap" if se_fused and _on(f.switch) and getattr(ops, f.fit)(C, Ho * Wo) else "images"
+
+
+# the switch-by-switch questions of tests and tools: views of the chooser
 def grouped_mfma_widths_on(C, gw):
     """whether conv b of C channels in groups of gw runs on ldn_grouped_mfma_conv3x3_rows: its switch, USE_GROUPED_MFMA, bf16x3 mode and the shape"""
-    return bool(USE_GROUPED_MFMA_WIDTHS and USE_GROUPED_MFMA and ops.get_math_mode() == "bf16x3" and ops.grouped_mfma_ok(C, gw))
-
-
-USE_GROUPED_MFMA_WIDTHS_IMAGES = os.environ.get("LDN_GROUPED_MFMA_WIDTHS_IMAGES", "0") == "1"   # ... and their whole-image / SE-fused form (OFF by default)
+    return conv_b_choice("rows", C, gw)[0] == "gw"
 
 
 def grouped_mfma_images_on(C, gw, Hi, Wi, stride):
     """whether conv b of C channels in groups of gw over whole images in order runs on ldn_grouped_mfma_conv3x3_images: its switch, everything
     grouped_mfma_widths_on asks for, and a map that fits the LDS"""
-    return bool(USE_GROUPED_MFMA_WIDTHS_IMAGES and stride in (1, 2) and grouped_mfma_widths_on(C, gw)
-                and ops.grouped_mfma_images_fit(Hi, Wi, C, gw) > 0)
-
-
-USE_GROUPED_MFMA_CHANNEL = os.environ.get("LDN_GROUPED_MFMA_CHANNEL", "0") == "1"   # ... conv b of channel / both mode on the matrix cores (OFF by default)
+    return conv_b_choice("rows", C, gw, images=(1, Hi, Wi, 0, 0, stride)) == ("gw", "images")
 
 
 def grouped_chan_mfma_on(C, gw, Hi, Wi, stride):
     """whether conv b of a channel / both block runs on ldn_grouped_chan_mfma_conv3x3_image: its switch, USE_GROUPED_MFMA, bf16x3 mode and the shape"""
-    return bool(USE_GROUPED_MFMA_CHANNEL and USE_GROUPED_MFMA and ops.get_math_mode() == "bf16x3"
-                and ops.grouped_chan_mfma_ok(C, gw, Hi, Wi, stride))
-
-
-USE_GROUPED_MFMA_WIDE = os.environ.get("LDN_GROUPED_MFMA_WIDE", "0") == "1"   # ... and at group widths 56 and 112 (OFF by default)
+    return conv_b_choice("image", C, gw, images=(1, Hi, Wi, 0, 0, stride))[0] in ("g16", "gw")
 
 
 def grouped_wide_on(C, gw, Hi, Wi, stride):
     """whether conv b of a channel / both block runs on ldn_grouped_wide_conv3x3_image: its switch, USE_GROUPED_MFMA, bf16x3 mode and the shape"""
-    return bool(USE_GROUPED_MFMA_WIDE and USE_GROUPED_MFMA and ops.get_math_mode() == "bf16x3"
-                and ops.grouped_wide_ok(C, gw, Hi, Wi, stride))
-
-
-USE_GROUPED_MFMA_WIDE_ROWS = os.environ.get("LDN_GROUPED_MFMA_WIDE_ROWS", "0") == "1"   # ... and their packed-row form: layer skip, 'spatial', training (OFF by default)
+    return conv_b_choice("image", C, gw, images=(1, Hi, Wi, 0, 0, stride))[0] == "wide"
 
 
 def grouped_wide_rows_on(C, gw):
     """whether conv b of C channels in groups of gw over packed rows runs on ldn_grouped_wide_conv3x3_rows: its switch, USE_GROUPED_MFMA, bf16x3 mode and the shape"""
-    return bool(USE_GROUPED_MFMA_WIDE_ROWS and USE_GROUPED_MFMA and ops.get_math_mode() == "bf16x3" and ops.grouped_wide_rows_ok(C, gw))
+    return conv_b_choice("rows", C, gw)[0] == "wide"
+
+
+def _gw_arg(family, gw):
+    """(the width-16 packer, fit query and row / image-list entry points take no group width)"""
+    return () if family == "g16" else (gw,)
+
+
+def _conv_b_frag(p, family, gw):
+    """the weights the family reads: p["wb"] for the VALU kernel, else its fragments, packed from p["wb"] where p does not hold them yet
+    (prepared before the switch was turned on)"""
+    fam = CONV_B[family]
+    if fam.key not in p:
+        p[fam.key] = getattr(ops, fam.packer)(p["wb"], *_gw_arg(family, gw))
+    return p[fam.key]
+
+
+def _conv_b_run(choice, p, gw, h_a, nbr, h_b, m_count, m_cap, images, relu=1):
+    """conv b over packed rows on the chosen (family, form) -> what the entry point returns (h_b; the channel sums from 'images_gap')"""
+    family, form = choice
+    fam = CONV_B[family]
+    w = p[fam.key] if fam.key in p else _conv_b_frag(p, family, gw)
+    op = getattr(ops, fam.forms[form].op)
+    # (the width-16 entry points take no group width; spelled out, because a starred argument list costs this host-bound path 0.3 us a call)
+    if form == "rows":
+        if family == "g16":
+            return op(h_a, nbr, w, p["sb"], p["tb"], h_b, m_count=m_count, m_cap=m_cap, relu=relu)
+        return op(h_a, nbr, w, gw, p["sb"], p["tb"], h_b, m_count=m_count, m_cap=m_cap, relu=relu)
+    if family == "g16":
+        return op(h_a, w, p["sb"], p["tb"], h_b, m_count=m_count, images=images, relu=relu)
+    return op(h_a, w, gw, p["sb"], p["tb"], h_b, m_count=m_count, images=images, relu=relu)
+
+
+def _conv_b_rows(p, f, h_a, nbr, h_b, m_count, m_cap, images=None):
+    """conv b (grouped 3x3 + BN + ReLU) over packed rows, on the kernel conv_b_choice names.  images = (B, Hi, Wi, Ho, Wo, stride) when the rows
+    are whole images in order (layer skip, dense index)."""
+    choice = conv_b_choice("rows", h_b.shape[1], f.group_width, images=images, have_count=m_count is not None)
+    _conv_b_run(choice, p, f.group_width, h_a, nbr, h_b, m_count, m_cap, images)
+
+
+def _conv_b_rows_se(p, f, h_a, nbr, h_b, m_count, m_cap, images):
+    """_conv_b_rows for a caller that can fold the SE block into its neighbours (whole kept images in order): where the chooser takes the fold,
+    conv b leaves the channel sums of its output and the SE head turns them into a gate per kept image, which conv c multiplies into its input
+    rows in flight -- three launches instead of six.  -> that gate [B, C], or None: h_b is plain conv b output and SE is still to run."""
+    choice = conv_b_choice("rows", h_b.shape[1], f.group_width, images=images, have_count=m_count is not None, se_fused=True)
+    gap = _conv_b_run(choice, p, f.group_width, h_a, nbr, h_b, m_count, m_cap, images)
+    if choice[1] != "images_gap":
+        return None
+    return ops.se_gate_slots(gap, m_count, images[3] * images[4], p["se_w1"], p["se_b1"], p["se_w2"], p["se_b2"])
 
 
 def _conv_b_image(p, f, h_a, idx, cnt, h_b, stride):
-    """conv b (grouped 3x3 + BN + ReLU) on the per-image active channels of a dense image (channel mode, and 'both'): on the matrix cores
-    for group widths 8 / 16 / 24 in bf16x3 mode with LDN_GROUPED_MFMA_CHANNEL=1 and for widths 56 / 112 with LDN_GROUPED_MFMA_WIDE=1, else
-    the fp32 VALU kernel."""
+    """conv b (grouped 3x3 + BN + ReLU) on the per-image active channels of a dense image (channel mode, and 'both'), on the kernel
+    conv_b_choice names"""
     gw = f.group_width
-    if grouped_chan_mfma_on(h_b.shape[3], gw, h_a.shape[1], h_a.shape[2], stride):
-        key = "wb_frag" if gw == 16 else "wb_frag_gw"
-        if key not in p:                    # (prepared before the switch was turned on)
-            p[key] = ops.pack_grouped16_weights(p["wb"]) if gw == 16 else ops.pack_grouped_mfma_weights(p["wb"], gw)
-        ops.grouped_chan_mfma_conv3x3_image(h_a, p[key], gw, idx, cnt, p["sb"], p["tb"], h_b, stride=stride, relu=1)
-    elif grouped_wide_on(h_b.shape[3], gw, h_a.shape[1], h_a.shape[2], stride):
-        if "wb_frag_wide" not in p:         # (prepared before the switch was turned on)
-            p["wb_frag_wide"] = ops.pack_grouped_wide_weights(p["wb"], gw)
-        ops.grouped_wide_conv3x3_image(h_a, p["wb_frag_wide"], gw, idx, cnt, p["sb"], p["tb"], h_b, stride=stride, relu=1)
-    else:
-        ops.grouped_conv3x3_image(h_a, p["wb"], gw, idx, cnt, p["sb"], p["tb"], h_b, stride=stride, relu=1)
-
-
-USE_SE_FUSED = os.environ.get("LDN_SE_FUSED", "1") != "0"               # ... the SE block folded into conv b's epilogue and conv c's input rows
+    family, form = conv_b_choice("image", h_b.shape[3], gw, images=(h_a.shape[0], h_a.shape[1], h_a.shape[2], h_b.shape[1], h_b.shape[2], stride))
+    getattr(ops, CONV_B[family].forms[form].op)(h_a, _conv_b_frag(p, family, gw), gw, idx, cnt, p["sb"], p["tb"], h_b, stride=stride, relu=1)
 
 
 class ResBottleneckBlock(_PrepCache):
@@ -327,24 +389,8 @@ class ResBottleneckBlock(_PrepCache):
         h_a = torch.empty(ix.cap1, w_b, device=dev, dtype=torch.float32)
         ops.conv_rows(x2d, p["wa"], p["sa"], p["ta"], h_a, a_rows=ix.idx1, taps=1, m_count=ix.cnt[1:2], m_cap=ix.cap1, rows_hint=n1)
         h_b = torch.empty(ix.cap3, w_b, device=dev, dtype=torch.float32)
-        # the SE block folded into its neighbours (whole kept images in order): conv b leaves the channel sums of its output, the SE head
-        # turns them into a gate per kept image, conv c multiplies its input rows by it in flight -- three launches instead of six
-        gate = None
-        if (USE_SE_FUSED and "wb_frag" in p and ops.get_math_mode() == "bf16x3" and USE_GROUPED_MFMA and USE_GROUPED_IMAGES
-                and ops.conv_rows_gated_fits(w_b, Ho * Wo) and ops.grouped16_images_fit(Hi, Wi, w_b) > 0):
-            gap = ops.grouped16_conv3x3_images_gap(h_a, p["wb_frag"], p["sb"], p["tb"], h_b, m_count=ix.cnt[0:1],
-                                                   images=(B, Hi, Wi, Ho, Wo, self.stride), relu=1)
-            gate = ops.se_gate_slots(gap, ix.cnt[0:1], Ho * Wo, p["se_w1"], p["se_b1"], p["se_w2"], p["se_b2"])
-        elif (USE_SE_FUSED and ops.conv_rows_gated_fits(w_b, Ho * Wo)
-                and grouped_mfma_images_on(w_b, f.group_width, Hi, Wi, self.stride)):
-            # ... the same fold at group widths 8 and 24 (LDN_GROUPED_MFMA_WIDTHS=1 and LDN_GROUPED_MFMA_WIDTHS_IMAGES=1)
-            if "wb_frag_gw" not in p:           # (prepared before the switch was turned on)
-                p["wb_frag_gw"] = ops.pack_grouped_mfma_weights(p["wb"], f.group_width)
-            gap = ops.grouped_mfma_conv3x3_images_gap(h_a, p["wb_frag_gw"], f.group_width, p["sb"], p["tb"], h_b, m_count=ix.cnt[0:1],
-                                                      images=(B, Hi, Wi, Ho, Wo, self.stride), relu=1)
-            gate = ops.se_gate_slots(gap, ix.cnt[0:1], Ho * Wo, p["se_w1"], p["se_b1"], p["se_w2"], p["se_b2"])
-        else:
-            _conv_b_rows(p, f, h_a, ix.nbr, h_b, ix.cnt[0:1], ix.cap3, images=(B, Hi, Wi, Ho, Wo, self.stride))
+        gate = _conv_b_rows_se(p, f, h_a, ix.nbr, h_b, ix.cnt[0:1], ix.cap3, (B, Hi, Wi, Ho, Wo, self.stride))
+        if gate is None:
             ops.se_packed(h_b, ix.pre3, p["se_w1"], p["se_b1"], p["se_w2"], p["se_b2"], Ho * Wo)
         cout = p["wc"].shape[0]
         if self.proj is not None:

@@ -6,6 +6,7 @@ import contextlib
 import os
 import threading
 import weakref
+from collections import namedtuple
 from dataclasses import dataclass
 
 import torch
@@ -1067,18 +1068,73 @@ def conv_packed(a2d, w, scale, shift, out2d, *, B=1, row_prefix=None, m_count=No
 
 
 # ---------------------------------------------------------------------------------------- a9 (LAD-RegNet, layer skip)
+# The grouped 3x3 (conv b of LAD-RegNet): the fragment families of its matrix-core kernels and the three argument shapes of its entry points (packed
+# rows, per-image channel lists, whole images).  `built` is the "(...)" of the refusal of another width; `geometry` = per width (K steps, row tiles of
+# 32 out channels) of k_grouped_wide, which its packer needs.
+_Frag = namedtuple("_Frag", "widths weight_bytes packer built geometry")
+_FRAG = {"g16": _Frag((16,), "ldn_grouped16_weight_bytes", "pack_grouped16_weights", "16", None),
+         "gw": _Frag((8, 24), "ldn_grouped_mfma_weight_bytes", "pack_grouped_mfma_weights", "8 and 24; width 16 is {twin}", None),
+         "wide": _Frag((56, 112), "ldn_grouped_wide_weight_bytes", "pack_grouped_wide_weights", "56 and 112", {56: (32, 2), 112: (63, 4)})}
+
+
+def _check_frag(name, w_frag, family, gw):
+    """w_frag is the packed tensor of the family at group width gw -> C"""
+    f = _FRAG[family]
+    if gw not in f.widths:
+        raise L.LdnError(f"{name}: group width {gw} is not built ({f.built.format(twin=name.replace('grouped_mfma_', 'grouped16_'))})")
+    C = w_frag.shape[0] * gw
+    want = getattr(L.load(), f.weight_bytes)(*((C,) if family == "g16" else (C, gw)))
+    if w_frag.dtype != torch.bfloat16 or not w_frag.is_contiguous() or C == 0 or w_frag.numel() * 2 != want:
+        raise L.LdnError(f"{name}: w_frag must be the contiguous bf16 tensor of {f.packer} for this group width")
+    return C
+
+
+def _grouped_rows(entry, f32, a2d, nbr, w, C, gw_arg, scale, shift, out2d, m_count, m_cap, relu):
+    """(a, lda, nbr, m_count, m_cap, w, C[, gw], scale, shift, relu, out, ldo, stream); f32 = _f32c, or _f32rows where a / out may be column slices"""
+    L.require_device(a2d, nbr, w, out2d)
+    m_cap = out2d.shape[0] if m_cap is None else m_cap
+    L.check(getattr(L.load(), entry)(L.ptr(f32(a2d, "a")), a2d.stride(0), L.ptr(_i32c(nbr, "nbr")), L.ptr(_i32c(m_count, "m_count")), m_cap,
+                                     L.ptr(w), C, *gw_arg, L.ptr(_f32c(scale, "scale")), L.ptr(_f32c(shift, "shift")), relu,
+                                     L.ptr(f32(out2d, "out")), out2d.stride(0), L.stream_ptr()), entry)
+    return out2d
+
+
+def _grouped_images(entry, f32, a2d, w_frag, C, gw_arg, scale, shift, out2d, m_count, images, relu, gap=None):
+    """(a, lda, m_count, B, Hi, Wi, Ho, Wo, stride, w, C[, gw], scale, shift, relu, out, ldo[, gap], stream); gap = (the bands query, its refusal) of
+    the _gap form, which returns the channel sums [B, bands, C] instead of out"""
+    L.require_device(a2d, w_frag, out2d, m_count)
+    lib, name = L.load(), entry[4:]
+    B, Hi, Wi, Ho, Wo, stride = (int(v) for v in images)
+    if a2d.shape[0] < B * Hi * Wi or out2d.shape[0] < B * Ho * Wo or (f32 is _f32rows and (a2d.shape[1] != C or out2d.shape[1] != C)):
+        raise L.LdnError(f"{name}: a / out must hold B whole images of C channels")
+    sums = ()
+    if gap is not None:
+        bands = getattr(lib, gap[0])(Hi, Wi, Ho, stride, C, *gw_arg)
+        if bands <= 0:
+            raise L.LdnError(f"{name}: {gap[1]}")
+        sums = (torch.empty(B, bands, C, device=a2d.device, dtype=torch.float32),)
+    L.check(getattr(lib, entry)(L.ptr(f32(a2d, "a")), a2d.stride(0), L.ptr(_i32c(m_count, "m_count")), B, Hi, Wi, Ho, Wo, stride, L.ptr(w_frag), C,
+                                *gw_arg, L.ptr(_f32c(scale, "scale")), L.ptr(_f32c(shift, "shift")), relu, L.ptr(f32(out2d, "out")),
+                                out2d.stride(0), *(L.ptr(t) for t in sums), L.stream_ptr()), entry)
+    return sums[0] if sums else out2d
+
+
+def _grouped_image(entry, a_nhwc, w, C, gw, ch_idx, ch_cnt, scale, shift, out_nhwc, stride, relu):
+    """(a, lda, B, Hi, Wi, stride, Ho, Wo, w, C, gw, ch_idx, ch_cnt, scale, shift, relu, out, ldo, stream)"""
+    L.require_device(a_nhwc, w, out_nhwc, ch_idx)
+    if a_nhwc.dim() != 4 or out_nhwc.dim() != 4:
+        raise L.LdnError(f"{entry[4:]}: a and out must be [B, H, W, columns]")
+    B, Hi, Wi, lda = a_nhwc.shape
+    _, Ho, Wo, ldo = out_nhwc.shape
+    L.check(getattr(L.load(), entry)(L.ptr(_f32c(a_nhwc, "a")), lda, B, Hi, Wi, stride, Ho, Wo, L.ptr(w), C, gw, L.ptr(_i32c(ch_idx, "ch_idx")),
+                                     L.ptr(_i32c(ch_cnt, "ch_cnt")), L.ptr(_f32c(scale, "scale")), L.ptr(_f32c(shift, "shift")), relu,
+                                     L.ptr(_f32c(out_nhwc, "out")), ldo, L.stream_ptr(out_nhwc)), entry)
+    return out_nhwc
+
+
 def grouped_conv3x3_rows(a2d, nbr, w, group_width, scale, shift, out2d, *, m_count=None, m_cap=None, relu=1):
     """Grouped 3x3 conv + BN (+ReLU) over packed rows (see ldn_grouped_conv3x3_rows).  w [C,9,gw]."""
-    L.require_device(a2d, nbr, w, out2d)
-    lib = L.load()
-    C = w.shape[0]
-    m_cap = out2d.shape[0] if m_cap is None else m_cap
-    L.check(lib.ldn_grouped_conv3x3_rows(L.ptr(_f32c(a2d, "a")), a2d.stride(0), L.ptr(_i32c(nbr, "nbr")),
-                                         L.ptr(_i32c(m_count, "m_count")), m_cap, L.ptr(_f32c(w, "w")), C, group_width,
-                                         L.ptr(_f32c(scale, "scale")), L.ptr(_f32c(shift, "shift")), relu,
-                                         L.ptr(_f32c(out2d, "out")), out2d.stride(0), L.stream_ptr()),
-            "ldn_grouped_conv3x3_rows")
-    return out2d
+    return _grouped_rows("ldn_grouped_conv3x3_rows", _f32c, a2d, nbr, _f32c(w, "w"), w.shape[0], (group_width,), scale, shift, out2d, m_count, m_cap, relu)
 
 
 def pack_grouped16_weights(w):
@@ -1097,17 +1153,8 @@ def pack_grouped16_weights(w):
 
 def grouped16_conv3x3_rows(a2d, nbr, w_frag, scale, shift, out2d, *, m_count=None, m_cap=None, relu=1):
     """Grouped 3x3 conv (group width 16) + BN (+ReLU) over packed rows on the matrix cores (see ldn_grouped16_conv3x3_rows)."""
-    L.require_device(a2d, nbr, w_frag, out2d)
-    lib = L.load()
-    C = w_frag.shape[0] * 16
-    if w_frag.dtype != torch.bfloat16 or not w_frag.is_contiguous() or w_frag.numel() * 2 != lib.ldn_grouped16_weight_bytes(C):
-        raise L.LdnError("grouped16_conv3x3_rows: w_frag must be the contiguous bf16 tensor of pack_grouped16_weights")
-    m_cap = out2d.shape[0] if m_cap is None else m_cap
-    L.check(lib.ldn_grouped16_conv3x3_rows(L.ptr(_f32c(a2d, "a")), a2d.stride(0), L.ptr(_i32c(nbr, "nbr")),
-                                           L.ptr(_i32c(m_count, "m_count")), m_cap, L.ptr(w_frag), C, L.ptr(_f32c(scale, "scale")),
-                                           L.ptr(_f32c(shift, "shift")), relu, L.ptr(_f32c(out2d, "out")), out2d.stride(0),
-                                           L.stream_ptr()), "ldn_grouped16_conv3x3_rows")
-    return out2d
+    C = _check_frag("grouped16_conv3x3_rows", w_frag, "g16", 16)
+    return _grouped_rows("ldn_grouped16_conv3x3_rows", _f32c, a2d, nbr, w_frag, C, (), scale, shift, out2d, m_count, m_cap, relu)
 
 
 def grouped_mfma_ok(C, group_width):
@@ -1136,22 +1183,9 @@ def pack_grouped_mfma_weights(w, group_width):
 def grouped_mfma_conv3x3_rows(a2d, nbr, w_frag, group_width, scale, shift, out2d, *, m_count=None, m_cap=None, relu=1):
     """Grouped 3x3 conv (group width 8 or 24) + BN (+ReLU) over packed rows on the matrix cores (see ldn_grouped_mfma_conv3x3_rows).
     a2d / out2d may be column slices of wider matrices (row strides multiples of 4): the columns past C are neither read nor written."""
-    L.require_device(a2d, nbr, w_frag, out2d)
-    lib = L.load()
     gw = int(group_width)
-    if gw not in (8, 24):
-        raise L.LdnError(f"grouped_mfma_conv3x3_rows: group width {gw} is not built (8 and 24; width 16 is grouped16_conv3x3_rows)")
-    C = w_frag.shape[0] * gw
-    if (w_frag.dtype != torch.bfloat16 or not w_frag.is_contiguous() or C == 0
-            or w_frag.numel() * 2 != lib.ldn_grouped_mfma_weight_bytes(C, gw)):
-        raise L.LdnError("grouped_mfma_conv3x3_rows: w_frag must be the contiguous bf16 tensor of pack_grouped_mfma_weights for this group width")
-    m_cap = out2d.shape[0] if m_cap is None else m_cap
-    L.check(lib.ldn_grouped_mfma_conv3x3_rows(L.ptr(_f32rows(a2d, "a")), a2d.stride(0), L.ptr(_i32c(nbr, "nbr")),
-                                              L.ptr(_i32c(m_count, "m_count")), m_cap, L.ptr(w_frag), C, gw,
-                                              L.ptr(_f32c(scale, "scale")), L.ptr(_f32c(shift, "shift")), relu,
-                                              L.ptr(_f32rows(out2d, "out")), out2d.stride(0), L.stream_ptr()),
-            "ldn_grouped_mfma_conv3x3_rows")
-    return out2d
+    C = _check_frag("grouped_mfma_conv3x3_rows", w_frag, "gw", gw)
+    return _grouped_rows("ldn_grouped_mfma_conv3x3_rows", _f32rows, a2d, nbr, w_frag, C, (gw,), scale, shift, out2d, m_count, m_cap, relu)
 
 
 def grouped16_images_fit(Hi, Wi, C):
@@ -1162,19 +1196,8 @@ def grouped16_images_fit(Hi, Wi, C):
 def grouped16_conv3x3_images(a2d, w_frag, scale, shift, out2d, *, m_count, images, relu=1):
     """Grouped 3x3 conv (group width 16) + BN (+ReLU) over packed rows that are WHOLE IMAGES in order (see
     ldn_grouped16_conv3x3_images).  images = (B, Hi, Wi, Ho, Wo, stride); m_count = device-side number of output rows."""
-    L.require_device(a2d, w_frag, out2d, m_count)
-    lib = L.load()
-    C = w_frag.shape[0] * 16
-    if w_frag.dtype != torch.bfloat16 or not w_frag.is_contiguous() or w_frag.numel() * 2 != lib.ldn_grouped16_weight_bytes(C):
-        raise L.LdnError("grouped16_conv3x3_images: w_frag must be the contiguous bf16 tensor of pack_grouped16_weights")
-    B, Hi, Wi, Ho, Wo, stride = (int(v) for v in images)
-    if a2d.shape[0] < B * Hi * Wi or out2d.shape[0] < B * Ho * Wo:
-        raise L.LdnError("grouped16_conv3x3_images: a / out must hold B whole images")
-    L.check(lib.ldn_grouped16_conv3x3_images(L.ptr(_f32c(a2d, "a")), a2d.stride(0), L.ptr(_i32c(m_count, "m_count")), B, Hi, Wi, Ho,
-                                             Wo, stride, L.ptr(w_frag), C, L.ptr(_f32c(scale, "scale")),
-                                             L.ptr(_f32c(shift, "shift")), relu, L.ptr(_f32c(out2d, "out")), out2d.stride(0),
-                                             L.stream_ptr()), "ldn_grouped16_conv3x3_images")
-    return out2d
+    C = _check_frag("grouped16_conv3x3_images", w_frag, "g16", 16)
+    return _grouped_images("ldn_grouped16_conv3x3_images", _f32c, a2d, w_frag, C, (), scale, shift, out2d, m_count, images, relu)
 
 
 def grouped16_images_bands(Hi, Wi, Ho, stride, C):
@@ -1185,23 +1208,9 @@ def grouped16_images_bands(Hi, Wi, Ho, stride, C):
 def grouped16_conv3x3_images_gap(a2d, w_frag, scale, shift, out2d, *, m_count, images, relu=1):
     """grouped16_conv3x3_images that also returns the channel sums of its output per kept image and band: gap [B, bands, C]
     (ldn_grouped16_conv3x3_images_gap) -- the squeeze of the SE block that follows conv b, without a second pass over h_b."""
-    L.require_device(a2d, w_frag, out2d, m_count)
-    lib = L.load()
-    C = w_frag.shape[0] * 16
-    if w_frag.dtype != torch.bfloat16 or not w_frag.is_contiguous() or w_frag.numel() * 2 != lib.ldn_grouped16_weight_bytes(C):
-        raise L.LdnError("grouped16_conv3x3_images_gap: w_frag must be the contiguous bf16 tensor of pack_grouped16_weights")
-    B, Hi, Wi, Ho, Wo, stride = (int(v) for v in images)
-    if a2d.shape[0] < B * Hi * Wi or out2d.shape[0] < B * Ho * Wo:
-        raise L.LdnError("grouped16_conv3x3_images_gap: a / out must hold B whole images")
-    bands = grouped16_images_bands(Hi, Wi, Ho, stride, C)
-    if bands <= 0:
-        raise L.LdnError("grouped16_conv3x3_images_gap: the map does not fit the LDS (grouped16_images_fit)")
-    gap = torch.empty(B, bands, C, device=a2d.device, dtype=torch.float32)
-    L.check(lib.ldn_grouped16_conv3x3_images_gap(L.ptr(_f32c(a2d, "a")), a2d.stride(0), L.ptr(_i32c(m_count, "m_count")), B, Hi, Wi, Ho,
-                                                 Wo, stride, L.ptr(w_frag), C, L.ptr(_f32c(scale, "scale")),
-                                                 L.ptr(_f32c(shift, "shift")), relu, L.ptr(_f32c(out2d, "out")), out2d.stride(0),
-                                                 L.ptr(gap), L.stream_ptr()), "ldn_grouped16_conv3x3_images_gap")
-    return gap
+    C = _check_frag("grouped16_conv3x3_images_gap", w_frag, "g16", 16)
+    return _grouped_images("ldn_grouped16_conv3x3_images_gap", _f32c, a2d, w_frag, C, (), scale, shift, out2d, m_count, images, relu,
+                           gap=("ldn_grouped16_images_bands", "the map does not fit the LDS (grouped16_images_fit)"))
 
 
 def grouped_mfma_images_fit(Hi, Wi, C, group_width):
@@ -1215,52 +1224,24 @@ def grouped_mfma_images_bands(Hi, Wi, Ho, stride, C, group_width):
     return int(L.load().ldn_grouped_mfma_images_bands(int(Hi), int(Wi), int(Ho), int(stride), int(C), int(group_width)))
 
 
-def _grouped_mfma_images_args(name, a2d, w_frag, gw, out2d, images):
-    """the checks the two image forms share -> (lib, C, B, Hi, Wi, Ho, Wo, stride)"""
-    lib = L.load()
-    if gw not in (8, 24):
-        raise L.LdnError(f"{name}: group width {gw} is not built (8 and 24; width 16 is grouped16_conv3x3_images)")
-    C = w_frag.shape[0] * gw
-    if (w_frag.dtype != torch.bfloat16 or not w_frag.is_contiguous() or C == 0
-            or w_frag.numel() * 2 != lib.ldn_grouped_mfma_weight_bytes(C, gw)):
-        raise L.LdnError(f"{name}: w_frag must be the contiguous bf16 tensor of pack_grouped_mfma_weights for this group width")
-    B, Hi, Wi, Ho, Wo, stride = (int(v) for v in images)
-    if a2d.shape[0] < B * Hi * Wi or out2d.shape[0] < B * Ho * Wo or a2d.shape[1] != C or out2d.shape[1] != C:
-        raise L.LdnError(f"{name}: a / out must hold B whole images of C channels")
-    return lib, C, B, Hi, Wi, Ho, Wo, stride
-
-
 def grouped_mfma_conv3x3_images(a2d, w_frag, group_width, scale, shift, out2d, *, m_count, images, relu=1):
     """Grouped 3x3 conv (group width 8 or 24) + BN (+ReLU) over packed rows that are WHOLE IMAGES in order (see
     ldn_grouped_mfma_conv3x3_images): bit-identical to grouped_mfma_conv3x3_rows over the same images' neighbour table, with the same
     w_frag.  images = (B, Hi, Wi, Ho, Wo, stride); m_count = device-side number of output rows.  a2d / out2d may be column slices of wider
     matrices (row strides multiples of 4)."""
-    L.require_device(a2d, w_frag, out2d, m_count)
     gw = int(group_width)
-    lib, C, B, Hi, Wi, Ho, Wo, stride = _grouped_mfma_images_args("grouped_mfma_conv3x3_images", a2d, w_frag, gw, out2d, images)
-    L.check(lib.ldn_grouped_mfma_conv3x3_images(L.ptr(_f32rows(a2d, "a")), a2d.stride(0), L.ptr(_i32c(m_count, "m_count")), B, Hi, Wi, Ho,
-                                                Wo, stride, L.ptr(w_frag), C, gw, L.ptr(_f32c(scale, "scale")),
-                                                L.ptr(_f32c(shift, "shift")), relu, L.ptr(_f32rows(out2d, "out")), out2d.stride(0),
-                                                L.stream_ptr()), "ldn_grouped_mfma_conv3x3_images")
-    return out2d
+    C = _check_frag("grouped_mfma_conv3x3_images", w_frag, "gw", gw)
+    return _grouped_images("ldn_grouped_mfma_conv3x3_images", _f32rows, a2d, w_frag, C, (gw,), scale, shift, out2d, m_count, images, relu)
 
 
 def grouped_mfma_conv3x3_images_gap(a2d, w_frag, group_width, scale, shift, out2d, *, m_count, images, relu=1):
     """grouped_mfma_conv3x3_images that also returns the channel sums of its output per kept image and band: gap [B, bands, C]
     (ldn_grouped_mfma_conv3x3_images_gap) -- the squeeze of the SE block that follows conv b, without a second pass over h_b."""
-    L.require_device(a2d, w_frag, out2d, m_count)
     gw = int(group_width)
-    lib, C, B, Hi, Wi, Ho, Wo, stride = _grouped_mfma_images_args("grouped_mfma_conv3x3_images_gap", a2d, w_frag, gw, out2d, images)
-    bands = grouped_mfma_images_bands(Hi, Wi, Ho, stride, C, gw)
-    if bands <= 0:
-        raise L.LdnError("grouped_mfma_conv3x3_images_gap: not a 3x3 / pad 1 / stride 1 or 2 geometry, or the map does not fit the LDS "
-                         "(grouped_mfma_images_fit)")
-    gap = torch.empty(B, bands, C, device=a2d.device, dtype=torch.float32)
-    L.check(lib.ldn_grouped_mfma_conv3x3_images_gap(L.ptr(_f32rows(a2d, "a")), a2d.stride(0), L.ptr(_i32c(m_count, "m_count")), B, Hi, Wi,
-                                                    Ho, Wo, stride, L.ptr(w_frag), C, gw, L.ptr(_f32c(scale, "scale")),
-                                                    L.ptr(_f32c(shift, "shift")), relu, L.ptr(_f32rows(out2d, "out")), out2d.stride(0),
-                                                    L.ptr(gap), L.stream_ptr()), "ldn_grouped_mfma_conv3x3_images_gap")
-    return gap
+    C = _check_frag("grouped_mfma_conv3x3_images_gap", w_frag, "gw", gw)
+    return _grouped_images("ldn_grouped_mfma_conv3x3_images_gap", _f32rows, a2d, w_frag, C, (gw,), scale, shift, out2d, m_count, images, relu,
+                           gap=("ldn_grouped_mfma_images_bands", "not a 3x3 / pad 1 / stride 1 or 2 geometry, or the map does not fit the LDS "
+                                                                 "(grouped_mfma_images_fit)"))
 
 
 def se_gate_slots(gap, m_count, rows_per_image, w1, b1, w2, b2):
@@ -1306,16 +1287,7 @@ def conv_rows_gated(a2d, w, scale, shift, out2d, gate, gate_rows, *, m_count=Non
 
 def grouped_conv3x3_image(a_nhwc, w, group_width, ch_idx, ch_cnt, scale, shift, out_nhwc, *, stride=1, relu=1):
     """Grouped 3x3 conv + BN (+ReLU) on left-packed per-image channel subsets (see ldn_grouped_conv3x3_image).  w [C,9,gw]."""
-    L.require_device(a_nhwc, w, out_nhwc, ch_idx)
-    lib = L.load()
-    B, Hi, Wi, lda = a_nhwc.shape
-    _, Ho, Wo, ldo = out_nhwc.shape
-    C = w.shape[0]
-    L.check(lib.ldn_grouped_conv3x3_image(L.ptr(_f32c(a_nhwc, "a")), lda, B, Hi, Wi, stride, Ho, Wo, L.ptr(_f32c(w, "w")), C,
-                                          group_width, L.ptr(_i32c(ch_idx, "ch_idx")), L.ptr(_i32c(ch_cnt, "ch_cnt")),
-                                          L.ptr(_f32c(scale, "scale")), L.ptr(_f32c(shift, "shift")), relu,
-                                          L.ptr(_f32c(out_nhwc, "out")), ldo, L.stream_ptr(out_nhwc)), "ldn_grouped_conv3x3_image")
-    return out_nhwc
+    return _grouped_image("ldn_grouped_conv3x3_image", a_nhwc, _f32c(w, "w"), w.shape[0], group_width, ch_idx, ch_cnt, scale, shift, out_nhwc, stride, relu)
 
 
 def grouped_chan_mfma_ok(C, group_width, Hi, Wi, stride):
@@ -1328,29 +1300,11 @@ def grouped_chan_mfma_conv3x3_image(a_nhwc, w_frag, group_width, ch_idx, ch_cnt,
     """Grouped 3x3 conv (group width 8, 16 or 24) + BN (+ReLU) on left-packed per-image channel subsets on the matrix cores: the contract
     of grouped_conv3x3_image (see ldn_grouped_chan_mfma_conv3x3_image) with w_frag = pack_grouped16_weights(w) for width 16,
     pack_grouped_mfma_weights(w, gw) for widths 8 and 24."""
-    L.require_device(a_nhwc, w_frag, out_nhwc, ch_idx)
-    lib = L.load()
     gw = int(group_width)
     if gw not in (8, 16, 24):
         raise L.LdnError(f"grouped_chan_mfma_conv3x3_image: group width {gw} is not built (8, 16 and 24)")
-    C = w_frag.shape[0] * gw
-    want = lib.ldn_grouped16_weight_bytes(C) if gw == 16 else lib.ldn_grouped_mfma_weight_bytes(C, gw)
-    if w_frag.dtype != torch.bfloat16 or not w_frag.is_contiguous() or C == 0 or w_frag.numel() * 2 != want:
-        raise L.LdnError("grouped_chan_mfma_conv3x3_image: w_frag must be the contiguous bf16 tensor of pack_grouped16_weights (width 16) / "
-                         "pack_grouped_mfma_weights (widths 8 and 24) for this group width")
-    if a_nhwc.dim() != 4 or out_nhwc.dim() != 4:
-        raise L.LdnError("grouped_chan_mfma_conv3x3_image: a and out must be [B, H, W, columns]")
-    B, Hi, Wi, lda = a_nhwc.shape
-    _, Ho, Wo, ldo = out_nhwc.shape
-    L.check(lib.ldn_grouped_chan_mfma_conv3x3_image(L.ptr(_f32c(a_nhwc, "a")), lda, B, Hi, Wi, stride, Ho, Wo, L.ptr(w_frag), C, gw,
-                                                    L.ptr(_i32c(ch_idx, "ch_idx")), L.ptr(_i32c(ch_cnt, "ch_cnt")),
-                                                    L.ptr(_f32c(scale, "scale")), L.ptr(_f32c(shift, "shift")), relu,
-                                                    L.ptr(_f32c(out_nhwc, "out")), ldo, L.stream_ptr(out_nhwc)),
-            "ldn_grouped_chan_mfma_conv3x3_image")
-    return out_nhwc
-
-
-_WIDE = {56: (32, 2), 112: (63, 4)}          # group width -> (K steps, row tiles of 32 out channels) of k_grouped_wide
+    C = _check_frag("grouped_chan_mfma_conv3x3_image", w_frag, "g16" if gw == 16 else "gw", gw)
+    return _grouped_image("ldn_grouped_chan_mfma_conv3x3_image", a_nhwc, w_frag, C, gw, ch_idx, ch_cnt, scale, shift, out_nhwc, stride, relu)
 
 
 def grouped_wide_ok(C, group_width, Hi, Wi, stride):
@@ -1370,9 +1324,9 @@ def pack_grouped_wide_weights(w, group_width):
     >= gw (pad rows 56-63 / 112-127) or the octet q is >= 9 * Q (q = 63 at gw 56).  K is cut into octets q of 8 consecutive in channels
     of one tap; a lane's 16 values [8 hi | 8 lo] are contiguous, a (step, row tile) is one 2 KB line, a group's fragments are 128 KB / 504 KB."""
     gw = int(group_width)
-    if gw not in _WIDE or w.dim() != 3 or w.shape[0] == 0 or w.shape[0] % gw or tuple(w.shape[1:]) != (9, gw):
+    if gw not in _FRAG["wide"].widths or w.dim() != 3 or w.shape[0] == 0 or w.shape[0] % gw or tuple(w.shape[1:]) != (9, gw):
         raise L.LdnError(f"pack_grouped_wide_weights: expected [C % gw == 0, 9, gw] with gw 56 or 112 (got {tuple(w.shape)}, group width {gw})")
-    steps, mt = _WIDE[gw]
+    steps, mt = _FRAG["wide"].geometry[gw]
     G = w.shape[0] // gw
     k = torch.zeros(G, 32 * mt, 2 * steps, 8, device=w.device, dtype=torch.float32)
     k[:, :gw, :9 * gw // 8] = w.detach().float().reshape(G, gw, 9 * gw // 8, 8)          # [g][out channel][q = tap * Q + octet][e]
@@ -1384,25 +1338,9 @@ def pack_grouped_wide_weights(w, group_width):
 def grouped_wide_conv3x3_image(a_nhwc, w_frag, group_width, ch_idx, ch_cnt, scale, shift, out_nhwc, *, stride=1, relu=1):
     """Grouped 3x3 conv (group width 56 or 112) + BN (+ReLU) on left-packed per-image channel subsets on the matrix cores: the contract of
     grouped_conv3x3_image (see ldn_grouped_wide_conv3x3_image) with w_frag = pack_grouped_wide_weights(w, gw)."""
-    L.require_device(a_nhwc, w_frag, out_nhwc, ch_idx)
-    lib = L.load()
     gw = int(group_width)
-    if gw not in _WIDE:
-        raise L.LdnError(f"grouped_wide_conv3x3_image: group width {gw} is not built (56 and 112)")
-    C = w_frag.shape[0] * gw
-    if (w_frag.dtype != torch.bfloat16 or not w_frag.is_contiguous() or C == 0
-            or w_frag.numel() * 2 != lib.ldn_grouped_wide_weight_bytes(C, gw)):
-        raise L.LdnError("grouped_wide_conv3x3_image: w_frag must be the contiguous bf16 tensor of pack_grouped_wide_weights for this group width")
-    if a_nhwc.dim() != 4 or out_nhwc.dim() != 4:
-        raise L.LdnError("grouped_wide_conv3x3_image: a and out must be [B, H, W, columns]")
-    B, Hi, Wi, lda = a_nhwc.shape
-    _, Ho, Wo, ldo = out_nhwc.shape
-    L.check(lib.ldn_grouped_wide_conv3x3_image(L.ptr(_f32c(a_nhwc, "a")), lda, B, Hi, Wi, stride, Ho, Wo, L.ptr(w_frag), C, gw,
-                                               L.ptr(_i32c(ch_idx, "ch_idx")), L.ptr(_i32c(ch_cnt, "ch_cnt")),
-                                               L.ptr(_f32c(scale, "scale")), L.ptr(_f32c(shift, "shift")), relu,
-                                               L.ptr(_f32c(out_nhwc, "out")), ldo, L.stream_ptr(out_nhwc)),
-            "ldn_grouped_wide_conv3x3_image")
-    return out_nhwc
+    C = _check_frag("grouped_wide_conv3x3_image", w_frag, "wide", gw)
+    return _grouped_image("ldn_grouped_wide_conv3x3_image", a_nhwc, w_frag, C, gw, ch_idx, ch_cnt, scale, shift, out_nhwc, stride, relu)
 
 
 def grouped_wide_rows_ok(C, group_width):
@@ -1414,22 +1352,9 @@ def grouped_wide_conv3x3_rows(a2d, nbr, w_frag, group_width, scale, shift, out2d
     """Grouped 3x3 conv (group width 56 or 112) + BN (+ReLU) over packed rows on the matrix cores: the contract of grouped_mfma_conv3x3_rows
     (see ldn_grouped_wide_conv3x3_rows) with w_frag = pack_grouped_wide_weights(w, gw), the fragments of grouped_wide_conv3x3_image.
     a2d / out2d may be column slices of wider matrices (row strides multiples of 4): the columns past C are neither read nor written."""
-    L.require_device(a2d, nbr, w_frag, out2d)
-    lib = L.load()
     gw = int(group_width)
-    if gw not in _WIDE:
-        raise L.LdnError(f"grouped_wide_conv3x3_rows: group width {gw} is not built (56 and 112)")
-    C = w_frag.shape[0] * gw
-    if (w_frag.dtype != torch.bfloat16 or not w_frag.is_contiguous() or C == 0
-            or w_frag.numel() * 2 != lib.ldn_grouped_wide_weight_bytes(C, gw)):
-        raise L.LdnError("grouped_wide_conv3x3_rows: w_frag must be the contiguous bf16 tensor of pack_grouped_wide_weights for this group width")
-    m_cap = out2d.shape[0] if m_cap is None else m_cap
-    L.check(lib.ldn_grouped_wide_conv3x3_rows(L.ptr(_f32rows(a2d, "a")), a2d.stride(0), L.ptr(_i32c(nbr, "nbr")),
-                                              L.ptr(_i32c(m_count, "m_count")), m_cap, L.ptr(w_frag), C, gw,
-                                              L.ptr(_f32c(scale, "scale")), L.ptr(_f32c(shift, "shift")), relu,
-                                              L.ptr(_f32rows(out2d, "out")), out2d.stride(0), L.stream_ptr()),
-            "ldn_grouped_wide_conv3x3_rows")
-    return out2d
+    C = _check_frag("grouped_wide_conv3x3_rows", w_frag, "wide", gw)
+    return _grouped_rows("ldn_grouped_wide_conv3x3_rows", _f32rows, a2d, nbr, w_frag, C, (gw,), scale, shift, out2d, m_count, m_cap, relu)
 
 
 def se_packed(a2d, row_prefix, w1, b1, w2, b2, max_rows_per_image, ch_idx=None, ch_cnt=None):

@@ -104,7 +104,7 @@ import torch.nn.functional as F
 from . import ops
 from ._lib import LdnError
 from ._shared import channel_constants, dense_channel_convs, dense_index, image_prefix
-from .laud_regnet import LAD_RegNet, ResBottleneckBlock, _conv_b_rows, grouped_mfma_widths_on, grouped_wide_rows_on
+from .laud_regnet import LAD_RegNet, ResBottleneckBlock, _conv_b_frag, _conv_b_rows, _conv_b_run, conv_b_choice
 
 # weight gradients on ldn_wgrad_rows / ldn_wgrad_grouped_rows; LDN_WGRAD=0 = the gather + PyTorch GEMM / bmm path.  On by default: the median step is shorter with the kernel for
 # all three full-width workloads at batch 32 and 128 (profiles/train_step_wgrad.jsonl), and for LAD-RegNetY-800MF layer skip with the grouped
@@ -583,29 +583,24 @@ def _se_gate(sq, w1, b1, w2, b2):
 
 
 def _conv_b_params(wbr, sb, tb, gw):
-    """what laud_regnet._conv_b_rows reads of a prepared block, from the live weights (the matrix-core form's fragments only where it runs)"""
+    """what laud_regnet._conv_b_rows reads of a prepared block, from the live weights (the fragments of the family the chooser names, no other)"""
     pb = {"wb": wbr, "sb": sb, "tb": tb}
-    if gw == 16 and wbr.shape[0] % 16 == 0 and ops.get_math_mode() == "bf16x3":
-        pb["wb_frag"] = ops.pack_grouped16_weights(wbr)
-    elif grouped_mfma_widths_on(wbr.shape[0], gw):
-        pb["wb_frag_gw"] = ops.pack_grouped_mfma_weights(wbr, gw)
-    elif grouped_wide_rows_on(wbr.shape[0], gw):
-        pb["wb_frag_wide"] = ops.pack_grouped_wide_weights(wbr, gw)
+    _conv_b_frag(pb, conv_b_choice("rows", wbr.shape[0], gw)[0], gw)
     return pb
 
 
+def _conv_b_bare(wr, gw, x, nbr, y, m_count, m_cap, families=None):
+    """the grouped 3x3 of weights wr [W, 9, gw] alone -- scale 1, shift 0, no ReLU -- over the neighbour table nbr, on laud_regnet.conv_b_choice's
+    kernel among `families` (None: all)"""
+    W, dev = wr.shape[0], x.device
+    pb = {"wb": wr, "sb": torch.ones(W, device=dev), "tb": torch.zeros(W, device=dev)}
+    _conv_b_run(conv_b_choice("rows", W, gw, families=families), pb, gw, x, nbr, y, m_count, m_cap, None, relu=0)
+
+
 def _conv_b_adjoint(dy, nbrT, wbr, gw, dha, m_count, m_cap):
-    """b^T: the forward kernel over the transposed neighbour table with per-group transposed weights, scale 1, shift 0, no ReLU, into the zeroed dha.
-    The fp32 VALU kernel, or the matrix-core one for group widths 8 and 24 where laud_regnet.grouped_mfma_widths_on says so and for widths 56 and
-    112 where laud_regnet.grouped_wide_rows_on does."""
-    W, dev = wbr.shape[0], dy.device
-    one, zero, wT = torch.ones(W, device=dev), torch.zeros(W, device=dev), grouped_weight_T(wbr, gw)
-    if grouped_mfma_widths_on(W, gw):
-        ops.grouped_mfma_conv3x3_rows(dy, nbrT, ops.pack_grouped_mfma_weights(wT, gw), gw, one, zero, dha, m_count=m_count, m_cap=m_cap, relu=0)
-    elif grouped_wide_rows_on(W, gw):
-        ops.grouped_wide_conv3x3_rows(dy, nbrT, ops.pack_grouped_wide_weights(wT, gw), gw, one, zero, dha, m_count=m_count, m_cap=m_cap, relu=0)
-    else:
-        ops.grouped_conv3x3_rows(dy, nbrT, wT, gw, one, zero, dha, m_count=m_count, m_cap=m_cap, relu=0)
+    """b^T: the forward kernel over the transposed neighbour table with per-group transposed weights, into the zeroed dha.  Never the width-16
+    matrix-core kernel: the VALU one, or those of widths 8 / 24 and 56 / 112 behind their switches."""
+    _conv_b_bare(grouped_weight_T(wbr, gw), gw, dy, nbrT, dha, m_count, m_cap, families=("gw", "wide"))
 
 
 def _regnet_chain(x2d, ix, P, f, war, wbr, wcs, sa, ta, sb, tb, tc, se, br):
@@ -869,17 +864,7 @@ class _BatchStatsBranchFn(torch.autograd.Function):
 def _conv_b_plain(wbr, gw, h_a, nbr, y_b, m_count, m_cap):
     """the grouped 3x3 alone -- scale 1, shift 0, no ReLU -- with laud_regnet._conv_b_rows' choice of kernel: the matrix cores for group width 16
     in bf16x3 mode (widths 8 / 24 and 56 / 112 behind their switches), else the fp32 VALU kernel"""
-    W, dev = wbr.shape[0], h_a.device
-    one, zero = torch.ones(W, device=dev), torch.zeros(W, device=dev)
-    pb = _conv_b_params(wbr, one, zero, gw)
-    if "wb_frag" in pb:
-        ops.grouped16_conv3x3_rows(h_a, nbr, pb["wb_frag"], one, zero, y_b, m_count=m_count, m_cap=m_cap, relu=0)
-    elif "wb_frag_gw" in pb:
-        ops.grouped_mfma_conv3x3_rows(h_a, nbr, pb["wb_frag_gw"], gw, one, zero, y_b, m_count=m_count, m_cap=m_cap, relu=0)
-    elif "wb_frag_wide" in pb:
-        ops.grouped_wide_conv3x3_rows(h_a, nbr, pb["wb_frag_wide"], gw, one, zero, y_b, m_count=m_count, m_cap=m_cap, relu=0)
-    else:
-        ops.grouped_conv3x3_rows(h_a, nbr, wbr, gw, one, zero, y_b, m_count=m_count, m_cap=m_cap, relu=0)
+    _conv_b_bare(wbr, gw, h_a, nbr, y_b, m_count, m_cap)
 
 
 class _RegNetBatchStatsBranchFn(torch.autograd.Function):
