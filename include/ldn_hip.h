@@ -258,8 +258,8 @@ size_t ldn_wgrad_grouped_rows_workspace_bytes(int m_cap, int C, int gw);
 int ldn_wgrad_grouped_rows(const float* dy, int lddy, const float* a, int lda, int a_valid, const int32_t* nbr, const int32_t* m_count,
                            int m_cap, int C, int gw, float* dw, float* work, int math_mode, void* stream);
 
-/* ---- the same WEIGHT GRADIENT at group widths 56 and 112, on the matrix cores (csrc/ldn_wgrad_grouped_wide.hip): per group a gw x 9 gw GEMM
- * (56 x 504 / 112 x 1008) reduced over the packed rows
+/* ---- the same WEIGHT GRADIENT at group widths 56, 112 and 232, on the matrix cores (csrc/ldn_wgrad_grouped_wide.hip): per group a gw x 9 gw GEMM
+ * (56 x 504 / 112 x 1008 / 232 x 2088; width 232 in two tiles of 128 out channels, the second with 104 live) reduced over the packed rows
  *   dW[c, t, j] = sum_{r < count} dY[r, c] * A[nbr[r * 9 + t], (c / gw) * gw + j]          for c < C, t < 9, j < gw
  *   an entry of nbr < 0 or >= a_valid is a ZERO row (a missing 3x3 neighbour)
  *   count = m_count ? clamp(*m_count, 0, m_cap) : m_cap, read on the device (no host read, no synchronisation)
@@ -273,7 +273,7 @@ int ldn_wgrad_grouped_rows(const float* dy, int lddy, const float* a, int lda, i
  * launch can be captured into a graph -- the partial tiles go to `work` (ldn_wgrad_grouped_wide_rows_workspace_bytes = splits * C * 9 * gw * 4
  * bytes, 0 when the rows are not split; `work` may be NULL then) and the live splits are added in ascending order by a second small launch.
  * No floating-point atomics: two runs are bit-identical.
- * Shapes (ldn_wgrad_grouped_wide_rows_ok): gw 56 | 112, C > 0, C % gw == 0, C <= 4096 (widths 8 | 16 | 24 belong to ldn_wgrad_grouped_rows and
+ * Shapes (ldn_wgrad_grouped_wide_rows_ok): gw 56 | 112 | 232, C > 0, C % gw == 0, C <= 4096 (widths 8 | 16 | 24 belong to ldn_wgrad_grouped_rows and
  * are false here); lddy, lda % 4 == 0, 16-byte aligned pointers.  Anything else is LDN_EINVAL with a message, before any launch -- there is
  * no fallback inside the library.  LDN_DEBUG build: nbr entries below -1 are counted (code 621). */
 int ldn_wgrad_grouped_wide_rows_ok(int C, int gw);
@@ -749,15 +749,16 @@ int ldn_grouped_chan_mfma_bands(int C, int group_width, int Hi, int Wi, int Ho, 
 int ldn_grouped_chan_mfma_conv3x3_image(const float* a, int lda, int B, int Hi, int Wi, int stride, int Ho, int Wo, const void* w_frag,
                                         int C, int group_width, const int32_t* ch_idx, const int32_t* ch_cnt, const float* scale,
                                         const float* shift, int relu, float* out, int ldo, void* stream);
-/* b in channel mode on the matrix cores at group widths 56 and 112 (RegNetY-8GF / 16GF; bf16x3 arithmetic; csrc/ldn_grouped_wide.hip): the
- *    contract and the argument list of ldn_grouped_chan_mfma_conv3x3_image, word for word.  A group's fragments (128 KB / 504 KB) do not fit
+/* b in channel mode on the matrix cores at group widths 56, 112 and 232 (RegNetY-8GF / 16GF / 32GF; bf16x3 arithmetic; csrc/ldn_grouped_wide.hip): the
+ *    contract and the argument list of ldn_grouped_chan_mfma_conv3x3_image, word for word.  A group's fragments (128 KB / 504 KB / 2096 KB) do not fit
  *    the LDS: they stream through registers while the LDS holds the expanded, pre-split input of up to 8 images or of one rectangle of one
  *    image.  w_frag is exactly ldn_grouped_wide_weight_bytes(C, gw) bytes of bf16 in the order
- *      [group g][K step s][row tile m][lane l][8 hi | 8 lo],   K steps: 32 (gw 56) / 63 (gw 112), row tiles of 32 out channels: 2 / 4,
+ *      [group g][K step s][row tile m][lane l][8 hi | 8 lo],   K steps: 32 (gw 56) / 63 (gw 112) / 131 (gw 232), row tiles of 32 out channels: 2 / 4 / 8,
  *    lane l = i + 32 h holds out channel 32 m + i of the group (zeros for >= gw) and K octet q = 2 s + h = tap * (gw / 8) + o, i.e. the in
- *    channels 8 o .. 8 o + 7 of the group at tap q / (gw / 8) (zeros for q = 63 at gw 56); 0 bytes for any other width or C % gw != 0.
- *    ldn_grouped_wide_ok = 1 iff gw is 56 or 112, C > 0, C % gw == 0, stride is 1 or 2 and the plan finds a rectangle of the Hi x Wi map that
- *    fits the LDS (host arithmetic only); ldn_grouped_wide_bands = bands of output rows per image (1: whole rows of the image in one
+ *    channels 8 o .. 8 o + 7 of the group at tap q / (gw / 8) (zeros for q = 63 at gw 56 and q = 261 at gw 232); one group is 131 x 8 x 2048 = 2 146 304 bytes at gw 232; 0 bytes for any other width or
+ *    C % gw != 0.
+ *    ldn_grouped_wide_ok = 1 iff gw is 56, 112 or 232, C > 0, C % gw == 0, stride is 1 or 2 and the plan finds a rectangle of the Hi x Wi map that
+ *    fits the LDS (224 / 480 / 928 bytes per staged pixel in 150 KB; host arithmetic only); ldn_grouped_wide_bands = bands of output rows per image (1: whole rows of the image in one
  *    workgroup), 0 outside _ok or when Ho is not this geometry's; ldn_grouped_wide_strips = column strips the rows of a band are cut into
  *    (1: whole rows); ldn_grouped_wide_images = images that share a workgroup; both 0 outside _ok. */
 int ldn_grouped_wide_ok(int C, int group_width, int Hi, int Wi, int stride);
@@ -768,22 +769,22 @@ size_t ldn_grouped_wide_weight_bytes(int C, int group_width);
 int ldn_grouped_wide_conv3x3_image(const float* a, int lda, int B, int Hi, int Wi, int stride, int Ho, int Wo, const void* w_frag,
                                    int C, int group_width, const int32_t* ch_idx, const int32_t* ch_cnt, const float* scale,
                                    const float* shift, int relu, float* out, int ldo, void* stream);
-/* b over PACKED ROWS on the matrix cores at group widths 56 and 112 (layer skip, the dense 'spatial' path, every training forward and adjoint;
+/* b over PACKED ROWS on the matrix cores at group widths 56, 112 and 232 (layer skip, the dense 'spatial' path, every training forward and adjoint;
  *    bf16x3 arithmetic; csrc/ldn_grouped_wide_rows.hip): the contract and the argument list of ldn_grouped_mfma_conv3x3_rows,
  *      out[r, gw g + n] = act(scale[c] * sum_{t<9} sum_{i<gw} a[nbr[r*9+t], gw g + i] * w[gw g + n, t, i] + shift[c]),   r < M,
  *      M = m_count ? min(m_count[0], m_cap) : m_cap,
  *    with w_frag EXACTLY the ldn_grouped_wide_weight_bytes(C, gw) bytes of ldn_grouped_wide_conv3x3_image above (one packed copy serves the
  *    image form and the row form; the adjoint packs the per-group transposed weights the same way).  The fragments stream through registers;
- *    one wave holds every row tile of its one or two pixel tiles of 32 rows, so an input octet is gathered and split once.
+ *    one wave holds every row tile of its one or two pixel tiles of 32 rows (width 232: one; 8 row tiles are 128 accumulator registers), so an input octet is gathered and split once.
  *    A table entry of -1 is a zero row.  Rows >= M are neither read through the table nor written.  Columns of a at or past C (row stride
  *    lda >= C, lda % 4 == 0) are never read, columns of out at or past C (ldo >= C, ldo % 4 == 0) never written; the padded out channels of a
- *    group (56-63, 112-127) are dropped.  16-byte aligned pointers.  m_cap <= 0 launches nothing.  The grid is a function of m_cap and the
+ *    group (56-63, 112-127, 232-255) are dropped.  16-byte aligned pointers.  m_cap <= 0 launches nothing.  The grid is a function of m_cap and the
  *    shapes only, never of the device-side count (graph-capturable).  No atomics: two runs are bit-identical.
  *    Refused with LDN_EINVAL before any launch: a null pointer (m_count may be null), a shape outside _ok, a row stride that is not a
  *    multiple of 4 or is below C, a misaligned pointer, m_cap > INT32_MAX - 256.
- *    ldn_grouped_wide_rows_ok(C, gw) = 1 iff gw is 56 or 112, C > 0 and C % gw == 0 (host arithmetic only).
+ *    ldn_grouped_wide_rows_ok(C, gw) = 1 iff gw is 56, 112 or 232, C > 0 and C % gw == 0 (host arithmetic only).
  *    ldn_grouped_wide_rows_tiles(C, gw, m_cap) = pixel tiles of 32 rows a wave keeps in that launch: 2, or 1 where
- *    (C / gw) * ceil(ceil(m_cap / 32) / 2) < 3072 (fewer than 3 waves per SIMD of 256 CUs at the cap); 0 outside _ok or for m_cap <= 0 (host arithmetic only). */
+ *    (C / gw) * ceil(ceil(m_cap / 32) / 2) < 3072 (fewer than 3 waves per SIMD of 256 CUs at the cap) and always 1 at gw 232; 0 outside _ok or for m_cap <= 0 (host arithmetic only). */
 int ldn_grouped_wide_rows_ok(int C, int group_width);
 int ldn_grouped_wide_rows_tiles(int C, int group_width, int m_cap);
 int ldn_grouped_wide_conv3x3_rows(const float* a, int lda, const int32_t* nbr, const int32_t* m_count, int m_cap,

@@ -18,7 +18,7 @@ from .laud_resnet import (Bottleneck, ExpandMask, Masker_channel_conv_linear, Ma
                           Masker_spatial, ResNet, uni_resnet50, uni_resnet101)
 
 from .laud_regnet import (LAD_RegNet, BlockParams, lad_regnet_y_400mf, lad_regnet_y_800mf,  # noqa: F401
-                          lad_regnet_y_1_6gf, lad_regnet_y_3_2gf, lad_regnet_y_8gf, lad_regnet_y_16gf)
+                          lad_regnet_y_1_6gf, lad_regnet_y_3_2gf, lad_regnet_y_8gf, lad_regnet_y_16gf, lad_regnet_y_32gf)
 
 from . import sparsity_loss  # noqa: F401,E402  (the criteria the caller applies to the 7-tuple, train/main.py:311,670)
 from . import training  # noqa: F401,E402  (forward + backward of spatial / layer blocks under frozen BatchNorm on the packed kernels)

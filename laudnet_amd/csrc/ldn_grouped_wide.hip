@@ -1,15 +1,16 @@
-// k_grouped_wide<56 | 112> -- LAD-RegNet conv b in CHANNEL mode (and the 'both' branch) on the matrix cores at the group widths of RegNetY-8GF
-// and RegNetY-16GF: the contract of k_grouped_chan (ldn_grouped_chan.hip) and its DENSE-SLOT form -- the packed columns of an image are EXPANDED
+// k_grouped_wide<56 | 112 | 232> -- LAD-RegNet conv b in CHANNEL mode (and the 'both' branch) on the matrix cores at the group widths of RegNetY-8GF,
+// RegNetY-16GF and RegNetY-32GF: the contract of k_grouped_chan (ldn_grouped_chan.hip) and its DENSE-SLOT form -- the packed columns of an image are EXPANDED
 // into their group slots with zeros in the inactive slots, the dense gw x gw x 9 product of the group runs in bf16x3, the active output slots
 // are COMPRESSED back to their packed columns in the epilogue; exact because the mask multiplies after conv + BN + ReLU.
-// What is different: a group's pre-split fragments are 128 KB (width 56) / 504 KB (width 112) and do not fit a CU's LDS, so
-//   * the WEIGHTS STREAM THROUGH REGISTERS.  v_mfma_f32_32x32x16_bf16; the out channels are padded to MT = 2 / 4 row tiles of 32.  Wave w of
+// What is different: a group's pre-split fragments are 128 KB (width 56) / 504 KB (width 112) / 2096 KB (width 232) and do not fit a CU's LDS, so
+//   * the WEIGHTS STREAM THROUGH REGISTERS.  v_mfma_f32_32x32x16_bf16; the out channels are padded to MT = 2 / 4 / 8 row tiles of 32.  Wave w of
 //     the 8 owns row tile w % MT and pixel-tile set w / MT: per K step it loads ITS 32 B per lane of ITS row tile straight from global memory
 //     (one coalesced 2 KB line per wave; the fragment order makes a lane's [8 hi | 8 lo] contiguous), one step ahead, and uses them for the
-//     up to PT = 4 pixel tiles whose accumulators it keeps resident across the whole K loop.  No LDS ring, no barrier inside the K loop; the
+//     up to PT = 4 pixel tiles whose accumulators it keeps resident across the whole K loop (width 232: MT = 8, every wave its own row tile,
+//     one tile set).  No LDS ring, no barrier inside the K loop; the
 //     LDS holds the input only, and the waves that share a row tile read the same lines within a few hundred cycles of each other (L1 / L2);
 //   * one workgroup = (group, RUN OF IMAGES, rectangle of output pixels): on small maps up to 8 whole images share a workgroup, so one pass
-//     over a group's fragments serves 8 (width 112) / 16 (width 56) pixel tiles.  A pixel tile never mixes images.  An (image, group) pair
+//     over a group's fragments serves 4 (width 232) / 8 (width 112) / 16 (width 56) pixel tiles.  A pixel tile never mixes images.  An (image, group) pair
 //     without an active channel is not staged and gets no tile;
 //   * the input is staged PRE-SPLIT ([8 hi | 8 lo] bf16 per octet, the 4 B per element of fp32) WITH ITS ZERO HALO: a rectangle of R x Wc
 //     output pixels stages ((R - 1) stride + 3) x ((Wc - 1) stride + 3) pixels, those outside the image as zeros, so the im2col address of a
@@ -17,7 +18,8 @@
 //     Maps that do not fit are cut into bands of output rows and, where a band of full rows does not fit either (width 112 keeps 480 B per
 //     staged pixel: three rows of a 112-wide map are 161 KB), into column strips as well.
 // K = 9 gw in octets q = tap * (gw / 8) + octet of 8 consecutive channels; K step s covers octets 2 s and 2 s + 1 (lane half h = lane >> 5).
-// Width 56: 63 octets in 32 steps (octet 63 is a zero pad of the fragments); width 112: 126 octets in 63 steps.
+// Width 56: 63 octets in 32 steps (octet 63 is a zero pad of the fragments); width 112: 126 octets in 63 steps; width 232: 261 octets in 131
+// steps (octet 261 is the zero pad).
 // Input columns >= ch_cnt[b] and the pad columns of lda are never read; output columns >= C are never written.  No atomics: deterministic.
 #include <algorithm>
 
@@ -26,8 +28,10 @@
 
 namespace ldn {
 
-// bytes of a staged pixel.  Width 56: 224, 8 consecutive pixels cover the 64 banks; width 112: 448 + 32, the same bank walk (448 B would repeat after 4)
-constexpr int gwd_pixb(int gw) { return gw == 56 ? 224 : 480; }
+// bytes of a staged pixel.  Width 56: 224, 8 consecutive pixels cover the 64 banks; width 112: 448 + 32, the same bank walk (448 B would repeat after 4);
+// width 232: 928 = 32 x 29 with no pad -- an odd count of 32-byte pieces, so 8 consecutive pixels again start in the 8 different 32-byte
+// pieces of the 256 bytes the banks span (chosen on paper by that rule; not measured with counters)
+constexpr int gwd_pixb(int gw) { return gw == 56 ? 224 : gw == 112 ? 480 : 928; }
 constexpr int GWD_THREADS = 512;
 constexpr int GWD_PT = 4;                    // pixel tiles (of 32) a wave keeps accumulators for
 constexpr int GWD_MAXIMG = 8;                // images per workgroup
@@ -63,7 +67,7 @@ __device__ __forceinline__ void gw_kloop(const unsigned char* wbase, const unsig
         const int q8 = 2 * s + h;
         int t = q8 / OCT;
         const int oct = q8 - t * OCT;
-        if (GW == 56) t = min(t, 8);                                               // octet 63: zero weights; any staged (finite) input serves
+        if (gw_frag_pad_octet<GW>()) t = min(t, 8);                                // octet 63 / 261: zero weights; any staged (finite) input serves
         const int dy = t / 3, dx = t - 3 * dy;
         const int koff = (dy * sw + dx) * PIXB + oct * 32;
         bf16x8 bh[NPT], bl[NPT];
@@ -253,7 +257,7 @@ __global__ __launch_bounds__(GWD_THREADS, 4) void k_grouped_wide(const GwArgs p)
 // The plan: images per workgroup and the rectangle of output pixels of one workgroup.  Everything counts against one budget: the tables and
 // (images x staged pixels) x PIXB, staged pixels = ((R - 1) stride + 3) x ((Wc - 1) stride + 3) -- the halo is staged as zeros, so a whole
 // 7 x 7 image is 81 staged pixels.  In staged pixels of one image: width 56: 364 (80 KB, two workgroups per CU) / 684 (150 KB); width 112:
-// 169 / 318 (each further image of the workgroup takes one or two pixels' worth of tables).  A candidate's cost is its matrix-core time per output pixel (a pass over the group's fragments costs one tile slot
+// 169 / 318; width 232: 87 / 164 (each further image of the workgroup takes one or two pixels' worth of tables).  A candidate's cost is its matrix-core time per output pixel (a pass over the group's fragments costs one tile slot
 // for the stream plus the most tiles one wave has; 32 NSET pixels per slot) plus a tenth of its staged pixels per output pixel, times 1.1
 // when only one workgroup fits a CU.  Candidates: 1-8 whole images; one image cut into 1-32 row bands x 1-32 column strips.  A map that no
 // candidate holds is answered "does not fit", never by a failed launch.
@@ -356,7 +360,7 @@ extern "C" int ldn_grouped_wide_conv3x3_image(const float* a, int lda, int B, in
     LDN_REQUIRE(B > 0 && Hi > 0 && Wi > 0 && stride >= 1 && Ho == (Hi - 1) / stride + 1 && Wo == (Wi - 1) / stride + 1,
                 "ldn_grouped_wide_conv3x3_image: %dx%d -> %dx%d is not a 3x3 / pad 1 / stride %d geometry", Hi, Wi, Ho, Wo, stride);
     LDN_REQUIRE(ldn_grouped_wide_ok(C, group_width, Hi, Wi, stride),
-                "ldn_grouped_wide_conv3x3_image: group width %d with %d channels on a %dx%d map at stride %d is not built (widths 56 and 112, "
+                "ldn_grouped_wide_conv3x3_image: group width %d with %d channels on a %dx%d map at stride %d is not built (widths 56, 112 and 232, "
                 "channels a multiple of the width, stride 1 or 2, a rectangle of the map in the LDS: ldn_grouped_wide_ok)", group_width, C, Hi, Wi, stride);
     LDN_REQUIRE(lda % 4 == 0 && ldo % 4 == 0 && lda >= C && ldo >= C, "ldn_grouped_wide_conv3x3_image: strides must be multiples of 4 and at least C");
     LDN_REQUIRE((uintptr_t)a % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)w_frag % 16 == 0 && (uintptr_t)scale % 16 == 0 &&
@@ -375,5 +379,6 @@ extern "C" int ldn_grouped_wide_conv3x3_image(const float* a, int lda, int B, in
     const long nwg = (long)(C / group_width) * ceil_div(B, g.nimg) * g.nrb * g.ncb;
     LDN_REQUIRE(nwg < (1l << 31), "ldn_grouped_wide_conv3x3_image: too many workgroups (%ld)", nwg);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return group_width == 56 ? launch_grouped_wide<56>(g, lds, (unsigned)nwg, st) : launch_grouped_wide<112>(g, lds, (unsigned)nwg, st);
+    return group_width == 56 ? launch_grouped_wide<56>(g, lds, (unsigned)nwg, st)
+                             : group_width == 112 ? launch_grouped_wide<112>(g, lds, (unsigned)nwg, st) : launch_grouped_wide<232>(g, lds, (unsigned)nwg, st);
 }

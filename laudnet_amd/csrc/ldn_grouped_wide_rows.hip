@@ -1,11 +1,11 @@
-// k_grouped_wide_rows<56 | 112> -- grouped 3x3 convolution + BN (+ReLU) over PACKED PIXEL ROWS on the matrix cores at the group widths of
-// RegNetY-8GF (56) and RegNetY-16GF (112); gfx950, bf16x3 arithmetic, v_mfma_f32_32x32x16_bf16.  The contract of k_grouped_gw
+// k_grouped_wide_rows<56 | 112 | 232> -- grouped 3x3 convolution + BN (+ReLU) over PACKED PIXEL ROWS on the matrix cores at the group widths of
+// RegNetY-8GF (56), RegNetY-16GF (112) and RegNetY-32GF (232); gfx950, bf16x3 arithmetic, v_mfma_f32_32x32x16_bf16.  The contract of k_grouped_gw
 // (ldn_grouped_gw.hip), the fragments of k_grouped_wide (ldn_grouped_wide.hip), unchanged:
 //     out[r, gw g + n] = act(scale * sum_{t < 9} sum_{i < gw} a[nbr[r, t], gw g + i] * w[gw g + n, t, i] + shift),   r < M
-// Per group a GEMM with M = gw output channels padded to MT = 2 / 4 row tiles of 32, N = rows in pixel tiles of 32, K = 9 gw in octets
+// Per group a GEMM with M = gw output channels padded to MT = 2 / 4 / 8 row tiles of 32, N = rows in pixel tiles of 32, K = 9 gw in octets
 // q = tap * (gw / 8) + octet of 8 consecutive channels; K step s covers octets 2 s and 2 s + 1 (lane half h = lane >> 5): 32 steps at width
-// 56 (octet 63 is a zero pad of the fragments: no load), 63 at width 112.
-//   * A group's fragments (128 KB / 504 KB) do not fit the LDS: they STREAM THROUGH REGISTERS as in k_grouped_wide, one coalesced 2 KB line per
+// 56 (octet 63 is a zero pad of the fragments: no load), 63 at width 112, 131 at width 232 (octet 261 is the zero pad).
+//   * A group's fragments (128 KB / 504 KB / 2096 KB) do not fit the LDS: they STREAM THROUGH REGISTERS as in k_grouped_wide, one coalesced 2 KB line per
 //     (step, row tile), one step ahead of the MFMAs.  The four waves of a workgroup read the same lines of the same group within a few steps
 //     of each other (L1, then the XCD's L2).
 //   * WAVE = RT row tiles x up to NPT pixel tiles, accumulators resident over the whole K loop.  The form that is launched is RT = MT (one
@@ -13,9 +13,10 @@
 //     straight from global memory into registers as in k_grouped_gw<24>, two steps ahead.  No LDS, no barrier, no atomics.
 //     RT = 1 (a wave = one row tile, the MT waves that share a pixel tile gather it again) is compiled for the A/B of DESIGN.md 4zc only.
 //   * one workgroup = (group, row-tile set) x 4 NPT consecutive pixel tiles; NPT = 2, or 1 where two would leave a SIMD fewer than 3 waves at the cap
-//     (gwr_tiles_per_wave); the grid and NPT depend on m_cap and the shapes only.
+//     (gwr_tiles_per_wave); the grid and NPT depend on m_cap and the shapes only.  Width 232: RT = MT = 8 keeps 128 accumulator registers
+//     per pixel tile, so NPT = 1 is the only form with every row tile in one wave (two tiles would be 256 accumulators: the whole file).
 // Rows >= M are neither looked up nor written; a table entry of -1 is a zero row; columns >= C of a / out are never touched; the padded out
-// channels (56-63, 112-127) are dropped in the epilogue.
+// channels (56-63, 112-127, 232-255) are dropped in the epilogue.
 #include <stdlib.h>
 #include <string.h>
 
@@ -45,7 +46,7 @@ __device__ __forceinline__ void gwr_kloop(const unsigned char* wbase, const floa
     constexpr int MT = GwCfg<GW>::MT, NSTEP = GwCfg<GW>::NSTEP, OCT = GW / 8;
     auto request = [&](int s, f32x4 (&x0)[NPT], f32x4 (&x1)[NPT]) {
         const int q = 2 * s + h;
-        const int t = q / OCT, oct = q - t * OCT;                                    // t = 9: octet 63 of width 56, zero weights
+        const int t = q / OCT, oct = q - t * OCT;                                    // t = 9: octet 63 of width 56 / 261 of width 232, zero weights
 #pragma unroll
         for (int pt = 0; pt < NPT; ++pt) {
             int ar = -1;
@@ -92,8 +93,9 @@ __device__ __forceinline__ void gwr_kloop(const unsigned char* wbase, const floa
     }
 }
 
+// RT = 8 (width 232, 128 accumulator registers): held to two waves per SIMD -- 234 registers, no scratch; unbounded the compiler takes 374 and one wave
 template <int GW, int RT, int NPT>
-__global__ __launch_bounds__(GWR_THREADS) void k_grouped_wide_rows(const GwrArgs p) {
+__global__ __launch_bounds__(GWR_THREADS, RT == 8 ? 2 : 1) void k_grouped_wide_rows(const GwrArgs p) {
     typedef GwCfg<GW> cfg;
     constexpr int MT = cfg::MT, NSTEP = cfg::NSTEP, NRS = MT / RT;
     static_assert(MT % RT == 0, "wave roles");
@@ -179,21 +181,26 @@ static int launch_grouped_wide_rows(const GwrArgs& g, hipStream_t stream) {
 // SIMD (256 CUs x 4) AT THE CAP, the threshold that separates the shapes measured with half the cap kept.
 constexpr long GWR_FILL = 3 * 1024;
 static int gwr_tiles_per_wave(int C, int gw, int m_cap) {
+    if (gw_frag_mt(gw) * 2 * 16 > 128) return 1;                                     // width 232: one tile's accumulators are 128 registers
     return (long)(C / gw) * (((long)m_cap + 63) / 64) < GWR_FILL ? 1 : 2;
 }
 
 // The wave roles.  Launched: every row tile of the group in one wave, one or two pixel tiles (gwr_tiles_per_wave).
 // LDN_GROUPED_WIDE_ROWS_FORM (read per call; tuning, tests and the measurements of DESIGN.md 4zc only) overrides the plan: "b1" / "b2" / "b4" =
 // that form with one / two / four pixel tiles, "a" = one row tile x four pixel tiles per wave (k_grouped_wide's split, the input gathered once
-// per row tile).
+// per row tile).  At width 232 only "a" and "b1" are compiled: "b2" and "b4" launch the plan's choice.
 template <int GW>
 static int dispatch_grouped_wide_rows(const GwrArgs& g, hipStream_t stream) {
     constexpr int MT = GwCfg<GW>::MT;
     const char* form = getenv("LDN_GROUPED_WIDE_ROWS_FORM");
     if (form && !strcmp(form, "a")) return launch_grouped_wide_rows<GW, 1, 4>(g, stream);
-    if (form && !strcmp(form, "b4")) return launch_grouped_wide_rows<GW, MT, 4>(g, stream);
-    const int npt = form && !strcmp(form, "b1") ? 1 : form && !strcmp(form, "b2") ? 2 : gwr_tiles_per_wave(g.C, GW, g.m_cap);
-    return npt == 1 ? launch_grouped_wide_rows<GW, MT, 1>(g, stream) : launch_grouped_wide_rows<GW, MT, 2>(g, stream);
+    if constexpr (MT * 2 * 16 > 128) {       // width 232: two pixel tiles of every row tile do not fit the accumulators; "b2" / "b4" are not
+        return launch_grouped_wide_rows<GW, MT, 1>(g, stream);      // compiled and fall back to the plan's choice, which is always "b1"
+    } else {
+        if (form && !strcmp(form, "b4")) return launch_grouped_wide_rows<GW, MT, 4>(g, stream);
+        const int npt = form && !strcmp(form, "b1") ? 1 : form && !strcmp(form, "b2") ? 2 : gwr_tiles_per_wave(g.C, GW, g.m_cap);
+        return npt == 1 ? launch_grouped_wide_rows<GW, MT, 1>(g, stream) : launch_grouped_wide_rows<GW, MT, 2>(g, stream);
+    }
 }
 
 }  // namespace ldn
@@ -213,7 +220,7 @@ extern "C" int ldn_grouped_wide_conv3x3_rows(const float* a, int lda, const int3
                                              int relu, float* out, int ldo, void* stream) {
     LDN_REQUIRE(a && nbr && w_frag && scale && shift && out, "ldn_grouped_wide_conv3x3_rows: null pointer");
     LDN_REQUIRE(ldn_grouped_wide_rows_ok(C, group_width),
-                "ldn_grouped_wide_conv3x3_rows: group width %d with %d channels is not built (widths 56 and 112, channels a multiple of the width)",
+                "ldn_grouped_wide_conv3x3_rows: group width %d with %d channels is not built (widths 56, 112 and 232, channels a multiple of the width)",
                 group_width, C);
     LDN_REQUIRE(lda % 4 == 0 && ldo % 4 == 0 && lda >= C && ldo >= C,
                 "ldn_grouped_wide_conv3x3_rows: strides must be multiples of 4 and at least C");
@@ -225,5 +232,6 @@ extern "C" int ldn_grouped_wide_conv3x3_rows(const float* a, int lda, const int3
     g.a = a; g.lda = lda; g.nbr = nbr; g.m_count = m_count; g.m_cap = m_cap; g.wf = static_cast<const unsigned char*>(w_frag); g.C = C;
     g.scale = scale; g.shift = shift; g.relu = relu; g.out = out; g.ldo = ldo;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return group_width == 56 ? dispatch_grouped_wide_rows<56>(g, st) : dispatch_grouped_wide_rows<112>(g, st);
+    return group_width == 56 ? dispatch_grouped_wide_rows<56>(g, st)
+                             : group_width == 112 ? dispatch_grouped_wide_rows<112>(g, st) : dispatch_grouped_wide_rows<232>(g, st);
 }

@@ -1,9 +1,9 @@
-// ldn_wgrad_grouped_wide.hip -- the weight gradient of the grouped 3x3 over packed rows at group widths 56 and 112, on the matrix cores
+// ldn_wgrad_grouped_wide.hip -- the weight gradient of the grouped 3x3 over packed rows at group widths 56, 112 and 232, on the matrix cores
 // (ldn_wgrad_grouped_wide_rows; include/ldn_hip.h):
 //
-//     dW[c, t, j] = sum_{r < count} dY[r, c] * A[nbr[r * 9 + t], (c / gw) * gw + j]         c < C, t < 9, j < gw,  gw = 56 | 112
+//     dW[c, t, j] = sum_{r < count} dY[r, c] * A[nbr[r * 9 + t], (c / gw) * gw + j]         c < C, t < 9, j < gw,  gw = 56 | 112 | 232
 //
-// Per group a gw x 9 gw GEMM (56 x 504 or 112 x 1008) whose REDUCTION runs over the packed rows: the GEMM of ldn_wgrad.hip (k_wgrad) with
+// Per group a gw x 9 gw GEMM (56 x 504, 112 x 1008 or 232 x 2088) whose REDUCTION runs over the packed rows: the GEMM of ldn_wgrad.hip (k_wgrad) with
 // cin = cout = gw, a column offset g * gw into dY and into A and a row offset g * gw into dW.  The groups ride in the grid: one launch covers
 // every group (plus the reduce launch when the rows are split).  The staging scheme is k_wgrad's, restated here so that that translation
 // unit's kernels stay what they are: a thread reads 8 consecutive rows of one column quad (8 x 16 B), transposes them in registers and writes
@@ -13,7 +13,9 @@
 // nbr[r * 9 + t], channels g * gw + j; gw % 4 == 0, so a column quad never straddles a tap.  No [rows, 9 gw] matrix exists.
 //
 // Tiles: the dY tile is 64 (gw 56: 56 live) or 128 (gw 112: 112 live) columns, the A tile 128 columns of the flattened (tap, channel) axis --
-// 4 column tiles over F = 504, 8 over F = 1008.  The group's dY tile is re-staged once per column tile (the form that was launched; a
+// 4 column tiles over F = 504, 8 over F = 1008.  Width 232 has TWO dY tiles of 128 (n-tiles; the second with 104 live columns) and 17 column
+// tiles over F = 2088 (the last with 40 live): the n-tile is one more index of the grid over the gw 112 kernel, a column offset into dY and a
+// row offset into dW.  The group's dY tile is re-staged once per column tile (the form that was launched; a
 // workgroup that stages dY once and walks several column tiles was NOT built or timed).
 //
 // Rows r >= count are never read (neither dY nor nbr); a table entry < 0 or >= a_valid is a zero row.  Determinism: the rows are split over
@@ -39,7 +41,7 @@ constexpr int WGW_MAX_SPLITS = 256;
 struct WgradGroupedWideArgs {
     const float* dy; const float* a; const int32_t* nbr; const int32_t* m_count;
     float* out; float* work;
-    int lddy, lda, a_valid, m_cap, C, gw, splits, rps, ftn;
+    int lddy, lda, a_valid, m_cap, C, gw, splits, rps, ftn, ntn;
 };
 
 __device__ __forceinline__ int wgw_count(const WgradGroupedWideArgs& p) {
@@ -47,7 +49,8 @@ __device__ __forceinline__ int wgw_count(const WgradGroupedWideArgs& p) {
     return c < 0 ? 0 : (c > p.m_cap ? p.m_cap : c);
 }
 
-// grid = ((C / gw) * ftn, splits); 256 threads = 4 waves as 2 (n) x 2 (columns); wave tile = (NS x 32) x 64; NS = 1: gw 56, NS = 2: gw 112
+// grid = ((C / gw) * ntn * ftn, splits); 256 threads = 4 waves as 2 (n) x 2 (columns); wave tile = (NS x 32) x 64; NS = 1: gw 56, NS = 2: gw 112
+// and (ntn = 2 n-tiles) gw 232
 template <int NS, bool F32>
 __global__ __launch_bounds__(256) void k_wgrad_gwide(const WgradGroupedWideArgs p) {
     constexpr int NT = 64 * NS;
@@ -59,7 +62,8 @@ __global__ __launch_bounds__(256) void k_wgrad_gwide(const WgradGroupedWideArgs 
     if (p.splits > 1 && r_begin >= count) return;       // (uniform) this split holds no rows: the reduce launch does not read its tile
     const int r_end = min(count, r_begin + p.rps);
     const int nchunks = r_begin < r_end ? (r_end - r_begin + WGW_CHUNK - 1) / WGW_CHUNK : 0;
-    const int ft = blockIdx.x % p.ftn, grp = blockIdx.x / p.ftn;      // a group's column tiles are neighbours in the grid
+    const int ft = blockIdx.x % p.ftn, gn = blockIdx.x / p.ftn;       // a group's column tiles are neighbours in the grid
+    const int grp = gn / p.ntn, n0 = (gn - grp * p.ntn) * NT;         // the n-tile: dY columns / dW rows n0 .. n0 + NT - 1 of the group
     const int c0 = grp * p.gw, f0 = ft * WGW_KT;
     const int F = 9 * p.gw;
 
@@ -70,7 +74,7 @@ __global__ __launch_bounds__(256) void k_wgrad_gwide(const WgradGroupedWideArgs 
     const bool stager = cc < NT + WGW_KT;
     const int lcol = is_dy ? cc : cc - NT;               // column inside the operand's image
     unsigned char* s_dst = s_img + (is_dy ? 0 : NT * WGW_PITCH) + lcol * WGW_PITCH;
-    const int gcol = is_dy ? lcol : f0 + lcol;           // column inside the group: n, or f = t * gw + j
+    const int gcol = is_dy ? n0 + lcol : f0 + lcol;      // column inside the group: n, or f = t * gw + j
     const bool col_ok = stager && (is_dy ? gcol < p.gw : gcol < F);
     const int tap = is_dy ? 0 : gcol / p.gw;
     const int kch = c0 + (is_dy ? gcol : gcol - tap * p.gw);     // channel of dY / of A: < C wherever col_ok
@@ -180,7 +184,7 @@ __global__ __launch_bounds__(256) void k_wgrad_gwide(const WgradGroupedWideArgs 
             const int f = f0 + (wk * 2 + b) * 32 + l31;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int n = (wn * NS + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int n = n0 + (wn * NS + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
                 if (n < p.gw && f < F) dst[(size_t)n * F + f] = acc[a][b][r];
             }
         }
@@ -201,13 +205,14 @@ __global__ __launch_bounds__(256) void k_wgrad_gwide_reduce(const WgradGroupedWi
 LDN_DEFINE_TU_VIOLATIONS(tu_violations_wgrad_grouped_wide)
 
 static bool wgw_ok(int C, int gw) {
-    return (gw == 56 || gw == 112) && C > 0 && C % gw == 0 && C <= 4096;
+    return (gw == 56 || gw == 112 || gw == 232) && C > 0 && C % gw == 0 && C <= 4096;
 }
 
 // the launch plan: a function of m_cap and the shapes ONLY
-static void wgw_plan(int m_cap, int C, int gw, int* ftn, int* splits, int* rps) {
+static void wgw_plan(int m_cap, int C, int gw, int* ftn, int* ntn, int* splits, int* rps) {
     *ftn = ceil_div(9 * gw, WGW_KT);
-    int s = ceil_div(WGW_TARGET_WGS, (C / gw) * *ftn);
+    *ntn = ceil_div(gw, 128);                             // dY tiles of the group: 1 at gw 56 / 112, 2 at gw 232
+    int s = ceil_div(WGW_TARGET_WGS, (C / gw) * *ntn * *ftn);
     const int most = m_cap / WGW_MIN_SPLIT_ROWS;
     if (s > most) s = most;
     if (s > WGW_MAX_SPLITS) s = WGW_MAX_SPLITS;
@@ -224,8 +229,8 @@ extern "C" int ldn_wgrad_grouped_wide_rows_ok(int C, int gw) { return wgw_ok(C, 
 
 extern "C" size_t ldn_wgrad_grouped_wide_rows_workspace_bytes(int m_cap, int C, int gw) {
     if (!wgw_ok(C, gw) || m_cap < 0) return 0;
-    int ftn, splits, rps;
-    wgw_plan(m_cap, C, gw, &ftn, &splits, &rps);
+    int ftn, ntn, splits, rps;
+    wgw_plan(m_cap, C, gw, &ftn, &ntn, &splits, &rps);
     return splits > 1 ? (size_t)splits * C * 9 * gw * sizeof(float) : 0;
 }
 
@@ -235,7 +240,7 @@ extern "C" int ldn_wgrad_grouped_wide_rows(const float* dy, int lddy, const floa
     LDN_REQUIRE(dy && a && nbr && dw, "ldn_wgrad_grouped_wide_rows: null pointer");
     LDN_REQUIRE(math_mode >= -1 && math_mode <= 1, "ldn_wgrad_grouped_wide_rows: math_mode must be LDN_MATH_DEFAULT (-1), LDN_MATH_FP32 (0) or LDN_MATH_BF16X3 (1), got %d", math_mode);
     const int math = math_mode < 0 ? ldn_default_math_mode() : math_mode;
-    LDN_REQUIRE(wgw_ok(C, gw), "ldn_wgrad_grouped_wide_rows: unsupported shape C %d group width %d (group width 56 | 112, C %% group width == 0, C <= 4096)", C, gw);
+    LDN_REQUIRE(wgw_ok(C, gw), "ldn_wgrad_grouped_wide_rows: unsupported shape C %d group width %d (group width 56 | 112 | 232, C %% group width == 0, C <= 4096)", C, gw);
     LDN_REQUIRE(m_cap >= 0 && a_valid >= 0, "ldn_wgrad_grouped_wide_rows: negative row count");
     LDN_REQUIRE(lddy >= C && lda >= C && lddy % 4 == 0 && lda % 4 == 0, "ldn_wgrad_grouped_wide_rows: lddy >= C, lda >= C, both multiples of 4 (got %d, %d)", lddy, lda);
     LDN_REQUIRE((uintptr_t)dy % 16 == 0 && (uintptr_t)a % 16 == 0 && (uintptr_t)dw % 16 == 0 && (uintptr_t)work % 16 == 0,
@@ -243,10 +248,10 @@ extern "C" int ldn_wgrad_grouped_wide_rows(const float* dy, int lddy, const floa
     WgradGroupedWideArgs p;
     p.dy = dy; p.a = a; p.nbr = nbr; p.m_count = m_count; p.out = dw; p.work = work;
     p.lddy = lddy; p.lda = lda; p.a_valid = a_valid; p.m_cap = m_cap; p.C = C; p.gw = gw;
-    wgw_plan(m_cap, C, gw, &p.ftn, &p.splits, &p.rps);
+    wgw_plan(m_cap, C, gw, &p.ftn, &p.ntn, &p.splits, &p.rps);
     LDN_REQUIRE(p.splits == 1 || work, "ldn_wgrad_grouped_wide_rows: this shape splits its rows %d ways and needs the workspace (ldn_wgrad_grouped_wide_rows_workspace_bytes)", p.splits);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)((C / gw) * p.ftn), (unsigned)p.splits);
+    const dim3 grid((unsigned)((C / gw) * p.ntn * p.ftn), (unsigned)p.splits);
     if (math == LDN_MATH_FP32) {
         if (gw == 56) k_wgrad_gwide<1, true><<<grid, 256, 0, st>>>(p); else k_wgrad_gwide<2, true><<<grid, 256, 0, st>>>(p);
     } else {

@@ -29,7 +29,7 @@ from .laud_resnet import (Masker_channel_conv_linear, Masker_channel_MLP, Masker
                           _eval_only, _fold_bn)
 
 __all__ = ["LAD_RegNet", "BlockParams", "lad_regnet_y_400mf", "lad_regnet_y_800mf", "lad_regnet_y_1_6gf",
-           "lad_regnet_y_3_2gf", "lad_regnet_y_8gf", "lad_regnet_y_16gf"]
+           "lad_regnet_y_3_2gf", "lad_regnet_y_8gf", "lad_regnet_y_16gf", "lad_regnet_y_32gf"]
 
 
 def _make_divisible(v, divisor, min_value=None):
@@ -154,7 +154,7 @@ USE_GROUPED_IMAGES = os.environ.get("LDN_GROUPED_IMAGES", "1") != "0"   # ... th
 USE_GROUPED_MFMA_WIDTHS = os.environ.get("LDN_GROUPED_MFMA_WIDTHS", "0") == "1"   # ... group widths 8 and 24 on the matrix cores (OFF by default)
 USE_GROUPED_MFMA_WIDTHS_IMAGES = os.environ.get("LDN_GROUPED_MFMA_WIDTHS_IMAGES", "0") == "1"   # ... and their whole-image / SE-fused form (OFF by default)
 USE_GROUPED_MFMA_CHANNEL = os.environ.get("LDN_GROUPED_MFMA_CHANNEL", "0") == "1"   # ... conv b of channel / both mode on the matrix cores (OFF by default)
-USE_GROUPED_MFMA_WIDE = os.environ.get("LDN_GROUPED_MFMA_WIDE", "0") == "1"   # ... and at group widths 56 and 112 (OFF by default)
+USE_GROUPED_MFMA_WIDE = os.environ.get("LDN_GROUPED_MFMA_WIDE", "0") == "1"   # ... and at group widths 56, 112 and 232 (OFF by default)
 USE_GROUPED_MFMA_WIDE_ROWS = os.environ.get("LDN_GROUPED_MFMA_WIDE_ROWS", "0") == "1"   # ... and their packed-row form: layer skip, 'spatial', training (OFF by default)
 USE_SE_FUSED = os.environ.get("LDN_SE_FUSED", "1") != "0"               # ... the SE block folded into conv b's epilogue and conv c's input rows
 
@@ -176,7 +176,7 @@ CONV_B = {
         "images": ConvBForm("grouped_mfma_conv3x3_images", "USE_GROUPED_MFMA_WIDTHS_IMAGES", "grouped_mfma_images_fit"),
         "images_gap": ConvBForm("grouped_mfma_conv3x3_images_gap", "USE_SE_FUSED", "conv_rows_gated_fits"),
         "image": ConvBForm("grouped_chan_mfma_conv3x3_image", "USE_GROUPED_MFMA_CHANNEL", "grouped_chan_mfma_ok")}),
-    "wide": ConvBFamily("wb_frag_wide", "pack_grouped_wide_weights", (56, 112), {
+    "wide": ConvBFamily("wb_frag_wide", "pack_grouped_wide_weights", (56, 112, 232), {
         "rows": ConvBForm("grouped_wide_conv3x3_rows", "USE_GROUPED_MFMA_WIDE_ROWS", None),
         "image": ConvBForm("grouped_wide_conv3x3_image", "USE_GROUPED_MFMA_WIDE", "grouped_wide_ok")}),
 }
@@ -775,7 +775,8 @@ _Y = {"400mf": dict(depth=16, w_0=48, w_a=27.89, w_m=2.09, group_width=8),
       "1_6gf": dict(depth=27, w_0=48, w_a=20.71, w_m=2.65, group_width=24),
       "3_2gf": dict(depth=21, w_0=80, w_a=42.63, w_m=2.66, group_width=24),
       "8gf": dict(depth=17, w_0=192, w_a=76.82, w_m=2.19, group_width=56),
-      "16gf": dict(depth=18, w_0=200, w_a=106.23, w_m=2.48, group_width=112)}
+      "16gf": dict(depth=18, w_0=200, w_a=106.23, w_m=2.48, group_width=112),
+      "32gf": dict(depth=20, w_0=232, w_a=115.89, w_m=2.53, group_width=232)}
 
 
 def _factory(tag):
@@ -793,3 +794,4 @@ lad_regnet_y_1_6gf = _factory("1_6gf")
 lad_regnet_y_3_2gf = _factory("3_2gf")
 lad_regnet_y_8gf = _factory("8gf")
 lad_regnet_y_16gf = _factory("16gf")
+lad_regnet_y_32gf = _factory("32gf")

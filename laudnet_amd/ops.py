@@ -592,12 +592,12 @@ def wgrad_grouped_rows(dy2d, a2d, nbr, group_width, *, m_count=None, m_cap=None,
 
 
 def wgrad_grouped_wide_rows_ok(C, gw):
-    """Does ldn_wgrad_grouped_wide_rows take this shape (group width 56 | 112, C % gw == 0, C <= 4096)?"""
+    """Does ldn_wgrad_grouped_wide_rows take this shape (group width 56 | 112 | 232, C % gw == 0, C <= 4096)?"""
     return bool(L.load().ldn_wgrad_grouped_wide_rows_ok(int(C), int(gw)))
 
 
 def wgrad_grouped_wide_rows(dy2d, a2d, nbr, group_width, *, m_count=None, m_cap=None, a_valid=None, out=None, math=None):
-    """Weight gradient of the grouped 3x3 over packed rows at group widths 56 / 112, on the matrix cores (see ldn_wgrad_grouped_wide_rows):
+    """Weight gradient of the grouped 3x3 over packed rows at group widths 56 / 112 / 232, on the matrix cores (see ldn_wgrad_grouped_wide_rows):
     dW[c, t, j] = sum_{r < count} dy2d[r, c] * a2d[nbr[r * 9 + t], (c // gw) * gw + j] (an index < 0 or >= a_valid is a zero row).  The
     signature and the checks of wgrad_grouped_rows: dy2d [m_cap, lddy >= C], a2d [rows, lda >= C], both with C columns; rows past the
     device-side count are not read.  Returns out [C, 9, gw] (= the weight layout of grouped_conv3x3_rows), fully overwritten.  Deterministic
@@ -1074,7 +1074,8 @@ def conv_packed(a2d, w, scale, shift, out2d, *, B=1, row_prefix=None, m_count=No
 _Frag = namedtuple("_Frag", "widths weight_bytes packer built geometry")
 _FRAG = {"g16": _Frag((16,), "ldn_grouped16_weight_bytes", "pack_grouped16_weights", "16", None),
          "gw": _Frag((8, 24), "ldn_grouped_mfma_weight_bytes", "pack_grouped_mfma_weights", "8 and 24; width 16 is {twin}", None),
-         "wide": _Frag((56, 112), "ldn_grouped_wide_weight_bytes", "pack_grouped_wide_weights", "56 and 112", {56: (32, 2), 112: (63, 4)})}
+         "wide": _Frag((56, 112, 232), "ldn_grouped_wide_weight_bytes", "pack_grouped_wide_weights", "56, 112 and 232",
+                       {56: (32, 2), 112: (63, 4), 232: (131, 8)})}
 
 
 def _check_frag(name, w_frag, family, gw):
@@ -1308,24 +1309,24 @@ def grouped_chan_mfma_conv3x3_image(a_nhwc, w_frag, group_width, ch_idx, ch_cnt,
 
 
 def grouped_wide_ok(C, group_width, Hi, Wi, stride):
-    """Whether ldn_grouped_wide_conv3x3_image takes the shape: group width 56 or 112, C a positive multiple of it, stride 1 or 2 and a
+    """Whether ldn_grouped_wide_conv3x3_image takes the shape: group width 56, 112 or 232, C a positive multiple of it, stride 1 or 2 and a
     rectangle of the Hi x Wi input map fits the LDS (host arithmetic only)."""
     return bool(L.load().ldn_grouped_wide_ok(int(C), int(group_width), int(Hi), int(Wi), int(stride)))
 
 
 def pack_grouped_wide_weights(w, group_width):
-    """w [C, 9, gw] fp32 (out channel, tap, in channel of the group), gw 56 or 112 -> the pre-split fragments of
+    """w [C, 9, gw] fp32 (out channel, tap, in channel of the group), gw 56, 112 or 232 -> the pre-split fragments of
     ldn_grouped_wide_conv3x3_image, bf16 [G = C / gw][S][M][64][2][8] with S = 32 K steps and M = 2 row tiles (gw 56), S = 63 and M = 4
-    (gw 112); ldn_grouped_wide_weight_bytes(C, gw) bytes.  The index formula: with Q = gw / 8 octets per tap,
+    (gw 112), S = 131 and M = 8 (gw 232); ldn_grouped_wide_weight_bytes(C, gw) bytes.  The index formula: with Q = gw / 8 octets per tap,
 
         frag[g, s, m, l, p, e] = split_p( w[g * gw + 32 * m + (l & 31),  q // Q,  8 * (q % Q) + e] ),    q = 2 * s + (l >> 5),
 
     p = 0 the hi part bf16(w), p = 1 the lo part bf16(w - hi); the element is ZERO where the out channel of the group 32 * m + (l & 31) is
-    >= gw (pad rows 56-63 / 112-127) or the octet q is >= 9 * Q (q = 63 at gw 56).  K is cut into octets q of 8 consecutive in channels
-    of one tap; a lane's 16 values [8 hi | 8 lo] are contiguous, a (step, row tile) is one 2 KB line, a group's fragments are 128 KB / 504 KB."""
+    >= gw (pad rows 56-63 / 112-127 / 232-255) or the octet q is >= 9 * Q (q = 63 at gw 56, q = 261 at gw 232).  K is cut into octets q of 8 consecutive in channels
+    of one tap; a lane's 16 values [8 hi | 8 lo] are contiguous, a (step, row tile) is one 2 KB line, a group's fragments are 128 KB / 504 KB / 2096 KB."""
     gw = int(group_width)
     if gw not in _FRAG["wide"].widths or w.dim() != 3 or w.shape[0] == 0 or w.shape[0] % gw or tuple(w.shape[1:]) != (9, gw):
-        raise L.LdnError(f"pack_grouped_wide_weights: expected [C % gw == 0, 9, gw] with gw 56 or 112 (got {tuple(w.shape)}, group width {gw})")
+        raise L.LdnError(f"pack_grouped_wide_weights: expected [C % gw == 0, 9, gw] with gw 56, 112 or 232 (got {tuple(w.shape)}, group width {gw})")
     steps, mt = _FRAG["wide"].geometry[gw]
     G = w.shape[0] // gw
     k = torch.zeros(G, 32 * mt, 2 * steps, 8, device=w.device, dtype=torch.float32)
@@ -1336,7 +1337,7 @@ def pack_grouped_wide_weights(w, group_width):
 
 
 def grouped_wide_conv3x3_image(a_nhwc, w_frag, group_width, ch_idx, ch_cnt, scale, shift, out_nhwc, *, stride=1, relu=1):
-    """Grouped 3x3 conv (group width 56 or 112) + BN (+ReLU) on left-packed per-image channel subsets on the matrix cores: the contract of
+    """Grouped 3x3 conv (group width 56, 112 or 232) + BN (+ReLU) on left-packed per-image channel subsets on the matrix cores: the contract of
     grouped_conv3x3_image (see ldn_grouped_wide_conv3x3_image) with w_frag = pack_grouped_wide_weights(w, gw)."""
     gw = int(group_width)
     C = _check_frag("grouped_wide_conv3x3_image", w_frag, "wide", gw)
@@ -1344,12 +1345,12 @@ def grouped_wide_conv3x3_image(a_nhwc, w_frag, group_width, ch_idx, ch_cnt, scal
 
 
 def grouped_wide_rows_ok(C, group_width):
-    """Whether ldn_grouped_wide_conv3x3_rows takes the shape: group width 56 or 112, C a positive multiple of it (host arithmetic only)."""
+    """Whether ldn_grouped_wide_conv3x3_rows takes the shape: group width 56, 112 or 232, C a positive multiple of it (host arithmetic only)."""
     return bool(L.load().ldn_grouped_wide_rows_ok(int(C), int(group_width)))
 
 
 def grouped_wide_conv3x3_rows(a2d, nbr, w_frag, group_width, scale, shift, out2d, *, m_count=None, m_cap=None, relu=1):
-    """Grouped 3x3 conv (group width 56 or 112) + BN (+ReLU) over packed rows on the matrix cores: the contract of grouped_mfma_conv3x3_rows
+    """Grouped 3x3 conv (group width 56, 112 or 232) + BN (+ReLU) over packed rows on the matrix cores: the contract of grouped_mfma_conv3x3_rows
     (see ldn_grouped_wide_conv3x3_rows) with w_frag = pack_grouped_wide_weights(w, gw), the fragments of grouped_wide_conv3x3_image.
     a2d / out2d may be column slices of wider matrices (row strides multiples of 4): the columns past C are neither read nor written."""
     gw = int(group_width)

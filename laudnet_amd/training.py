@@ -49,7 +49,7 @@ where no ReLU can flip (tests/test_hip_training_f64.py, tests/train_ref.py), the
 LAD-RegNet (`laud_regnet.ResBottleneckBlock`) trains in its LAYER-SKIP form -- dyn_mode 'spatial' with one keep / skip bit per image, SE present, stride
 1 and 2, with and without `proj`: a kept image runs a -> grouped b -> SE -> c on packed rows in both directions (`_RegNetSkipBranchFn`: the grouped
 3x3's adjoint is its forward kernel over the transposed neighbour table with per-group transposed weights, its weight gradient `ops.wgrad_grouped_rows`
-at group widths 8 / 16 / 24 -- at widths 56 / 112 `ops.wgrad_grouped_wide_rows` behind USE_WGRAD_GROUPED_WIDE (env LDN_WGRAD_GROUPED_WIDE=1; default OFF:
+at group widths 8 / 16 / 24 -- at widths 56 / 112 / 232 `ops.wgrad_grouped_wide_rows` behind USE_WGRAD_GROUPED_WIDE (env LDN_WGRAD_GROUPED_WIDE=1; default OFF:
 the gather + bmm path, as before that kernel existed; LDN_WGRAD=0 forces that path everywhere; one chooser, `_weight_grad_conv_b`, for all three
 LAD-RegNet branch Fns; tests/test_hip_training_wgrad_grouped_wide.py) --
 the squeeze / excite and their backward tensor ops on the [slots, Ho Wo, C] view of the rows); the same three entry points take it and a whole
@@ -111,7 +111,7 @@ from .laud_regnet import LAD_RegNet, ResBottleneckBlock, _conv_b_frag, _conv_b_r
 # kernel (profiles/train_step_regnet.jsonl)
 USE_WGRAD_KERNEL = os.environ.get("LDN_WGRAD", "1") != "0"
 
-# conv b's weight gradient at group widths 56 / 112 (lad_regnet_y_8gf / 16gf) on ldn_wgrad_grouped_wide_rows (the matrix cores); env
+# conv b's weight gradient at group widths 56 / 112 / 232 (lad_regnet_y_8gf / 16gf / 32gf) on ldn_wgrad_grouped_wide_rows (the matrix cores); env
 # LDN_WGRAD_GROUPED_WIDE=1 turns it on, under USE_WGRAD_KERNEL.  Off by default: with it off every dispatch is what it was before the kernel
 # existed (the gather + bmm path at these widths).  Independent of laud_regnet.USE_GROUPED_MFMA_WIDE_ROWS (the forward's and the adjoint's switch)
 USE_WGRAD_GROUPED_WIDE = os.environ.get("LDN_WGRAD_GROUPED_WIDE", "0") == "1"
@@ -198,13 +198,13 @@ def _wgrad_grouped_kernel(C, gw):
 
 def _wgrad_grouped_wide_kernel(C, gw):
     """Does the grouped weight gradient run on ldn_wgrad_grouped_wide_rows (both switches -- LDN_WGRAD=0 still forces the PyTorch path
-    everywhere -- and that kernel's shape predicate: group widths 56 / 112)?"""
+    everywhere -- and that kernel's shape predicate: group widths 56 / 112 / 232)?"""
     return USE_WGRAD_KERNEL and USE_WGRAD_GROUPED_WIDE and ops.wgrad_grouped_wide_rows_ok(C, gw)
 
 
 def _weight_grad_conv_b(dy, h_a, ix, gw, m_count, count3=None):
     """d W_b [C, gw, 3, 3] of LAD-RegNet's conv b from d y_b [cap3, C] and conv b's input h_a [cap1, C]: the one place that chooses between
-    ldn_wgrad_grouped_rows (widths 8 / 16 / 24), ldn_wgrad_grouped_wide_rows (widths 56 / 112, behind USE_WGRAD_GROUPED_WIDE) and the
+    ldn_wgrad_grouped_rows (widths 8 / 16 / 24), ldn_wgrad_grouped_wide_rows (widths 56 / 112 / 232, behind USE_WGRAD_GROUPED_WIDE) and the
     gather + bmm path.  m_count = the device-side row count for the kernels; count3 = the same for the fallback (None: rows past the
     count carry d y_b == 0 and valid table entries)."""
     C = dy.shape[1]
@@ -599,7 +599,7 @@ def _conv_b_bare(wr, gw, x, nbr, y, m_count, m_cap, families=None):
 
 def _conv_b_adjoint(dy, nbrT, wbr, gw, dha, m_count, m_cap):
     """b^T: the forward kernel over the transposed neighbour table with per-group transposed weights, into the zeroed dha.  Never the width-16
-    matrix-core kernel: the VALU one, or those of widths 8 / 24 and 56 / 112 behind their switches."""
+    matrix-core kernel: the VALU one, or those of widths 8 / 24 and 56 / 112 / 232 behind their switches."""
     _conv_b_bare(grouped_weight_T(wbr, gw), gw, dy, nbrT, dha, m_count, m_cap, families=("gw", "wide"))
 
 
@@ -863,7 +863,7 @@ class _BatchStatsBranchFn(torch.autograd.Function):
 
 def _conv_b_plain(wbr, gw, h_a, nbr, y_b, m_count, m_cap):
     """the grouped 3x3 alone -- scale 1, shift 0, no ReLU -- with laud_regnet._conv_b_rows' choice of kernel: the matrix cores for group width 16
-    in bf16x3 mode (widths 8 / 24 and 56 / 112 behind their switches), else the fp32 VALU kernel"""
+    in bf16x3 mode (widths 8 / 24 and 56 / 112 / 232 behind their switches), else the fp32 VALU kernel"""
     _conv_b_bare(wbr, gw, h_a, nbr, y_b, m_count, m_cap)
 
 

@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""ops.grouped_wide_conv3x3_image (LAD-RegNet conv b of channel / both mode on the matrix cores at group widths 56 and 112, bf16x3,
-k_grouped_wide<56 | 112>) beside ops.grouped_conv3x3_image (k_grouped3x3_chan, the fp32 VALU kernel that runs while
-laud_regnet.USE_GROUPED_MFMA_WIDE is off), then a whole channel-mode eval step of lad_regnet_y_8gf with the switch on and off under the same
+"""ops.grouped_wide_conv3x3_image (LAD-RegNet conv b of channel / both mode on the matrix cores at group widths 56, 112 and 232, bf16x3,
+k_grouped_wide<56 | 112 | 232>) beside ops.grouped_conv3x3_image (k_grouped3x3_chan, the fp32 VALU kernel that runs while
+laud_regnet.USE_GROUPED_MFMA_WIDE is off), then a whole channel-mode eval step of lad_regnet_y_8gf (`--only step`) or lad_regnet_y_32gf (`--only step32`) with the switch on and off under the same
 forced masks.  This comparison -- the switch being the only difference -- is what decides a later flip of the default.
 
 Shapes: conv b (folded BatchNorm, ReLU) of the four stages of RegNetY-8GF (group width 56, w_b 224 / 448 / 896 / 2016) and RegNetY-16GF (112,
-224 / 448 / 1232 / 3024) on 56^2 / 28^2 / 14^2 / 7^2 output maps at stride 1, and each stage's stride-2 first-block shape (input map twice
+224 / 448 / 1232 / 3024; `--only regnet_y_32gf`: 232, w_b 232 / 696 / 1392 / 3712, which the driver leaves out) on 56^2 / 28^2 / 14^2 / 7^2 output maps at stride 1, and each stage's stride-2 first-block shape (input map twice
 the output map), `--batch` images.  Every image keeps each channel GRANULE with probability 0.5 (seeded), at granularity 1 and at
 granularity = group width -- the second is where whole groups drop, which is the only way a mask saves the matrix-core form any work.
 
@@ -19,7 +19,8 @@ pixels x padded out channels x padded K per active (image, group) pair) and thei
 Without `--only` this is a driver: every step is a child process under its own time limit, and the driver stops at the first step that
 fails or runs into its limit.  The first child (`--only probe`) times one warm-up window of each leg at every shape; the limit of a model's
 child is derived from that: twice (rounds x both windows + the warm-ups + a second per shape to build its inputs), plus a minute.
-usage: tools/bench_grouped_wide.py [--batch 64] [--rounds 9] [--window 0.5] [--out FILE] [--only probe|regnet_y_8gf|regnet_y_16gf|step]"""
+usage: tools/bench_grouped_wide.py [--batch 64] [--rounds 9] [--window 0.5] [--out FILE]
+                                   [--only probe|regnet_y_8gf|regnet_y_16gf|regnet_y_32gf|step|step32]"""
 import argparse
 import json
 import os
@@ -27,9 +28,11 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MODELS = {"regnet_y_8gf": (56, [224, 448, 896, 2016]), "regnet_y_16gf": (112, [224, 448, 1232, 3024])}
+MODELS = {"regnet_y_8gf": (56, [224, 448, 896, 2016]), "regnet_y_16gf": (112, [224, 448, 1232, 3024]), "regnet_y_32gf": (232, [232, 696, 1392, 3712])}
+DRIVEN = ("regnet_y_8gf", "regnet_y_16gf")     # the models of the driver and its probe; the 32GF shapes run by name (--only regnet_y_32gf, step32)
+SLOW_WINDOW_S, SLOW_ROUNDS = 5.0, 3            # a leg whose one window takes longer (the VALU kernel at width 232) runs 3 rounds
 MAPS = [56, 28, 14, 7]
-PAD = {56: (64, 512), 112: (128, 1008)}        # padded out channels, padded K of a group
+PAD = {56: (64, 512), 112: (128, 1008), 232: (256, 2096)}        # padded out channels, padded K of a group
 ROOF = 2.5e15                                  # bf16 matrix FLOP/s of one MI355X
 PROBE_LIMIT, STEP_CHILD_LIMIT = 420, 420       # seconds: the probe child, the eval-step child
 
@@ -38,7 +41,7 @@ ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--rounds", type=int, default=9)
 ap.add_argument("--window", type=float, default=0.5)
 ap.add_argument("--out", default=None)
-ap.add_argument("--only", default=None, choices=["probe", "step"] + sorted(MODELS))
+ap.add_argument("--only", default=None, choices=["probe", "step", "step32"] + sorted(MODELS))
 args = ap.parse_args()
 assert args.rounds >= 9, "the median of at least 9 rounds"
 assert args.window >= 0.5, "windows of at least half a second"
@@ -56,7 +59,7 @@ if args.only is None:
         return p.stdout
 
     probe = [json.loads(l[6:]) for l in child("probe", PROBE_LIMIT, capture=True).splitlines() if l.startswith("PROBE ")]
-    for model in MODELS:
+    for model in DRIVEN:
         need = 0.0
         for r in (r for r in probe if r["model"] == model):
             need += 1.0 + sum(r["warmup_s"].values()) + args.rounds * sum(max(args.window, 1e-3 * ms) for ms in r["ms_per_call"].values())
@@ -114,10 +117,11 @@ def alternate(legs):
     """-> {leg: (median, min, max, calls per window)} in milliseconds per call; the legs alternate round by round"""
     calls = {k: warm_up(fn)[1] for k, fn in legs.items()}
     ms = {k: [] for k in legs}
-    for _ in range(args.rounds):
+    for i in range(args.rounds):
         for k, fn in legs.items():
-            ms[k].append(window(fn, calls[k]))
-    return {k: (sorted(v)[len(v) // 2], min(v), max(v), calls[k]) for k, v in ms.items()}
+            if i < SLOW_ROUNDS or 1e-3 * ms[k][0] * calls[k] <= SLOW_WINDOW_S:
+                ms[k].append(window(fn, calls[k]))
+    return {k: (sorted(v)[len(v) // 2], min(v), max(v), calls[k], len(v)) for k, v in ms.items()}
 
 
 def verdict(res, new, old):
@@ -158,7 +162,7 @@ def problems(model):
 
 
 def probe():
-    for model in MODELS:
+    for model in DRIVEN:
         for head, legs, _, _ in problems(model):
             wu = {k: warm_up(fn) for k, fn in legs.items()}
             print("PROBE " + json.dumps({"model": model, "stage": head["stage"], "stride": head["stride"], "granularity": head["granularity"],
@@ -178,15 +182,16 @@ def shapes(model):
               "mfma_us_median": round(1e3 * res["mfma"][0], 2), "valu_us_median": round(1e3 * res["valu"][0], 2),
               "mfma_us_min_max": [round(1e3 * res["mfma"][1], 2), round(1e3 * res["mfma"][2], 2)],
               "valu_us_min_max": [round(1e3 * res["valu"][1], 2), round(1e3 * res["valu"][2], 2)],
-              "calls_per_window": {k: v[3] for k, v in res.items()}, **verdict(res, "mfma", "valu"),
+              "calls_per_window": {k: v[3] for k, v in res.items()}, "rounds_per_leg": {k: v[4] for k, v in res.items()}, **verdict(res, "mfma", "valu"),
               "executed_gflop": round(flops / 1e9, 3), "executed_tflops": round(flops / (res["mfma"][0] * 1e-3) / 1e12, 1),
               "fraction_of_bf16_matrix_roof": round(flops / (res["mfma"][0] * 1e-3) / ROOF, 4),
               "max_abs_diff": float(f"{diff:.3g}"), "ref_max": float(f"{ref_max:.3g}")})
 
 
-def steps():
-    for gran in (1, 56):
-        net = laudnet_amd.lad_regnet_y_8gf(dyn_mode=["channel"] * 4, channel_dyn_granularity=[gran] * 4, channel_masker=["MLP"] * 4,
+def steps(model="regnet_y_8gf"):
+    gw = MODELS[model][0]
+    for gran in (1, gw):
+        net = getattr(laudnet_amd, "lad_" + model)(dyn_mode=["channel"] * 4, channel_dyn_granularity=[gran] * 4, channel_masker=["MLP"] * 4,
                                            channel_masker_layers=[2] * 4, num_classes=1000, input_size=224).eval()
         net.load_state_dict(damp_residual_branches(fill_state_dict(net.state_dict(), 1)))
         net = net.to(dev)
@@ -217,12 +222,12 @@ def steps():
         finally:
             ops.grouped_wide_conv3x3_image = real
             laud_regnet.USE_GROUPED_MFMA_WIDE = before
-        emit({"what": "channel-mode eval step of lad_regnet_y_8gf (forced masks, every granule kept with probability 0.5, bf16x3) with "
+        emit({"what": f"channel-mode eval step of lad_{model} (forced masks, every granule kept with probability 0.5, bf16x3) with "
                       "laud_regnet.USE_GROUPED_MFMA_WIDE on vs off",
-              "model": "regnet_y_8gf", "group_width": 56, "batch": args.batch, "granularity": gran, "rounds": args.rounds,
+              "model": model, "group_width": gw, "batch": args.batch, "granularity": gran, "rounds": args.rounds,
               "on_ms_median": round(res["on"][0], 3), "off_ms_median": round(res["off"][0], 3),
               "on_ms_min_max": [round(res["on"][1], 3), round(res["on"][2], 3)], "off_ms_min_max": [round(res["off"][1], 3), round(res["off"][2], 3)],
-              "calls_per_window": {k: v[3] for k, v in res.items()}, **verdict(res, "on", "off"),
+              "calls_per_window": {k: v[3] for k, v in res.items()}, "rounds_per_leg": {k: v[4] for k, v in res.items()}, **verdict(res, "on", "off"),
               "logits_max_abs_diff": float(f"{diff:.3g}"), "logits_ref_max": float(f"{ref_max:.3g}")})
         del net
 
@@ -231,5 +236,7 @@ if args.only == "probe":
     probe()
 elif args.only == "step":
     steps()
+elif args.only == "step32":
+    steps("regnet_y_32gf")
 else:
     shapes(args.only)

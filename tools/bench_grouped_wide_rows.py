@@ -1,24 +1,24 @@
 #!/usr/bin/env python3
-"""ops.grouped_wide_conv3x3_rows (LAD-RegNet conv b over packed rows at group widths 56 and 112 on the matrix cores, bf16x3) beside
+"""ops.grouped_wide_conv3x3_rows (LAD-RegNet conv b over packed rows at group widths 56, 112 and 232 on the matrix cores, bf16x3) beside
 ops.grouped_conv3x3_rows (the fp32 VALU kernel those widths run on while laud_regnet.USE_GROUPED_MFMA_WIDE_ROWS is off), then a whole
-layer-skip eval step and a whole training step of lad_regnet_y_8gf with the switch on and off.  The baseline is always the switch-off path
+layer-skip eval step and a whole training step of `--step-model` (lad_regnet_y_8gf) with the switch on and off.  The baseline is always the switch-off path
 in the same run -- the switch being the only difference -- which is what decides a later flip of the default.
 
 Shapes: conv b (folded BatchNorm, ReLU) of the four stages of RegNetY-8GF (group width 56, w_b 224 / 448 / 896 / 2016) and RegNetY-16GF
-(group width 112, w_b 224 / 448 / 1232 / 3024) on 56^2 / 28^2 / 14^2 / 7^2 output maps at stride 1, and each stage's stride-2 first-block
+(group width 112, w_b 224 / 448 / 1232 / 3024) and RegNetY-32GF (group width 232, w_b 232 / 696 / 1392 / 3712; `--models` picks) on 56^2 / 28^2 / 14^2 / 7^2 output maps at stride 1, and each stage's stride-2 first-block
 shape (input map twice the output map); `--batch` images of which a seeded half are kept (layer skip: the packed rows are the kept images'
 pixels, the lists built by ops.mask_to_index).
 
 The legs ALTERNATE round by round in one process.  A round is a window of back-to-back calls between two device events behind a
 synchronise, as many calls as fill `--window` seconds (>= 0.5; sized from a warm-up window per leg); the figure is the median over `--rounds`
-(>= 9) rounds, and a difference counts only where the two legs' ranges (min to max over the rounds) do not overlap.  Before the timing the
+(>= 9) rounds (a leg whose one window takes more than 5 s -- the VALU kernel at width 232 -- runs 3 rounds: `rounds_per_leg`), and a difference counts only where the two legs' ranges (min to max over the rounds) do not overlap.  Before the timing the
 two outputs are compared at the timed size and must agree to 1e-4 max(1, |ref|max) (asserted).  `frac_bf16_roof_executed` = 3 x the
 algorithmic FLOP rate (2 rows C 9 gw per call; bf16x3 executes three products per one) over the 2500 TFLOP/s dense bf16 matrix peak, as
 bench.py --full computes `frac_executed`.  `--forms` adds the other compiled wave roles (LDN_GROUPED_WIDE_ROWS_FORM = a / b1 / b4:
-csrc/ldn_grouped_wide_rows.hip) as further alternating legs on the stride-1 shapes.  One JSON line per shape and one per
+csrc/ldn_grouped_wide_rows.hip; width 232: a / b1, the forms compiled there) as further alternating legs on the stride-1 shapes.  One JSON line per shape and one per
 model step; `--out` also appends them to a file (profiles/grouped_wide_rows.jsonl).
 usage: tools/bench_grouped_wide_rows.py [--batch 64] [--train-batch 32] [--rounds 9] [--window 0.5] [--out FILE] [--forms] [--no-kernels]
-                                        [--no-models]"""
+                                        [--no-models] [--models regnet_y_8gf,regnet_y_16gf,regnet_y_32gf] [--step-model regnet_y_8gf]"""
 import argparse
 import json
 import os
@@ -42,13 +42,16 @@ ap.add_argument("--out", default=None)
 ap.add_argument("--forms", action="store_true")
 ap.add_argument("--no-kernels", action="store_true")
 ap.add_argument("--no-models", action="store_true")
+ap.add_argument("--models", default=None)
+ap.add_argument("--step-model", default="regnet_y_8gf")
 args = ap.parse_args()
 assert args.rounds >= 9, "the median of at least 9 rounds"
 assert args.window >= 0.5, "windows of at least half a second"
 dev = torch.device("cuda", 0)
 laudnet_amd.load_library()
 ops.set_math_mode("bf16x3")
-MODELS = {"regnet_y_8gf": (56, [224, 448, 896, 2016]), "regnet_y_16gf": (112, [224, 448, 1232, 3024])}
+MODELS = {"regnet_y_8gf": (56, [224, 448, 896, 2016]), "regnet_y_16gf": (112, [224, 448, 1232, 3024]), "regnet_y_32gf": (232, [232, 696, 1392, 3712])}
+SLOW_WINDOW_S, SLOW_ROUNDS = 5.0, 3
 MAPS = [56, 28, 14, 7]
 BF16_MFMA_PEAK_TFLOPS = 2500.0      # bench.py
 FORM_ENV = "LDN_GROUPED_WIDE_ROWS_FORM"
@@ -81,10 +84,11 @@ def alternate(legs, warm=10):
         window(fn, 2)
         calls[k] = max(3, int(args.window * 1e3 / window(fn, warm)) + 1)
     ms = {k: [] for k in legs}
-    for _ in range(args.rounds):
+    for i in range(args.rounds):
         for k, fn in legs.items():
-            ms[k].append(window(fn, calls[k]))
-    return {k: (sorted(v)[len(v) // 2], min(v), max(v), calls[k]) for k, v in ms.items()}
+            if i < SLOW_ROUNDS or 1e-3 * ms[k][0] * calls[k] <= SLOW_WINDOW_S:      # a leg whose window takes more than 5 s: 3 rounds
+                ms[k].append(window(fn, calls[k]))
+    return {k: (sorted(v)[len(v) // 2], min(v), max(v), calls[k], len(v)) for k, v in ms.items()}
 
 
 def verdict(res, new, old):
@@ -104,7 +108,8 @@ def with_form(form, fn):
 
 
 if not args.no_kernels:
-    for model, (gw, widths) in MODELS.items():
+    for model in (args.models.split(",") if args.models else MODELS):
+        gw, widths = MODELS[model]
         for stride in (1, 2):
             for stage, (C, S) in enumerate(zip(widths, MAPS)):
                 B = args.batch
@@ -120,7 +125,7 @@ if not args.no_kernels:
                 new = lambda: ops.grouped_wide_conv3x3_rows(h_a, ix.nbr, frag, gw, scale, shift, out_new, m_count=ix.cnt[0:1], m_cap=ix.cap3, relu=1)
                 legs = {"mfma": with_form(None, new),
                         "valu": lambda: ops.grouped_conv3x3_rows(h_a, ix.nbr, w, gw, scale, shift, out_old, m_count=ix.cnt[0:1], m_cap=ix.cap3, relu=1)}
-                forms = ("a", "b1", "b4") if args.forms and stride == 1 else ()
+                forms = (("a", "b1") if gw == 232 else ("a", "b1", "b4")) if args.forms and stride == 1 else ()
                 for form in forms:
                     legs["form_" + form] = with_form(form, new)
                 legs["valu"]()
@@ -142,8 +147,8 @@ if not args.no_kernels:
                        "mfma_us_median": round(1e3 * res["mfma"][0], 2), "valu_us_median": round(1e3 * res["valu"][0], 2),
                        "mfma_us_min_max": [round(1e3 * res["mfma"][1], 2), round(1e3 * res["mfma"][2], 2)],
                        "valu_us_min_max": [round(1e3 * res["valu"][1], 2), round(1e3 * res["valu"][2], 2)],
-                       "calls_per_window": {k: v[3] for k, v in res.items()}, **verdict(res, "mfma", "valu"),
-                       "algorithmic_tflops_mfma": round(tflops, 2), "frac_bf16_roof_executed": round(3 * tflops / BF16_MFMA_PEAK_TFLOPS, 4),
+                       "calls_per_window": {k: v[3] for k, v in res.items()}, "rounds_per_leg": {k: v[4] for k, v in res.items()},
+                       **verdict(res, "mfma", "valu"), "algorithmic_tflops_mfma": round(tflops, 2), "frac_bf16_roof_executed": round(3 * tflops / BF16_MFMA_PEAK_TFLOPS, 4),
                        "max_abs_diff": float(f"{diffs['mfma']:.3g}"), "ref_max": float(f"{ref_max:.3g}")}
                 for form in forms:
                     r = res["form_" + form]
@@ -152,10 +157,10 @@ if not args.no_kernels:
 
 if not args.no_models:
     from laudnet_amd.training import prepare_for_training, train_forward
-    model, gw = "regnet_y_8gf", 56
+    model, gw = args.step_model, MODELS[args.step_model][0]
 
     def build(batch):
-        net = laudnet_amd.lad_regnet_y_8gf(dyn_mode=["spatial"] * 4, mask_spatial_granularity=MAPS, num_classes=1000, input_size=224).eval()
+        net = getattr(laudnet_amd, "lad_" + model)(dyn_mode=["spatial"] * 4, mask_spatial_granularity=MAPS, num_classes=1000, input_size=224).eval()
         net.load_state_dict(damp_residual_branches(fill_state_dict(net.state_dict(), 1)))
         net = net.to(dev)
         for i, blk in enumerate(net.blocks()):      # layer skip: one decision per image, a seeded half kept in every block
@@ -173,7 +178,7 @@ if not args.no_models:
         emit({"what": what, "model": model, "group_width": gw, "batch": batch, "rounds": args.rounds,
               "on_ms_median": round(res["on"][0], 3), "off_ms_median": round(res["off"][0], 3),
               "on_ms_min_max": [round(res["on"][1], 3), round(res["on"][2], 3)], "off_ms_min_max": [round(res["off"][1], 3), round(res["off"][2], 3)],
-              "calls_per_window": {k: v[3] for k, v in res.items()}, **verdict(res, "on", "off"),
+              "calls_per_window": {k: v[3] for k, v in res.items()}, "rounds_per_leg": {k: v[4] for k, v in res.items()}, **verdict(res, "on", "off"),
               key + "_max_abs_diff": float(f"{diff:.3g}"), key + "_ref_max": float(f"{ref_max:.3g}")})
 
     net, x = build(args.batch)

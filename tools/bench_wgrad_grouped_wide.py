@@ -1,16 +1,17 @@
 #!/usr/bin/env python3
-"""ops.wgrad_grouped_wide_rows (the weight gradient of LAD-RegNet's conv b over packed rows at group widths 56 and 112 on the matrix cores,
-bf16x3) beside the two ways to compute it without that kernel, then a whole training step of lad_regnet_y_8gf with
+"""ops.wgrad_grouped_wide_rows (the weight gradient of LAD-RegNet's conv b over packed rows at group widths 56, 112 and 232 on the matrix
+cores, bf16x3) beside the two ways to compute it without that kernel, then a whole training step of `--step-model` (lad_regnet_y_8gf) with
 training.USE_WGRAD_GROUPED_WIDE on and off.  The yardstick is always the switch-off path in the same run.
 
 Legs per shape:
     (a) kernel       ops.wgrad_grouped_wide_rows: one launch over all groups (+ the reduce launch when the rows are split)
     (b) gather_bmm   training._weight_grad_grouped_3x3: the [rows, 9, C] gather, the per-group permute and one torch.bmm -- what training runs
                      at these widths while the switch is off
-    (c) slice_loop   a host loop of ops.wgrad_rows over the G column slices of dY and h_a into row slices of one output (2 G launches)
+    (c) slice_loop   a host loop of ops.wgrad_rows over the G column slices of dY and h_a into row slices of one output (2 G launches); left
+                     out, and said so in the record, where ops.wgrad_rows refuses the slice's width
 
 Shapes: conv b of the four stages of RegNetY-8GF (group width 56, w_b 224 / 448 / 896 / 2016) and RegNetY-16GF (group width 112, w_b 224 /
-448 / 1232 / 3024) on 56^2 / 28^2 / 14^2 / 7^2 output maps at stride 1, and each stage's stride-2 first-block shape (input map twice the
+448 / 1232 / 3024) and RegNetY-32GF (group width 232, w_b 232 / 696 / 1392 / 3712; `--models` picks) on 56^2 / 28^2 / 14^2 / 7^2 output maps at stride 1, and each stage's stride-2 first-block shape (input map twice the
 output map); `--batch` images of which a seeded half are kept (layer skip: the packed rows are the kept images' pixels, the lists built by
 ops.mask_to_index).  dY is a seeded normal matrix with zero rows past the count (what the backward hands over), h_a a seeded ReLU output.
 
@@ -21,7 +22,8 @@ synchronise, as many calls as fill `--window` seconds (>= 0.5; sized from a warm
 algorithmic FLOP rate (2 rows C 9 gw per call; bf16x3 executes three products per one) over the 2500 TFLOP/s dense bf16 matrix peak, as
 bench.py --full computes `frac_executed`.  One JSON line per shape and one for the model step; `--out` also appends them to a file
 (profiles/wgrad_grouped_wide.jsonl).
-usage: tools/bench_wgrad_grouped_wide.py [--batch 32] [--rounds 9] [--window 0.5] [--out FILE] [--no-kernels] [--no-models]"""
+usage: tools/bench_wgrad_grouped_wide.py [--batch 32] [--rounds 9] [--window 0.5] [--out FILE] [--no-kernels] [--no-models]
+                                         [--models regnet_y_8gf,regnet_y_16gf,regnet_y_32gf] [--step-model regnet_y_8gf]"""
 import argparse
 import json
 import os
@@ -43,13 +45,15 @@ ap.add_argument("--window", type=float, default=0.5)
 ap.add_argument("--out", default=None)
 ap.add_argument("--no-kernels", action="store_true")
 ap.add_argument("--no-models", action="store_true")
+ap.add_argument("--models", default=None)
+ap.add_argument("--step-model", default="regnet_y_8gf")
 args = ap.parse_args()
 assert args.rounds >= 9, "the median of at least 9 rounds"
 assert args.window >= 0.5, "windows of at least half a second"
 dev = torch.device("cuda", 0)
 laudnet_amd.load_library()
 ops.set_math_mode("bf16x3")
-MODELS = {"regnet_y_8gf": (56, [224, 448, 896, 2016]), "regnet_y_16gf": (112, [224, 448, 1232, 3024])}
+MODELS = {"regnet_y_8gf": (56, [224, 448, 896, 2016]), "regnet_y_16gf": (112, [224, 448, 1232, 3024]), "regnet_y_32gf": (232, [232, 696, 1392, 3712])}
 MAPS = [56, 28, 14, 7]
 BF16_MFMA_PEAK_TFLOPS = 2500.0      # bench.py
 
@@ -98,7 +102,8 @@ def us(r):
 
 
 if not args.no_kernels:
-    for model, (gw, widths) in MODELS.items():
+    for model in (args.models.split(",") if args.models else MODELS):
+        gw, widths = MODELS[model]
         for stride in (1, 2):
             for stage, (C, S) in enumerate(zip(widths, MAPS)):
                 B, G = args.batch, C // gw
@@ -122,30 +127,42 @@ if not args.no_kernels:
                         ops.wgrad_rows(dy[:, g * gw:(g + 1) * gw], h_a[:, g * gw:(g + 1) * gw], a_rows=ix.nbr, taps=9, m_count=ix.cnt[0:1],
                                        m_cap=ix.cap3, a_valid=ix.cap1, out=out_c[g * gw:(g + 1) * gw])
                 legs = {"kernel": kernel, "gather_bmm": gather_bmm, "slice_loop": slice_loop}
+                try:
+                    slice_loop()
+                except laudnet_amd.LdnError as e:            # ops.wgrad_rows does not take this width: two legs
+                    del legs["slice_loop"]
+                    refused = str(e)
                 for fn in legs.values():
                     fn()
                 torch.cuda.synchronize()
                 ref = held["b"].reshape(C, gw, 9).permute(0, 2, 1)
                 ref_max = ref.abs().max().item()
-                diffs = {"kernel": (out_a - ref).abs().max().item(), "slice_loop": (out_c - ref).abs().max().item()}
+                diffs = {"kernel": (out_a - ref).abs().max().item()}
+                if "slice_loop" in legs:
+                    diffs["slice_loop"] = (out_c - ref).abs().max().item()
                 for k, d in diffs.items():
                     assert d <= 1e-4 * max(1.0, ref_max), f"{model} stage {stage + 1} stride {stride} {k}: differs from the gather + bmm path by {d:.3e} (|ref|max {ref_max:.3e})"
                 held.clear()
                 res = alternate(legs, warm=3)
                 held.clear()
                 tflops = 2.0 * n3 * C * 9 * gw / (res["kernel"][0] * 1e-3) / 1e12
-                vb, vc = verdict(res, "kernel", "gather_bmm"), verdict(res, "kernel", "slice_loop")
+                vb = verdict(res, "kernel", "gather_bmm")
+                if "slice_loop" in legs:
+                    vc = verdict(res, "kernel", "slice_loop")
+                    third = {"slice_loop_us_median_min_max": us(res["slice_loop"]), "slice_loop_over_kernel": vc["old_over_new"],
+                             "kernel_faster_than_slice_loop_ranges_apart": vc["new_faster_ranges_apart"],
+                             "kernel_slower_than_slice_loop_ranges_apart": vc["new_slower_ranges_apart"]}
+                else:
+                    third = {"slice_loop": "not timed: " + refused}
                 emit({"what": "d W of LAD-RegNet conv b (grouped 3x3) over the packed rows of the kept images: (a) ops.wgrad_grouped_wide_rows (bf16x3, matrix "
                               "cores) vs (b) training._weight_grad_grouped_3x3 (gather + torch.bmm, the switch-off path) vs (c) a host loop of ops.wgrad_rows "
                               "over the G column slices",
                       "model": model, "stage": stage + 1, "stride": stride, "group_width": gw, "C": C, "groups": G, "map": S, "batch": B, "rows": n3,
                       "m_cap": ix.cap3, "rounds": args.rounds,
                       "kernel_us_median_min_max": us(res["kernel"]), "gather_bmm_us_median_min_max": us(res["gather_bmm"]),
-                      "slice_loop_us_median_min_max": us(res["slice_loop"]), "calls_per_window": {k: v[3] for k, v in res.items()},
+                      **third, "calls_per_window": {k: v[3] for k, v in res.items()},
                       "gather_bmm_over_kernel": vb["old_over_new"], "kernel_faster_than_gather_bmm_ranges_apart": vb["new_faster_ranges_apart"],
                       "kernel_slower_than_gather_bmm_ranges_apart": vb["new_slower_ranges_apart"],
-                      "slice_loop_over_kernel": vc["old_over_new"], "kernel_faster_than_slice_loop_ranges_apart": vc["new_faster_ranges_apart"],
-                      "kernel_slower_than_slice_loop_ranges_apart": vc["new_slower_ranges_apart"],
                       "algorithmic_tflops_kernel": round(tflops, 2), "frac_bf16_roof_executed": round(3 * tflops / BF16_MFMA_PEAK_TFLOPS, 4),
                       "max_abs_diff_vs_gather_bmm": {k: float(f"{d:.3g}") for k, d in diffs.items()}, "ref_max": float(f"{ref_max:.3g}")})
                 del h_a, dy, out_a, out_c, ref, ix
@@ -153,8 +170,8 @@ if not args.no_kernels:
 
 if not args.no_models:
     from laudnet_amd.training import prepare_for_training, train_forward
-    model, gw = "regnet_y_8gf", 56
-    net = laudnet_amd.lad_regnet_y_8gf(dyn_mode=["spatial"] * 4, mask_spatial_granularity=MAPS, num_classes=1000, input_size=224).eval()
+    model, gw = args.step_model, MODELS[args.step_model][0]
+    net = getattr(laudnet_amd, "lad_" + model)(dyn_mode=["spatial"] * 4, mask_spatial_granularity=MAPS, num_classes=1000, input_size=224).eval()
     net.load_state_dict(damp_residual_branches(fill_state_dict(net.state_dict(), 1)))
     net = net.to(dev)
     for i, blk in enumerate(net.blocks()):      # layer skip: one decision per image, a seeded half kept in every block
