@@ -34,6 +34,7 @@
 //   * Epilogue (consumers): folded-BN affine per lane-column, then a per-wave 32x32 transpose through LDS so
 //     residual loads and output stores are 16 B per lane along the channel axis.
 #include "ldn_common.h"
+#include "ldn_conv_plan.h"
 
 #ifndef LDN_ABLATE
 #define LDN_ABLATE 0   // tuning only: 1 = no MFMA, 2 = no A loads in the K loop, 4 = no weight loads, 8 = no weight split/store, 16 = no output stores, 32 = no residual loads (results are wrong)
@@ -70,8 +71,6 @@ struct ImgArgs {
     int out_split;   // 1: out rows are written PRE-SPLIT for ldn_bottleneck_tail -- per octet of 8 channels [8 hi bf16 | 8 lo bf16]
                      //    (same 4 bytes per element), zero-filled up to the next multiple of 32 channels (bf16x3 kernel only)
 };
-
-constexpr int BK = 32;   // K chunk = one 128-byte LDS row
 
 __device__ __attribute__((aligned(16))) float g_zero16[4] = {0.f, 0.f, 0.f, 0.f};
 __device__ __attribute__((aligned(16))) float g_one16[4] = {1.f, 1.f, 1.f, 1.f};
@@ -454,7 +453,7 @@ __device__ __forceinline__ void tile_store_rows(const ImgArgs& p, const Tile& t,
 //        (k-major keeps every weight fetch inside one or a few 128-byte lines of a single row; the n-major
 //         layout with a K gather touched ~2.6x more lines than it used)
 // KSKIP= skip the empty 8-wide k groups of a partial chunk (pays when the per-tap K is short).
-enum { B_NK = 0, B_KN4 = 1, B_KN2 = 2, B_KN1 = 3 };
+// (the enumeration, and KSKIP / MINW as functions of the tile: csrc/ldn_conv_plan.h)
 
 template <int MS, int NS, int BMODE, bool KSKIP, int MINW>
 __global__ __launch_bounds__(512, MINW) void k_conv_image(const ImgArgs p) {
@@ -1243,12 +1242,7 @@ __global__ __launch_bounds__(512, MINW) void k_conv_bf3(const ImgArgs p) {
 //        B_NK  = n-major weights [cout][cin], no lists (conv3 of spatial / layer mode, projection shortcuts, dense execution).
 // Residual loads and output stores are NON-TEMPORAL: both stream through the XCD's L2 exactly once; without the hint they evict the A tile /
 // weight rows every N tile re-reads (measured: 20.0 -> 19.6 ms per step).
-constexpr int ST_BM = 128, ST_BN = 128;
-constexpr int ST_TILE = ST_BM * BK;                       // 4096 floats = 16 KiB: one A slot, one raw-B slot, one converted-B slot
-constexpr int ST_A_SLOTS = 4, ST_B_SLOTS = 3;
-constexpr int ST_OFF_BRAW = ST_A_SLOTS * ST_TILE, ST_OFF_CB = ST_OFF_BRAW + ST_B_SLOTS * ST_TILE;
-constexpr int ST_LDS_FLOATS = ST_OFF_CB + 2 * ST_TILE;    // 9 slots = 144 KiB
-constexpr int ST_MAXROWS = 1024;                          // rows per workgroup (8 M blocks)
+// (ST_BM, ST_BN, the slot layout ST_*, ST_LDS_FLOATS and ST_MAXROWS: csrc/ldn_conv_plan.h, shared with the chooser)
 constexpr int ST_ROW_RELU = 1 << 30;
 
 __device__ __forceinline__ void lds_write16(unsigned addr, const bf16x8& v) {
@@ -1620,137 +1614,49 @@ static int default_math_mode() {
     return v;
 }
 
-static size_t tile_lds_bytes(const ImgArgs& p, int MS, int NS) {
-    return (size_t)2 * (MS + NS) * 32 * BK * sizeof(float) + (size_t)((2 + p.shift_classes) * NS * 32) * sizeof(float) +
-           (size_t)(2 * MS * 32 + NS * 32 + (p.k_idx ? p.cin : 0) + (p.packed ? MS * 32 * (1 + p.ksize) : 0)) * sizeof(int);
-}
-
-template <int MS, int NS, int WM, int BMODE, bool KSKIP>
-static int launch_bf3(const ImgArgs& p, hipStream_t st) {
-    constexpr int MINW = (MS + NS) <= 8 ? 4 : 2;
-    const size_t lds = tile_lds_bytes(p, MS, NS);
-    LDN_REQUIRE(lds <= 160 * 1024, "k_conv_bf3: %zu B of LDS exceed 160 KiB (cin too large for k_idx)", lds);
-    LDN_REQUIRE(allow_dynamic_lds(reinterpret_cast<const void*>(&k_conv_bf3<MS, NS, WM, BMODE, KSKIP, MINW>), lds),
-                "k_conv_bf3: cannot reserve %zu B of LDS", lds);
-    ImgArgs q = p;
-    const int msubs = ceil_div(p.packed ? p.m_cap : p.Ho * p.Wo, 32);
-    const int mtn = ceil_div(msubs, MS);
-    q.bm = ceil_div(msubs, mtn) * 32;
-    q.mtn = mtn;
-    const unsigned grid = (unsigned)round_up(p.B * mtn, 8) * p.ntn;   // units padded to the 8 XCDs (tile_setup)
-    hipLaunchKernelGGL((k_conv_bf3<MS, NS, WM, BMODE, KSKIP, MINW>), dim3(grid), dim3(512), lds, st, q);
-    LDN_CHECK_LAUNCH("k_conv_bf3");
-    return LDN_OK;
-}
-
-template <int MS, int NS, int BMODE, bool KSKIP>
-static int launch_k(const ImgArgs& p, hipStream_t st) {
-    if (p.math == 1) {
-        // consumer wave grid WM x 4/WM: every wave owns whole m-subtiles (A fragments are split once and reused);
-        // 4 x 1 for the tall 8 x 6 tile, 2 x 2 otherwise; 7x7 images (<= 2 m-subtiles) get a 2-subtile-high tile
-        const int msubs = ceil_div(p.packed ? p.m_cap : p.Ho * p.Wo, 32);
-        if constexpr (MS == 4 && NS == 10) {
-            if (msubs <= 2) return launch_bf3<2, 10, 2, BMODE, KSKIP>(p, st);
-        }
-        if constexpr (MS == 4 && NS == 4) {
-            // 4x4 tiles: 4 x 1 wave grid (one A split per four tiles) unless the epilogue adds a residual, where the
-            // 2 x 2 grid measured 5-8 % faster (conv3-type launches)
-            if (!p.residual) return launch_bf3<4, 4, 4, BMODE, KSKIP>(p, st);
-        }
-        return launch_bf3<MS, NS, (MS >= 8 ? 4 : 2), BMODE, KSKIP>(p, st);
-    }
-    // blocks of <= 64 KiB LDS run two per CU (memory-bound early stages need the extra waves in flight)
-    constexpr int MINW = (MS + NS) <= 8 ? 4 : 2;
-    const size_t lds = tile_lds_bytes(p, MS, NS);
-    LDN_REQUIRE(lds <= 160 * 1024, "k_conv_image: %zu B of LDS exceed 160 KiB (cin too large for k_idx)", lds);
-    LDN_REQUIRE(allow_dynamic_lds(reinterpret_cast<const void*>(&k_conv_image<MS, NS, BMODE, KSKIP, MINW>), lds),
-                "k_conv_image: cannot reserve %zu B of LDS", lds);
-    ImgArgs q = p;
-    const int msubs = ceil_div(p.packed ? p.m_cap : p.Ho * p.Wo, 32);
-    const int mtn = ceil_div(msubs, MS);              // M blocks per image, then balance their sizes
-    q.bm = ceil_div(msubs, mtn) * 32;
-    q.mtn = mtn;
-    const unsigned grid = (unsigned)round_up(p.B * mtn, 8) * p.ntn;   // units padded to the 8 XCDs (tile_setup)
-    hipLaunchKernelGGL((k_conv_image<MS, NS, BMODE, KSKIP, MINW>), dim3(grid), dim3(512), lds, st, q);
-    LDN_CHECK_LAUNCH("k_conv_image");
-    return LDN_OK;
-}
-
-template <int BMODE>
-static int launch_shape(const ImgArgs& a, hipStream_t st) {
-    ImgArgs p = a;
-    const int nsubs = ceil_div(a.cout, 32);
-    const int hw = a.packed ? a.m_cap : a.Ho * a.Wo;
-    // tile shape: as many output pixels as the LDS budget allows for the layer's width, so that every byte pulled
-    // into the CU is reused by as many MFMAs as possible (whole 14x14 / 7x7 images at stages 3 / 4)
-    int per;                                   // n-subtiles per N block
-    if (nsubs <= 4) per = nsubs;               // <= 128 columns: memory-bound layers, two 64 KiB blocks per CU
-    else if (hw <= 128) per = min(nsubs, 10);  // 7x7 images: wide N blocks (weights dominate the traffic)
-    else if (hw <= 256 && a.n_idx) per = min(nsubs, 6);   // 14x14 images: whole image x <= 192 columns per block
-    // (measured: the wide 1x1 convs without an output list -- conv3, downsample -- are faster as two co-resident
-    //  64 KiB blocks per CU whose phases overlap than as one whole-image block: 208 vs 294 us at stage 3)
-    else per = 4;
-    p.bn = per * 32;
-    p.ntn = ceil_div(a.cout, p.bn);
-    // KSKIP (skip empty k groups of a partial chunk) only pays for the narrow layers, which use the small shapes
-    if (per <= 2) return launch_k<6, 2, BMODE, true>(p, st);
-    if (per <= 4) return launch_k<4, 4, BMODE, true>(p, st);
-    if (per <= 6) return launch_k<8, 6, BMODE, false>(p, st);
-    return launch_k<4, 10, BMODE, false>(p, st);
-}
-
 // rows per workgroup of k_conv1x1_stream (tuning: env LDN_STREAM_ROWS, multiple of 128, <= 1024; 0 disables the kernel)
 static int stream_rows() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("LDN_STREAM_ROWS");
-        v = e ? atoi(e) : 512;
-        if (v > ST_MAXROWS) v = ST_MAXROWS;
-    }
+    static const int v = [] { const char* e = getenv("LDN_STREAM_ROWS"); const int r = e ? atoi(e) : 512; return r > ST_MAXROWS ? ST_MAXROWS : r; }();
     return v;
 }
 
-template <int BMODE>
-static int launch_stream(const ImgArgs& p, hipStream_t st) {
-    const size_t lds = (size_t)ST_LDS_FLOATS * sizeof(float) + (size_t)(2 * ST_MAXROWS + p.cin + 32) * sizeof(int);
-    LDN_REQUIRE(lds <= 160 * 1024, "k_conv1x1_stream: %zu B of LDS exceed 160 KiB", lds);
-    LDN_REQUIRE(allow_dynamic_lds(reinterpret_cast<const void*>(&k_conv1x1_stream<BMODE>), lds),
-                "k_conv1x1_stream: cannot reserve %zu B of LDS", lds);
+// One launch of any of the three kernels with the plan's geometry.
+static int launch_conv_kernel(void (*kernel)(const ImgArgs), const char* name, const ConvPlan& plan, const ImgArgs& p, hipStream_t st) {
+    const size_t lds = (size_t)plan.lds_bytes;
+    LDN_REQUIRE(plan.lds_bytes <= kConvLdsLimit, "%s: %zu B of LDS exceed 160 KiB%s", name, lds, plan.family == CONV_STREAM ? "" : " (cin too large for k_idx)");
+    LDN_REQUIRE(allow_dynamic_lds(reinterpret_cast<const void*>(kernel), lds), "%s: cannot reserve %zu B of LDS", name, lds);
     ImgArgs q = p;
-    const int rows = p.packed ? p.m_cap : p.Ho * p.Wo;
-    int rpb = stream_rows();                           // rows per workgroup: fewer when that is needed to fill the chip
-    while (rpb > ST_BM && p.B * ceil_div(rows, rpb) < 512) rpb /= 2;
-    int nblk = ceil_div(rows, rpb);
-    q.bm = round_up(ceil_div(rows, nblk), ST_BM);      // balanced, whole M blocks
-    nblk = ceil_div(rows, q.bm);
-    q.mtn = nblk;
-    // too few row blocks to fill the chip (shared-weight launches over a few thousand packed rows): split the N tiles too
-    const int ntiles = p.cout / ST_BN;
-    int nsplit = 1;
-    while (p.B * nblk * nsplit < 512 && nsplit < ntiles) nsplit *= 2;
-    q.bn = ceil_div(ntiles, nsplit);
-    q.ntn = ceil_div(ntiles, q.bn);
-    hipLaunchKernelGGL((k_conv1x1_stream<BMODE>), dim3((unsigned)p.B * nblk * q.ntn), dim3(512), lds, st, q);
-    LDN_CHECK_LAUNCH("k_conv1x1_stream");
+    q.bn = plan.bn; q.ntn = plan.ntn; q.bm = plan.bm; q.mtn = plan.mtn;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)plan.grid), dim3(512), lds, st, q);
+    LDN_CHECK_LAUNCH(name);
     return LDN_OK;
 }
 
-static int dispatch_mode(const ImgArgs& p, int kgran, hipStream_t st) {
-    const long taps = p.packed ? p.ksize : (long)p.ksize * p.ksize;
-    LDN_REQUIRE(!p.k_idx || p.cin % 8 == 0, "conv: an input-channel list needs cin to be a multiple of 8 (got %d)", p.cin);
-    LDN_REQUIRE(taps * p.cin * p.cout < (1L << 31), "conv: weight tensor of %ld elements exceeds the 32-bit offsets of the weight staging",
-                taps * p.cin * p.cout);
-    // wide 1x1 convolutions without an output-channel list: the persistent streaming kernel (bf16x3 arithmetic only;
-    // its epilogue stores fp32 rows, so a pre-split output stays with k_conv_bf3)
-    if (p.math == 1 && stream_rows() >= ST_BM && taps == 1 && !p.n_idx && p.shift_classes == 1 && !p.out_split &&
-        p.cout % ST_BN == 0 && p.cout >= 2 * ST_BN && !(p.residual && p.scale) && p.cin <= 1024 &&
-        (p.packed ? p.m_cap : p.Ho * p.Wo) >= 96)   // (7x7 images would leave most of every 128-row M block empty)
-        return p.k_idx ? launch_stream<B_KN4>(p, st) : launch_stream<B_NK>(p, st);
-    if (!p.k_idx) return launch_shape<B_NK>(p, st);                  // w is [cout][taps][cin]
-    const int g = p.n_idx ? kgran : 4;                               // w is [taps][cin][cout]
-    if (g % 4 == 0) return launch_shape<B_KN4>(p, st);
-    if (g % 2 == 0) return launch_shape<B_KN2>(p, st);
-    return launch_shape<B_KN1>(p, st);
+// Launches the row of LDN_CONV_KERNELS (csrc/ldn_conv_plan.h) that the plan is -- the only place that instantiates the three kernels.
+// A plan that is no row is refused: it never falls through to a neighbouring kernel.
+static int launch_conv_plan(const ConvPlan& plan, const ImgArgs& p, hipStream_t st) {
+#define LDN_I(MS, NS, BMODE) \
+    if (plan == LDN_CONV_ROW_I(MS, NS, BMODE)) return launch_conv_kernel(&k_conv_image<MS, NS, BMODE, conv_kskip(MS, NS), conv_minw(MS, NS)>, "k_conv_image", plan, p, st);
+#define LDN_F(MS, NS, WM, BMODE) \
+    if (plan == LDN_CONV_ROW_F(MS, NS, WM, BMODE)) return launch_conv_kernel(&k_conv_bf3<MS, NS, WM, BMODE, conv_kskip(MS, NS), conv_minw(MS, NS)>, "k_conv_bf3", plan, p, st);
+#define LDN_S(BMODE) if (plan == LDN_CONV_ROW_S(BMODE)) return launch_conv_kernel(&k_conv1x1_stream<BMODE>, "k_conv1x1_stream", plan, p, st);
+    LDN_CONV_KERNELS(LDN_I, LDN_F, LDN_S)
+#undef LDN_I
+#undef LDN_F
+#undef LDN_S
+    LDN_REQUIRE(false, "conv: %s is not built (taps %d, cin %d, cout %d, rows %d)", conv_plan_name(plan).c_str(), p.packed ? p.ksize : p.ksize * p.ksize, p.cin,
+                p.cout, p.packed ? p.m_cap : p.Ho * p.Wo);
+}
+
+// The launch as the chooser sees it (csrc/ldn_conv_plan.h), the refusals that depend on the shape, the plan, the launch.
+static int launch_conv(const ImgArgs& p, int kgran, hipStream_t st) {
+    ConvShape s{};
+    s.packed = p.packed != 0; s.B = p.B; s.rows = p.packed ? p.m_cap : p.Ho * p.Wo; s.taps = p.packed ? p.ksize : p.ksize * p.ksize;
+    s.cin = p.cin; s.cout = p.cout; s.has_k = p.k_idx != nullptr; s.has_n = p.n_idx != nullptr; s.kgran = kgran; s.shift_classes = p.shift_classes;
+    s.residual = p.residual != nullptr; s.scale = p.scale != nullptr; s.out_split = p.out_split != 0; s.math = p.math; s.stream_rows = stream_rows();
+    LDN_REQUIRE(conv_list_ok(s), "conv: an input-channel list needs cin to be a multiple of 8 (got %d)", p.cin);
+    LDN_REQUIRE(conv_weight_elems(s) < kConvWeightLimit, "conv: weight tensor of %ld elements exceeds the 32-bit offsets of the weight staging", conv_weight_elems(s));
+    return launch_conv_plan(conv_plan(s), p, st);
 }
 
 LDN_DEFINE_TU_VIOLATIONS(tu_violations_conv)
@@ -1805,7 +1711,7 @@ extern "C" int ldn_conv_image(const float* a, int lda, int B, int Hi, int Wi, in
               0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, math, out_format};
     LDN_REQUIRE(out_format == 0 || (out_format == 1 && math == 1 && !residual && !colsum && ldo % 32 == 0 && ldo >= round_up(cout, 32)),
                 "ldn_conv_image: out_format 1 (pre-split bf16 pairs) needs math_mode bf16x3, no residual / colsum and ldo %% 32 == 0");
-    return dispatch_mode(p, kgran, static_cast<hipStream_t>(stream));
+    return launch_conv(p, kgran, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int ldn_conv_packed(const float* a, int lda, int B, const int32_t* row_prefix, const int32_t* m_count,
@@ -1838,7 +1744,7 @@ extern "C" int ldn_conv_packed(const float* a, int lda, int B, const int32_t* ro
     ImgArgs p{a, lda, B, Hi > 0 ? Hi : 1, Wi > 0 ? Wi : 1, taps, stride >= 1 ? stride : 1, Ho > 0 ? Ho : 1, Wo > 0 ? Wo : 1,
               w, cin, cout, k_idx, k_cnt, n_idx, n_cnt, scale, shift, shift_classes, post_sub, relu, residual, ldr, out, ldo,
               nullptr, 1, row_prefix, m_count, m_cap, a_map, out_map, pix_map, relu_if_neg, 0, 0, 0, 0, math, 0};
-    return dispatch_mode(p, kgran, static_cast<hipStream_t>(stream));
+    return launch_conv(p, kgran, static_cast<hipStream_t>(stream));
 }
 
 // the shared-weight packed-row convolution of the spatial / layer path: one "image" holding every active row

@@ -2,7 +2,8 @@
 float64 (tests/conv_image_ref.py).  The packed-row form of the same three kernels has tests/test_hip_packed.py; this file is its
 counterpart for what every channel-mode ResNet block, the RegNet a / c convs, the projection shortcuts and the dense path launch.
 
-a  CPU: `expected_variant` (tests/conv_dispatch_ref.py) enumerated over every launch the entry point admits comes to REACHABLE, and the
+a  CPU: `expected_variant` (tests/conv_plan.py: the library's own chooser, conv_plan() of csrc/ldn_conv_plan.h, through a host-only
+   program) enumerated over every launch the entry point admits comes to REACHABLE, and the
    case table below runs exactly that set in both arithmetic modes -- every tile shape and weight-staging mode of k_conv_image and
    k_conv_bf3, both wave grids of the 4 x 4 tile, k_conv1x1_stream with and without an input list.
 b  The cases are the smallest shapes that still reach each variant, on maps that are never square: wider than high, higher than wide,
@@ -21,7 +22,8 @@ import torch
 import torch.nn.functional as F
 
 import conv_image_ref as R
-from conv_dispatch_ref import expected_variant, expected_wave_rows
+import conv_plan
+from conv_plan import expected_variant, expected_wave_rows
 from fill import seeded_bernoulli, seeded_randn
 from helpers import apply_math_mode  # noqa: F401  (autouse fixture: a test that takes math_mode runs in that mode)
 from helpers import assert_close
@@ -53,50 +55,48 @@ def launch_kw(kind, taps, rows, cin, cout, kgran=1, residual=False, scale=True, 
 
 
 def reachable_variants():
-    """Every (kernel, MS, NS, BMODE, math) an image launch can run, by ENUMERATION of expected_variant over what ldn_conv_image admits: the six
+    """Every (kernel, MS, NS, BMODE, math, WM) an image launch can run, by ENUMERATION of the chooser over what ldn_conv_image admits: the six
     launch kinds x residual none / with scale / without scale (none with an output list) x list granularity 1 / 2 / 4 x cout 4 .. 2048 x
     Ho * Wo on both sides of every row threshold of the dispatch (64 | 96 | 128 | 256) x cin on both sides of the streaming kernel's 1024 x
     a 1- / 16-class table x out_format 0 / 1 (bf16x3 without a residual only) x both arithmetic modes."""
     couts = sorted(set(range(4, 513, 4)) | {768, 1024, 2048})
     rows = [1, 15, 31, 32, 33, 63, 64, 65, 95, 96, 97, 100, 127, 128, 129, 130, 180, 255, 256, 257, 520, 3136, 12544]
     found = set()
-    for math in MATHS:
+    for math in MATHS:      # one line of the CLI's grid form per (kind, residual, format, table): granularities, widths and row counts as lists
+        lines = []
         for kind, taps in LAUNCH_KINDS:
             for residual, scale in ((False, True), (False, False), (True, True), (True, False)):
                 if residual and KINDS[kind][1]:
                     continue
                 for split in ((False, True) if math == "bf16x3" and not residual else (False,)):
                     for classes in (1, 16):
-                        for gran in (1, 2, 4):
-                            for cin in (32, 2048):
-                                for cout in couts:
-                                    for hw in rows:
-                                        kw = launch_kw(kind, taps, hw, cin, cout, gran, residual, scale, classes, split)
-                                        found.add(expected_variant(math=math, **kw) + (math,))
+                        lines.append(conv_plan.shape_line(math=math, **launch_kw(kind, taps, rows, (32, 2048), couts, (1, 2, 4), residual, scale, classes, split)))
+        found |= {k[:4] + (math, k[4]) for k in conv_plan.reachable(lines)}
     return found
 
 
 # What reachable_variants() must come to, written out: every tile shape x every staging mode (no input list: B_NK; an input list alone:
-# B_KN4; both lists: B_KN<granularity>) in both modes, and the streaming kernel without and with an input list.  fp32 has no 2 x 10 tile
-# and no streaming kernel.  16 + 22 instantiations.
+# B_KN4; both lists: B_KN<granularity>) in both modes, the 4 x 4 tile of bf16x3 on both wave grids (2 x 2 behind a residual, which an
+# output list excludes: B_NK and B_KN4 only), and the streaming kernel without and with an input list.  fp32 has no 2 x 10 tile and no
+# streaming kernel.  16 + 24 instantiations: every row of LDN_CONV_KERNELS.  The last element is WM, the rows of k_conv_bf3's wave grid.
 REACHABLE = {
-    ("k_conv_image", 6, 2, "B_NK", "fp32"), ("k_conv_image", 4, 4, "B_NK", "fp32"), ("k_conv_image", 8, 6, "B_NK", "fp32"),
-    ("k_conv_image", 4, 10, "B_NK", "fp32"),
-    ("k_conv_image", 6, 2, "B_KN1", "fp32"), ("k_conv_image", 4, 4, "B_KN1", "fp32"), ("k_conv_image", 8, 6, "B_KN1", "fp32"),
-    ("k_conv_image", 4, 10, "B_KN1", "fp32"),
-    ("k_conv_image", 6, 2, "B_KN2", "fp32"), ("k_conv_image", 4, 4, "B_KN2", "fp32"), ("k_conv_image", 8, 6, "B_KN2", "fp32"),
-    ("k_conv_image", 4, 10, "B_KN2", "fp32"),
-    ("k_conv_image", 6, 2, "B_KN4", "fp32"), ("k_conv_image", 4, 4, "B_KN4", "fp32"), ("k_conv_image", 8, 6, "B_KN4", "fp32"),
-    ("k_conv_image", 4, 10, "B_KN4", "fp32"),
-    ("k_conv_bf3", 6, 2, "B_NK", "bf16x3"), ("k_conv_bf3", 4, 4, "B_NK", "bf16x3"), ("k_conv_bf3", 8, 6, "B_NK", "bf16x3"),
-    ("k_conv_bf3", 4, 10, "B_NK", "bf16x3"), ("k_conv_bf3", 2, 10, "B_NK", "bf16x3"),
-    ("k_conv_bf3", 6, 2, "B_KN1", "bf16x3"), ("k_conv_bf3", 4, 4, "B_KN1", "bf16x3"), ("k_conv_bf3", 8, 6, "B_KN1", "bf16x3"),
-    ("k_conv_bf3", 4, 10, "B_KN1", "bf16x3"), ("k_conv_bf3", 2, 10, "B_KN1", "bf16x3"),
-    ("k_conv_bf3", 6, 2, "B_KN2", "bf16x3"), ("k_conv_bf3", 4, 4, "B_KN2", "bf16x3"), ("k_conv_bf3", 8, 6, "B_KN2", "bf16x3"),
-    ("k_conv_bf3", 4, 10, "B_KN2", "bf16x3"), ("k_conv_bf3", 2, 10, "B_KN2", "bf16x3"),
-    ("k_conv_bf3", 6, 2, "B_KN4", "bf16x3"), ("k_conv_bf3", 4, 4, "B_KN4", "bf16x3"), ("k_conv_bf3", 8, 6, "B_KN4", "bf16x3"),
-    ("k_conv_bf3", 4, 10, "B_KN4", "bf16x3"), ("k_conv_bf3", 2, 10, "B_KN4", "bf16x3"),
-    ("k_conv1x1_stream", None, None, "B_NK", "bf16x3"), ("k_conv1x1_stream", None, None, "B_KN4", "bf16x3"),
+    ("k_conv_image", 6, 2, "B_NK", "fp32", None), ("k_conv_image", 4, 4, "B_NK", "fp32", None), ("k_conv_image", 8, 6, "B_NK", "fp32", None),
+    ("k_conv_image", 4, 10, "B_NK", "fp32", None),
+    ("k_conv_image", 6, 2, "B_KN1", "fp32", None), ("k_conv_image", 4, 4, "B_KN1", "fp32", None), ("k_conv_image", 8, 6, "B_KN1", "fp32", None),
+    ("k_conv_image", 4, 10, "B_KN1", "fp32", None),
+    ("k_conv_image", 6, 2, "B_KN2", "fp32", None), ("k_conv_image", 4, 4, "B_KN2", "fp32", None), ("k_conv_image", 8, 6, "B_KN2", "fp32", None),
+    ("k_conv_image", 4, 10, "B_KN2", "fp32", None),
+    ("k_conv_image", 6, 2, "B_KN4", "fp32", None), ("k_conv_image", 4, 4, "B_KN4", "fp32", None), ("k_conv_image", 8, 6, "B_KN4", "fp32", None),
+    ("k_conv_image", 4, 10, "B_KN4", "fp32", None),
+    ("k_conv_bf3", 6, 2, "B_NK", "bf16x3", 2), ("k_conv_bf3", 4, 4, "B_NK", "bf16x3", 4), ("k_conv_bf3", 4, 4, "B_NK", "bf16x3", 2), ("k_conv_bf3", 8, 6, "B_NK", "bf16x3", 4),
+    ("k_conv_bf3", 4, 10, "B_NK", "bf16x3", 2), ("k_conv_bf3", 2, 10, "B_NK", "bf16x3", 2),
+    ("k_conv_bf3", 6, 2, "B_KN1", "bf16x3", 2), ("k_conv_bf3", 4, 4, "B_KN1", "bf16x3", 4), ("k_conv_bf3", 8, 6, "B_KN1", "bf16x3", 4),
+    ("k_conv_bf3", 4, 10, "B_KN1", "bf16x3", 2), ("k_conv_bf3", 2, 10, "B_KN1", "bf16x3", 2),
+    ("k_conv_bf3", 6, 2, "B_KN2", "bf16x3", 2), ("k_conv_bf3", 4, 4, "B_KN2", "bf16x3", 4), ("k_conv_bf3", 8, 6, "B_KN2", "bf16x3", 4),
+    ("k_conv_bf3", 4, 10, "B_KN2", "bf16x3", 2), ("k_conv_bf3", 2, 10, "B_KN2", "bf16x3", 2),
+    ("k_conv_bf3", 6, 2, "B_KN4", "bf16x3", 2), ("k_conv_bf3", 4, 4, "B_KN4", "bf16x3", 4), ("k_conv_bf3", 4, 4, "B_KN4", "bf16x3", 2), ("k_conv_bf3", 8, 6, "B_KN4", "bf16x3", 4),
+    ("k_conv_bf3", 4, 10, "B_KN4", "bf16x3", 2), ("k_conv_bf3", 2, 10, "B_KN4", "bf16x3", 2),
+    ("k_conv1x1_stream", None, None, "B_NK", "bf16x3", None), ("k_conv1x1_stream", None, None, "B_KN4", "bf16x3", None),
 }
 
 
@@ -147,6 +147,8 @@ CASES = [
     C("ps44", 3, 7, 11, 1, 1, 40, 128, "n", gran=1, ps=True, fmt=1),
     C("ps86", 4, 10, 13, 1, 1, 32, 192, "n", gran=2, fmt=1),
     C("ps_dense", 4, 10, 10, 1, 1, 32, 256, "dense", ps=True, fmt=1),
+    # ---- (last, so that the cases above keep their seeds) an input list alone WITH a residual on 4 x 4: the 2 x 2 wave grid of B_KN4
+    C("k44r", 4, 6, 11, 1, 1, 32, 128, "k", gran=2, res="sep", scale=False),
 ]
 BY_NAME = {c["name"]: c for c in CASES}
 assert len(BY_NAME) == len(CASES)
@@ -166,12 +168,13 @@ def test_case_table_reaches_every_variant():
     """The set of variants the case table runs equals what the enumeration of the dispatch rule finds (REACHABLE is that set written out) --
     and, branch by branch: every tile shape and staging mode per arithmetic mode, 4 x 4 with and without a residual, the streaming kernel with
     both weight layouts, and the launches that must NOT take it."""
-    assert reachable_variants() == REACHABLE and len(REACHABLE) == 16 + 22
+    assert reachable_variants() == REACHABLE and len(REACHABLE) == 16 + 24
     seen, detail = set(), {}
+    conv_plan.plans([dict(case_kw(c), math=math) for c in CASES for math in case_modes(c)])      # (one run of the chooser for all)
     for c in CASES:
         for math in case_modes(c):
             v = expected_variant(math=math, **case_kw(c))
-            seen.add(v + (math,))
+            seen.add(v + (math, expected_wave_rows(math=math, **case_kw(c))))
             detail.setdefault((v, math, c["res"] is not None), c["name"])
     assert seen == REACHABLE, f"missing {sorted(map(str, REACHABLE - seen))}, unexpected {sorted(map(str, seen - REACHABLE))}"
     shapes = {m: {(k[0][1], k[0][2]) for k in detail if k[1] == m and k[0][1] is not None} for m in MATHS}
@@ -182,7 +185,7 @@ def test_case_table_reaches_every_variant():
         assert modes == {"B_NK", "B_KN1", "B_KN2", "B_KN4"}, (math, modes)
         four = {k[2] for k in detail if k[1] == math and (k[0][1], k[0][2]) == (4, 4)}
         assert four == {False, True}, f"{math}: the 4 x 4 tile must run with and without a residual"
-    waves = {expected_wave_rows(k[0], k[2]) for k in detail if k[1] == "bf16x3" and (k[0][1], k[0][2]) == (4, 4)}
+    waves = {expected_wave_rows(math="bf16x3", **case_kw(BY_NAME[name])) for k, name in detail.items() if k[1] == "bf16x3" and (k[0][1], k[0][2]) == (4, 4)}
     assert waves == {4, 2}
     stream = {k[0][3] for k in detail if k[0][0] == "k_conv1x1_stream"}
     assert stream == {"B_NK", "B_KN4"}
@@ -395,7 +398,7 @@ def test_conv_image_case_vs_float64(ops, name, math_mode):
 # ------------------------------------------------------------------ d: the argument checks
 @gpu
 def test_argument_checks_refuse_before_any_launch(ops):
-    """The checks of ldn_conv_image (csrc/ldn_conv_image.hip:1783-1808): an error code, and neither the output nor colsum is touched."""
+    """The checks of ldn_conv_image (csrc/ldn_conv_image.hip, ldn_conv_image): an error code, and neither the output nor colsum is touched."""
     from laudnet_amd import LdnError
     B, Hi, Wi, cin, cout = 2, 4, 6, 32, 32
     a = torch.zeros(B, Hi, Wi, cin, device=DEV)

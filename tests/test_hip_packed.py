@@ -6,9 +6,9 @@ A1  The three launches of Bottleneck._run_both -- conv1 on the dilated pixel lis
     float64 (helpers.bottleneck_stages_f64).  The model-level checks see these kernels only through a global average pool.
 A2  The options of the entry point that _run_both never combines, as literal-contract tests of include/ldn_hip.h:285-308,447-462.
 
-`expected_variant` (tests/conv_dispatch_ref.py) restates the dispatch of csrc/ldn_conv_image.hip in Python; the non-GPU test
-test_case_table_reaches_every_variant proves from it that the case table runs every tile shape, weight-staging mode and kernel a
-packed launch with channel lists can reach, in both arithmetic modes.
+`expected_variant` (tests/conv_plan.py) asks the library's own chooser, conv_plan() of csrc/ldn_conv_plan.h, through a host-only program;
+the non-GPU test test_case_table_reaches_every_variant proves from it that the case table runs every tile shape, wave grid,
+weight-staging mode and kernel a packed launch with channel lists can reach, in both arithmetic modes.
 
 Bounds (the library's own direct tests of the same arithmetic, tests/test_hip_ops.py::test_conv_image_channel_subsets and
 tests/test_hip_tail.py): conv1 1e-4 + 1e-4 |ref|, conv2 2e-4 + 1e-4 |ref|, conv3 after residual and ReLU 2e-4 + 1e-4 |ref|."""
@@ -19,7 +19,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from conv_dispatch_ref import expected_variant, expected_wave_rows
+import conv_plan
+from conv_plan import expected_variant, expected_wave_rows
 from fill import seeded_bernoulli, seeded_randn
 from helpers import apply_math_mode  # noqa: F401  (autouse fixture: a test that takes math_mode runs in that mode)
 from helpers import assert_close, bn_shift_f64, bottleneck_stages_f64, upsample_mask
@@ -56,12 +57,13 @@ CASES = [
     (4, 7, 7, 1024, 256, 1, 1, 1),      # 4 x 10 (fp32) / 2 x 10 (bf16x3) + B_KN1
     (4, 10, 10, 1024, 256, 1, 1, 1),    # 4 x 10 + B_KN1 in both modes
     (4, 10, 10, 1024, 256, 2, 1, 1),    # 4 x 10 + B_KN2 in bf16x3
+    (4, 14, 14, 512, 128, 4, 1, 1),     # 4 x 4 + B_KN4 WITHOUT a residual (conv2 at granularity 4): the 4 x 1 wave grid of that instantiation
 ]
 MATHS = ("fp32", "bf16x3")
 
 
 def block_launches(rows_in, rows_out, cin, width, gran, sg):
-    """The conv_packed launches of _run_both (laud_resnet.py:937-972) for a block: (name, expected_variant keywords).  rows_in / rows_out:
+    """The conv_packed launches of _run_both (laud_resnet.py, Bottleneck._run_both) for a block: (name, expected_variant keywords).  rows_in / rows_out:
     pixels of the input / output map (the m_cap of conv1 / of conv2 and conv3)."""
     cout = 4 * width
     return [
@@ -80,47 +82,49 @@ def case_launches(case):
 
 
 def reachable_variants():
-    """Every (kernel, MS, NS, BMODE, math) the three launches of a `both` block can run, by ENUMERATION of expected_variant over the blocks the
-    library admits: widths that are multiples of 8 (an input list needs cin % 8, :1740) from 8 to 2048, maps from one pixel to 112 x 112 on
+    """Every (kernel, MS, NS, BMODE, math, WM) the three launches of a `both` block can run, by ENUMERATION of the chooser over the blocks the
+    library admits: widths that are multiples of 8 (an input list needs cin % 8, conv_list_ok) from 8 to 2048, maps from one pixel to 112 x 112 on
     both sides of every row threshold of the dispatch (64 | 96 | 128 | 256 rows), channel granularity 1 / 2 / 4, one / two / four spatial mask
     groups, stride 1 and 2, both arithmetic modes.  Nothing is excluded."""
     widths = sorted(set(range(8, 513, 8)) | {768, 1024, 2048})
     rows = [1, 31, 32, 33, 49, 63, 64, 65, 95, 96, 97, 100, 127, 128, 129, 196, 255, 256, 257, 784, 3136, 12544]
     found = set()
-    for math in MATHS:
+    for math in MATHS:      # one line of the CLI's grid form per (launch, width, stride, mask groups): the row counts and granularities as lists
+        lines = []
         for width in widths:
-            for rows_out in rows:
-                for stride in (1, 2):
-                    for gran in (1, 2, 4):
-                        for sg in (1, 2, 4):
-                            if (4 * width) % (4 * sg):
-                                continue
-                            for _, kw in block_launches(rows_out * stride * stride, rows_out, 4 * width, width, gran, sg):
-                                found.add(expected_variant(math=math, **kw) + (math,))
+            for stride in (1, 2):
+                for sg in (1, 2, 4):
+                    if (4 * width) % (4 * sg):
+                        continue
+                    for name, kw in block_launches(1, 1, 4 * width, width, (1, 2, 4), sg):
+                        kw["rows_per_image"] = [r * stride * stride for r in rows] if name == "conv1" else rows
+                        lines.append(conv_plan.shape_line(math=math, **kw))
+        found |= {k[:4] + (math, k[4]) for k in conv_plan.reachable(lines)}
     return found
 
 
 # What reachable_variants() must come to, written out so that a reader sees it: every tile shape x every staging mode (conv1: B_NK, conv2:
-# B_KN<granularity>, conv3: B_KN4, :1749-1753) in both modes, and the streaming kernel with an input list.  fp32 has no 2 x 10 tile and no
-# streaming kernel.  16 + 21 instantiations.
+# B_KN<granularity>, conv3: B_KN4, conv_plan) in both modes, the 4 x 4 tile of bf16x3 on both wave grids (4 x 1: conv1 / conv2, 2 x 2: conv3 behind
+# its residual), and the streaming kernel with an input list.  fp32 has no 2 x 10 tile and no streaming kernel.  16 + 22 instantiations; the last
+# element is WM, the rows of k_conv_bf3's wave grid.
 REACHABLE = {
-    ("k_conv_image", 6, 2, "B_NK", "fp32"), ("k_conv_image", 4, 4, "B_NK", "fp32"), ("k_conv_image", 8, 6, "B_NK", "fp32"),
-    ("k_conv_image", 4, 10, "B_NK", "fp32"),
-    ("k_conv_image", 6, 2, "B_KN1", "fp32"), ("k_conv_image", 4, 4, "B_KN1", "fp32"), ("k_conv_image", 8, 6, "B_KN1", "fp32"),
-    ("k_conv_image", 4, 10, "B_KN1", "fp32"),
-    ("k_conv_image", 6, 2, "B_KN2", "fp32"), ("k_conv_image", 4, 4, "B_KN2", "fp32"), ("k_conv_image", 8, 6, "B_KN2", "fp32"),
-    ("k_conv_image", 4, 10, "B_KN2", "fp32"),
-    ("k_conv_image", 6, 2, "B_KN4", "fp32"), ("k_conv_image", 4, 4, "B_KN4", "fp32"), ("k_conv_image", 8, 6, "B_KN4", "fp32"),
-    ("k_conv_image", 4, 10, "B_KN4", "fp32"),
-    ("k_conv_bf3", 6, 2, "B_NK", "bf16x3"), ("k_conv_bf3", 4, 4, "B_NK", "bf16x3"), ("k_conv_bf3", 8, 6, "B_NK", "bf16x3"),
-    ("k_conv_bf3", 4, 10, "B_NK", "bf16x3"), ("k_conv_bf3", 2, 10, "B_NK", "bf16x3"),
-    ("k_conv_bf3", 6, 2, "B_KN1", "bf16x3"), ("k_conv_bf3", 4, 4, "B_KN1", "bf16x3"), ("k_conv_bf3", 8, 6, "B_KN1", "bf16x3"),
-    ("k_conv_bf3", 4, 10, "B_KN1", "bf16x3"), ("k_conv_bf3", 2, 10, "B_KN1", "bf16x3"),
-    ("k_conv_bf3", 6, 2, "B_KN2", "bf16x3"), ("k_conv_bf3", 4, 4, "B_KN2", "bf16x3"), ("k_conv_bf3", 8, 6, "B_KN2", "bf16x3"),
-    ("k_conv_bf3", 4, 10, "B_KN2", "bf16x3"), ("k_conv_bf3", 2, 10, "B_KN2", "bf16x3"),
-    ("k_conv_bf3", 6, 2, "B_KN4", "bf16x3"), ("k_conv_bf3", 4, 4, "B_KN4", "bf16x3"), ("k_conv_bf3", 8, 6, "B_KN4", "bf16x3"),
-    ("k_conv_bf3", 4, 10, "B_KN4", "bf16x3"), ("k_conv_bf3", 2, 10, "B_KN4", "bf16x3"),
-    ("k_conv1x1_stream", None, None, "B_KN4", "bf16x3"),
+    ("k_conv_image", 6, 2, "B_NK", "fp32", None), ("k_conv_image", 4, 4, "B_NK", "fp32", None), ("k_conv_image", 8, 6, "B_NK", "fp32", None),
+    ("k_conv_image", 4, 10, "B_NK", "fp32", None),
+    ("k_conv_image", 6, 2, "B_KN1", "fp32", None), ("k_conv_image", 4, 4, "B_KN1", "fp32", None), ("k_conv_image", 8, 6, "B_KN1", "fp32", None),
+    ("k_conv_image", 4, 10, "B_KN1", "fp32", None),
+    ("k_conv_image", 6, 2, "B_KN2", "fp32", None), ("k_conv_image", 4, 4, "B_KN2", "fp32", None), ("k_conv_image", 8, 6, "B_KN2", "fp32", None),
+    ("k_conv_image", 4, 10, "B_KN2", "fp32", None),
+    ("k_conv_image", 6, 2, "B_KN4", "fp32", None), ("k_conv_image", 4, 4, "B_KN4", "fp32", None), ("k_conv_image", 8, 6, "B_KN4", "fp32", None),
+    ("k_conv_image", 4, 10, "B_KN4", "fp32", None),
+    ("k_conv_bf3", 6, 2, "B_NK", "bf16x3", 2), ("k_conv_bf3", 4, 4, "B_NK", "bf16x3", 4), ("k_conv_bf3", 8, 6, "B_NK", "bf16x3", 4),
+    ("k_conv_bf3", 4, 10, "B_NK", "bf16x3", 2), ("k_conv_bf3", 2, 10, "B_NK", "bf16x3", 2),
+    ("k_conv_bf3", 6, 2, "B_KN1", "bf16x3", 2), ("k_conv_bf3", 4, 4, "B_KN1", "bf16x3", 4), ("k_conv_bf3", 8, 6, "B_KN1", "bf16x3", 4),
+    ("k_conv_bf3", 4, 10, "B_KN1", "bf16x3", 2), ("k_conv_bf3", 2, 10, "B_KN1", "bf16x3", 2),
+    ("k_conv_bf3", 6, 2, "B_KN2", "bf16x3", 2), ("k_conv_bf3", 4, 4, "B_KN2", "bf16x3", 4), ("k_conv_bf3", 8, 6, "B_KN2", "bf16x3", 4),
+    ("k_conv_bf3", 4, 10, "B_KN2", "bf16x3", 2), ("k_conv_bf3", 2, 10, "B_KN2", "bf16x3", 2),
+    ("k_conv_bf3", 6, 2, "B_KN4", "bf16x3", 2), ("k_conv_bf3", 4, 4, "B_KN4", "bf16x3", 4), ("k_conv_bf3", 4, 4, "B_KN4", "bf16x3", 2), ("k_conv_bf3", 8, 6, "B_KN4", "bf16x3", 4),
+    ("k_conv_bf3", 4, 10, "B_KN4", "bf16x3", 2), ("k_conv_bf3", 2, 10, "B_KN4", "bf16x3", 2),
+    ("k_conv1x1_stream", None, None, "B_KN4", "bf16x3", None),
 }
 
 
@@ -128,14 +132,15 @@ def test_case_table_reaches_every_variant():
     """The set of variants the case table runs equals the set an enumeration of the dispatch rule over every admissible block finds
     (reachable_variants; REACHABLE is that set written out) -- and, branch by branch: every tile shape, every staging mode, 4 x 4 with and
     without a residual, the streaming kernel and the 49-row launch that must not take it."""
-    assert reachable_variants() == REACHABLE and len(REACHABLE) == 16 + 21
+    assert reachable_variants() == REACHABLE and len(REACHABLE) == 16 + 22
     seen, detail = set(), {}
+    conv_plan.plans([dict(kw, math=math) for case in CASES for math in MATHS for _, kw in case_launches(case)])      # (one run of the chooser for all)
     for case in CASES:
         for math in MATHS:
             for name, kw in case_launches(case):
                 v = expected_variant(math=math, **kw)
-                seen.add(v + (math,))
-                detail.setdefault((v, math, name, kw["residual"]), case)
+                seen.add(v + (math, expected_wave_rows(math=math, **kw)))
+                detail.setdefault((v, math, name, kw["residual"]), dict(kw, math=math))
     assert seen == REACHABLE, f"missing {sorted(map(str, REACHABLE - seen))}, unexpected {sorted(map(str, seen - REACHABLE))}"
     shapes = {m: {(k[0][1], k[0][2]) for k in detail if k[1] == m and k[0][1] is not None} for m in MATHS}
     assert shapes["fp32"] == {(6, 2), (4, 4), (8, 6), (4, 10)}                      # n-subtiles per block <= 2, <= 4, 6, 10
@@ -145,7 +150,7 @@ def test_case_table_reaches_every_variant():
         assert modes == {"B_NK", "B_KN1", "B_KN2", "B_KN4"}, (math, modes)
         four = {k[3] for k in detail if k[1] == math and (k[0][1], k[0][2]) == (4, 4)}
         assert four == {False, True}, f"{math}: the 4 x 4 tile must run with and without a residual"
-    waves = {expected_wave_rows(k[0], k[3]) for k in detail if k[1] == "bf16x3" and (k[0][1], k[0][2]) == (4, 4)}
+    waves = {expected_wave_rows(**kw) for k, kw in detail.items() if k[1] == "bf16x3" and (k[0][1], k[0][2]) == (4, 4)}
     assert waves == {4, 2}
     # the streaming kernel with an input list; the same launch at 49 rows per image must not take it
     conv3 = dict(case_launches(CASES[4])[2][1])
@@ -554,7 +559,7 @@ def test_border_class_shift_table(ops, B, Hi, Wi, stride, math_mode):
 
 @gpu
 def test_argument_checks_refuse_before_any_launch(ops):
-    """The checks of ldn_conv_packed (csrc/ldn_conv_image.hip:1818-1836): an error code, and the output is not touched."""
+    """The checks of ldn_conv_packed (csrc/ldn_conv_image.hip, ldn_conv_packed): an error code, and the output is not touched."""
     from laudnet_amd import LdnError
     rows, cin, cout, B = 64, 32, 32, 2
     a = torch.zeros(rows, cin, device=DEV)

@@ -95,6 +95,7 @@ def _sites(gw, w_b, block):
         return lambda: seq(lambda: laud_regnet._conv_b_image(prepared_dict(), F, _Shape(4, Hi, Hi, w_b), None, None, _Shape(4, Ho, Ho, w_b), stride))
     wbr, x, nbr = torch.zeros(w_b, 9, gw), torch.zeros(4, w_b), None
     _tags[id(wbr)] = "wbr"
+    _keep.extend((wbr, x))      # (a tag is an id: no tagged tensor may die, or a later untagged one takes its id and its tag)
 
     def prepared():
         block.invalidate()

@@ -8,9 +8,15 @@ Every entry of build.SOURCES is compiled device-only with build.FLAGS (+ the -D 
 unbundled, and two things are compared per translation unit: the disassembly (`llvm-objdump -d`, without its file-name line) and
 the kernel metadata note (`llvm-readelf --notes`: VGPR / SGPR counts, LDS bytes, scratch, kernarg layout).  The raw objects are
 NOT the criterion: hipcc derives a per-compilation id from the source text.  One line per unit; exit status 1 on any difference.
+
+A unit whose text differs is compared again kernel by kernel (by_symbol): instantiating the same templates in another order, or fewer
+of them, moves every kernel in the code object.  Per symbol the instruction text is compared without its address column, and without
+the literal of the s_add_u32 behind an s_getpc_b64 (the distance to one of the unit's globals, which moves with the layout); per
+kernel, its entry of the metadata note.  "same kernels" counts as identical; kernels added, removed or changed are named and do not.
 """
 import argparse
 import os
+import re
 import subprocess
 import sys
 import tempfile
@@ -46,6 +52,37 @@ def device_code(tree: str, src: str, defs: list, out: str) -> tuple:
     return [ln for ln in dis.splitlines() if "file format" not in ln], note.splitlines()
 
 
+SYMBOL = re.compile(r"^[0-9a-f]{16} <(.+)>:$")
+
+
+def by_symbol(dis: list, note: list) -> dict:
+    """{symbol: (instruction text, metadata entry)} of one code object, free of everything that only says where a kernel lies."""
+    code, sym, pcrel = {}, None, 0
+    for ln in dis:
+        m = SYMBOL.match(ln)
+        if m:
+            sym = m.group(1)
+            code[sym] = []
+        elif sym is not None and ln.strip() not in ("", "..."):      # ("...": the zero fill behind the last kernel of the section)
+            text = ln.split("//")[0].strip()
+            if pcrel and text.startswith("s_add_u32 "):
+                text, pcrel = text.rsplit(",", 1)[0] + ", <pc-relative>", 0
+            else:
+                pcrel = 2 if text.startswith("s_getpc_b64") else max(pcrel - 1, 0)
+            code[sym].append(text)
+    meta, entry = {}, None
+    for ln in note:      # the entries of amdhsa.kernels: each begins "  - ." and names its kernel in .name
+        if ln.startswith("  - ."):
+            entry = [ln]
+        elif entry is not None and ln.startswith("    "):
+            entry.append(ln)
+            if ln.startswith("    .name:"):
+                meta[ln.split(":", 1)[1].strip()] = entry
+        else:
+            entry = None
+    return {k: (code[k], meta.get(k)) for k in code}
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("old")
@@ -62,9 +99,19 @@ def main() -> int:
         for s in build.SOURCES:
             (d0, n0), (d1, n1) = jobs[s, 0].result(), jobs[s, 1].result()
             same = d0 == d1 and n0 == n1
+            what, names = "identical", []
+            if not same:
+                k0, k1 = by_symbol(d0, n0), by_symbol(d1, n1)
+                removed, added = sorted(set(k0) - set(k1)), sorted(set(k1) - set(k0))
+                changed = sorted(k for k in set(k0) & set(k1) if k0[k] != k1[k])
+                same = not (removed or added or changed)
+                what = (f"same kernels ({len(k1)})" if same else
+                        f"DIFFERENT: {len(removed)} removed, {len(added)} added, {len(changed)} changed, {len(set(k0) & set(k1)) - len(changed)} same")
+                names = [f"    {w} {k}" for w, ks in (("removed", removed), ("added", added), ("changed", changed)) for k in ks]
             bad += not same
-            what = "identical" if same else "DIFFERENT:" + (" disassembly" if d0 != d1 else "") + (" metadata" if n0 != n1 else "")
             print(f"{s:24s} {what:24s} {len(d1)} disassembly lines, {len(n1)} metadata lines", flush=True)
+            for ln in names:
+                print(ln, flush=True)
         print(f"# {len(build.SOURCES) - bad} of {len(build.SOURCES)} translation units identical")
     return 1 if bad else 0
 
