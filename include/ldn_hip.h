@@ -820,6 +820,44 @@ int ldn_conv_rows_gated(const float* a, int lda, const int32_t* m_count, int m_c
                         const float* scale, const float* shift, int relu, const int32_t* relu_if_neg, const int32_t* out_rows,
                         const float* residual, int ldr, float* out, int ldo, const float* gate, int gate_rows, void* stream);
 
+/* The SE block folded into its neighbours in CHANNEL mode (a dense batch whose columns are left-packed per image; group widths 8, 16 and
+ * 24; bf16x3 arithmetic), the same three steps:
+ *   1. ldn_grouped_chan_mfma_conv3x3_image_gap = ldn_grouped_chan_mfma_conv3x3_image (the same plan, `out` bit-identical) that also leaves
+ *      the channel SUMS of its output: gap_partial [B][bands][C], bands = ldn_grouped_chan_mfma_bands(C, gw, Hi, Wi, Ho, stride); element
+ *      [b][band][j] = sum over the band's output pixels p of out[b, p, j] (after BN and ReLU), in PACKED-COLUMN order (column j is channel
+ *      ch_idx[b, j]); columns j >= ch_cnt[b] are zeros.  Every element is written by exactly one workgroup in every launch (the caller
+ *      never clears the buffer; an image with ch_cnt 0 and a group chunk without an active group leave their zeros); a fixed order of
+ *      additions (a tree over each piece of 16 pixels, pieces in ascending order), no atomics: two launches give the same bits.
+ *      The sums' scratch lies in LDS behind the staged rows of the plain plan: ldn_grouped_chan_mfma_gap_ok = 1 iff
+ *      ldn_grouped_chan_mfma_ok and that still fits the 160 KB of a CU (host arithmetic only).  Refused with LDN_EINVAL before any launch:
+ *      whatever the plain entry point refuses, a shape outside _gap_ok, a null gap_partial, a gap_partial that is not 16-byte aligned.
+ *   2. ldn_se_gate_image: gate[b][j] = sigmoid(W2[ch] . relu(W1[:, list] . (sum over splits of gap_partial / rows_per_image) + b1) + b2[ch]),
+ *      ch = ch_idx[b, j], for j < ch_cnt[b] and 0 for ch_cnt[b] <= j < C: the head of ldn_se_packed with channel lists (weights gathered
+ *      through the list) on every image of the batch at rows_per_image rows.  gap_partial [B][splits][C], gate [B][C], both in
+ *      packed-column order; w1 [S][C], w2 [C][S].
+ *   3. ldn_conv_image_gated: ldn_conv_image (its argument list, plus `gate` [B][cin], contiguous, 16-byte aligned, in front of math_mode)
+ *      with A[b, p, k] used as fp32(A[b, p, k] * gate[b][k]): bit-identical to scaling the input first and calling ldn_conv_image (where that
+ *      runs k_conv_bf3 as well, which it does behind a residual with a scale vector -- conv c of a block; its streaming kernel adds in another order).  Packed
+ *      input columns k >= k_cnt[b] are used as exact zeros whatever they and their gates hold.  Admitted: what conv c of a channel block
+ *      is -- bf16x3, ksize 1, stride 1, k_idx / k_cnt given (cin % 8 == 0, lda >= cin), n_idx / n_cnt null, shift_classes 1, post_sub
+ *      null, relu 0 / 1, out_format 0, colsum null; scale and residual optional; out may alias residual.  It runs the gated k_conv_bf3 at the
+ *      tile ldn_conv_image's chooser takes without its streaming kernel; the image's gate vector lies in LDS (roundup32(cin) * 4 bytes
+ *      more than the ungated plan).  ldn_conv_image_gated_ok = 1 iff such a launch of B images of `rows` pixels is admitted and fits
+ *      (host arithmetic only).  Everything else is LDN_EINVAL before any launch; there is no fallback inside the library.
+ * Three launches instead of five (conv b, the row sums, the SE head, the row scaling, conv c); h_b is never rewritten. */
+int ldn_grouped_chan_mfma_gap_ok(int C, int group_width, int Hi, int Wi, int stride);
+int ldn_grouped_chan_mfma_conv3x3_image_gap(const float* a, int lda, int B, int Hi, int Wi, int stride, int Ho, int Wo, const void* w_frag,
+                                            int C, int group_width, const int32_t* ch_idx, const int32_t* ch_cnt, const float* scale,
+                                            const float* shift, int relu, float* out, int ldo, float* gap_partial, void* stream);
+int ldn_se_gate_image(const float* gap_partial, int splits, int B, int rows_per_image, int C, int S, const float* w1, const float* b1,
+                      const float* w2, const float* b2, const int32_t* ch_idx, const int32_t* ch_cnt, float* gate, void* stream);
+int ldn_conv_image_gated_ok(int B, int rows, int cin, int cout, int has_residual, int has_scale);
+int ldn_conv_image_gated(const float* a, int lda, int B, int Hi, int Wi, int ksize, int stride, int Ho, int Wo,
+                         const float* w, int cin, int cout, const int32_t* k_idx, const int32_t* k_cnt, int kgran,
+                         const int32_t* n_idx, const int32_t* n_cnt, const float* scale, const float* shift, int shift_classes,
+                         const float* post_sub, int relu, const float* residual, int ldr, float* out, int ldo, float* colsum,
+                         int out_format, const float* gate, int math_mode, void* stream);
+
 /* ---- a14: token skipping (BASELINE config 5, AdaViT / DeiT-S shaped blocks).  The reference holds no model code for it, only the
  * latency model of the operator (DyNetSimulator/adavit/simulate_adavit.py:77-131: q / k / v for every token, attention
  * [B, heads, L_select, d] over the selected tokens): parity of this entry point is therefore UNPINNED -- it is tested against a

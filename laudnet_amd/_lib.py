@@ -97,6 +97,12 @@ SIGNATURES = {
     "ldn_grouped_chan_mfma_ok": ([_I, _I, _I, _I, _I], _I),
     "ldn_grouped_chan_mfma_bands": ([_I, _I, _I, _I, _I, _I], _I),
     "ldn_grouped_chan_mfma_conv3x3_image": ([_P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _P, _I, _P], _I),
+    "ldn_grouped_chan_mfma_gap_ok": ([_I, _I, _I, _I, _I], _I),
+    "ldn_grouped_chan_mfma_conv3x3_image_gap": ([_P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P], _I),
+    "ldn_se_gate_image": ([_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P], _I),
+    "ldn_conv_image_gated_ok": ([_I, _I, _I, _I, _I, _I], _I),
+    "ldn_conv_image_gated": ([_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I,
+                              _P, _I, _P, _I, _P, _I, _P, _I, _P], _I),
     "ldn_grouped_wide_ok": ([_I, _I, _I, _I, _I], _I),
     "ldn_grouped_wide_bands": ([_I, _I, _I, _I, _I, _I], _I),
     "ldn_grouped_wide_strips": ([_I, _I, _I, _I, _I], _I),

@@ -62,7 +62,10 @@ struct ImgArgs {
     const int32_t* a_map;            // [rows][taps] A row of each tap (-1 = zero), NULL = identity (taps == 1)
     const int32_t* out_map;          // [rows] destination row in out/residual, NULL = identity
     const int32_t* pix_map;          // [rows] flat output pixel (b*Ho*Wo + oy*Wo + ox) for the border classes, or NULL
-    const int32_t* relu_if_neg;      // relu == 2: ReLU only where relu_if_neg[row] < 0
+    union {
+        const int32_t* relu_if_neg;  // relu == 2: ReLU only where relu_if_neg[row] < 0
+        const float* gate;           // gated k_conv_bf3 (dense image mode, relu < 2): [B][cin] multiplier of the packed input columns
+    };                               // (one slot for both: the kernel arguments of the ungated kernels keep their layout)
     int ntn;    // N blocks per image
     int mtn;    // M blocks per image
     int bn;     // columns per N block (multiple of 32, <= NS*32)
@@ -739,6 +742,17 @@ __global__ __launch_bounds__(512, MINW) void k_conv_image(const ImgArgs p) {
 #endif
 }
 
+// (GATE) x <- fp32(x * g) for the eight values of a raw A octet, zeros from position `left` of the octet on.  Contraction is off: the
+// product must round to fp32 before split8 subtracts its bf16 head from it.
+__device__ __forceinline__ void gate8(f32x4& x0, f32x4& x1, const f32x4& g0, const f32x4& g1, int left) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        x0[e] = e < left ? x0[e] * g0[e] : 0.f;
+        x1[e] = e + 4 < left ? x1[e] * g1[e] : 0.f;
+    }
+}
+
 // ================================================================================================ bf16x3 kernel
 // Split-precision variant (math mode 1).  Same block structure, A staging, tables and epilogue as k_conv_image, but
 //   * every fp32 operand x is used as bf16 hi + bf16 lo (both round-to-nearest-even, x = hi + lo + O(2^-17 |x|)) and a
@@ -750,8 +764,21 @@ __global__ __launch_bounds__(512, MINW) void k_conv_image(const ImgArgs p) {
 //   * the ACTIVATION tile still lands as raw fp32 through LDS-DMA; each consumer wave owns whole m-subtiles (wave grid
 //     WM x 4/WM over the block's subtiles), splits its A fragments once per K16 step and reuses them against every
 //     n-subtile it owns -- register blocking that keeps both the VALU work and the LDS reads per MFMA low.
-template <int MS, int NS, int WM, int BMODE, bool KSKIP, int MINW>
+//   * GATE (k_conv_bf3<.., B_KN4 | B_GATE, ..>: conv c of a channel-mode block behind the folded SE, ldn_conv_image_gated): A[b, p, k] is used as
+//     fp32(A[b, p, k] * gate[b][k]).  The image's gate vector lies in LDS behind the input-channel list (the consumers fill it with the
+//     epilogue tables; zeros from K_b on), and a consumer multiplies its raw A octet by the octet's eight gates -- two broadcast
+//     ds_read_b128 per K16 step, shared by its m-subtiles -- in front of the split: a plain fp32 product, never contracted into the
+//     split's subtraction, so the result has the bits of the same launch on pre-scaled rows.  Packed positions from K_b on are used as
+//     exact zeros whatever the columns hold.  1x1, one tap: the flat K position IS the packed column.
+//     GATE is a compile-time flag carried ON the BMODE argument (B_KN4 | B_GATE): a seventh template argument would rename every built
+//     k_conv_bf3, and the body moved into a function of its own changed their register allocation; this way the symbols and the code of
+//     the ungated instantiations stay what they were (tools/same_isa.py).
+constexpr int B_GATE = 8;
+template <int MS, int NS, int WM, int BMODE_, bool KSKIP, int MINW>
 __global__ __launch_bounds__(512, MINW) void k_conv_bf3(const ImgArgs p) {
+    constexpr bool GATE = (BMODE_ & B_GATE) != 0;
+    constexpr int BMODE = BMODE_ & ~B_GATE;
+    static_assert(!GATE || BMODE == B_KN4, "the gated form is built for an input-channel list without an output list");
     static_assert(MS >= 1 && MS + NS <= 18 && NS % 2 == 0 && (WM == 1 || WM == 2 || WM == 4), "tile shape");
     constexpr int WN = 4 / WM;                             // consumer wave grid WM (m) x WN (n)
     constexpr int AM = (MS + WM - 1) / WM, CN = (NS + WN - 1) / WN;   // subtiles per wave in m / n
@@ -781,10 +808,13 @@ __global__ __launch_bounds__(512, MINW) void k_conv_bf3(const ImgArgs p) {
     const int Kp = KN ? max(round_up(Kb, 8), BK) : round_up(p.cin, BK);
     const int Ktot = T * Kp;
     const int nch = Kb > 0 ? ceil_div(Ktot, BK) : 0;
+    float* const s_gate = reinterpret_cast<float*>(t.s_kidx + p.cin);   // (GATE) [round_up(cin, 32)], counted by conv_plan_gated
     if (wave8 < 4) {
         // the consumers gather the epilogue tables while the producers' first loads are in flight; one extra
         // workgroup barrier (matched in the producer prologue) publishes them
         tile_tables<NS>(p, t, tid, 256);
+        if constexpr (GATE)
+            for (int i = tid; i < round_up(p.cin, BK); i += 256) s_gate[i] = i < Kb ? p.gate[(size_t)t.b * p.cin + i] : 0.f;
         lds_barrier();
     }
 
@@ -1149,6 +1179,12 @@ __global__ __launch_bounds__(512, MINW) void k_conv_bf3(const ImgArgs p) {
             for (int ks = 0; ks < BK / 16; ++ks) {
                 if (KSKIP && 2 * ks >= kgroups) break;
                 bf16x8 ah[AM], al[AM];
+                if constexpr (GATE) {
+                    const int k0 = ch * BK + 8 * (2 * ks + h);       // packed column of the lane's octet
+                    const f32x4 g0 = *reinterpret_cast<const f32x4*>(s_gate + k0), g1 = *reinterpret_cast<const f32x4*>(s_gate + k0 + 4);
+#pragma unroll
+                    for (int a = 0; a < AM; ++a) gate8(ar[a][0], ar[a][1], g0, g1, Kb - k0);
+                }
 #pragma unroll
                 for (int a = 0; a < AM; ++a) split8<const f32x4&>(ar[a][0], ar[a][1], ah[a], al[a]);
                 if (ks + 1 < BK / 16) {
@@ -1659,6 +1695,23 @@ static int launch_conv(const ImgArgs& p, int kgran, hipStream_t st) {
     return launch_conv_plan(conv_plan(s), p, st);
 }
 
+// The gated launch: the row of LDN_CONV_GATED_KERNELS that the plan is, through the same launcher; anything else is refused.
+static int launch_conv_gated(const ImgArgs& p, int kgran, hipStream_t st) {
+    ConvShape s{};
+    s.packed = false; s.B = p.B; s.rows = p.Ho * p.Wo; s.taps = p.ksize * p.ksize;
+    s.cin = p.cin; s.cout = p.cout; s.has_k = p.k_idx != nullptr; s.has_n = p.n_idx != nullptr; s.kgran = kgran; s.shift_classes = p.shift_classes;
+    s.residual = p.residual != nullptr; s.scale = p.scale != nullptr; s.out_split = p.out_split != 0; s.math = p.math; s.stream_rows = 0;
+    LDN_REQUIRE(conv_gated_shape_ok(s), "ldn_conv_image_gated: not a gated shape (bf16x3, 1x1 at stride 1, an input-channel list over a cin that is a "
+                "multiple of 8, no output list, one shift class, out_format 0)");
+    LDN_REQUIRE(conv_weight_elems(s) < kConvWeightLimit, "ldn_conv_image_gated: weight tensor of %ld elements exceeds the 32-bit offsets of the weight staging", conv_weight_elems(s));
+    const ConvPlan plan = conv_plan_gated(s);
+#define LDN_G(MS, NS, WM, BMODE) \
+    if (plan == LDN_CONV_ROW_F(MS, NS, WM, BMODE)) return launch_conv_kernel(&k_conv_bf3<MS, NS, WM, BMODE | B_GATE, conv_kskip(MS, NS), conv_minw(MS, NS)>, "k_conv_bf3 (gated)", plan, p, st);
+    LDN_CONV_GATED_KERNELS(LDN_G)
+#undef LDN_G
+    LDN_REQUIRE(false, "ldn_conv_image_gated: %s is not built with a gate (cin %d, cout %d, rows %d)", conv_plan_name(plan).c_str(), p.cin, p.cout, p.Ho * p.Wo);
+}
+
 LDN_DEFINE_TU_VIOLATIONS(tu_violations_conv)
 
 }  // namespace ldn
@@ -1712,6 +1765,42 @@ extern "C" int ldn_conv_image(const float* a, int lda, int B, int Hi, int Wi, in
     LDN_REQUIRE(out_format == 0 || (out_format == 1 && math == 1 && !residual && !colsum && ldo % 32 == 0 && ldo >= round_up(cout, 32)),
                 "ldn_conv_image: out_format 1 (pre-split bf16 pairs) needs math_mode bf16x3, no residual / colsum and ldo %% 32 == 0");
     return launch_conv(p, kgran, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int ldn_conv_image_gated_ok(int B, int rows, int cin, int cout, int has_residual, int has_scale) {
+    ConvShape s{};
+    s.B = B; s.rows = rows; s.taps = 1; s.cin = cin; s.cout = cout; s.has_k = true; s.kgran = 1; s.shift_classes = 1;
+    s.residual = has_residual != 0; s.scale = has_scale != 0; s.math = 1;
+    return conv_gated_ok(s) ? 1 : 0;
+}
+
+extern "C" int ldn_conv_image_gated(const float* a, int lda, int B, int Hi, int Wi, int ksize, int stride, int Ho, int Wo,
+                                    const float* w, int cin, int cout, const int32_t* k_idx, const int32_t* k_cnt,
+                                    int kgran, const int32_t* n_idx, const int32_t* n_cnt, const float* scale,
+                                    const float* shift, int shift_classes, const float* post_sub, int relu,
+                                    const float* residual, int ldr, float* out, int ldo, float* colsum, int out_format,
+                                    const float* gate, int math_mode, void* stream) {
+    LDN_REQUIRE(a && w && shift && out && gate, "ldn_conv_image_gated: null pointer");
+    int math;
+    if (int rc = resolve_math(math_mode, &math)) return rc;
+    LDN_REQUIRE(math == 1, "ldn_conv_image_gated: bf16x3 arithmetic only");
+    LDN_REQUIRE(ksize == 1 && stride == 1, "ldn_conv_image_gated: a 1x1 at stride 1 only (ksize %d, stride %d)", ksize, stride);
+    LDN_REQUIRE(B > 0 && Hi > 0 && Wi > 0 && Ho == Hi && Wo == Wi && Ho < 65536 && Wo < 65536 && (long)Ho * Wo < (1L << 31), "ldn_conv_image_gated: bad geometry");
+    LDN_REQUIRE(k_idx && k_cnt && kgran >= 1, "ldn_conv_image_gated: the input-channel list, its counts and kgran >= 1 are required");
+    LDN_REQUIRE(!n_idx && !n_cnt, "ldn_conv_image_gated: no output-channel list");
+    LDN_REQUIRE(shift_classes == 1 && !post_sub && !colsum && out_format == 0, "ldn_conv_image_gated: one shift class, no post_sub, no colsum, out_format 0");
+    LDN_REQUIRE(relu == 0 || relu == 1, "ldn_conv_image_gated: relu must be 0 or 1");
+    LDN_REQUIRE(cin > 0 && cout > 0 && cin % 8 == 0, "ldn_conv_image_gated: cin must be a positive multiple of 8 (got %d)", cin);
+    LDN_REQUIRE(lda % 4 == 0 && lda >= cin, "ldn_conv_image_gated: lda must be a multiple of 4 and >= cin");
+    LDN_REQUIRE(ldo >= cout && ldo % 4 == 0 && cout % 4 == 0, "ldn_conv_image_gated: cout and ldo must be multiples of 4, ldo >= cout");
+    LDN_REQUIRE((uintptr_t)out % 16 == 0 && (!residual || ((uintptr_t)residual % 16 == 0 && ldr % 4 == 0 && ldr >= cout)),
+                "ldn_conv_image_gated: out/residual must be 16-byte aligned with strides that are multiples of 4, ldr >= cout");
+    LDN_REQUIRE((uintptr_t)a % 16 == 0 && (uintptr_t)w % 16 == 0 && (uintptr_t)gate % 16 == 0, "ldn_conv_image_gated: a/w/gate must be 16-byte aligned");
+    ImgArgs p{a, lda, B, Hi, Wi, ksize, stride, Ho, Wo, w, cin, cout, k_idx, k_cnt, nullptr, nullptr,
+              scale, shift, shift_classes, nullptr, relu, residual, ldr, out, ldo, nullptr,
+              0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, math, 0};
+    p.gate = gate;
+    return launch_conv_gated(p, kgran, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int ldn_conv_packed(const float* a, int lda, int B, const int32_t* row_prefix, const int32_t* m_count,

@@ -85,6 +85,11 @@ inline std::string conv_plan_name(const ConvKernel& k) {
     F(6, 2, 2, B_KN2) F(4, 4, 4, B_KN2) F(8, 6, 4, B_KN2) F(4, 10, 2, B_KN2) F(2, 10, 2, B_KN2)                                \
     F(6, 2, 2, B_KN1) F(4, 4, 4, B_KN1) F(8, 6, 4, B_KN1) F(4, 10, 2, B_KN1) F(2, 10, 2, B_KN1)                                \
     S(B_NK) S(B_KN4)
+// The gated instantiations of k_conv_bf3 (ldn_conv_image_gated: conv c of a channel-mode block behind the folded SE), a list of its own:
+// the B_KN4 rows that conv_plan_gated() returns for the shapes conv_gated_shape_ok() admits, each reached by the sweep of
+// tests/test_conv_gated_plan.py.  A gated plan that is no row here is refused.
+#define LDN_CONV_GATED_KERNELS(F) \
+    F(6, 2, 2, B_KN4) F(4, 4, 4, B_KN4) F(4, 4, 2, B_KN4) F(8, 6, 4, B_KN4) F(4, 10, 2, B_KN4) F(2, 10, 2, B_KN4)
 // The kernel that a row of the list is.
 #define LDN_CONV_ROW_I(MS, NS, BMODE) ::ldn::ConvKernel{::ldn::CONV_IMAGE, MS, NS, 0, ::ldn::BMODE}
 #define LDN_CONV_ROW_F(MS, NS, WM, BMODE) ::ldn::ConvKernel{::ldn::CONV_BF3, MS, NS, WM, ::ldn::BMODE}
@@ -137,8 +142,8 @@ inline ConvPlan conv_plan_stream(const ConvShape& s) {
     return p;
 }
 
-inline ConvPlan conv_plan(const ConvShape& s) {
-    if (conv_streams(s)) return conv_plan_stream(s);
+// The k_conv_image / k_conv_bf3 plan of a shape (conv_plan() below asks the streaming kernel first).
+inline ConvPlan conv_plan_tile(const ConvShape& s) {
     // how the weights are staged: w is [cout][taps][cin] without an input list, [taps][cin][cout] with one
     const int g = s.has_n ? s.kgran : 4;
     const int bmode = !s.has_k ? B_NK : g % 4 == 0 ? B_KN4 : g % 2 == 0 ? B_KN2 : B_KN1;
@@ -172,6 +177,38 @@ inline ConvPlan conv_plan(const ConvShape& s) {
     p.grid = (long)conv_round_up(s.B * p.mtn, 8) * p.ntn;          // units padded to the 8 XCDs (tile_setup)
     p.lds_bytes = conv_tile_lds_bytes(s, ms, ns);
     return p;
+}
+
+inline ConvPlan conv_plan(const ConvShape& s) {
+    if (conv_streams(s)) return conv_plan_stream(s);
+    return conv_plan_tile(s);
+}
+
+// ---- the gated form of k_conv_bf3 ---------------------------------------------------------------------------------------------------
+// What it admits by shape: conv c of a channel-mode block -- bf16x3, a 1x1 at stride 1 over a dense image, an input list and no output
+// list, one shift class, fp32 rows out.  (post_sub, colsum and the alignment of the pointers are the entry point's to refuse.)
+inline bool conv_gated_shape_ok(const ConvShape& s) {
+    return !s.packed && s.math == 1 && s.taps == 1 && s.has_k && !s.has_n && s.shift_classes == 1 && !s.out_split && s.B > 0 && s.rows > 0 &&
+           s.cin > 0 && s.cin % 8 == 0 && s.cout > 0 && s.cout % 4 == 0 && s.kgran >= 1;
+}
+// Its plan: the tile plan of the shape, never the streaming kernel, plus the image's gate vector behind the input-channel list.
+inline long conv_gate_lds_bytes(const ConvShape& s) { return (long)conv_round_up(s.cin, BK) * 4; }
+inline ConvPlan conv_plan_gated(const ConvShape& s) {
+    ConvPlan p = conv_plan_tile(s);
+    p.lds_bytes += conv_gate_lds_bytes(s);
+    return p;
+}
+inline bool conv_gated_built(const ConvKernel& k) {
+#define LDN_G(MS, NS, WM, BMODE) if (k == ::ldn::ConvKernel{::ldn::CONV_BF3, MS, NS, WM, ::ldn::BMODE}) return true;
+    LDN_CONV_GATED_KERNELS(LDN_G)
+#undef LDN_G
+    return false;
+}
+// 1 iff ldn_conv_image_gated takes the shape: admitted, its plan a row of the gated list, within the LDS of a CU.
+inline bool conv_gated_ok(const ConvShape& s) {
+    if (!conv_gated_shape_ok(s)) return false;
+    const ConvPlan p = conv_plan_gated(s);
+    return conv_admitted(s, p) && conv_gated_built(p);
 }
 
 }  // namespace ldn

@@ -44,12 +44,18 @@ struct GcArgs {
     int gchunk, in_ld;                      // groups per workgroup; floats per staged pixel (gw gchunk + 4)
     int R, nbands;                          // output rows per workgroup (Ho: the whole image), bands per image
     int tab_bytes;                          // the tables in front of the fragments
+    float* gap;                             // (GAP) [image][band][C] channel sums of the band's output, packed-column order
 };
 
 __host__ __device__ inline int gc_frag_bytes(int gw) { return (gw == 24 ? 14 : gw == 16 ? 5 : 3) * 64 * 32; }
 __host__ __device__ inline int gc_tab_bytes(int gw, int ng) { return round_up((ng * gw + ng + 4) * 4, 16); }     // map [ng gw], active list [ng], count
 
-template <int GW>
+// GAP: the epilogue also leaves the sums of the band's output pixels per packed column (the SE squeeze of the block, ldn_se_gate_image),
+// as k_grouped_gw_img's gap form does: a DPP tree over the 16 pixels of a lane row, one slot of LDS per (active group, 16-pixel piece),
+// then the pieces in ascending order -- no atomics, the same bits in every launch.  The scratch lies behind the staged rows
+// (gc_gap_bytes: the plain form's plan does not count it; ldn_grouped_chan_mfma_gap_ok answers whether it still fits).  The zeros of the
+// columns behind the count are written with the output's zeros (step 2), so every element of gap has exactly one writer.
+template <int GW, bool GAP = false>
 __global__ __launch_bounds__(GC_THREADS, 2) void k_grouped_chan(const GcArgs p) {
     typedef GcCfg<GW> cfg;
     constexpr int STEPS = cfg::STEPS, TILE = cfg::TILE, FRAG = STEPS * 64 * 32, QG = GW / 4;
@@ -107,6 +113,8 @@ __global__ __launch_bounds__(GC_THREADS, 2) void k_grouped_chan(const GcArgs p) 
             const int px = i / nz;
             obase[(size_t)px * p.ldo + z0 + (i - px * nz)] = 0.f;
         }
+        if constexpr (GAP)
+            for (int i = tid; i < nz; i += GC_THREADS) p.gap[((size_t)b * p.nbands + band) * p.C + z0 + i] = 0.f;
     }
     if (nact == 0) return;                                      // (uniform) no active channel in the chunk: nothing staged, no MFMA
     // ---- 3. fragments of the active groups; the band's input rows, expanded
@@ -142,6 +150,8 @@ __global__ __launch_bounds__(GC_THREADS, 2) void k_grouped_chan(const GcArgs p) 
     // ---- 4. (pixel tile, active group) items
     const int n = lane & (TILE - 1), kg = lane / TILE;          // B operand / output column = pixel n of the tile; k-group kg of a step
     const int ntile = (npix + TILE - 1) / TILE;
+    const int nsub = ntile * (TILE / 16);                       // (GAP) 16-pixel pieces per group
+    float* const s_gap = s_in + ((size_t)HWi + 1) * p.in_ld;    // (GAP) [active group][piece][GW slots]
     for (int w = wave; w < ntile * nact; w += GC_THREADS / 64) {
         const int ga = w / ntile, tile = w - ga * ntile;
         const int gl = __builtin_amdgcn_readfirstlane(s_act[ga]);
@@ -183,7 +193,33 @@ __global__ __launch_bounds__(GC_THREADS, 2) void k_grouped_chan(const GcArgs p) 
 #pragma unroll
         for (int Q = 0; Q < (GW == 24 ? 3 : 1); ++Q) {
             const int sb = GW == 24 ? 8 * Q + 4 * kg : 4 * kg;
-            if (valid && (GW != 8 || kg < 2)) {
+            if constexpr (GAP) {
+                // every lane takes part in the DPP sums; lanes without output (tile tail; width 8, kg >= 2) add zeros and store nothing.
+                // The values are those of the plain branch below (the same expression on the same operands), inactive slots included:
+                // their sums go to LDS and are dropped by the final pass.
+                const bool has_out = GW != 8 || kg < 2;
+                const int c = (g0 + gl) * GW + (has_out ? sb : sb - 8);
+                const f32x4 sc = *reinterpret_cast<const f32x4*>(p.scale + c), sh = *reinterpret_cast<const f32x4*>(p.shift + c);
+                f32x4 v, t4;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    v[e] = acc[4 * Q + e] * sc[e] + sh[e];
+                    if (p.relu) v[e] = fmaxf(v[e], 0.f);
+                    t4[e] = row16_sum(valid && has_out ? v[e] : 0.f);
+                }
+                if (valid && has_out) {
+                    const i32x4 m = *reinterpret_cast<const i32x4*>(s_map + gl * GW + sb);
+                    if (m[0] >= 0 && (m[0] & 3) == 0 && m[1] == m[0] + 1 && m[2] == m[0] + 2 && m[3] == m[0] + 3) {
+                        *reinterpret_cast<f32x4*>(orow + m[0]) = v;
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (m[e] >= 0) orow[m[e]] = v[e];
+                    }
+                }
+                const int sub = GW == 24 ? 2 * tile + ((lane >> 4) & 1) : tile;
+                if ((lane & 15) == 0 && has_out) *reinterpret_cast<f32x4*>(s_gap + ((size_t)ga * nsub + sub) * GW + sb) = t4;
+            } else if (valid && (GW != 8 || kg < 2)) {
                 const int c = (g0 + gl) * GW + sb;
                 const f32x4 sc = *reinterpret_cast<const f32x4*>(p.scale + c), sh = *reinterpret_cast<const f32x4*>(p.shift + c);
                 const i32x4 m = *reinterpret_cast<const i32x4*>(s_map + gl * GW + sb);
@@ -203,6 +239,17 @@ __global__ __launch_bounds__(GC_THREADS, 2) void k_grouped_chan(const GcArgs p) 
             }
         }
     }
+    if constexpr (GAP) {
+        __syncthreads();
+        for (int i = tid; i < nact * GW; i += GC_THREADS) {
+            const int ga = i / GW, sl = i - ga * GW;
+            const int m = s_map[s_act[ga] * GW + sl];
+            if (m < 0) continue;
+            float s = 0.f;
+            for (int t = 0; t < nsub; ++t) s += s_gap[((size_t)ga * nsub + t) * GW + sl];
+            p.gap[((size_t)b * p.nbands + band) * p.C + m] = s;
+        }
+    }
 }
 
 // Groups per workgroup and output rows per workgroup (false: not even the three input rows of one output row of one group fit).
@@ -212,6 +259,12 @@ __global__ __launch_bounds__(GC_THREADS, 2) void k_grouped_chan(const GcArgs p) 
 // so a map near a limit is answered "does not fit", never by a failed launch (the lesson recorded at gi_plan, ldn_grouped.hip).
 static size_t gc_bytes(int gw, int ng, long in_rows, int Wi) {
     return (size_t)gc_tab_bytes(gw, ng) + (size_t)ng * gc_frag_bytes(gw) + ((size_t)in_rows * Wi + 1) * (gw * ng + 4) * 4;
+}
+
+// (GAP) the scratch of the channel sums behind the staged rows: one slot per (group, 16 output pixels), out_rows output rows a workgroup
+static size_t gc_gap_bytes(int gw, int ng, long out_rows, int Wo) {
+    const int tile = gw == 24 ? 32 : 16;
+    return (size_t)ng * ceil_div((int)(out_rows * Wo), tile) * (tile / 16) * gw * 4;
 }
 
 static bool gc_plan(int C, int gw, int Hi, int Wi, int Ho, int stride, int* ng_out, int* R_out) {
@@ -235,10 +288,10 @@ static bool gc_plan(int C, int gw, int Hi, int Wi, int Ho, int stride, int* ng_o
     return false;
 }
 
-template <int GW>
+template <int GW, bool GAP>
 static int launch_grouped_chan(const GcArgs& g, size_t lds, unsigned nwg, hipStream_t stream) {
-    LDN_REQUIRE(allow_dynamic_lds(reinterpret_cast<const void*>(&k_grouped_chan<GW>), lds), "k_grouped_chan<%d>: cannot reserve %zu B of LDS", GW, lds);
-    hipLaunchKernelGGL(k_grouped_chan<GW>, dim3(nwg), dim3(GC_THREADS), lds, stream, g);
+    LDN_REQUIRE(allow_dynamic_lds(reinterpret_cast<const void*>(&k_grouped_chan<GW, GAP>), lds), "k_grouped_chan<%d>: cannot reserve %zu B of LDS", GW, lds);
+    hipLaunchKernelGGL((k_grouped_chan<GW, GAP>), dim3(nwg), dim3(GC_THREADS), lds, stream, g);
     LDN_CHECK_LAUNCH("k_grouped_chan");
     return LDN_OK;
 }
@@ -262,33 +315,67 @@ extern "C" int ldn_grouped_chan_mfma_bands(int C, int group_width, int Hi, int W
     return ceil_div(Ho, R);
 }
 
-extern "C" int ldn_grouped_chan_mfma_conv3x3_image(const float* a, int lda, int B, int Hi, int Wi, int stride, int Ho, int Wo,
-                                                   const void* w_frag, int C, int group_width, const int32_t* ch_idx, const int32_t* ch_cnt,
-                                                   const float* scale, const float* shift, int relu, float* out, int ldo, void* stream) {
-    LDN_REQUIRE(a && w_frag && ch_idx && ch_cnt && scale && shift && out, "ldn_grouped_chan_mfma_conv3x3_image: null pointer");
+// LDS of a launch of the plan (ng groups, R output rows a workgroup), with the channel sums' scratch when gap
+static size_t gc_launch_bytes(int gw, int ng, int R, int Hi, int Wi, int Ho, int Wo, int stride, bool gap) {
+    const long in_rows = R == Ho ? (long)Hi : std::min<long>(Hi, (long)(R - 1) * stride + 3);
+    return gc_bytes(gw, ng, in_rows, Wi) + (gap ? gc_gap_bytes(gw, ng, R, Wo) : 0);
+}
+
+constexpr size_t GC_LDS_CU = 160 * 1024;    // the LDS of a CU: the gap form may use what the plain plan's budget leaves of it
+
+extern "C" int ldn_grouped_chan_mfma_gap_ok(int C, int group_width, int Hi, int Wi, int stride) {
+    int ng = 0, R = 0;
+    if (!ldn_grouped_chan_mfma_ok(C, group_width, Hi, Wi, stride)) return 0;
+    const int Ho = (Hi - 1) / stride + 1, Wo = (Wi - 1) / stride + 1;
+    if (!gc_plan(C, group_width, Hi, Wi, Ho, stride, &ng, &R)) return 0;
+    return gc_launch_bytes(group_width, ng, R, Hi, Wi, Ho, Wo, stride, true) <= GC_LDS_CU ? 1 : 0;
+}
+
+static int grouped_chan_image(const char* name, const float* a, int lda, int B, int Hi, int Wi, int stride, int Ho, int Wo, const void* w_frag, int C,
+                              int group_width, const int32_t* ch_idx, const int32_t* ch_cnt, const float* scale, const float* shift, int relu,
+                              float* out, int ldo, float* gap, void* stream) {
+    LDN_REQUIRE(a && w_frag && ch_idx && ch_cnt && scale && shift && out, "%s: null pointer", name);
     LDN_REQUIRE(B > 0 && Hi > 0 && Wi > 0 && stride >= 1 && Ho == (Hi - 1) / stride + 1 && Wo == (Wi - 1) / stride + 1,
-                "ldn_grouped_chan_mfma_conv3x3_image: %dx%d -> %dx%d is not a 3x3 / pad 1 / stride %d geometry", Hi, Wi, Ho, Wo, stride);
+                "%s: %dx%d -> %dx%d is not a 3x3 / pad 1 / stride %d geometry", name, Hi, Wi, Ho, Wo, stride);
     LDN_REQUIRE(ldn_grouped_chan_mfma_ok(C, group_width, Hi, Wi, stride),
-                "ldn_grouped_chan_mfma_conv3x3_image: group width %d with %d channels on a %dx%d map at stride %d is not built (widths 8, 16 and 24, "
-                "channels a multiple of the width, stride 1 or 2, three rows of one group in the LDS: ldn_grouped_chan_mfma_ok)", group_width, C, Hi, Wi, stride);
-    LDN_REQUIRE(lda % 4 == 0 && ldo % 4 == 0 && lda >= C && ldo >= C, "ldn_grouped_chan_mfma_conv3x3_image: strides must be multiples of 4 and at least C");
+                "%s: group width %d with %d channels on a %dx%d map at stride %d is not built (widths 8, 16 and 24, "
+                "channels a multiple of the width, stride 1 or 2, three rows of one group in the LDS: ldn_grouped_chan_mfma_ok)", name, group_width, C, Hi, Wi, stride);
+    LDN_REQUIRE(lda % 4 == 0 && ldo % 4 == 0 && lda >= C && ldo >= C, "%s: strides must be multiples of 4 and at least C", name);
     LDN_REQUIRE((uintptr_t)a % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)w_frag % 16 == 0 && (uintptr_t)scale % 16 == 0 &&
-                (uintptr_t)shift % 16 == 0, "ldn_grouped_chan_mfma_conv3x3_image: pointers must be 16-byte aligned");
+                (uintptr_t)shift % 16 == 0 && (uintptr_t)gap % 16 == 0, "%s: pointers must be 16-byte aligned", name);
     GcArgs g{};
     g.a = a; g.lda = lda; g.B = B; g.Hi = Hi; g.Wi = Wi; g.Ho = Ho; g.Wo = Wo; g.stride = stride;
     g.wf = static_cast<const unsigned char*>(w_frag); g.C = C; g.ch_idx = ch_idx; g.ch_cnt = ch_cnt;
-    g.scale = scale; g.shift = shift; g.relu = relu; g.out = out; g.ldo = ldo;
-    LDN_REQUIRE(gc_plan(C, group_width, Hi, Wi, Ho, stride, &g.gchunk, &g.R), "ldn_grouped_chan_mfma_conv3x3_image: the map does not fit the LDS");
+    g.scale = scale; g.shift = shift; g.relu = relu; g.out = out; g.ldo = ldo; g.gap = gap;
+    LDN_REQUIRE(gc_plan(C, group_width, Hi, Wi, Ho, stride, &g.gchunk, &g.R), "%s: the map does not fit the LDS", name);
     g.nbands = ceil_div(Ho, g.R);
     g.in_ld = group_width * g.gchunk + 4;
     g.tab_bytes = gc_tab_bytes(group_width, g.gchunk);
-    const long in_rows = g.R == Ho ? (long)Hi : std::min<long>(Hi, (long)(g.R - 1) * stride + 3);
-    const size_t lds = gc_bytes(group_width, g.gchunk, in_rows, Wi);
-    LDN_REQUIRE(lds <= GC_LDS_ONE, "ldn_grouped_chan_mfma_conv3x3_image: %zu B of LDS planned", lds);
+    const size_t lds = gc_launch_bytes(group_width, g.gchunk, g.R, Hi, Wi, Ho, Wo, stride, gap != nullptr);
+    LDN_REQUIRE(lds <= (gap ? GC_LDS_CU : GC_LDS_ONE), "%s: %zu B of LDS planned%s", name, lds, gap ? " (ldn_grouped_chan_mfma_gap_ok)" : "");
     const long pairs = (long)B * g.nbands;
     const long nwg = (pairs + 7) / 8 * 8 * ceil_div(C / group_width, g.gchunk);
-    LDN_REQUIRE(nwg < (1l << 31), "ldn_grouped_chan_mfma_conv3x3_image: too many workgroups (%ld)", nwg);
+    LDN_REQUIRE(nwg < (1l << 31), "%s: too many workgroups (%ld)", name, nwg);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return group_width == 24 ? launch_grouped_chan<24>(g, lds, (unsigned)nwg, st)
-         : group_width == 16 ? launch_grouped_chan<16>(g, lds, (unsigned)nwg, st) : launch_grouped_chan<8>(g, lds, (unsigned)nwg, st);
+    if (gap)
+        return group_width == 24 ? launch_grouped_chan<24, true>(g, lds, (unsigned)nwg, st)
+             : group_width == 16 ? launch_grouped_chan<16, true>(g, lds, (unsigned)nwg, st) : launch_grouped_chan<8, true>(g, lds, (unsigned)nwg, st);
+    return group_width == 24 ? launch_grouped_chan<24, false>(g, lds, (unsigned)nwg, st)
+         : group_width == 16 ? launch_grouped_chan<16, false>(g, lds, (unsigned)nwg, st) : launch_grouped_chan<8, false>(g, lds, (unsigned)nwg, st);
+}
+
+extern "C" int ldn_grouped_chan_mfma_conv3x3_image(const float* a, int lda, int B, int Hi, int Wi, int stride, int Ho, int Wo,
+                                                   const void* w_frag, int C, int group_width, const int32_t* ch_idx, const int32_t* ch_cnt,
+                                                   const float* scale, const float* shift, int relu, float* out, int ldo, void* stream) {
+    return grouped_chan_image("ldn_grouped_chan_mfma_conv3x3_image", a, lda, B, Hi, Wi, stride, Ho, Wo, w_frag, C, group_width, ch_idx, ch_cnt, scale, shift,
+                              relu, out, ldo, nullptr, stream);
+}
+
+extern "C" int ldn_grouped_chan_mfma_conv3x3_image_gap(const float* a, int lda, int B, int Hi, int Wi, int stride, int Ho, int Wo,
+                                                       const void* w_frag, int C, int group_width, const int32_t* ch_idx, const int32_t* ch_cnt,
+                                                       const float* scale, const float* shift, int relu, float* out, int ldo, float* gap_partial,
+                                                       void* stream) {
+    LDN_REQUIRE(gap_partial, "ldn_grouped_chan_mfma_conv3x3_image_gap: null pointer");
+    return grouped_chan_image("ldn_grouped_chan_mfma_conv3x3_image_gap", a, lda, B, Hi, Wi, stride, Ho, Wo, w_frag, C, group_width, ch_idx, ch_cnt, scale,
+                              shift, relu, out, ldo, gap_partial, stream);
 }

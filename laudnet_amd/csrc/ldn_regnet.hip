@@ -151,7 +151,8 @@ __global__ __launch_bounds__(NT) void k_se_head(const float* __restrict__ partia
     constexpr int NW = NT / 64;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // slot form (slot_rows > 0): b is the b-th KEPT image, whole images of slot_rows rows each, *m_count rows in all
-    const int n = slot_rows > 0 ? ((long)b * slot_rows < (long)m_count[0] ? slot_rows : 0) : prefix[b + 1] - prefix[b];
+    // (m_count == NULL: every image of the batch is present -- the dense batch of channel mode, ldn_se_gate_image)
+    const int n = slot_rows > 0 ? (!m_count || (long)b * slot_rows < (long)m_count[0] ? slot_rows : 0) : prefix[b + 1] - prefix[b];
     if (n == 0) return;         // skipped image: its gate is never read
     const int Cb = ch_idx ? ch_cnt[b] : C;
     const float inv = 1.f / (float)n;
@@ -388,6 +389,16 @@ extern "C" int ldn_se_gate_slots(const float* gap_partial, int splits, const int
     if (images_cap == 0) return LDN_OK;
     hipLaunchKernelGGL(k_se_head<1024>, dim3(images_cap), dim3(1024), (size_t)(2 * C + S) * sizeof(float), static_cast<hipStream_t>(stream),
                        gap_partial, nullptr, C, S, splits, w1, b1, w2, b2, nullptr, nullptr, gate, rows_per_image, m_count);
+    LDN_CHECK_LAUNCH("k_se_head");
+    return LDN_OK;
+}
+
+extern "C" int ldn_se_gate_image(const float* gap_partial, int splits, int B, int rows_per_image, int C, int S, const float* w1, const float* b1,
+                                 const float* w2, const float* b2, const int32_t* ch_idx, const int32_t* ch_cnt, float* gate, void* stream) {
+    LDN_REQUIRE(gap_partial && w1 && b1 && w2 && b2 && ch_idx && ch_cnt && gate, "ldn_se_gate_image: null pointer");
+    LDN_REQUIRE(B > 0 && splits > 0 && rows_per_image > 0 && C > 0 && S > 0, "ldn_se_gate_image: bad shape");
+    hipLaunchKernelGGL(k_se_head<1024>, dim3(B), dim3(1024), (size_t)(2 * C + S) * sizeof(float), static_cast<hipStream_t>(stream),
+                       gap_partial, nullptr, C, S, splits, w1, b1, w2, b2, ch_idx, ch_cnt, gate, rows_per_image, nullptr);
     LDN_CHECK_LAUNCH("k_se_head");
     return LDN_OK;
 }

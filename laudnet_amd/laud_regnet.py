@@ -157,10 +157,12 @@ USE_GROUPED_MFMA_CHANNEL = os.environ.get("LDN_GROUPED_MFMA_CHANNEL", "0") == "1
 USE_GROUPED_MFMA_WIDE = os.environ.get("LDN_GROUPED_MFMA_WIDE", "0") == "1"   # ... and at group widths 56, 112 and 232 (OFF by default)
 USE_GROUPED_MFMA_WIDE_ROWS = os.environ.get("LDN_GROUPED_MFMA_WIDE_ROWS", "0") == "1"   # ... and their packed-row form: layer skip, 'spatial', training (OFF by default)
 USE_SE_FUSED = os.environ.get("LDN_SE_FUSED", "1") != "0"               # ... the SE block folded into conv b's epilogue and conv c's input rows
+USE_CHANNEL_SE_FUSED = os.environ.get("LDN_CHANNEL_SE_FUSED", "0") == "1"   # ... the same fold in channel mode, where USE_GROUPED_MFMA_CHANNEL routes conv b (OFF by default)
 
 # The families of conv b (grouped 3x3 + BN + ReLU).  Everything but the widths is a NAME, of ops or of a switch above, resolved at call time.
 # A form: 'rows' = packed rows through the neighbour table, 'images' = packed rows that are whole images in order (the map staged in the LDS),
-# 'images_gap' = that with the SE squeeze in its epilogue, 'image' = the per-image active channel lists of a dense image (channel mode, 'both');
+# 'images_gap' = that with the SE squeeze in its epilogue, 'image' = the per-image active channel lists of a dense image (channel mode, 'both'),
+# 'image_gap' = that with the SE squeeze in its epilogue (channel mode, where conv c takes the gate: ops.conv_image_gated_ok);
 # it runs behind its switch (None: none) where its host-arithmetic fit query (None: none) says yes.
 ConvBForm = namedtuple("ConvBForm", "op switch fit")
 ConvBFamily = namedtuple("ConvBFamily", "key packer widths forms")      # key: the weights' key in the prepared dict
@@ -170,12 +172,14 @@ CONV_B = {
         "rows": ConvBForm("grouped16_conv3x3_rows", None, None),
         "images": ConvBForm("grouped16_conv3x3_images", "USE_GROUPED_IMAGES", "grouped16_images_fit"),
         "images_gap": ConvBForm("grouped16_conv3x3_images_gap", "USE_SE_FUSED", "conv_rows_gated_fits"),
-        "image": ConvBForm("grouped_chan_mfma_conv3x3_image", "USE_GROUPED_MFMA_CHANNEL", "grouped_chan_mfma_ok")}),
+        "image": ConvBForm("grouped_chan_mfma_conv3x3_image", "USE_GROUPED_MFMA_CHANNEL", "grouped_chan_mfma_ok"),
+        "image_gap": ConvBForm("grouped_chan_mfma_conv3x3_image_gap", "USE_CHANNEL_SE_FUSED", "grouped_chan_mfma_gap_ok")}),
     "gw": ConvBFamily("wb_frag_gw", "pack_grouped_mfma_weights", (8, 24), {
         "rows": ConvBForm("grouped_mfma_conv3x3_rows", "USE_GROUPED_MFMA_WIDTHS", None),
         "images": ConvBForm("grouped_mfma_conv3x3_images", "USE_GROUPED_MFMA_WIDTHS_IMAGES", "grouped_mfma_images_fit"),
         "images_gap": ConvBForm("grouped_mfma_conv3x3_images_gap", "USE_SE_FUSED", "conv_rows_gated_fits"),
-        "image": ConvBForm("grouped_chan_mfma_conv3x3_image", "USE_GROUPED_MFMA_CHANNEL", "grouped_chan_mfma_ok")}),
+        "image": ConvBForm("grouped_chan_mfma_conv3x3_image", "USE_GROUPED_MFMA_CHANNEL", "grouped_chan_mfma_ok"),
+        "image_gap": ConvBForm("grouped_chan_mfma_conv3x3_image_gap", "USE_CHANNEL_SE_FUSED", "grouped_chan_mfma_gap_ok")}),
     "wide": ConvBFamily("wb_frag_wide", "pack_grouped_wide_weights", (56, 112, 232), {
         "rows": ConvBForm("grouped_wide_conv3x3_rows", "USE_GROUPED_MFMA_WIDE_ROWS", None),
         "image": ConvBForm("grouped_wide_conv3x3_image", "USE_GROUPED_MFMA_WIDE", "grouped_wide_ok")}),
@@ -195,10 +199,12 @@ def _mfma_mode():
     return USE_GROUPED_MFMA and ops.get_math_mode() == "bf16x3"
 
 
-def conv_b_choice(layout, C, gw, *, images=None, have_count=True, se_fused=False, families=None):
+def conv_b_choice(layout, C, gw, *, images=None, have_count=True, se_fused=False, families=None, conv_c=None):
     """-> (family, form) of CONV_B that conv b of C channels in groups of gw runs on.  layout 'rows': packed rows; images = (B, Hi, Wi, Ho, Wo,
     stride) when they are whole images in order, have_count = a device-side row count comes with them, se_fused = the caller can take the SE
-    squeeze from conv b's epilogue.  layout 'image': the channel lists of the dense images.  families: the matrix-core families the caller may
+    squeeze from conv b's epilogue.  layout 'image': the channel lists of the dense images; with se_fused, conv_c = the output channels of the
+    block's conv c (a 1x1 with a residual and a scale vector over the same lists), and the form is 'image_gap' where the plain 'image' form
+    would be chosen, that form's switch is on, ops.conv_image_gated_ok takes that conv c and the sums fit.  families: the matrix-core families the caller may
     use (None: all).  The family is the one built for the width (C a positive multiple of it), with USE_GROUPED_MFMA and bf16x3 mode, behind the
     switch and fit query of its 'rows' / 'image' form; whole images go to 'images' behind that form's (widths 8 / 24: at stride 1 or 2) and to
     'images_gap' behind that one's; everything else is the fp32 VALU kernel.  Cheap questions first: this runs once per block and forward."""
@@ -209,7 +215,14 @@ def conv_b_choice(layout, C, gw, *, images=None, have_count=True, se_fused=False
     if layout == "image":
         f = forms["image"]
         ok = _on(f.switch) and _mfma_mode() and getattr(ops, f.fit)(C, gw, images[1], images[2], images[5])
-        return (name if ok else "valu"), "image"
+        if not ok:
+            return "valu", "image"
+        f = forms.get("image_gap")
+        if (se_fused and f is not None and _on(f.switch) and conv_c is not None and
+                ops.conv_image_gated_ok(images[0], images[3] * images[4], C, conv_c, True, True) and
+                getattr(ops, f.fit)(C, gw, images[1], images[2], images[5])):
+            return name, "image_gap"
+        return name, "image"
     switch = forms["rows"].switch
     if (switch is not None and not _SWITCHES[switch]) or not _mfma_mode():
         return "valu", "rows"
@@ -304,6 +317,20 @@ def _conv_b_image(p, f, h_a, idx, cnt, h_b, stride):
     gw = f.group_width
     family, form = conv_b_choice("image", h_b.shape[3], gw, images=(h_a.shape[0], h_a.shape[1], h_a.shape[2], h_b.shape[1], h_b.shape[2], stride))
     getattr(ops, CONV_B[family].forms[form].op)(h_a, _conv_b_frag(p, family, gw), gw, idx, cnt, p["sb"], p["tb"], h_b, stride=stride, relu=1)
+
+
+def _conv_b_image_se(p, f, h_a, idx, cnt, h_b, stride, conv_c):
+    """_conv_b_image for a caller that can fold the SE block into its neighbours (channel mode; conv_c = the output channels of its conv c):
+    where the chooser takes the fold, conv b leaves the channel sums of its output and the SE head turns them into a gate per image, in
+    packed-column order, which conv c multiplies into its input in flight -- three launches instead of five.  -> that gate [B, C], or None:
+    h_b is plain conv b output and SE is still to run."""
+    gw = f.group_width
+    images = (h_a.shape[0], h_a.shape[1], h_a.shape[2], h_b.shape[1], h_b.shape[2], stride)
+    family, form = conv_b_choice("image", h_b.shape[3], gw, images=images, se_fused=True, conv_c=conv_c)
+    out = getattr(ops, CONV_B[family].forms[form].op)(h_a, _conv_b_frag(p, family, gw), gw, idx, cnt, p["sb"], p["tb"], h_b, stride=stride, relu=1)
+    if form != "image_gap":
+        return None
+    return ops.se_gate_image(out, images[3] * images[4], p["se_w1"], p["se_b1"], p["se_w2"], p["se_b2"], idx, cnt)
 
 
 class ResBottleneckBlock(_PrepCache):
@@ -520,10 +547,12 @@ class ResBottleneckBlock(_PrepCache):
         h_a = torch.empty(B, Hi, Wi, w_b, device=dev, dtype=torch.float32)
         ops.conv_image(xn, p["wa"], p["sa"], p["ta"], h_a, n_idx=idx, n_cnt=cnt, relu=1)
         h_b = torch.empty(B, Ho, Wo, w_b, device=dev, dtype=torch.float32)
-        _conv_b_image(p, f, h_a, idx, cnt, h_b, s)
-        ops.se_packed(h_b.view(B * Ho * Wo, w_b), self._img_prefix(B, Ho * Wo, dev), p["se_w1"], p["se_b1"], p["se_w2"],
-                      p["se_b2"], Ho * Wo, ch_idx=idx, ch_cnt=cnt)
         cout = p["wc"].shape[0]
+        # the SE block folded into conv b's epilogue and conv c's input where the chooser takes it (USE_CHANNEL_SE_FUSED): h_b is never rewritten
+        gate = _conv_b_image_se(p, f, h_a, idx, cnt, h_b, s, cout) if USE_CHANNEL_SE_FUSED else _conv_b_image(p, f, h_a, idx, cnt, h_b, s)
+        if gate is None:
+            ops.se_packed(h_b.view(B * Ho * Wo, w_b), self._img_prefix(B, Ho * Wo, dev), p["se_w1"], p["se_b1"], p["se_w2"],
+                          p["se_b2"], Ho * Wo, ch_idx=idx, ch_cnt=cnt)
         if self.proj is not None:
             wp, sp, tp = self._proj(dev)
             identity = torch.empty(B, Ho, Wo, cout, device=dev, dtype=torch.float32)
@@ -532,7 +561,10 @@ class ResBottleneckBlock(_PrepCache):
         else:
             identity = xn
             out = xn if inplace else torch.empty_like(xn)
-        ops.conv_image(h_b, p["wc_k"], p["sc"], p["tc"], out, k_idx=idx, k_cnt=cnt, kgran=gran, relu=1, residual=identity)
+        if gate is None:
+            ops.conv_image(h_b, p["wc_k"], p["sc"], p["tc"], out, k_idx=idx, k_cnt=cnt, kgran=gran, relu=1, residual=identity)
+        else:
+            ops.conv_image_gated(h_b, p["wc_k"], p["sc"], p["tc"], out, gate, k_idx=idx, k_cnt=cnt, kgran=gran, relu=1, residual=identity)
         f.last_channel_mask = mask
         stats = torch.ones(4, device=dev)
         stats[3] = mask.mean()

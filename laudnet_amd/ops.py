@@ -1308,6 +1308,97 @@ def grouped_chan_mfma_conv3x3_image(a_nhwc, w_frag, group_width, ch_idx, ch_cnt,
     return _grouped_image("ldn_grouped_chan_mfma_conv3x3_image", a_nhwc, w_frag, C, gw, ch_idx, ch_cnt, scale, shift, out_nhwc, stride, relu)
 
 
+def grouped_chan_mfma_bands(C, group_width, Hi, Wi, Ho, stride):
+    """Bands of output rows per image of ldn_grouped_chan_mfma_conv3x3_image and its _gap form (1: a workgroup holds whole images; 0: refused)."""
+    return int(L.load().ldn_grouped_chan_mfma_bands(int(C), int(group_width), int(Hi), int(Wi), int(Ho), int(stride)))
+
+
+def grouped_chan_mfma_gap_ok(C, group_width, Hi, Wi, stride):
+    """Whether ldn_grouped_chan_mfma_conv3x3_image_gap takes the shape: grouped_chan_mfma_ok, and the channel sums' scratch fits the LDS
+    behind the plain plan's staged rows (host arithmetic only)."""
+    return bool(L.load().ldn_grouped_chan_mfma_gap_ok(int(C), int(group_width), int(Hi), int(Wi), int(stride)))
+
+
+def grouped_chan_mfma_conv3x3_image_gap(a_nhwc, w_frag, group_width, ch_idx, ch_cnt, scale, shift, out_nhwc, *, stride=1, relu=1, gap=None):
+    """grouped_chan_mfma_conv3x3_image that also returns the channel sums of its output per image and band, in packed-column order:
+    gap [B, bands, C] (ldn_grouped_chan_mfma_conv3x3_image_gap) -- the squeeze of the SE block that follows conv b, without a second pass
+    over h_b.  out_nhwc is written as by the plain op, bit for bit.  gap: a [B, bands, C] buffer to write (every element is written; it need
+    not be cleared), bands = grouped_chan_mfma_bands(C, gw, Hi, Wi, Ho, stride); None: a new one."""
+    gw = int(group_width)
+    if gw not in (8, 16, 24):
+        raise L.LdnError(f"grouped_chan_mfma_conv3x3_image_gap: group width {gw} is not built (8, 16 and 24)")
+    C = _check_frag("grouped_chan_mfma_conv3x3_image_gap", w_frag, "g16" if gw == 16 else "gw", gw)
+    L.require_device(a_nhwc, w_frag, out_nhwc, ch_idx)
+    if a_nhwc.dim() != 4 or out_nhwc.dim() != 4:
+        raise L.LdnError("grouped_chan_mfma_conv3x3_image_gap: a and out must be [B, H, W, columns]")
+    B, Hi, Wi, lda = a_nhwc.shape
+    _, Ho, Wo, ldo = out_nhwc.shape
+    bands = grouped_chan_mfma_bands(C, gw, Hi, Wi, Ho, stride)
+    if bands <= 0 or not grouped_chan_mfma_gap_ok(C, gw, Hi, Wi, stride):
+        raise L.LdnError("grouped_chan_mfma_conv3x3_image_gap: not a 3x3 / pad 1 / stride 1 or 2 geometry, or the map does not fit the LDS "
+                         "(grouped_chan_mfma_gap_ok)")
+    if gap is None:
+        gap = torch.empty(B, bands, C, device=out_nhwc.device, dtype=torch.float32)
+    elif tuple(gap.shape) != (B, bands, C):
+        raise L.LdnError(f"grouped_chan_mfma_conv3x3_image_gap: gap must be [{B}, {bands}, {C}], got {tuple(gap.shape)}")
+    L.check(L.load().ldn_grouped_chan_mfma_conv3x3_image_gap(
+        L.ptr(_f32c(a_nhwc, "a")), lda, B, Hi, Wi, stride, Ho, Wo, L.ptr(w_frag), C, gw, L.ptr(_i32c(ch_idx, "ch_idx")),
+        L.ptr(_i32c(ch_cnt, "ch_cnt")), L.ptr(_f32c(scale, "scale")), L.ptr(_f32c(shift, "shift")), relu, L.ptr(_f32c(out_nhwc, "out")), ldo,
+        L.ptr(_f32c(gap, "gap")), L.stream_ptr(out_nhwc)), "ldn_grouped_chan_mfma_conv3x3_image_gap")
+    return gap
+
+
+def se_gate_image(gap, rows_per_image, w1, b1, w2, b2, ch_idx, ch_cnt):
+    """SE gate of every image of a dense batch with channel lists, from the channel sums of grouped_chan_mfma_conv3x3_image_gap
+    (ldn_se_gate_image) -> gate [B, C] in packed-column order, zeros from ch_cnt[b] on."""
+    L.require_device(gap, w1, ch_idx)
+    B, bands, C = gap.shape
+    S = w1.shape[0]
+    if tuple(ch_idx.shape) != (B, C) or ch_cnt.numel() != B:
+        raise L.LdnError("se_gate_image: ch_idx must be [B, C] and ch_cnt [B]")
+    gate = torch.empty(B, C, device=gap.device, dtype=torch.float32)
+    L.check(L.load().ldn_se_gate_image(L.ptr(_f32c(gap, "gap")), bands, B, int(rows_per_image), C, S, L.ptr(_f32c(w1, "w1")),
+                                       L.ptr(_f32c(b1, "b1")), L.ptr(_f32c(w2, "w2")), L.ptr(_f32c(b2, "b2")),
+                                       L.ptr(_i32c(ch_idx, "ch_idx")), L.ptr(_i32c(ch_cnt, "ch_cnt")), L.ptr(gate), L.stream_ptr()),
+            "ldn_se_gate_image")
+    return gate
+
+
+def conv_image_gated_ok(B, rows, cin, cout, has_residual, has_scale):
+    """Whether ldn_conv_image_gated takes a 1x1 over B images of `rows` pixels, cin -> cout, with / without a residual and a scale vector
+    (host arithmetic only)."""
+    return bool(L.load().ldn_conv_image_gated_ok(int(B), int(rows), int(cin), int(cout), int(bool(has_residual)), int(bool(has_scale))))
+
+
+def conv_image_gated(a_nhwc, w, scale, shift, out_nhwc, gate, *, ksize=1, stride=1, k_idx=None, k_cnt=None, kgran=1, n_idx=None,
+                     n_cnt=None, post_sub=None, relu=1, residual=None, colsum=None, math=None, out_split=False):
+    """conv_image whose input column k of image b is multiplied by gate[b, k] in flight (ldn_conv_image_gated; bf16x3): bit-identical to
+    conv_image on the pre-scaled input.  Admitted: conv c of a channel block (1x1, stride 1, k_idx / k_cnt, no n_idx, one shift class);
+    the other keywords are those of conv_image and are refused by the library where the gated form does not take them."""
+    L.require_device(a_nhwc, w, out_nhwc)
+    lib = L.load()
+    B, Hi, Wi, lda = a_nhwc.shape
+    _, Ho, Wo, ldo = out_nhwc.shape
+    if k_idx is None:
+        cout, t, cin = w.shape
+    else:
+        t, cin, cout = w.shape
+    if t != ksize * ksize:
+        raise L.LdnError("conv_image_gated: weight taps do not match ksize")
+    if gate is None or tuple(gate.shape) != (B, cin) or not gate.is_contiguous() or gate.dtype != torch.float32:
+        raise L.LdnError("conv_image_gated: gate must be a contiguous fp32 [B, cin] tensor")
+    classes = 1 if shift.dim() == 1 else shift.shape[0]
+    L.check(lib.ldn_conv_image_gated(L.ptr(_f32c(a_nhwc, "a")), lda, B, Hi, Wi, ksize, stride, Ho, Wo, L.ptr(_f32c(w, "w")),
+                                     cin, cout, L.ptr(_i32c(k_idx, "k_idx")), L.ptr(_i32c(k_cnt, "k_cnt")), kgran,
+                                     L.ptr(_i32c(n_idx, "n_idx")), L.ptr(_i32c(n_cnt, "n_cnt")),
+                                     L.ptr(_f32c(scale, "scale")), L.ptr(_f32c(shift, "shift")), classes, L.ptr(post_sub),
+                                     relu, L.ptr(residual), residual.shape[-1] if residual is not None else 0,
+                                     L.ptr(_f32c(out_nhwc, "out")), ldo, L.ptr(colsum), 1 if out_split else 0, L.ptr(gate), _mm(math),
+                                     L.stream_ptr(out_nhwc)),
+            "ldn_conv_image_gated")
+    return out_nhwc
+
+
 def grouped_wide_ok(C, group_width, Hi, Wi, stride):
     """Whether ldn_grouped_wide_conv3x3_image takes the shape: group width 56, 112 or 232, C a positive multiple of it, stride 1 or 2 and a
     rectangle of the Hi x Wi input map fits the LDS (host arithmetic only)."""
