@@ -769,6 +769,23 @@ size_t ldn_grouped_wide_weight_bytes(int C, int group_width);
 int ldn_grouped_wide_conv3x3_image(const float* a, int lda, int B, int Hi, int Wi, int stride, int Ho, int Wo, const void* w_frag,
                                    int C, int group_width, const int32_t* ch_idx, const int32_t* ch_cnt, const float* scale,
                                    const float* shift, int relu, float* out, int ldo, void* stream);
+/* ... and step 1 of the SE fold of channel mode (ldn_grouped_chan_mfma_conv3x3_image_gap below, whose steps 2 and 3 -- ldn_se_gate_image,
+ *    ldn_conv_image_gated -- take any split count and any C) at these widths: ldn_grouped_wide_conv3x3_image_gap =
+ *    ldn_grouped_wide_conv3x3_image (the same plan and fragments, `out` bit-identical) that also leaves the channel SUMS of its output:
+ *    gap_partial [B][splits][C], splits = ldn_grouped_wide_bands(...) x ldn_grouped_wide_strips(...) (1 for a whole-image plan, however many
+ *    images share a workgroup), split index = band x strips + strip; element [b][split][j] = sum over the output pixels p of that rectangle of
+ *    out[b, p, j] (after BN and ReLU), in PACKED-COLUMN order; columns j >= ch_cnt[b] are exact zeros.  Every element is written by exactly
+ *    one workgroup in every launch (the caller never clears the buffer; the zeros behind the count go out with the output's zeros, so an
+ *    image without an active channel in a group leaves nothing unwritten); a fixed order of additions (a tree over the 32 pixels of a pixel
+ *    tile, the tiles of the image in ascending order), no atomics: two launches give the same bits.  The tile sums' scratch
+ *    (tiles x 64 / 128 / 256 floats, at most 6 KB) lies in LDS behind the plain plan's staged input and is not part of that plan:
+ *    ldn_grouped_wide_gap_ok = 1 iff ldn_grouped_wide_ok and plan + scratch fit the 160 KB of a CU -- which is every shape of
+ *    ldn_grouped_wide_ok (host arithmetic only).  Refused with LDN_EINVAL before any launch: whatever the plain entry point refuses, a shape
+ *    outside _gap_ok, a null gap_partial, a gap_partial that is not 16-byte aligned. */
+int ldn_grouped_wide_gap_ok(int C, int group_width, int Hi, int Wi, int stride);
+int ldn_grouped_wide_conv3x3_image_gap(const float* a, int lda, int B, int Hi, int Wi, int stride, int Ho, int Wo, const void* w_frag,
+                                       int C, int group_width, const int32_t* ch_idx, const int32_t* ch_cnt, const float* scale,
+                                       const float* shift, int relu, float* out, int ldo, float* gap_partial, void* stream);
 /* b over PACKED ROWS on the matrix cores at group widths 56, 112 and 232 (layer skip, the dense 'spatial' path, every training forward and adjoint;
  *    bf16x3 arithmetic; csrc/ldn_grouped_wide_rows.hip): the contract and the argument list of ldn_grouped_mfma_conv3x3_rows,
  *      out[r, gw g + n] = act(scale[c] * sum_{t<9} sum_{i<gw} a[nbr[r*9+t], gw g + i] * w[gw g + n, t, i] + shift[c]),   r < M,

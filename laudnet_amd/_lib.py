@@ -109,6 +109,8 @@ SIGNATURES = {
     "ldn_grouped_wide_images": ([_I, _I, _I, _I, _I], _I),
     "ldn_grouped_wide_weight_bytes": ([_I, _I], C.c_size_t),
     "ldn_grouped_wide_conv3x3_image": ([_P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _P, _I, _P], _I),
+    "ldn_grouped_wide_gap_ok": ([_I, _I, _I, _I, _I], _I),
+    "ldn_grouped_wide_conv3x3_image_gap": ([_P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P], _I),
     "ldn_grouped_wide_rows_ok": ([_I, _I], _I),
     "ldn_grouped_wide_rows_tiles": ([_I, _I, _I], _I),
     "ldn_grouped_wide_conv3x3_rows": ([_P, _I, _P, _P, _I, _P, _I, _I, _P, _P, _I, _P, _I, _P], _I),

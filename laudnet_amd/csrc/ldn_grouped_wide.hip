@@ -21,6 +21,7 @@
 // Width 56: 63 octets in 32 steps (octet 63 is a zero pad of the fragments); width 112: 126 octets in 63 steps; width 232: 261 octets in 131
 // steps (octet 261 is the zero pad).
 // Input columns >= ch_cnt[b] and the pad columns of lda are never read; output columns >= C are never written.  No atomics: deterministic.
+// k_grouped_wide<GW, true> (ldn_grouped_wide_conv3x3_image_gap) is the same kernel that also leaves the channel sums of its output: see GAP below.
 #include <algorithm>
 
 #include "ldn_common.h"
@@ -49,6 +50,7 @@ struct GwArgs {
     int nimg;                               // images per workgroup (> 1 only when the rectangle is the whole image)
     int R, Wc, nrb, ncb;                    // output rows / columns per rectangle, row bands / column strips per image
     int tab_bytes;                          // the tables in front of the staged input
+    float* gap; int gap_off;                // (GAP) [image][rectangle][C] channel sums of the rectangle's output, packed-column order; the tile sums' scratch in LDS
 };
 
 __host__ __device__ inline int gwd_tab_bytes(int gw, int nimg) { return round_up((nimg * gw + 2 * GWD_MAXIMG + 4) * 4, 32); }   // map, active list, counts, n
@@ -88,7 +90,21 @@ __device__ __forceinline__ void gw_kloop(const unsigned char* wbase, const unsig
     }
 }
 
-template <int GW>
+// sum over the 32 lanes of a half-wave, in each of them: the DPP tree of the 16-lane row, then row 0 + row 1 (row 2 + row 3) through the
+// gfx950 row exchange (a + b in both rows); fixed order.  EVERY lane of the wave must be active.
+__device__ __forceinline__ float half32_sum(float v) {
+    const float t = row16_sum(v);
+    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(t), __float_as_uint(t), false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+
+// GAP: the epilogue also leaves the sums of the rectangle's output pixels per packed column (the SE squeeze of the block, ldn_se_gate_image),
+// as k_grouped_chan's gap form does: a tree over the 32 pixels of a tile (half32_sum), one row of LDS per pixel tile [tile][MT x 32 slots],
+// then, behind the last pass, one thread per (active image, active slot) adds its image's tiles in ascending order -- no atomics, the same
+// bits in every launch.  The scratch lies behind the staged input (gwd_gap_bytes: the plain form's plan does not count it;
+// ldn_grouped_wide_gap_ok answers whether it still fits).  The zeros of the columns behind the count are written with the output's zeros
+// (step 2), so every element of gap has exactly one writer.
+template <int GW, bool GAP = false>
 __global__ __launch_bounds__(GWD_THREADS, 4) void k_grouped_wide(const GwArgs p) {
     typedef GwCfg<GW> cfg;
     constexpr int MT = cfg::MT, NSTEP = cfg::NSTEP, PIXB = gwd_pixb(GW), OCT = GW / 8, NSET = 8 / MT, PT = GWD_PT, CAP = NSET * PT;
@@ -150,6 +166,8 @@ __global__ __launch_bounds__(GWD_THREADS, 4) void k_grouped_wide(const GwArgs p)
             const int px = i / nz, ly = px / cols, lx = px - ly * cols;
             ob[((size_t)(y0 + ly) * p.Wo + x0 + lx) * p.ldo + z0 + (i - px * nz)] = 0.f;
         }
+        if constexpr (GAP)
+            for (int i = tid; i < nz; i += GWD_THREADS) p.gap[((size_t)(b0 + il) * nrect + rect) * p.C + z0 + i] = 0.f;
     }
     if (nact == 0) return;                                      // (uniform) no active channel of this group in the run: nothing staged, no MFMA
     // ---- 3. the rectangle's input pixels with their halo, expanded into the group's slots and pre-split
@@ -195,6 +213,7 @@ __global__ __launch_bounds__(GWD_THREADS, 4) void k_grouped_wide(const GwArgs p)
     const int n = lane & 31, h = lane >> 5;
     const int tpr = (npix + 31) / 32, ntile = nact * tpr;
     const unsigned char* const wbase = p.wf + (size_t)g * (NSTEP * MT * 2048) + mt * 2048 + lane * 32;
+    float* const s_gap = reinterpret_cast<float*>(smem + p.gap_off);               // (GAP) [pixel tile of the workgroup][MT x 32 slots]
     for (int t0 = 0; t0 < ntile; t0 += CAP) {
         const int left = ntile - t0 - set;
         const int npt = left <= 0 ? 0 : min(PT, (left + NSET - 1) / NSET);      // (wave-uniform) this wave's tiles of the pass
@@ -223,7 +242,42 @@ __global__ __launch_bounds__(GWD_THREADS, 4) void k_grouped_wide(const GwArgs p)
             if (pt < npt) {
                 const int T = t0 + pt * NSET + set;
                 const int ia = T / tpr, q = (T - ia * tpr) * 32 + n;
-                if (q < npix) {
+                if constexpr (GAP) {
+                    // every lane takes part in the sums; lanes past the rectangle computed pixel 0, add zeros and store nothing.  The values
+                    // are those of the plain branch below (the same expression on the same operands), inactive slots included: their sums
+                    // go to LDS and are dropped by the final pass.  Pad slots (32 mt + 8 Q >= GW: wave-uniform) are skipped.
+                    const bool live = q < npix;
+                    const int qq = live ? q : 0;
+                    const int il = s_act[ia];
+                    const int ly = qq / cols, lx = qq - ly * cols;
+                    float* const orow = p.out + (((size_t)(b0 + il) * p.Ho + y0 + ly) * p.Wo + x0 + lx) * p.ldo;
+#pragma unroll
+                    for (int Q = 0; Q < 4; ++Q) {
+                        if (32 * mt + 8 * Q < GW) {
+                            const int sb = 32 * mt + 8 * Q + 4 * h;
+                            const int c = g * GW + sb;
+                            const f32x4 sc = *reinterpret_cast<const f32x4*>(p.scale + c), sf = *reinterpret_cast<const f32x4*>(p.shift + c);
+                            f32x4 v, t4;
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                v[e] = acc[pt][4 * Q + e] * sc[e] + sf[e];
+                                if (p.relu) v[e] = fmaxf(v[e], 0.f);
+                                t4[e] = half32_sum(live ? v[e] : 0.f);
+                            }
+                            if (live) {
+                                const i32x4 m = *reinterpret_cast<const i32x4*>(s_map + il * GW + sb);
+                                if (m[0] >= 0 && (m[0] & 3) == 0 && m[1] == m[0] + 1 && m[2] == m[0] + 2 && m[3] == m[0] + 3) {
+                                    *reinterpret_cast<f32x4*>(orow + m[0]) = v;
+                                } else {
+#pragma unroll
+                                    for (int e = 0; e < 4; ++e)
+                                        if (m[e] >= 0) orow[m[e]] = v[e];
+                                }
+                            }
+                            if (n == 0) *reinterpret_cast<f32x4*>(s_gap + (size_t)T * (MT * 32) + sb) = t4;
+                        }
+                    }
+                } else if (q < npix) {
                     const int il = s_act[ia];
                     const int ly = q / cols, lx = q - ly * cols;
                     float* const orow = p.out + (((size_t)(b0 + il) * p.Ho + y0 + ly) * p.Wo + x0 + lx) * p.ldo;
@@ -252,6 +306,18 @@ __global__ __launch_bounds__(GWD_THREADS, 4) void k_grouped_wide(const GwArgs p)
                 }
             }
     }
+    if constexpr (GAP) {
+        __syncthreads();
+        for (int i = tid; i < nact * GW; i += GWD_THREADS) {
+            const int ia = i / GW, sl = i - ia * GW;
+            const int il = s_act[ia];
+            const int m = s_map[il * GW + sl];
+            if (m < 0) continue;
+            float s = 0.f;
+            for (int t = 0; t < tpr; ++t) s += s_gap[(size_t)(ia * tpr + t) * (MT * 32) + sl];
+            p.gap[((size_t)(b0 + il) * nrect + rect) * p.C + m] = s;
+        }
+    }
 }
 
 // The plan: images per workgroup and the rectangle of output pixels of one workgroup.  Everything counts against one budget: the tables and
@@ -264,6 +330,11 @@ __global__ __launch_bounds__(GWD_THREADS, 4) void k_grouped_wide(const GwArgs p)
 struct GwPlan { int nimg, R, Wc, nrb, ncb; size_t lds; };
 
 static size_t gwd_bytes(int gw, int nimg, long sp) { return (size_t)gwd_tab_bytes(gw, nimg) + (size_t)nimg * (size_t)sp * gwd_pixb(gw); }
+
+// (GAP) the scratch of the tile sums behind the staged input: a row of MT x 32 slots per pixel tile of the workgroup's images.  Within the
+// plain plan's 150 KB a rectangle has at most 22 / 10 / 6 pixel tiles (width 56 / 112 / 232): at most 6 KB, inside the 160 KB of a CU
+constexpr size_t GWD_LDS_CU = 160 * 1024;
+static size_t gwd_gap_bytes(int gw, int nimg, int R, int Wc) { return (size_t)nimg * ceil_div(R * Wc, 32) * gw_frag_mt(gw) * 32 * 4; }
 
 static double gwd_cost(int gw, int nimg, int R, int Wc, long sp, size_t lds) {
     const int nset = 8 / gw_frag_mt(gw), cap = nset * GWD_PT;
@@ -308,10 +379,10 @@ static bool gwd_plan(int gw, int Hi, int Wi, int Ho, int Wo, int stride, GwPlan*
     return found;
 }
 
-template <int GW>
+template <int GW, bool GAP>
 static int launch_grouped_wide(const GwArgs& g, size_t lds, unsigned nwg, hipStream_t stream) {
-    LDN_REQUIRE(allow_dynamic_lds(reinterpret_cast<const void*>(&k_grouped_wide<GW>), lds), "k_grouped_wide<%d>: cannot reserve %zu B of LDS", GW, lds);
-    hipLaunchKernelGGL(k_grouped_wide<GW>, dim3(nwg), dim3(GWD_THREADS), lds, stream, g);
+    LDN_REQUIRE(allow_dynamic_lds(reinterpret_cast<const void*>(&k_grouped_wide<GW, GAP>), lds), "k_grouped_wide<%d>: cannot reserve %zu B of LDS", GW, lds);
+    hipLaunchKernelGGL((k_grouped_wide<GW, GAP>), dim3(nwg), dim3(GWD_THREADS), lds, stream, g);
     LDN_CHECK_LAUNCH("k_grouped_wide");
     return LDN_OK;
 }
@@ -322,7 +393,7 @@ LDN_DEFINE_TU_VIOLATIONS(tu_violations_grouped_wide)
 
 using namespace ldn;
 
-// the shape check and the plan behind the four queries: false outside ldn_grouped_wide_ok
+// the shape check and the plan behind the five queries: false outside ldn_grouped_wide_ok
 static bool gwd_query(int C, int gw, int Hi, int Wi, int stride, GwPlan* pl) {
     return gw_frag_width(gw) && C > 0 && C % gw == 0 && (stride == 1 || stride == 2) && Hi > 0 && Wi > 0 &&
            gwd_plan(gw, Hi, Wi, (Hi - 1) / stride + 1, (Wi - 1) / stride + 1, stride, pl);
@@ -353,32 +424,64 @@ extern "C" size_t ldn_grouped_wide_weight_bytes(int C, int group_width) {
     return (size_t)(C / group_width) * gw_frag_bytes(group_width);
 }
 
-extern "C" int ldn_grouped_wide_conv3x3_image(const float* a, int lda, int B, int Hi, int Wi, int stride, int Ho, int Wo,
-                                              const void* w_frag, int C, int group_width, const int32_t* ch_idx, const int32_t* ch_cnt,
-                                              const float* scale, const float* shift, int relu, float* out, int ldo, void* stream) {
-    LDN_REQUIRE(a && w_frag && ch_idx && ch_cnt && scale && shift && out, "ldn_grouped_wide_conv3x3_image: null pointer");
-    LDN_REQUIRE(B > 0 && Hi > 0 && Wi > 0 && stride >= 1 && Ho == (Hi - 1) / stride + 1 && Wo == (Wi - 1) / stride + 1,
-                "ldn_grouped_wide_conv3x3_image: %dx%d -> %dx%d is not a 3x3 / pad 1 / stride %d geometry", Hi, Wi, Ho, Wo, stride);
-    LDN_REQUIRE(ldn_grouped_wide_ok(C, group_width, Hi, Wi, stride),
-                "ldn_grouped_wide_conv3x3_image: group width %d with %d channels on a %dx%d map at stride %d is not built (widths 56, 112 and 232, "
-                "channels a multiple of the width, stride 1 or 2, a rectangle of the map in the LDS: ldn_grouped_wide_ok)", group_width, C, Hi, Wi, stride);
-    LDN_REQUIRE(lda % 4 == 0 && ldo % 4 == 0 && lda >= C && ldo >= C, "ldn_grouped_wide_conv3x3_image: strides must be multiples of 4 and at least C");
-    LDN_REQUIRE((uintptr_t)a % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)w_frag % 16 == 0 && (uintptr_t)scale % 16 == 0 &&
-                (uintptr_t)shift % 16 == 0, "ldn_grouped_wide_conv3x3_image: pointers must be 16-byte aligned");
+// LDS of a launch of the plan on nimg images a workgroup, with the tile sums' scratch when gap
+static size_t gwd_launch_bytes(int gw, int nimg, const GwPlan& pl, int stride, bool gap) {
+    const long sp = ((long)(pl.R - 1) * stride + 3) * ((long)(pl.Wc - 1) * stride + 3);
+    return gwd_bytes(gw, nimg, sp) + (gap ? gwd_gap_bytes(gw, nimg, pl.R, pl.Wc) : 0);
+}
+
+extern "C" int ldn_grouped_wide_gap_ok(int C, int group_width, int Hi, int Wi, int stride) {
     GwPlan pl;
-    LDN_REQUIRE(gwd_plan(group_width, Hi, Wi, Ho, Wo, stride, &pl), "ldn_grouped_wide_conv3x3_image: the map does not fit the LDS");
+    return gwd_query(C, group_width, Hi, Wi, stride, &pl) && gwd_launch_bytes(group_width, pl.nimg, pl, stride, true) <= GWD_LDS_CU ? 1 : 0;
+}
+
+static int grouped_wide_image(const char* name, const float* a, int lda, int B, int Hi, int Wi, int stride, int Ho, int Wo, const void* w_frag, int C,
+                              int group_width, const int32_t* ch_idx, const int32_t* ch_cnt, const float* scale, const float* shift, int relu,
+                              float* out, int ldo, float* gap, void* stream) {
+    LDN_REQUIRE(a && w_frag && ch_idx && ch_cnt && scale && shift && out, "%s: null pointer", name);
+    LDN_REQUIRE(B > 0 && Hi > 0 && Wi > 0 && stride >= 1 && Ho == (Hi - 1) / stride + 1 && Wo == (Wi - 1) / stride + 1,
+                "%s: %dx%d -> %dx%d is not a 3x3 / pad 1 / stride %d geometry", name, Hi, Wi, Ho, Wo, stride);
+    LDN_REQUIRE(ldn_grouped_wide_ok(C, group_width, Hi, Wi, stride),
+                "%s: group width %d with %d channels on a %dx%d map at stride %d is not built (widths 56, 112 and 232, "
+                "channels a multiple of the width, stride 1 or 2, a rectangle of the map in the LDS: ldn_grouped_wide_ok)", name, group_width, C, Hi, Wi, stride);
+    LDN_REQUIRE(lda % 4 == 0 && ldo % 4 == 0 && lda >= C && ldo >= C, "%s: strides must be multiples of 4 and at least C", name);
+    LDN_REQUIRE((uintptr_t)a % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)w_frag % 16 == 0 && (uintptr_t)scale % 16 == 0 &&
+                (uintptr_t)shift % 16 == 0 && (uintptr_t)gap % 16 == 0, "%s: pointers must be 16-byte aligned", name);
+    GwPlan pl;
+    LDN_REQUIRE(gwd_plan(group_width, Hi, Wi, Ho, Wo, stride, &pl), "%s: the map does not fit the LDS", name);
     GwArgs g{};
     g.a = a; g.lda = lda; g.B = B; g.Hi = Hi; g.Wi = Wi; g.Ho = Ho; g.Wo = Wo; g.stride = stride;
     g.wf = static_cast<const unsigned char*>(w_frag); g.C = C; g.ch_idx = ch_idx; g.ch_cnt = ch_cnt;
-    g.scale = scale; g.shift = shift; g.relu = relu; g.out = out; g.ldo = ldo;
+    g.scale = scale; g.shift = shift; g.relu = relu; g.out = out; g.ldo = ldo; g.gap = gap;
     g.nimg = std::min(pl.nimg, B); g.R = pl.R; g.Wc = pl.Wc; g.nrb = pl.nrb; g.ncb = pl.ncb;
     g.tab_bytes = gwd_tab_bytes(group_width, g.nimg);
-    const long sp = ((long)(g.R - 1) * stride + 3) * ((long)(g.Wc - 1) * stride + 3);
-    const size_t lds = gwd_bytes(group_width, g.nimg, sp);
-    LDN_REQUIRE(lds <= GWD_LDS_ONE, "ldn_grouped_wide_conv3x3_image: %zu B of LDS planned", lds);
+    const size_t plain = gwd_launch_bytes(group_width, g.nimg, pl, stride, false);
+    LDN_REQUIRE(plain <= GWD_LDS_ONE, "%s: %zu B of LDS planned", name, plain);
+    g.gap_off = (int)plain;                 // (a multiple of 32: the tables and every staged pixel are)
+    const size_t lds = gwd_launch_bytes(group_width, g.nimg, pl, stride, gap != nullptr);
+    LDN_REQUIRE(lds <= GWD_LDS_CU, "%s: %zu B of LDS planned (ldn_grouped_wide_gap_ok)", name, lds);
     const long nwg = (long)(C / group_width) * ceil_div(B, g.nimg) * g.nrb * g.ncb;
-    LDN_REQUIRE(nwg < (1l << 31), "ldn_grouped_wide_conv3x3_image: too many workgroups (%ld)", nwg);
+    LDN_REQUIRE(nwg < (1l << 31), "%s: too many workgroups (%ld)", name, nwg);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return group_width == 56 ? launch_grouped_wide<56>(g, lds, (unsigned)nwg, st)
-                             : group_width == 112 ? launch_grouped_wide<112>(g, lds, (unsigned)nwg, st) : launch_grouped_wide<232>(g, lds, (unsigned)nwg, st);
+    if (gap)
+        return group_width == 56 ? launch_grouped_wide<56, true>(g, lds, (unsigned)nwg, st)
+             : group_width == 112 ? launch_grouped_wide<112, true>(g, lds, (unsigned)nwg, st) : launch_grouped_wide<232, true>(g, lds, (unsigned)nwg, st);
+    return group_width == 56 ? launch_grouped_wide<56, false>(g, lds, (unsigned)nwg, st)
+         : group_width == 112 ? launch_grouped_wide<112, false>(g, lds, (unsigned)nwg, st) : launch_grouped_wide<232, false>(g, lds, (unsigned)nwg, st);
+}
+
+extern "C" int ldn_grouped_wide_conv3x3_image(const float* a, int lda, int B, int Hi, int Wi, int stride, int Ho, int Wo,
+                                              const void* w_frag, int C, int group_width, const int32_t* ch_idx, const int32_t* ch_cnt,
+                                              const float* scale, const float* shift, int relu, float* out, int ldo, void* stream) {
+    return grouped_wide_image("ldn_grouped_wide_conv3x3_image", a, lda, B, Hi, Wi, stride, Ho, Wo, w_frag, C, group_width, ch_idx, ch_cnt, scale, shift,
+                              relu, out, ldo, nullptr, stream);
+}
+
+extern "C" int ldn_grouped_wide_conv3x3_image_gap(const float* a, int lda, int B, int Hi, int Wi, int stride, int Ho, int Wo,
+                                                  const void* w_frag, int C, int group_width, const int32_t* ch_idx, const int32_t* ch_cnt,
+                                                  const float* scale, const float* shift, int relu, float* out, int ldo, float* gap_partial,
+                                                  void* stream) {
+    LDN_REQUIRE(gap_partial, "ldn_grouped_wide_conv3x3_image_gap: null pointer");
+    return grouped_wide_image("ldn_grouped_wide_conv3x3_image_gap", a, lda, B, Hi, Wi, stride, Ho, Wo, w_frag, C, group_width, ch_idx, ch_cnt, scale,
+                              shift, relu, out, ldo, gap_partial, stream);
 }

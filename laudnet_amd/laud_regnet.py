@@ -158,11 +158,13 @@ USE_GROUPED_MFMA_WIDE = os.environ.get("LDN_GROUPED_MFMA_WIDE", "0") == "1"   # 
 USE_GROUPED_MFMA_WIDE_ROWS = os.environ.get("LDN_GROUPED_MFMA_WIDE_ROWS", "0") == "1"   # ... and their packed-row form: layer skip, 'spatial', training (OFF by default)
 USE_SE_FUSED = os.environ.get("LDN_SE_FUSED", "1") != "0"               # ... the SE block folded into conv b's epilogue and conv c's input rows
 USE_CHANNEL_SE_FUSED = os.environ.get("LDN_CHANNEL_SE_FUSED", "0") == "1"   # ... the same fold in channel mode, where USE_GROUPED_MFMA_CHANNEL routes conv b (OFF by default)
+USE_CHANNEL_SE_FUSED_WIDE = os.environ.get("LDN_CHANNEL_SE_FUSED_WIDE", "0") == "1"   # ... and where USE_GROUPED_MFMA_WIDE does, at group widths 56, 112 and 232; only with USE_CHANNEL_SE_FUSED (OFF by default)
 
 # The families of conv b (grouped 3x3 + BN + ReLU).  Everything but the widths is a NAME, of ops or of a switch above, resolved at call time.
 # A form: 'rows' = packed rows through the neighbour table, 'images' = packed rows that are whole images in order (the map staged in the LDS),
 # 'images_gap' = that with the SE squeeze in its epilogue, 'image' = the per-image active channel lists of a dense image (channel mode, 'both'),
-# 'image_gap' = that with the SE squeeze in its epilogue (channel mode, where conv c takes the gate: ops.conv_image_gated_ok);
+# 'image_gap' = that with the SE squeeze in its epilogue (channel mode, where conv c takes the gate: ops.conv_image_gated_ok),
+# 'image_gap_wide' = the same form of the wide family, under a key of its own because it runs behind a second switch on top of 'image_gap''s;
 # it runs behind its switch (None: none) where its host-arithmetic fit query (None: none) says yes.
 ConvBForm = namedtuple("ConvBForm", "op switch fit")
 ConvBFamily = namedtuple("ConvBFamily", "key packer widths forms")      # key: the weights' key in the prepared dict
@@ -182,8 +184,10 @@ CONV_B = {
         "image_gap": ConvBForm("grouped_chan_mfma_conv3x3_image_gap", "USE_CHANNEL_SE_FUSED", "grouped_chan_mfma_gap_ok")}),
     "wide": ConvBFamily("wb_frag_wide", "pack_grouped_wide_weights", (56, 112, 232), {
         "rows": ConvBForm("grouped_wide_conv3x3_rows", "USE_GROUPED_MFMA_WIDE_ROWS", None),
-        "image": ConvBForm("grouped_wide_conv3x3_image", "USE_GROUPED_MFMA_WIDE", "grouped_wide_ok")}),
+        "image": ConvBForm("grouped_wide_conv3x3_image", "USE_GROUPED_MFMA_WIDE", "grouped_wide_ok"),
+        "image_gap_wide": ConvBForm("grouped_wide_conv3x3_image_gap", "USE_CHANNEL_SE_FUSED_WIDE", "grouped_wide_gap_ok")}),
 }
+_IMAGE_GAP_FORMS = ("image_gap", "image_gap_wide")       # a family holds at most one of them
 _WIDTH_FAMILY = {gw: name for name, fam in CONV_B.items() for gw in fam.widths}
 
 
@@ -203,8 +207,9 @@ def conv_b_choice(layout, C, gw, *, images=None, have_count=True, se_fused=False
     """-> (family, form) of CONV_B that conv b of C channels in groups of gw runs on.  layout 'rows': packed rows; images = (B, Hi, Wi, Ho, Wo,
     stride) when they are whole images in order, have_count = a device-side row count comes with them, se_fused = the caller can take the SE
     squeeze from conv b's epilogue.  layout 'image': the channel lists of the dense images; with se_fused, conv_c = the output channels of the
-    block's conv c (a 1x1 with a residual and a scale vector over the same lists), and the form is 'image_gap' where the plain 'image' form
-    would be chosen, that form's switch is on, ops.conv_image_gated_ok takes that conv c and the sums fit.  families: the matrix-core families the caller may
+    block's conv c (a 1x1 with a residual and a scale vector over the same lists), and the form is 'image_gap' ('image_gap_wide' in the wide
+    family) where the plain 'image' form would be chosen, USE_CHANNEL_SE_FUSED and that form's switch are on, ops.conv_image_gated_ok takes
+    that conv c and the sums fit.  families: the matrix-core families the caller may
     use (None: all).  The family is the one built for the width (C a positive multiple of it), with USE_GROUPED_MFMA and bf16x3 mode, behind the
     switch and fit query of its 'rows' / 'image' form; whole images go to 'images' behind that form's (widths 8 / 24: at stride 1 or 2) and to
     'images_gap' behind that one's; everything else is the fp32 VALU kernel.  Cheap questions first: this runs once per block and forward."""
@@ -217,11 +222,11 @@ def conv_b_choice(layout, C, gw, *, images=None, have_count=True, se_fused=False
         ok = _on(f.switch) and _mfma_mode() and getattr(ops, f.fit)(C, gw, images[1], images[2], images[5])
         if not ok:
             return "valu", "image"
-        f = forms.get("image_gap")
-        if (se_fused and f is not None and _on(f.switch) and conv_c is not None and
-                ops.conv_image_gated_ok(images[0], images[3] * images[4], C, conv_c, True, True) and
-                getattr(ops, f.fit)(C, gw, images[1], images[2], images[5])):
-            return name, "image_gap"
+        gap = next((k for k in _IMAGE_GAP_FORMS if k in forms), None)
+        if se_fused and gap is not None and USE_CHANNEL_SE_FUSED and _on(forms[gap].switch) and conv_c is not None:      # the switches first
+            if (ops.conv_image_gated_ok(images[0], images[3] * images[4], C, conv_c, True, True) and
+                    getattr(ops, forms[gap].fit)(C, gw, images[1], images[2], images[5])):
+                return name, gap
         return name, "image"
     switch = forms["rows"].switch
     if (switch is not None and not _SWITCHES[switch]) or not _mfma_mode():
@@ -328,7 +333,7 @@ def _conv_b_image_se(p, f, h_a, idx, cnt, h_b, stride, conv_c):
     images = (h_a.shape[0], h_a.shape[1], h_a.shape[2], h_b.shape[1], h_b.shape[2], stride)
     family, form = conv_b_choice("image", h_b.shape[3], gw, images=images, se_fused=True, conv_c=conv_c)
     out = getattr(ops, CONV_B[family].forms[form].op)(h_a, _conv_b_frag(p, family, gw), gw, idx, cnt, p["sb"], p["tb"], h_b, stride=stride, relu=1)
-    if form != "image_gap":
+    if form not in _IMAGE_GAP_FORMS:
         return None
     return ops.se_gate_image(out, images[3] * images[4], p["se_w1"], p["se_b1"], p["se_w2"], p["se_b2"], idx, cnt)
 
@@ -548,7 +553,8 @@ class ResBottleneckBlock(_PrepCache):
         ops.conv_image(xn, p["wa"], p["sa"], p["ta"], h_a, n_idx=idx, n_cnt=cnt, relu=1)
         h_b = torch.empty(B, Ho, Wo, w_b, device=dev, dtype=torch.float32)
         cout = p["wc"].shape[0]
-        # the SE block folded into conv b's epilogue and conv c's input where the chooser takes it (USE_CHANNEL_SE_FUSED): h_b is never rewritten
+        # the SE block folded into conv b's epilogue and conv c's input where the chooser takes it (USE_CHANNEL_SE_FUSED; at group widths 56, 112
+        # and 232 with USE_CHANNEL_SE_FUSED_WIDE as well): h_b is never rewritten
         gate = _conv_b_image_se(p, f, h_a, idx, cnt, h_b, s, cout) if USE_CHANNEL_SE_FUSED else _conv_b_image(p, f, h_a, idx, cnt, h_b, s)
         if gate is None:
             ops.se_packed(h_b.view(B * Ho * Wo, w_b), self._img_prefix(B, Ho * Wo, dev), p["se_w1"], p["se_b1"], p["se_w2"],

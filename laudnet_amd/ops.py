@@ -1435,6 +1435,47 @@ def grouped_wide_conv3x3_image(a_nhwc, w_frag, group_width, ch_idx, ch_cnt, scal
     return _grouped_image("ldn_grouped_wide_conv3x3_image", a_nhwc, w_frag, C, gw, ch_idx, ch_cnt, scale, shift, out_nhwc, stride, relu)
 
 
+def grouped_wide_splits(C, group_width, Hi, Wi, Ho, stride):
+    """Rectangles per image of ldn_grouped_wide_conv3x3_image and its _gap form: row bands x column strips (1: a workgroup holds whole
+    images; 0: refused)."""
+    lib = L.load()
+    return (int(lib.ldn_grouped_wide_bands(int(C), int(group_width), int(Hi), int(Wi), int(Ho), int(stride))) *
+            int(lib.ldn_grouped_wide_strips(int(C), int(group_width), int(Hi), int(Wi), int(stride))))
+
+
+def grouped_wide_gap_ok(C, group_width, Hi, Wi, stride):
+    """Whether ldn_grouped_wide_conv3x3_image_gap takes the shape: grouped_wide_ok, and the tile sums' scratch fits the LDS behind the plain
+    plan's staged input -- which it does wherever grouped_wide_ok says yes (host arithmetic only)."""
+    return bool(L.load().ldn_grouped_wide_gap_ok(int(C), int(group_width), int(Hi), int(Wi), int(stride)))
+
+
+def grouped_wide_conv3x3_image_gap(a_nhwc, w_frag, group_width, ch_idx, ch_cnt, scale, shift, out_nhwc, *, stride=1, relu=1, gap=None):
+    """grouped_wide_conv3x3_image that also returns the channel sums of its output per image and rectangle, in packed-column order:
+    gap [B, bands x strips, C] (ldn_grouped_wide_conv3x3_image_gap) -- the squeeze of the SE block that follows conv b, without a second
+    pass over h_b.  out_nhwc is written as by the plain op, bit for bit.  gap: a [B, bands x strips, C] buffer to write (every element is
+    written; it need not be cleared), bands x strips = grouped_wide_splits(C, gw, Hi, Wi, Ho, stride); None: a new one."""
+    gw = int(group_width)
+    C = _check_frag("grouped_wide_conv3x3_image_gap", w_frag, "wide", gw)
+    L.require_device(a_nhwc, w_frag, out_nhwc, ch_idx)
+    if a_nhwc.dim() != 4 or out_nhwc.dim() != 4:
+        raise L.LdnError("grouped_wide_conv3x3_image_gap: a and out must be [B, H, W, columns]")
+    B, Hi, Wi, lda = a_nhwc.shape
+    _, Ho, Wo, ldo = out_nhwc.shape
+    splits = grouped_wide_splits(C, gw, Hi, Wi, Ho, stride)
+    if splits <= 0 or not grouped_wide_gap_ok(C, gw, Hi, Wi, stride):
+        raise L.LdnError("grouped_wide_conv3x3_image_gap: not a 3x3 / pad 1 / stride 1 or 2 geometry, or the map does not fit the LDS "
+                         "(grouped_wide_gap_ok)")
+    if gap is None:
+        gap = torch.empty(B, splits, C, device=out_nhwc.device, dtype=torch.float32)
+    elif tuple(gap.shape) != (B, splits, C):
+        raise L.LdnError(f"grouped_wide_conv3x3_image_gap: gap must be [{B}, {splits}, {C}], got {tuple(gap.shape)}")
+    L.check(L.load().ldn_grouped_wide_conv3x3_image_gap(
+        L.ptr(_f32c(a_nhwc, "a")), lda, B, Hi, Wi, stride, Ho, Wo, L.ptr(w_frag), C, gw, L.ptr(_i32c(ch_idx, "ch_idx")),
+        L.ptr(_i32c(ch_cnt, "ch_cnt")), L.ptr(_f32c(scale, "scale")), L.ptr(_f32c(shift, "shift")), relu, L.ptr(_f32c(out_nhwc, "out")), ldo,
+        L.ptr(_f32c(gap, "gap")), L.stream_ptr(out_nhwc)), "ldn_grouped_wide_conv3x3_image_gap")
+    return gap
+
+
 def grouped_wide_rows_ok(C, group_width):
     """Whether ldn_grouped_wide_conv3x3_rows takes the shape: group width 56, 112 or 232, C a positive multiple of it (host arithmetic only)."""
     return bool(L.load().ldn_grouped_wide_rows_ok(int(C), int(group_width)))
