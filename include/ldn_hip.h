@@ -875,6 +875,27 @@ int ldn_conv_image_gated(const float* a, int lda, int B, int Hi, int Wi, int ksi
                          const float* post_sub, int relu, const float* residual, int ldr, float* out, int ldo, float* colsum,
                          int out_format, const float* gate, int math_mode, void* stream);
 
+/* ... and in 'BOTH' mode (pixel x channel masks: conv b and the SE squeeze run on every pixel of the image's active channels, conv c only on
+ * the packed rows of the active pixels, once per mask group).  Steps 1 and 2 are the channel mode's; step 3 is
+ *   ldn_conv_packed_gated: ldn_conv_packed (its argument list, plus `gate` [B][cin], contiguous, 16-byte aligned, in front of math_mode)
+ *      with A[row, k] used as fp32(A[row, k] * gate[b][k]), b = the image that owns the packed row (row_prefix), k = the packed input
+ *      column: bit-identical to ldn_conv_packed on an input that was scaled first.  Columns k >= k_cnt[b] are used as exact zeros whatever
+ *      they and their gates hold; gate entries from k_cnt[b] on are never read.  Admitted: bf16x3, taps 1, row_prefix given, k_idx / k_cnt
+ *      given (cin % 8 == 0, lda >= cin, kgran >= 1), n_idx / n_cnt null, shift_classes 1, post_sub null, pix_map null, relu 0 / 1 (relu 2
+ *      and relu_if_neg are refused: the gate takes that argument's place in the kernel); a_map ([rows][1]), out_map, scale and residual
+ *      optional; out may alias residual; out / residual may be column slices (ldo, ldr >= cout, multiples of 4).  It runs the gated
+ *      k_conv_bf3 at the tile ldn_conv_packed's chooser takes without its streaming kernel; the image's gate vector lies in LDS behind the
+ *      packed tables (roundup32(cin) * 4 bytes more than the ungated plan).  ldn_conv_packed_gated_ok = 1 iff such a launch of B images of
+ *      at most m_cap rows each is admitted and fits (host arithmetic only).  Everything else is LDN_EINVAL before any launch.
+ * h_b is never rewritten, and the two passes of ldn_se_packed over every pixel are gone. */
+int ldn_conv_packed_gated_ok(int B, int m_cap, int cin, int cout, int has_residual, int has_scale);
+int ldn_conv_packed_gated(const float* a, int lda, int B, const int32_t* row_prefix, const int32_t* m_count, int m_cap,
+                          const int32_t* a_map, int taps, const int32_t* out_map, const int32_t* pix_map, int Hi, int Wi, int Ho, int Wo,
+                          int stride, const float* w, int cin, int cout, const int32_t* k_idx, const int32_t* k_cnt, int kgran,
+                          const int32_t* n_idx, const int32_t* n_cnt, const float* scale, const float* shift, int shift_classes,
+                          const float* post_sub, int relu, const int32_t* relu_if_neg, const float* residual, int ldr, float* out, int ldo,
+                          const float* gate, int math_mode, void* stream);
+
 /* ---- a14: token skipping (BASELINE config 5, AdaViT / DeiT-S shaped blocks).  The reference holds no model code for it, only the
  * latency model of the operator (DyNetSimulator/adavit/simulate_adavit.py:77-131: q / k / v for every token, attention
  * [B, heads, L_select, d] over the selected tokens): parity of this entry point is therefore UNPINNED -- it is tested against a

@@ -103,6 +103,9 @@ SIGNATURES = {
     "ldn_conv_image_gated_ok": ([_I, _I, _I, _I, _I, _I], _I),
     "ldn_conv_image_gated": ([_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I,
                               _P, _I, _P, _I, _P, _I, _P, _I, _P], _I),
+    "ldn_conv_packed_gated_ok": ([_I, _I, _I, _I, _I, _I], _I),
+    "ldn_conv_packed_gated": ([_P, _I, _I, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P,
+                               _I, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P], _I),
     "ldn_grouped_wide_ok": ([_I, _I, _I, _I, _I], _I),
     "ldn_grouped_wide_bands": ([_I, _I, _I, _I, _I, _I], _I),
     "ldn_grouped_wide_strips": ([_I, _I, _I, _I, _I], _I),

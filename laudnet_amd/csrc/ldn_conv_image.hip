@@ -64,7 +64,7 @@ struct ImgArgs {
     const int32_t* pix_map;          // [rows] flat output pixel (b*Ho*Wo + oy*Wo + ox) for the border classes, or NULL
     union {
         const int32_t* relu_if_neg;  // relu == 2: ReLU only where relu_if_neg[row] < 0
-        const float* gate;           // gated k_conv_bf3 (dense image mode, relu < 2): [B][cin] multiplier of the packed input columns
+        const float* gate;           // gated k_conv_bf3 (relu < 2): [B][cin] multiplier of the packed input columns
     };                               // (one slot for both: the kernel arguments of the ungated kernels keep their layout)
     int ntn;    // N blocks per image
     int mtn;    // M blocks per image
@@ -770,6 +770,8 @@ __device__ __forceinline__ void gate8(f32x4& x0, f32x4& x1, const f32x4& g0, con
 //     ds_read_b128 per K16 step, shared by its m-subtiles -- in front of the split: a plain fp32 product, never contracted into the
 //     split's subtraction, so the result has the bits of the same launch on pre-scaled rows.  Packed positions from K_b on are used as
 //     exact zeros whatever the columns hold.  1x1, one tap: the flat K position IS the packed column.
+//     Over packed rows (ldn_conv_packed_gated: conv c of a 'both' block, one launch per mask group) the same, with b the image that owns
+//     the packed row and the gate vector behind the rows' out-row / A-row tables, which take its place behind the input-channel list.
 //     GATE is a compile-time flag carried ON the BMODE argument (B_KN4 | B_GATE): a seventh template argument would rename every built
 //     k_conv_bf3, and the body moved into a function of its own changed their register allocation; this way the symbols and the code of
 //     the ungated instantiations stay what they were (tools/same_isa.py).
@@ -808,7 +810,8 @@ __global__ __launch_bounds__(512, MINW) void k_conv_bf3(const ImgArgs p) {
     const int Kp = KN ? max(round_up(Kb, 8), BK) : round_up(p.cin, BK);
     const int Ktot = T * Kp;
     const int nch = Kb > 0 ? ceil_div(Ktot, BK) : 0;
-    float* const s_gate = reinterpret_cast<float*>(t.s_kidx + p.cin);   // (GATE) [round_up(cin, 32)], counted by conv_plan_gated
+    // (GATE) [round_up(cin, 32)]: behind the input-channel list (conv_plan_gated), packed rows: behind their tables (conv_plan_packed_gated)
+    float* const s_gate = reinterpret_cast<float*>(GATE && p.packed ? t.s_arow + BM * T : t.s_kidx + p.cin);
     if (wave8 < 4) {
         // the consumers gather the epilogue tables while the producers' first loads are in flight; one extra
         // workgroup barrier (matched in the producer prologue) publishes them
@@ -1712,6 +1715,24 @@ static int launch_conv_gated(const ImgArgs& p, int kgran, hipStream_t st) {
     LDN_REQUIRE(false, "ldn_conv_image_gated: %s is not built with a gate (cin %d, cout %d, rows %d)", conv_plan_name(plan).c_str(), p.cin, p.cout, p.Ho * p.Wo);
 }
 
+// The same over packed rows: the plan of the packed shape with the gate vector behind the packed tables, on the same six instantiations
+// (packed is a run-time field of ImgArgs).
+static int launch_conv_packed_gated(const ImgArgs& p, int kgran, hipStream_t st) {
+    ConvShape s{};
+    s.packed = true; s.B = p.B; s.rows = p.m_cap; s.taps = p.ksize;
+    s.cin = p.cin; s.cout = p.cout; s.has_k = p.k_idx != nullptr; s.has_n = p.n_idx != nullptr; s.kgran = kgran; s.shift_classes = p.shift_classes;
+    s.residual = p.residual != nullptr; s.scale = p.scale != nullptr; s.out_split = false; s.math = p.math; s.stream_rows = 0;
+    LDN_REQUIRE(conv_packed_gated_shape_ok(s), "ldn_conv_packed_gated: not a gated shape (bf16x3, one tap, an input-channel list over a cin that is a "
+                "multiple of 8, no output list, one shift class)");
+    LDN_REQUIRE(conv_weight_elems(s) < kConvWeightLimit, "ldn_conv_packed_gated: weight tensor of %ld elements exceeds the 32-bit offsets of the weight staging", conv_weight_elems(s));
+    const ConvPlan plan = conv_plan_packed_gated(s);
+#define LDN_G(MS, NS, WM, BMODE) \
+    if (plan == LDN_CONV_ROW_F(MS, NS, WM, BMODE)) return launch_conv_kernel(&k_conv_bf3<MS, NS, WM, BMODE | B_GATE, conv_kskip(MS, NS), conv_minw(MS, NS)>, "k_conv_bf3 (gated, packed rows)", plan, p, st);
+    LDN_CONV_GATED_KERNELS(LDN_G)
+#undef LDN_G
+    LDN_REQUIRE(false, "ldn_conv_packed_gated: %s is not built with a gate (cin %d, cout %d, rows %d)", conv_plan_name(plan).c_str(), p.cin, p.cout, p.m_cap);
+}
+
 LDN_DEFINE_TU_VIOLATIONS(tu_violations_conv)
 
 }  // namespace ldn
@@ -1834,6 +1855,44 @@ extern "C" int ldn_conv_packed(const float* a, int lda, int B, const int32_t* ro
               w, cin, cout, k_idx, k_cnt, n_idx, n_cnt, scale, shift, shift_classes, post_sub, relu, residual, ldr, out, ldo,
               nullptr, 1, row_prefix, m_count, m_cap, a_map, out_map, pix_map, relu_if_neg, 0, 0, 0, 0, math, 0};
     return launch_conv(p, kgran, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int ldn_conv_packed_gated_ok(int B, int m_cap, int cin, int cout, int has_residual, int has_scale) {
+    ConvShape s{};
+    s.packed = true; s.B = B; s.rows = m_cap; s.taps = 1; s.cin = cin; s.cout = cout; s.has_k = true; s.kgran = 1; s.shift_classes = 1;
+    s.residual = has_residual != 0; s.scale = has_scale != 0; s.math = 1;
+    return conv_packed_gated_ok(s) ? 1 : 0;
+}
+
+extern "C" int ldn_conv_packed_gated(const float* a, int lda, int B, const int32_t* row_prefix, const int32_t* m_count,
+                                     int m_cap, const int32_t* a_map, int taps, const int32_t* out_map,
+                                     const int32_t* pix_map, int Hi, int Wi, int Ho, int Wo, int stride, const float* w,
+                                     int cin, int cout, const int32_t* k_idx, const int32_t* k_cnt, int kgran,
+                                     const int32_t* n_idx, const int32_t* n_cnt, const float* scale, const float* shift,
+                                     int shift_classes, const float* post_sub, int relu, const int32_t* relu_if_neg,
+                                     const float* residual, int ldr, float* out, int ldo, const float* gate, int math_mode, void* stream) {
+    (void)m_count; (void)Hi; (void)Wi; (void)Ho; (void)Wo; (void)stride;   // (row_prefix gives the rows; no border classes)
+    LDN_REQUIRE(a && w && shift && out && gate, "ldn_conv_packed_gated: null pointer");
+    int math;
+    if (int rc = resolve_math(math_mode, &math)) return rc;
+    LDN_REQUIRE(math == 1, "ldn_conv_packed_gated: bf16x3 arithmetic only");
+    LDN_REQUIRE(taps == 1, "ldn_conv_packed_gated: one tap only (got %d)", taps);
+    LDN_REQUIRE(B >= 1 && row_prefix && m_cap >= 0, "ldn_conv_packed_gated: the per-image row ranges (row_prefix) are required");
+    LDN_REQUIRE(k_idx && k_cnt && kgran >= 1, "ldn_conv_packed_gated: the input-channel list, its counts and kgran >= 1 are required");
+    LDN_REQUIRE(!n_idx && !n_cnt, "ldn_conv_packed_gated: no output-channel list");
+    LDN_REQUIRE(shift_classes == 1 && !post_sub && !pix_map, "ldn_conv_packed_gated: one shift class, no post_sub, no pix_map");
+    LDN_REQUIRE((relu == 0 || relu == 1) && !relu_if_neg, "ldn_conv_packed_gated: relu must be 0 or 1 (no relu_if_neg: the gate takes its slot)");
+    LDN_REQUIRE(cin > 0 && cout > 0 && cin % 8 == 0, "ldn_conv_packed_gated: cin must be a positive multiple of 8 (got %d)", cin);
+    LDN_REQUIRE(lda % 4 == 0 && lda >= cin, "ldn_conv_packed_gated: lda must be a multiple of 4 and >= cin");
+    LDN_REQUIRE(ldo >= cout && ldo % 4 == 0 && cout % 4 == 0, "ldn_conv_packed_gated: cout and ldo must be multiples of 4, ldo >= cout");
+    LDN_REQUIRE((uintptr_t)out % 16 == 0 && (!residual || ((uintptr_t)residual % 16 == 0 && ldr % 4 == 0 && ldr >= cout)),
+                "ldn_conv_packed_gated: out/residual must be 16-byte aligned with strides that are multiples of 4, ldr >= cout");
+    LDN_REQUIRE((uintptr_t)a % 16 == 0 && (uintptr_t)w % 16 == 0 && (uintptr_t)gate % 16 == 0, "ldn_conv_packed_gated: a/w/gate must be 16-byte aligned");
+    if (m_cap == 0) return LDN_OK;
+    ImgArgs p{a, lda, B, 1, 1, 1, 1, 1, 1, w, cin, cout, k_idx, k_cnt, nullptr, nullptr, scale, shift, 1, nullptr, relu, residual, ldr, out, ldo,
+              nullptr, 1, row_prefix, nullptr, m_cap, a_map, out_map, nullptr, nullptr, 0, 0, 0, 0, math, 0};
+    p.gate = gate;
+    return launch_conv_packed_gated(p, kgran, static_cast<hipStream_t>(stream));
 }
 
 // the shared-weight packed-row convolution of the spatial / layer path: one "image" holding every active row

@@ -211,4 +211,25 @@ inline bool conv_gated_ok(const ConvShape& s) {
     return conv_admitted(s, p) && conv_gated_built(p);
 }
 
+// ---- ... and over packed rows (ldn_conv_packed_gated: conv c of a 'both' block, per mask group, behind the folded SE) ---------------------
+// What it admits by shape: the same arithmetic over the packed rows of the images' active pixels (row_prefix) -- bf16x3, one tap, an input
+// list and no output list, one shift class.  (post_sub, pix_map, relu == 2 and the alignment of the pointers are the entry point's to refuse.)
+inline bool conv_packed_gated_shape_ok(const ConvShape& s) {
+    return s.packed && s.math == 1 && s.taps == 1 && s.has_k && !s.has_n && s.shift_classes == 1 && !s.out_split && s.B > 0 && s.rows > 0 &&
+           s.cin > 0 && s.cin % 8 == 0 && s.cout > 0 && s.cout % 4 == 0 && s.kgran >= 1;
+}
+// Its plan: the tile plan of the packed shape, never the streaming kernel, plus the image's gate vector, which lies BEHIND the packed
+// tables here (the rows' out row and A row sit where the image form keeps it).
+inline ConvPlan conv_plan_packed_gated(const ConvShape& s) {
+    ConvPlan p = conv_plan_tile(s);
+    p.lds_bytes += conv_gate_lds_bytes(s);
+    return p;
+}
+// 1 iff ldn_conv_packed_gated takes the shape: admitted, its plan a row of the gated list, within the LDS of a CU.
+inline bool conv_packed_gated_ok(const ConvShape& s) {
+    if (!conv_packed_gated_shape_ok(s)) return false;
+    const ConvPlan p = conv_plan_packed_gated(s);
+    return conv_admitted(s, p) && conv_gated_built(p);
+}
+
 }  // namespace ldn

@@ -159,6 +159,7 @@ USE_GROUPED_MFMA_WIDE_ROWS = os.environ.get("LDN_GROUPED_MFMA_WIDE_ROWS", "0") =
 USE_SE_FUSED = os.environ.get("LDN_SE_FUSED", "1") != "0"               # ... the SE block folded into conv b's epilogue and conv c's input rows
 USE_CHANNEL_SE_FUSED = os.environ.get("LDN_CHANNEL_SE_FUSED", "0") == "1"   # ... the same fold in channel mode, where USE_GROUPED_MFMA_CHANNEL routes conv b (OFF by default)
 USE_CHANNEL_SE_FUSED_WIDE = os.environ.get("LDN_CHANNEL_SE_FUSED_WIDE", "0") == "1"   # ... and where USE_GROUPED_MFMA_WIDE does, at group widths 56, 112 and 232; only with USE_CHANNEL_SE_FUSED (OFF by default)
+USE_BOTH_SE_FUSED = os.environ.get("LDN_BOTH_SE_FUSED", "0") == "1"   # ... and in 'both' mode (conv c over packed rows), wherever the channel-mode fold would be taken at that width (OFF by default)
 
 # The families of conv b (grouped 3x3 + BN + ReLU).  Everything but the widths is a NAME, of ops or of a switch above, resolved at call time.
 # A form: 'rows' = packed rows through the neighbour table, 'images' = packed rows that are whole images in order (the map staged in the LDS),
@@ -203,13 +204,15 @@ def _mfma_mode():
     return USE_GROUPED_MFMA and ops.get_math_mode() == "bf16x3"
 
 
-def conv_b_choice(layout, C, gw, *, images=None, have_count=True, se_fused=False, families=None, conv_c=None):
+def conv_b_choice(layout, C, gw, *, images=None, have_count=True, se_fused=False, families=None, conv_c=None, conv_c_rows=None):
     """-> (family, form) of CONV_B that conv b of C channels in groups of gw runs on.  layout 'rows': packed rows; images = (B, Hi, Wi, Ho, Wo,
     stride) when they are whole images in order, have_count = a device-side row count comes with them, se_fused = the caller can take the SE
     squeeze from conv b's epilogue.  layout 'image': the channel lists of the dense images; with se_fused, conv_c = the output channels of the
     block's conv c (a 1x1 with a residual and a scale vector over the same lists), and the form is 'image_gap' ('image_gap_wide' in the wide
     family) where the plain 'image' form would be chosen, USE_CHANNEL_SE_FUSED and that form's switch are on, ops.conv_image_gated_ok takes
-    that conv c and the sums fit.  families: the matrix-core families the caller may
+    that conv c and the sums fit.  conv_c_rows='packed' ('both' mode): conv c runs per mask group over the packed rows of the active pixels,
+    conv_c = the output channels of ONE mask group; USE_BOTH_SE_FUSED is asked first and ops.conv_packed_gated_ok(B, Ho * Wo, ...) takes the
+    place of ops.conv_image_gated_ok, everything else as above.  families: the matrix-core families the caller may
     use (None: all).  The family is the one built for the width (C a positive multiple of it), with USE_GROUPED_MFMA and bf16x3 mode, behind the
     switch and fit query of its 'rows' / 'image' form; whole images go to 'images' behind that form's (widths 8 / 24: at stride 1 or 2) and to
     'images_gap' behind that one's; everything else is the fp32 VALU kernel.  Cheap questions first: this runs once per block and forward."""
@@ -223,8 +226,11 @@ def conv_b_choice(layout, C, gw, *, images=None, have_count=True, se_fused=False
         if not ok:
             return "valu", "image"
         gap = next((k for k in _IMAGE_GAP_FORMS if k in forms), None)
-        if se_fused and gap is not None and USE_CHANNEL_SE_FUSED and _on(forms[gap].switch) and conv_c is not None:      # the switches first
-            if (ops.conv_image_gated_ok(images[0], images[3] * images[4], C, conv_c, True, True) and
+        packed = conv_c_rows == "packed"
+        if (se_fused and gap is not None and (not packed or USE_BOTH_SE_FUSED) and USE_CHANNEL_SE_FUSED and _on(forms[gap].switch) and
+                conv_c is not None):      # the switches first
+            conv_c_ok = ops.conv_packed_gated_ok if packed else ops.conv_image_gated_ok
+            if (conv_c_ok(images[0], images[3] * images[4], C, conv_c, True, True) and
                     getattr(ops, forms[gap].fit)(C, gw, images[1], images[2], images[5])):
                 return name, gap
         return name, "image"
@@ -324,14 +330,15 @@ def _conv_b_image(p, f, h_a, idx, cnt, h_b, stride):
     getattr(ops, CONV_B[family].forms[form].op)(h_a, _conv_b_frag(p, family, gw), gw, idx, cnt, p["sb"], p["tb"], h_b, stride=stride, relu=1)
 
 
-def _conv_b_image_se(p, f, h_a, idx, cnt, h_b, stride, conv_c):
-    """_conv_b_image for a caller that can fold the SE block into its neighbours (channel mode; conv_c = the output channels of its conv c):
+def _conv_b_image_se(p, f, h_a, idx, cnt, h_b, stride, conv_c, conv_c_rows=None):
+    """_conv_b_image for a caller that can fold the SE block into its neighbours (channel mode; conv_c = the output channels of its conv c;
+    'both' mode: conv_c_rows='packed' and conv_c = the output channels of one mask group):
     where the chooser takes the fold, conv b leaves the channel sums of its output and the SE head turns them into a gate per image, in
     packed-column order, which conv c multiplies into its input in flight -- three launches instead of five.  -> that gate [B, C], or None:
     h_b is plain conv b output and SE is still to run."""
     gw = f.group_width
     images = (h_a.shape[0], h_a.shape[1], h_a.shape[2], h_b.shape[1], h_b.shape[2], stride)
-    family, form = conv_b_choice("image", h_b.shape[3], gw, images=images, se_fused=True, conv_c=conv_c)
+    family, form = conv_b_choice("image", h_b.shape[3], gw, images=images, se_fused=True, conv_c=conv_c, conv_c_rows=conv_c_rows)
     out = getattr(ops, CONV_B[family].forms[form].op)(h_a, _conv_b_frag(p, family, gw), gw, idx, cnt, p["sb"], p["tb"], h_b, stride=stride, relu=1)
     if form not in _IMAGE_GAP_FORMS:
         return None
@@ -490,10 +497,13 @@ class ResBottleneckBlock(_PrepCache):
             h_a = torch.empty(B, Hi, Wi, w_b, device=dev, dtype=torch.float32)
             ops.conv_image(xn, p["wa"], p["sa"], p["ta"], h_a, n_idx=idx, n_cnt=cnt, relu=1)
             h_b = torch.empty(B, Ho, Wo, w_b, device=dev, dtype=torch.float32)
-            _conv_b_image(p, f, h_a, idx, cnt, h_b, s)
+            # the SE block folded into conv b's epilogue and the packed conv c's input where the chooser takes it (USE_BOTH_SE_FUSED on top of
+            # the channel-mode switches of the width): h_b is never rewritten, and the gate is the same for every mask group
+            gate = _conv_b_image_se(p, f, h_a, idx, cnt, h_b, s, cout // G, "packed") if USE_BOTH_SE_FUSED else _conv_b_image(p, f, h_a, idx, cnt, h_b, s)
             h_b2d = h_b.view(B * Ho * Wo, w_b)
-            ops.se_packed(h_b2d, self._img_prefix(B, Ho * Wo, dev), p["se_w1"], p["se_b1"], p["se_w2"], p["se_b2"], Ho * Wo,
-                          ch_idx=idx, ch_cnt=cnt)
+            if gate is None:
+                ops.se_packed(h_b2d, self._img_prefix(B, Ho * Wo, dev), p["se_w1"], p["se_b1"], p["se_w2"], p["se_b2"], Ho * Wo,
+                              ch_idx=idx, ch_cnt=cnt)
         else:
             dense = dense_index(B, Ho, Wo, s, dev)                            # every pixel: the neighbour table of conv b
             h_a = torch.empty(B * Hi * Wi, w_b, device=dev, dtype=torch.float32)
@@ -520,8 +530,12 @@ class ResBottleneckBlock(_PrepCache):
                     if gk not in p:
                         p[gk] = p["wc_k"][:, :, cs_].contiguous()
                     wck = p[gk]
-                ops.conv_packed(h_b2d, wck, p["sc"][cs_], p["tc"][cs_], out2d[:, cs_], B=B, row_prefix=ig.pre3, m_cap=Ho * Wo, a_map=ig.idx3,
-                                taps=1, out_map=ig.idx3, k_idx=idx, k_cnt=cnt, kgran=gran, relu=1, residual2d=resid[:, cs_])
+                if gate is None:
+                    ops.conv_packed(h_b2d, wck, p["sc"][cs_], p["tc"][cs_], out2d[:, cs_], B=B, row_prefix=ig.pre3, m_cap=Ho * Wo, a_map=ig.idx3,
+                                    taps=1, out_map=ig.idx3, k_idx=idx, k_cnt=cnt, kgran=gran, relu=1, residual2d=resid[:, cs_])
+                else:
+                    ops.conv_packed_gated(h_b2d, wck, p["sc"][cs_], p["tc"][cs_], out2d[:, cs_], gate, B=B, row_prefix=ig.pre3, m_cap=Ho * Wo,
+                                          a_map=ig.idx3, out_map=ig.idx3, k_idx=idx, k_cnt=cnt, kgran=gran, relu=1, residual2d=resid[:, cs_])
             f.last_channel_mask = cmask
             cs = cmask.mean().reshape(1)
         else:

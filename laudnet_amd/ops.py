@@ -1399,6 +1399,40 @@ def conv_image_gated(a_nhwc, w, scale, shift, out_nhwc, gate, *, ksize=1, stride
     return out_nhwc
 
 
+def conv_packed_gated_ok(B, m_cap, cin, cout, has_residual, has_scale):
+    """Whether ldn_conv_packed_gated takes a one-tap convolution over the packed rows of B images of at most m_cap rows each, cin -> cout,
+    with / without a residual and a scale vector (host arithmetic only)."""
+    return bool(L.load().ldn_conv_packed_gated_ok(int(B), int(m_cap), int(cin), int(cout), int(bool(has_residual)), int(bool(has_scale))))
+
+
+def conv_packed_gated(a2d, w, scale, shift, out2d, gate, *, B, row_prefix, m_cap, a_map=None, out_map=None, k_idx, k_cnt, kgran=1, relu=1,
+                      residual2d=None, math=None, taps=1, pix_map=None, geom=None, n_idx=None, n_cnt=None, post_sub=None, relu_if_neg=None):
+    """conv_packed whose input column k of a packed row of image b is multiplied by gate[b, k] in flight (ldn_conv_packed_gated; bf16x3):
+    bit-identical to conv_packed on the pre-scaled input.  Admitted: conv c of a 'both' block (one tap, row_prefix, k_idx / k_cnt, no n_idx,
+    one shift class); the keywords behind `math` are those of conv_packed and are refused by the library."""
+    L.require_device(a2d, w, out2d)
+    lib = L.load()
+    if k_idx is None:
+        cout, t, cin = w.shape
+    else:
+        t, cin, cout = w.shape
+    if t != taps:
+        raise L.LdnError(f"conv_packed_gated: weight has {t} taps, expected {taps}")
+    if gate is None or tuple(gate.shape) != (B, cin) or not gate.is_contiguous() or gate.dtype != torch.float32:
+        raise L.LdnError("conv_packed_gated: gate must be a contiguous fp32 [B, cin] tensor")
+    classes = 1 if shift.dim() == 1 else shift.shape[0]
+    hi, wi, ho, wo, stride = geom if geom is not None else (0, 0, 0, 0, 1)
+    L.check(lib.ldn_conv_packed_gated(L.ptr(_f32c(a2d, "a")), a2d.stride(0), B, L.ptr(_i32c(row_prefix, "row_prefix")), None, m_cap,
+                                      L.ptr(_i32c(a_map, "a_map")), taps, L.ptr(_i32c(out_map, "out_map")), L.ptr(_i32c(pix_map, "pix_map")),
+                                      hi, wi, ho, wo, stride, L.ptr(_f32c(w, "w")), cin, cout, L.ptr(_i32c(k_idx, "k_idx")),
+                                      L.ptr(_i32c(k_cnt, "k_cnt")), kgran, L.ptr(_i32c(n_idx, "n_idx")), L.ptr(_i32c(n_cnt, "n_cnt")),
+                                      L.ptr(_f32c(scale, "scale")), L.ptr(_f32c(shift, "shift")), classes, L.ptr(post_sub), relu,
+                                      L.ptr(_i32c(relu_if_neg, "relu_if_neg")), L.ptr(residual2d),
+                                      residual2d.stride(0) if residual2d is not None else 0, L.ptr(_f32rows(out2d, "out")), out2d.stride(0),
+                                      L.ptr(gate), _mm(math), L.stream_ptr(out2d)), "ldn_conv_packed_gated")
+    return out2d
+
+
 def grouped_wide_ok(C, group_width, Hi, Wi, stride):
     """Whether ldn_grouped_wide_conv3x3_image takes the shape: group width 56, 112 or 232, C a positive multiple of it, stride 1 or 2 and a
     rectangle of the Hi x Wi input map fits the LDS (host arithmetic only)."""
