@@ -52,11 +52,17 @@ class TokenSkipBlock(nn.Module):
         self.fc2 = nn.Linear(hidden, dim)
         self._w = None
 
+    def invalidate(self):
+        """Drop the folded weights (after an edit their key cannot see: through `p.data`, or of a parameter that is an inference tensor --
+        the blind spots of laud_resnet._PrepCache; a replaced parameter object IS seen here, the key walks the module on every call)."""
+        self._w = None
+
     def _weights(self, dev):
         """Linear weights as k_dense wants them ([out, 1, in] fp32).  The two LayerNorms are folded into the linears that follow them
         (ldn_conv_rows_split: LN(x) . w + b = rstd (x . (gamma * w) - mean c1) + (w . beta + b)): qkv and fc1 carry gamma-scaled
-        weights, c1 = their row sums and the constant as bias; only the rows' {mean, rstd} are computed per call (ldn_row_stats)."""
-        key = tuple((p.data_ptr(), p._version) for p in self.parameters())
+        weights, c1 = their row sums and the constant as bias; only the rows' {mean, rstd} are computed per call (ldn_row_stats).
+        Kept until a parameter changes: keyed on (data_ptr, version) of every parameter, the LayerNorms' included."""
+        key = ops.version_key(tuple(self.parameters()))
         if self._w is None or self._w[0] != key:
             with torch.no_grad():
                 def plain(lin):

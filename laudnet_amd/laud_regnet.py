@@ -734,7 +734,7 @@ class LAD_RegNet(nn.Module):
             return st(x)
         bn = st[1]
         src = (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)
-        key = tuple((t.data_ptr(), t._version) for t in src)
+        key = ops.version_key(src)
         if getattr(self, "_stem_key", None) != key:   # folded once, until a parameter or buffer changes
             with torch.no_grad():
                 scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)

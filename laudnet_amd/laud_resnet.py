@@ -108,9 +108,17 @@ _PREP_GEN = itertools.count()
 class _PrepCache(nn.Module):
     """Mixin: lazily built, device-resident folded weights.  The cache is keyed on (data_ptr, _version) of every parameter
     and buffer of the module's OWN sub-tree, so in-place edits through the tensor itself (p.copy_ / p.mul_ under no_grad, BN
-    re-estimation, an optimizer step) are noticed like load_state_dict / .to() / train() are.  NOT noticed: edits through
-    `p.data` (`p.data.copy_(...)` -- `.data` is a detached alias with its own version counter, p._version stays put): call
-    `invalidate()` on the module after such an edit, or the stale folded weights keep being used."""
+    re-estimation, an optimizer step) are noticed like load_state_dict / .to() / train() are.  The key ends in the process-wide count of
+    optimizer steps (ops.version_key): the fused optimizer implementations (fused=True) update parameters without touching their version
+    counters.  NOT noticed:
+      - edits through `p.data` (`p.data.copy_(...)` -- `.data` is a detached alias with its own version counter, p._version stays put);
+      - a parameter or buffer REPLACED by another object (`m.conv.weight = nn.Parameter(...)`): the list of source tensors is built once
+        per cache (this path is host-bound) and still names the old object;
+      - in-place edits of a parameter that is itself an inference tensor (made under torch.inference_mode(): it has no version counter and
+        counts as version -1, ops.tensor_version).
+    Call `invalidate()` on the module after such an edit, or the stale folded weights keep being used.  (A forward under
+    torch.inference_mode() on ordinary parameters is fine: the folded tensors it builds are inference tensors, the keys never read their
+    versions except through ops.tensor_version.)"""
 
     def _init_cache(self):
         self._prep = None
@@ -129,7 +137,7 @@ class _PrepCache(nn.Module):
         src = self._prep_src
         if src is None:
             src = self._prep_src = [t for t in list(self.parameters()) + list(self.buffers())]
-        return tuple((t.data_ptr(), t._version) for t in src)
+        return ops.version_key(src)
 
     def _cache_valid(self):
         """True when self._prep was built from the tensors as they are now."""
@@ -1275,7 +1283,7 @@ class ResNet(nn.Module):
         """conv1 weights scaled by bn1's eval affine (laud_resnet.py:318-320), cached until a parameter or buffer changes."""
         bn = self.bn1
         src = (self.conv1.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)
-        key = tuple((t.data_ptr(), t._version) for t in src)
+        key = ops.version_key(src)
         if getattr(self, "_stem_key", None) != key:
             with torch.no_grad():
                 scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
@@ -1364,7 +1372,8 @@ class GraphedForward:
     """Replay a model's eval forward as one hipGraph (no host launch gaps between the ~250 kernels of a forward).
     The channel/spatial paths keep all data-dependent sizes on the device, so the launch sequence is static.
     `model(x, temperature)` is captured once on a side stream for a fixed input shape; calling the object copies
-    the new batch into the static input buffer and replays."""
+    the new batch into the static input buffer and replays.  The captured launches hold raw pointers to the folded weights of the
+    moment of capture: after any weight edit the owner must build a new GraphedForward (a replay is outside what the caches track)."""
 
     def __init__(self, model, example_x, temperature=1.0, warmup=2):
         self.model = model

@@ -10,6 +10,7 @@ from collections import namedtuple
 from dataclasses import dataclass
 
 import torch
+from torch.optim.optimizer import register_optimizer_step_post_hook
 
 from . import _lib as L
 
@@ -358,7 +359,7 @@ def forward_stats(terms, static_flops, *, cnt=None, denom=None, st_in=None):
 
 
 # ---------------------------------------------------------------------------------------- a7 rows
-_SPLIT_CACHE = {}   # (data_ptr, _version, shape) of an fp32 weight -> its pre-split n-major copy (ldn_conv_rows_split)
+_SPLIT_CACHE = {}   # (data_ptr, shape, device, strides, version, optimizer steps) of an fp32 weight -> its pre-split n-major copy (ldn_conv_rows_split)
 DENSE_TAPS = tuple(int(t) for t in os.environ.get("LDN_DENSE_TAPS", "1,9").split(","))   # tuning: "1,9" sends the packed-row 3x3 to k_dense too
 DENSE_CHANNEL_3X3 = os.environ.get("LDN_DENSE_CHANNEL_3X3", "1") != "0"   # the 3x3 of the dense channel execution (stage 4's first block) on k_dense's neighbour-table form, mask and post-ReLU constant in its epilogue (round 2: no gain; round 4: -0.05 ms per step, no separate mask pass)
 DENSE_K_MULT = int(os.environ.get("LDN_DENSE_K_MULT", "8"))   # tuning: 32 keeps layers whose widths are not multiples of 32 (LAD-RegNet 144 / 784) on the round-1 kernels
@@ -387,15 +388,51 @@ def fused_kernel_ok():
     return mode == "bf16x3" or (mode == "fp32" and USE_FUSED_F32)
 
 
+def tensor_version(t):
+    """t._version as a cache key field.  A tensor made under torch.inference_mode() has no version counter (reading it raises): it counts
+    as version -1, always.  Such a tensor can only be edited in place under inference_mode, and no cache keyed on this notices that edit --
+    the same blind spot as an edit through `p.data` (laud_resnet._PrepCache): drop the cache by hand after one."""
+    try:
+        return t._version
+    except RuntimeError:
+        return -1
+
+
+# The fused optimizer implementations (torch.optim.AdamW / Adam / SGD with fused=True: torch._fused_adamw_ and its kin) update the parameters
+# WITHOUT bumping their version counters, so (data_ptr, version) alone would serve the weights of before the step.  Every derived-weight key
+# therefore ends in this count of optimizer steps taken in the process (any optimizer, through torch's global step hook: a step rebuilds the
+# folded weights of every model once, which a step of the model's own optimizer has to do anyway).  Not seen: a step replayed from a captured
+# graph (no Python runs), like every other edit behind `p.data`.
+_OPTIMIZER_STEPS = [0]
+
+
+def _after_optimizer_step(optimizer, args, kwargs):
+    _OPTIMIZER_STEPS[0] += 1
+
+
+register_optimizer_step_post_hook(_after_optimizer_step)
+
+
+def version_key(tensors):
+    """((data_ptr, version), ..., optimizer steps so far) of the source tensors (a sequence) of a derived-weight cache (tensor_version: an
+    inference tensor's version is -1)."""
+    try:
+        return tuple([(t.data_ptr(), t._version) for t in tensors] + _OPTIMIZER_STEPS)     # (spelled out: one call per key, not per tensor, on host-bound paths)
+    except RuntimeError:
+        return tuple([(t.data_ptr(), tensor_version(t)) for t in tensors] + _OPTIMIZER_STEPS)
+
+
 def split_rows_weight(w):
-    """[cout, 1, cin] (or [cout, cin]) fp32 -> [cout][cin/8][8 hi | 8 lo] bf16, cached until the tensor changes."""
-    ident = (w.data_ptr(), tuple(w.shape), str(w.device))
-    key = ident + (w._version,)
+    """[cout, 1, cin] (or [cout, cin]) fp32 -> [cout][cin/8][8 hi | 8 lo] bf16, cached until the tensor changes.  The tensor is identified by
+    address, shape, strides and device (two views of one storage that differ in strides alone hold different values) and by
+    tensor_version."""
+    ident = (w.data_ptr(), tuple(w.shape), str(w.device), w.stride())
+    key = ident + (tensor_version(w), _OPTIMIZER_STEPS[0])     # (a folded weight may alias its parameter: a fused optimizer step edits it unseen)
     hit = _SPLIT_CACHE.get(key)
     if hit is None:
         # a long-lived weight edited in place (BN re-estimation, fine-tuning loops that call the eval path) bumps _version at every
         # edit: drop the copies of its older versions, or the cache grows by one entry per edit until the tensor dies
-        for stale in [k for k in _SPLIT_CACHE if k[:3] == ident]:
+        for stale in [k for k in _SPLIT_CACHE if k[:4] == ident]:
             _SPLIT_CACHE.pop(stale, None)
         with torch.no_grad():
             w2 = w.detach().float().reshape(w.shape[0], -1)
@@ -444,7 +481,10 @@ class RowsHint:
         if (self.calls > 2 and self.calls % self.EVERY) or torch.cuda.is_current_stream_capturing():
             return
         if self.host is None:
-            self.host = torch.full((self.n,), -1, dtype=torch.int32).pin_memory()
+            # (an ordinary tensor even when the first forward runs under torch.inference_mode(): an inference tensor could not be
+            # written by the copies of a later forward outside it)
+            with torch.inference_mode(False):
+                self.host = torch.full((self.n,), -1, dtype=torch.int32).pin_memory()
         o = 0
         for t in dev_counts:
             k = t.numel()
